@@ -17,7 +17,12 @@ packed statistics.
 Timing: W warm-up steps, then R repetitions of a block of EXACTLY K steps, each block
 bracketed by barrier + stream synchronisation on both sides and reduced with MAX over
 ranks; the reported ms_per_step / value are the MEDIAN block (every block is listed in
-"ms_per_step_reps").
+"ms_per_step_reps").  A plain run times one block (R = 1: --steps is the number of timed
+steps); --full defaults R to as many blocks as span >= 5 s of GPU time.
+
+--dump-outputs DIR writes what the last timed step returned to its caller -- the packed
+statistics A_raw, xbar, neff, S, lb -- as DIR/<name>.npy (float64); the inputs are seeded,
+so two builds run with the same arguments can be compared output for output.
 
 Multi-GPU (configs[3]): one process per GPU, each with its own T=1M sequence, weak scaling,
 one RCCL all-reduce of the packed statistics per step.  Launch either with
@@ -26,11 +31,13 @@ LOCAL_RANK / WORLD_SIZE from the environment) or plainly as `python bench.py --g
 without WORLD_SIZE in the environment the script starts the N ranks itself (and fails if
 fewer than N GPUs are visible).  "ranks" in the output is ncclCommCount of the communicator.
 
-Side figures (world size 1, outside the headline timed region): the literal minibatch=64
+Side figures (--full only; world size 1, outside the headline timed region): the literal minibatch=64
 E-step, one full SVI iteration through the class surface (hmmsgd_metaobs.VBHMM.infer: E-step +
 global step + ELBO), the whole-chain E-step and FFBS, configs[4] (K=256, D=64), and the CPU
 baselines (the reference algorithm restated in C on 1 core and on all cores, and its NumPy
-restatement on 1 core) on bounded samples of the same workload.
+restatement on 1 core) on bounded samples of the same workload.  --full also adds the
+strong-scaling side record of an N>1 weak run and a short pass that times every kernel of the
+step (a plain run's `kernels` holds the dominant kernel, bracketed in the timed region).
 
 Prints ONE JSON line on rank 0.
 """
@@ -220,6 +227,14 @@ def packed_size(Kq, Dq):
     return Kq * Kq + Kq * Dq + Kq + Kq * Dq * Dq + 1
 
 
+def dump_outputs(path, out):
+    """--dump-outputs: the views of PackedStats a caller of the step receives, one float64 .npy each
+    (K=64, D=32: 0.57 MB in all)."""
+    os.makedirs(path, exist_ok=True)
+    for name in ("A_raw", "xbar", "neff", "S", "lb"):
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(getattr(out, name), dtype=np.float64))
+
+
 def headline_record(args, strong, world, ranks_seen, have_comm, block, per_rank, prof, rows, gen_ms, side):
     """The ONE JSON line from the measured blocks (seconds per block of args.steps steps, already
     MAX-reduced over ranks) and the HIP-event profile of the timed region."""
@@ -328,7 +343,7 @@ def headline_record(args, strong, world, ranks_seen, have_comm, block, per_rank,
                      "clock": "frac: the profiler's clock (reproducible from profiles/); frac_events: HIP events "
                               "around every launch of the kernel in the timed region (%d launches; a few %% "
                               "shorter than under the profiler; only this kernel is bracketed there, the other "
-                              "entries of `kernels` come from a short separate pass); whole_step_frac: algorithmic "
+                              "entries of `kernels` come from a short separate pass of --full); whole_step_frac: algorithmic "
                               "flop of emission + sweeps + statistics / ms_per_step / peak" % nlaunch,
                      "note": "fp64: v_mfma_f64_16x16x4_f64; peak = MI355X datasheet fp64 "
                              "(matrix = vector = 78.6 TF); traffic_ratio = counter bytes / "
@@ -397,8 +412,9 @@ REQUIRED = {"metric": str, "value": float, "unit": str, "n_gpus": int, "steps": 
             "config": dict, "roofline": dict, "ranks": int}
 
 
-def validate_record(res, n_gpus):
-    """Schema of the line the driver parses (contract of the task + the multi-GPU extras)."""
+def validate_record(res, n_gpus, full=True):
+    """Schema of the line the driver parses (contract of the task + the multi-GPU extras; the
+    strong-scaling side record only with full=True, i.e. a --full run)."""
     for k, t in REQUIRED.items():
         assert k in res, "missing key %s" % k
         assert isinstance(res[k], t), "%s: %r is not %s" % (k, res[k], t.__name__)
@@ -410,6 +426,7 @@ def validate_record(res, n_gpus):
     if n_gpus > 1:
         assert len(res["per_rank_ms_per_step"]) == n_gpus
         assert "ms_per_step" in res["allreduce"]
+    if n_gpus > 1 and full:
         ss = res["strong_scaling"]
         for leg in ("epoch", "minibatch_s64"):
             for k in ("windows", "windows_per_rank", "ms_per_step", "value", "allreduce_ms_per_step"):
@@ -452,13 +469,15 @@ def dry_run(args):
         per_rank = [3.2] * n
         leg = lambda w: {"windows": int(w), "windows_per_rank": int((w + n - 1) // n), "ms_per_step": 1.0,
                          "value": 1.0, "unit": "updates/s", "scaling": "strong", "allreduce_ms_per_step": 0.05}
-        if not strong and not args.no_strong:
+        if args.full and not strong and not args.no_strong:
             side["strong_scaling"] = {"epoch": leg(B), "minibatch_s64": leg(64), "note": "synthetic"}
+    if not args.full:       # (a plain run brackets the dominant kernel only: no per-kernel pass)
+        prof = {k: v for k, v in prof.items() if k in ("stats", "allreduce")}
     res = headline_record(args, strong, n, n, n > 1, block, per_rank, prof, rows, 0.0, side)
     res["data"] = "DRY RUN: synthetic timings, no device touched -- not a measurement"
-    if n > 1 and strong:
+    if n > 1 and strong and args.full:
         res["strong_scaling"] = {"epoch": leg(B), "minibatch_s64": leg(64)}     # (schema check only)
-    validate_record(res, n)
+    validate_record(res, n, full=args.full)
     print(json.dumps(res))
     return 0
 
@@ -469,24 +488,29 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--reps", type=int, default=0,
-                    help="repetitions of the --steps block (median reported); default: as many as make the "
-                         "headline region span >= 5 s of GPU time (80 blocks of 20 steps at ~3.1 ms), so that "
-                         "a coarse utilisation sampler sees it")
+                    help="repetitions of the --steps block (median reported); default: 1, with --full as many "
+                         "as make the headline region span >= 5 s of GPU time (80 blocks of 20 steps at ~3.1 ms), "
+                         "so that a coarse utilisation sampler sees it")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline line: the side figures, CPU baselines, the strong-scaling "
+                         "side record of an N>1 weak run, the per-kernel pass, and the default --reps above")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the packed statistics of the last timed step as DIR/<name>.npy (float64)")
     ap.add_argument("--dry-run", action="store_true",
                     help="no devices: build every rank's launch environment for --gpus N, run the record "
                          "assembly on synthetic timings and validate the schema of the line (tests)")
     ap.add_argument("--scaling", choices=("weak", "strong"), default="weak",
                     help="weak (default, BASELINE configs[3]): one independent T=1M sequence per GPU; strong: ONE "
                          "sequence, the epoch's 3891 windows dealt windows[rank::N] (north_star: 'minibatches shard "
-                         "across the GPUs'), one all-reduce per step.  At N>1 the weak run also reports the strong "
-                         "figure as a side record")
-    ap.add_argument("--no-strong", action="store_true", help="skip the strong-scaling side record of an N>1 weak run")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-side", action="store_true", help="skip the side figures (profiling runs)")
+                         "across the GPUs'), one all-reduce per step.  At N>1 the weak --full run also reports the "
+                         "strong figure as a side record")
+    ap.add_argument("--no-strong", action="store_true", help="--full: skip the strong-scaling side record of an N>1 weak run")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-side", action="store_true", help="--full: skip the side figures (profiling runs)")
     args = ap.parse_args()
 
     if args.reps <= 0:
-        args.reps = max(10, int(np.ceil(5.0 / (max(args.steps, 1) * 3.2e-3))))
+        args.reps = max(10, int(np.ceil(5.0 / (max(args.steps, 1) * 3.2e-3)))) if args.full else 1
     if args.dry_run:
         raise SystemExit(dry_run(args))
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -553,7 +577,7 @@ def run_rank(args, state):
     eng.generate(tran, means, chols, T, seed=SEED + seq)
     eng.sync()
     gen_ms = (time.perf_counter() - t0) * 1e3
-    need_host_obs = rank == 0 and world == 1 and not (args.no_side and args.no_cpu_baseline)
+    need_host_obs = rank == 0 and world == 1 and args.full and not (args.no_side and args.no_cpu_baseline)
     if need_host_obs:
         obs_host, sts_host = eng.read_generated()
         head = obs_host[:20000]
@@ -609,16 +633,20 @@ def run_rank(args, state):
     dispatched = {}
     if hasattr(eng, "last_kernel"):
         dispatched = {dom_slot: eng.last_kernel(dom_slot)}
-    # the other kernels of the step: a short separate pass with every slot bracketed (outside the
-    # timed region; the dominant kernel keeps its timed-region figure)
-    eng.profile(True)
-    eng.profile_reset()
-    for _ in range(min(args.steps, 10)):
-        step()
-    allprof = eng.profile_read()
-    eng.profile(False)
-    for k, v in allprof.items():
-        prof.setdefault(k, v)
+    # the statistics of the last timed step, as its caller received them (before anything else runs)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out)
+    # the other kernels of the step (--full): a short separate pass with every slot bracketed (outside
+    # the timed region; the dominant kernel keeps its timed-region figure)
+    if args.full:
+        eng.profile(True)
+        eng.profile_reset()
+        for _ in range(min(args.steps, 10)):
+            step()
+        allprof = eng.profile_read()
+        eng.profile(False)
+        for k, v in allprof.items():
+            prof.setdefault(k, v)
     mine = block.copy()
     per_rank = None
     if comm is not None:
@@ -632,10 +660,10 @@ def run_rank(args, state):
     assert abs(out.A_raw.sum() / tot_rows - 1.0) < 1e-9, out.A_raw.sum() / tot_rows
 
     side = {}
-    if world == 1 and not args.no_side:
+    if world == 1 and args.full and not args.no_side:
         side = side_figures(eng, L, pb, step, barrier, obs_host, args)
     side["_dispatched"] = dispatched
-    if comm is not None and not strong and not args.no_strong:
+    if comm is not None and args.full and not strong and not args.no_strong:
         # the other partitioning of DESIGN 6, measured in the same job: ONE sequence on every GPU
         # (rank 0's), the epoch's windows and the S=64 minibatch dealt round-robin over the ranks
         side["strong_scaling"] = strong_scaling(eng, L, comm, rank, world, args, barrier)

@@ -22,7 +22,7 @@ def run(*extra):
 
 @pytest.mark.parametrize("n", [1, 2, 4, 8])
 def test_dry_run_record_schema(n):
-    r = run("--gpus", str(n), "--steps", "5", "--warmup", "1")
+    r = run("--gpus", str(n), "--steps", "5", "--warmup", "1", "--full")
     assert r["n_gpus"] == n and r["ranks"] == n and r["steps"] == 5 and r["warmup"] == 1
     assert r["data"].startswith("DRY RUN")
     assert r["scaling"] == "weak" and r["config"]["sequences"] == n
@@ -40,6 +40,42 @@ def test_dry_run_record_schema(n):
         assert "per_rank_ms_per_step" not in r and r["ranks_source"] == "no communicator"
     # the headline region spans >= 5 s of GPU time by default (a coarse utilisation sampler sees it)
     assert r["reps"] * r["steps"] * 3.1e-3 >= 4.8
+
+
+@pytest.mark.parametrize("n", [1, 2])
+def test_plain_dry_run_times_one_block(n):
+    """Without --full the run times exactly --steps steps (one block) and carries no strong-scaling
+    side record; only the dominant kernel (and the all-reduce) is bracketed."""
+    r = run("--gpus", str(n), "--steps", "7", "--warmup", "2")
+    assert r["steps"] == 7 and r["warmup"] == 2 and r["reps"] == 1 and len(r["ms_per_step_reps"]) == 1
+    assert r["ms_per_step"] > 0 and "strong_scaling" not in r
+    assert set(r["kernels"]) <= {"stats", "allreduce"}
+
+
+@pytest.mark.gpu
+def test_plain_run_times_steps_and_dumps_outputs(tmp_path):
+    """A plain run on the device: one block of exactly --steps timed steps, none of --full's records, and
+    --dump-outputs writes the packed statistics of the last timed step (float64, as the caller gets them)."""
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
+    p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], env=env, capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-4000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, p.stdout[-2000:]
+    r = json.loads(lines[0])
+    assert r["steps"] == 3 and r["reps"] == 1 and len(r["ms_per_step_reps"]) == 1
+    assert r["ms_per_step"] > 0 and r["value"] > 1e9 and r["dtype"] == "f64"
+    assert not set(r) & {"minibatch_s64", "f32_mode", "whole_chain", "cpu_baseline", "c2_k16_d8", "c5_k256_d64",
+                         "strong_scaling"}
+    K, D, rows = 64, 32, (1000000 // 257) * 257
+    shapes = {"A_raw": (K, K), "xbar": (K, D), "neff": (K,), "S": (K, D, D), "lb": (1,)}
+    out = {}
+    for name, shape in shapes.items():
+        out[name] = np.load(str(tmp_path / (name + ".npy")))
+        assert out[name].shape == shape and out[name].dtype == np.float64 and np.all(np.isfinite(out[name]))
+    # posteriors sum to one: the wrap transition statistic and the state counts each sum to the row count
+    assert abs(out["A_raw"].sum() / rows - 1.0) < 1e-9 and abs(out["neff"].sum() / rows - 1.0) < 1e-9
 
 
 def test_dry_run_strong_scaling_line():
@@ -61,13 +97,14 @@ def test_rank_environments():
 
 
 def test_failed_rank_zero_still_prints_one_json_line():
-    """VERDICT r4 next #5b: a multi-rank run whose rank 0 cannot come up (here: no HIP device in the CPU
-    container, under a torchrun-style environment) leaves the error record, not silence."""
+    """VERDICT r4 next #5b: a multi-rank run whose rank 0 cannot come up (here: its HIP library does not load,
+    under a torchrun-style environment -- so also on a machine with a GPU, where rank 0 would otherwise wait
+    for a peer that never starts) leaves the error record, not silence."""
     import json
     import subprocess
     import sys
     env = dict(os.environ, RANK="0", LOCAL_RANK="0", WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT="29999",
-               SVIHMM_RENDEZVOUS_TIMEOUT="2")
+               SVIHMM_RENDEZVOUS_TIMEOUT="2", SVIHMM_HIP_LIB="/nonexistent/libsvihmm_hip.so")
     p = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "0"],
                        env=env, capture_output=True, text=True, timeout=120)
     assert p.returncode != 0

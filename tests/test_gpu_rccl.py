@@ -72,7 +72,7 @@ def _bench(extra_env, *argv):
 def test_bench_forced_comm_dry_run():
     """SVIHMM_FORCE_COMM=1: bench.py's multi-GPU code path (communicator, all-reduce in every
     step, RCCL barriers, max-over-ranks timing) at world size 1."""
-    j = _bench({"SVIHMM_FORCE_COMM": "1"}, "--steps", "3", "--warmup", "1", "--reps", "3", "--no-side",
+    j = _bench({"SVIHMM_FORCE_COMM": "1"}, "--steps", "3", "--warmup", "1", "--reps", "3", "--full", "--no-side",
                "--no-cpu-baseline")
     assert j["n_gpus"] == 1 and j["ranks"] == 1 and j["ranks_source"] == "ncclCommCount"
     assert j["steps"] == 3 and len(j["ms_per_step_reps"]) == 3 and j["value"] > 1e9

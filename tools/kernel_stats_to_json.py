@@ -36,7 +36,7 @@ def pick(rows, table):
 
 def main(path):
     rows = read_rows(path)
-    out = {"_note": "rocprofv3 --kernel-trace --stats of `bench.py --steps 5 --warmup 2 --reps 2 --no-cpu-baseline` "
+    out = {"_note": "rocprofv3 --kernel-trace --stats of `bench.py --steps 5 --warmup 2 --reps 2 --full --no-cpu-baseline` "
                     "(tools/profile_round.sh); average kernel durations of the headline step; source %s" % path}
     out.update(sorted(pick(rows, HEADLINE).items()))
     f32 = pick(rows, F32)

@@ -12,7 +12,7 @@ cd /tmp && export TMPDIR=/tmp
 # 2 blocks of 5 steps of the headline workload + the side figures (their kernels are told apart by
 # their launch grids: 3891-window epoch step, 64-window minibatch / SVI iteration, whole chain,
 # configs[4] K=256 D=64); PMC passes skip the side figures except the SVI iteration
-BENCH="python $ROOT/bench.py --steps 5 --warmup 2 --reps 2 --no-cpu-baseline"
+BENCH="python $ROOT/bench.py --steps 5 --warmup 2 --reps 2 --full --no-cpu-baseline"
 run() {  # name, rocprof args...
   local name=$1; shift
   rm -rf /tmp/prof_$name
@@ -24,7 +24,7 @@ run kt --kernel-trace --stats > $OUT/${TAG}_kernel_stats.txt
 python $ROOT/tools/svi_trace.py $(find /tmp/prof_kt -name "*.db" | head -1) > $OUT/${TAG}_svi_iteration_trace.txt
 # HBM counters on the headline workload alone (no side figures), fp64 and fp32 mode separately
 BENCH_ALL=$BENCH
-BENCH="python $ROOT/bench.py --steps 5 --warmup 2 --reps 2 --no-cpu-baseline --no-side"
+BENCH="python $ROOT/bench.py --steps 5 --warmup 2 --reps 2 --full --no-cpu-baseline --no-side"
 { run fetch --kernel-trace --pmc FETCH_SIZE; run write --kernel-trace --pmc WRITE_SIZE; } > $OUT/${TAG}_pmc_hbm.txt
 BENCH="python $ROOT/tools/f32_profile_workload.py"
 { run fetch32 --kernel-trace --pmc FETCH_SIZE; run write32 --kernel-trace --pmc WRITE_SIZE; } > $OUT/${TAG}_pmc_hbm_f32.txt
@@ -40,5 +40,5 @@ run sq --kernel-trace --pmc GRBM_GUI_ACTIVE SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYC
 cd $ROOT/tools && python kernel_stats_to_json.py $OUT/${TAG}_kernel_stats.txt | sed "s#$OUT/#profiles/#g" > $OUT/kernel_stats.json
 python pmc_to_traffic.py $OUT/${TAG}_pmc_hbm.txt $OUT/${TAG}_pmc_hbm_f32.txt | sed "s#$OUT/#profiles/#g" > $OUT/pmc_traffic.json
 cp $OUT/kernel_stats.json $OUT/pmc_traffic.json $ROOT/profiles/ 2>/dev/null
-cd $ROOT && python bench.py 2>/dev/null | tail -1 > $OUT/${TAG}_bench.json
+cd $ROOT && python bench.py --full 2>/dev/null | tail -1 > $OUT/${TAG}_bench.json
 tail -c 600 $OUT/${TAG}_bench.json
