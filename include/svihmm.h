@@ -231,6 +231,29 @@ int svihmm_estep_minibatch_ex(svihmm_ctx* h, const int64_t* starts, int32_t B,
                               int32_t Lm, int32_t inner_off, int32_t inner_len,
                               uint32_t flags, double* out_packed);
 
+/* Expected sufficient statistics of posteriors the CALLER supplies (a message or local-update override
+ * on the host: the reference's "Override this for specialized behavior", hmmbase.py:279,304), without
+ * an E-step.  var_x [B,Lm,K] is host memory; row t of window b is the posterior of observation row
+ * starts[b] + t, used as given (no renormalisation: zero rows and rows that do not sum to one are
+ * fine).  K is the handle's (svihmm_set_globals) and must equal the emission family's.
+ *   A_raw = sum_windows sum_t q[t-1] (x) q[t]:  with SVIHMM_TRANS_WRAP t = 0..Lm-1 and t-1 wrapping to
+ *           the window's last row (hmmsgd_metaobs.py:876-878, quirk Q1; Lm = 1: the row is its own
+ *           predecessor), without it t = 1..Lm-1 (hmmbatchcd.py:182-184);
+ *   emission statistics over the unmasked rows (NaN symbols of a Categorical model skipped) in the
+ *   packed layout of the current family (NIW, diagonal, Categorical), exactly as
+ *   svihmm_estep_minibatch returns it, in the caller's coordinates (util.py:73-83, :884-904);
+ *   lb = 0 (the caller adds B*(prior_tran-1), quirk Q2).
+ * Buffered windows (intermediate_pars_buffer, hmmsgd_metaobs.py:932-1008): pass the inner segment's
+ * posteriors with starts shifted to i1 + bufferL - L.  Always fp64 (the precision mode and what
+ * svihmm_get_precision reports are unchanged).  The posteriors go to a device buffer of their own: the
+ * intermediates of the last E-step (svihmm_read_intermediate / _read_rows, svihmm_state_argmax, the
+ * kept window of svihmm_svi_iteration) read the same afterwards.  Transfers above 4 MB are staged
+ * through pinned memory.  out_packed may be NULL (result in HBM for svihmm_read_packed /
+ * svihmm_allreduce_packed / svihmm_export_packed).  Fails without resident observations or an
+ * emission family, on a K mismatch, B < 1 or Lm < 1, or a window outside [0, T). */
+int svihmm_suffstats(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t Lm, uint32_t flags,
+                     const double* var_x, double* out_packed);
+
 /* ---- the SVI loop with the variational state resident in HBM ----------------------------------
  * hmmsgd_metaobs.VBHMM.infer (:347-445) iterates  { stationary init :413-418, psi-expectations
  * :502-504, E-step over the minibatch :405-436, global natural-gradient step :1010-1069

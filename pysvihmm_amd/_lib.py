@@ -58,6 +58,8 @@ SIGNATURES = {
     "svihmm_estep_minibatch": (C.c_int, [C.c_void_p, _c_int64_p, C.c_int32, C.c_int32,
                                          C.c_uint32, _c_double_p]),
     "svihmm_read_packed": (C.c_int, [C.c_void_p, _c_double_p]),
+    "svihmm_suffstats": (C.c_int, [C.c_void_p, _c_int64_p, C.c_int32, C.c_int32, C.c_uint32,
+                                   _c_double_p, _c_double_p]),
     "svihmm_estep_minibatch_ex": (C.c_int, [C.c_void_p, _c_int64_p, C.c_int32, C.c_int32,
                                             C.c_int32, C.c_int32, C.c_uint32, _c_double_p]),
     "svihmm_svi_begin": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [_c_double_p] * 11 + [C.c_int32, C.c_double]),

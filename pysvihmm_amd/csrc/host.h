@@ -148,6 +148,7 @@ struct svihmm_ctx {
   bool have_emission = false;
   // work
   Buf starts, ll, la, lb, q, lse_part, local_lb, logz, part, packed, scratch;
+  Buf user_q, user_starts;         // svihmm_suffstats: the caller's posteriors and windows (never the E-step's q / starts)
   // scaled linear-domain sweeps: per-row binary exponents, (na, k) records, 1/Z factors,
   // Eh of host-supplied lliks; log-domain intermediates materialised on demand (m_*)
   Buf kexp, hx, gx, zfac, llE, m_ll, m_la, m_lb, chain, chain2;
@@ -342,7 +343,9 @@ bool f32_wide_ok(const svihmm_ctx* h, int64_t n);
 bool stats_bf16w_shape_ok(const svihmm_ctx* h, int64_t n);
 int launch_stats(svihmm_ctx* h, int B, int Lq, int off, int Lm, uint32_t flags);
 int launch_stats_finalize(svihmm_ctx* h, int64_t nchunk, hipStream_t stream);
-int launch_stats_range(svihmm_ctx* h, int b0, int nb, int Lq, int off, int Lm, uint32_t flags, StatsPlan plan, int64_t chunk_base, hipStream_t stream);
+int launch_stats_range(svihmm_ctx* h, int b0, int nb, int Lq, int off, int Lm, uint32_t flags, StatsPlan plan, int64_t chunk_base, hipStream_t stream,
+                       const double* qsrc = nullptr, const int64_t* starts_src = nullptr);
+int launch_stats_posteriors(svihmm_ctx* h, const double* q, const int64_t* starts_dev, int B, int Lm, uint32_t flags);
 int launch_sum_lb(svihmm_ctx* h, int B, hipStream_t stream);
 int materialise(svihmm_ctx* h, int b0, int nb);
 int prepare_ll(svihmm_ctx* h, const int64_t* starts, int B, int Lm, uint32_t flags, bool need_obs_for_stats, bool lin = false);

@@ -76,7 +76,7 @@ int svihmm_destroy(svihmm_ctx* h) {
   for (auto& p : h->pending) { hipEventDestroy(p.e0); hipEventDestroy(p.e1); }
   for (auto e : h->pool) hipEventDestroy(e);
   Buf* bufs[] = {&h->obs, &h->mask, &h->mod_init, &h->ltran, &h->Aexp, &h->AexpT, &h->theta, &h->niw,
-                 &h->fab, &h->starts, &h->ll, &h->la, &h->lb, &h->q, &h->lse_part,
+                 &h->fab, &h->starts, &h->user_q, &h->user_starts, &h->ll, &h->la, &h->lb, &h->q, &h->lse_part,
                  &h->local_lb, &h->logz, &h->part, &h->packed, &h->scratch, &h->kexp, &h->hx, &h->gx,
                  &h->zfac, &h->llE, &h->m_ll, &h->m_la, &h->m_lb, &h->chain, &h->chain2, &h->cat_table, &h->partc, &h->theta_orb, &h->prior, &h->vlb_aux, &h->gen_z,
                  &h->svi_state, &h->svi_prior, &h->svi_work, &h->commtmp, &h->ll0, &h->a0v, &h->a0e,
@@ -1261,6 +1261,66 @@ int svihmm_estep_minibatch_ex(svihmm_ctx* h, const int64_t* starts, int32_t B, i
     h->starts_slot_inflight = false;      // (the stream is idle: the slot's readers are done)
     CK(check_emission_status(h));
   }
+  return 0;
+}
+
+// ---- a9 on posteriors the caller supplies (svihmm_suffstats) ---------------------------------
+// host -> device through the pinned staging ring in pieces of 4 MB: the DMA of one piece runs while the host
+// copies the next into another slot (a pageable source would make the runtime stage it synchronously itself)
+static int upload_staged(svihmm_ctx* h, void* dst, const void* src, size_t bytes) {
+  const size_t piece = (size_t)4 << 20;
+  for (size_t o = 0; o < bytes; o += piece) {
+    const size_t nb = bytes - o < piece ? bytes - o : piece;
+    void* pin = nullptr;
+    int slot = 0;
+    CK(pinned(h, nb, &pin, &slot));
+    std::memcpy(pin, (const char*)src + o, nb);
+    {
+      ProfScope ps(h, KS_H2D);
+      HIPCK(hipMemcpyAsync((char*)dst + o, pin, nb, hipMemcpyHostToDevice, h->stream));
+    }
+    CK(pin_release(h, slot));
+  }
+  return 0;
+}
+
+int svihmm_suffstats(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t Lm, uint32_t flags,
+                     const double* var_x, double* out_packed) {
+  if (!h) return fail("svihmm_suffstats: NULL handle");
+  if (h->T <= 0 || !h->obs.p) return fail("svihmm_suffstats: no observations: call svihmm_set_obs first");
+  if (!h->have_emission)
+    return fail("svihmm_suffstats: no emission family: call svihmm_set_emission_niw / _diag / _cat first");
+  if (h->K != h->eK)
+    return fail("svihmm_suffstats: K of the globals (" + std::to_string(h->K) + ") differs from the emission "
+                "family's K (" + std::to_string(h->eK) + ")");
+  if (h->eD != h->D) return fail("svihmm_suffstats: emission D does not match obs D");
+  if (B < 1 || Lm < 1) return fail("svihmm_suffstats: B and Lm must be positive");
+  if (!starts || !var_x) return fail("svihmm_suffstats: starts / var_x is NULL");
+  for (int b = 0; b < B; ++b)
+    if (starts[b] < 0 || starts[b] + Lm > h->T)
+      return fail("svihmm_suffstats: window " + std::to_string(b) + " reaches outside [0, T)");
+  CK(set_device(h));
+  CK(wait_side_streams(h));
+  const int K = h->K;
+  const size_t nq = (size_t)B * Lm * K * sizeof(double);
+  // buffers of their own: the last E-step's q / starts (read back lazily: read_intermediate, state_argmax,
+  // the kept last window of the SVI loop) stay as they are
+  CK(ensure(h->user_q, nq));
+  CK(ensure(h->user_starts, (size_t)B * sizeof(int64_t)));
+  CK(upload_staged(h, h->user_starts.p, starts, (size_t)B * sizeof(int64_t)));
+  CK(upload_staged(h, h->user_q.p, var_x, nq));
+  // fp64 statistics whatever the precision mode: the fp32-format kernels are never planned for this batch
+  // (cur_f32 is what the last E-step ran in: svihmm_get_precision reports it unchanged afterwards)
+  const bool cur_f32 = h->cur_f32;
+  h->cur_f32 = false;
+  const int rc = launch_stats_posteriors(h, (const double*)h->user_q.p, (const int64_t*)h->user_starts.p, B, Lm,
+                                         flags & SVIHMM_TRANS_WRAP);
+  h->cur_f32 = cur_f32;
+  if (rc) return rc;
+  h->have_packed = true;
+  h->mirror_valid = false;
+  CK(launch_mirror(h));
+  if (out_packed) CK(read_packed_host(h, out_packed));
   return 0;
 }
 

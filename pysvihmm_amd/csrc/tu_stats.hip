@@ -102,16 +102,19 @@ StatsPlan stats_plan(const svihmm_ctx* h, int64_t n, int forced) {
   return {rpc, (n + rpc - 1) / rpc};
 }
 // partial statistics of windows [b0, b0+nb) (inner segment [off, off+Lm) of each window of
-// length Lq) into partial slots [chunk_base, chunk_base + plan.nchunk) on `stream`
+// length Lq) into partial slots [chunk_base, chunk_base + plan.nchunk) on `stream`.
+// qsrc / starts_src (svihmm_suffstats): posteriors [B*Lq, K] and window starts the caller supplied, in
+// buffers of their own -- the plain-posterior GEMM on those instead of the E-step's q / starts
 int launch_stats_range(svihmm_ctx* h, int b0, int nb, int Lq, int off, int Lm, uint32_t flags,
-                              StatsPlan plan, int64_t chunk_base, hipStream_t stream) {
+                              StatsPlan plan, int64_t chunk_base, hipStream_t stream,
+                              const double* qsrc, const int64_t* starts_src) {
   const int D = h->D, K = h->K, Kp = h->Kp, Fp = h->Fp, F = h->F;
   const int Ftot = Fp + Kp;
   const int64_t n = (int64_t)nb * Lm;
   const int64_t rpc = plan.rpc, nchunk = plan.nchunk;
   const uint8_t* mk = h->have_mask ? (const uint8_t*)h->mask.p : nullptr;
   CK(ensure_starts_pulled(h));    // (an E-step without an emission launch -- host lliks -- still owes the device copy)
-  const int64_t* starts_dev = (const int64_t*)h->starts.p + b0;
+  const int64_t* starts_dev = (starts_src ? starts_src : (const int64_t*)h->starts.p) + b0;
   int var = h->variant[1];
   if (var != 2) var = 3;      // (2: the double-buffered generation; the VALU generation of round 1 is gone)
   if (var == 3) {   // feasibility of the pipelined kernel (same test as below)
@@ -124,10 +127,11 @@ int launch_stats_range(svihmm_ctx* h, int b0, int nb, int Lq, int off, int Lm, u
   // (wide models too, round 3: the separate posterior pass costs more than the second operand's loads;
   //  variant[15] = 1: K > 64 through q as before)
   // (variant[15] = 2, measurement only: posteriors by their own pass + the GEMM on plain q for every K)
-  const bool lin = h->lin_mode && !h->q_valid && var == 3 && (Kp <= 64 || h->variant[15] != 1) && h->variant[15] != 2;
-  if (h->lin_mode && !lin) CK(ensure_q(h, h->curB, Lq, stream));
+  const bool lin = !qsrc && h->lin_mode && !h->q_valid && var == 3 && (Kp <= 64 || h->variant[15] != 1) &&
+                   h->variant[15] != 2;
+  if (h->lin_mode && !lin && !qsrc) CK(ensure_q(h, h->curB, Lq, stream));
   const size_t qo = (size_t)b0 * Lq * K;
-  const double* qv = (const double*)(lin ? h->la.p : h->q.p) + qo;   // (reassigned: see the transition blocks)
+  const double* qv = (qsrc ? qsrc : (const double*)(lin ? h->la.p : h->q.p)) + qo;   // (reassigned: see the transition blocks)
   const double* bhv = lin ? (const double*)h->lb.p + qo : nullptr;
   const double* hxv = lin ? (const double*)h->hx.p + (size_t)b0 * Lq : nullptr;
   const double* gxv = lin ? (const double*)h->gx.p + (size_t)b0 * Lq : nullptr;
@@ -338,16 +342,21 @@ int ensure_stats(svihmm_ctx* h, int64_t nchunk_total) {
 }
 // Categorical statistics: transition block on the pipelined GEMM (transition-only mode),
 // symbol counts by k_stats_cat, both reduced by k_finalize_cat into [A_raw | counts | lb]
-static int launch_stats_cat(svihmm_ctx* h, int B, int Lq, int off, int Lm, uint32_t flags) {
+static int launch_stats_cat(svihmm_ctx* h, int B, int Lq, int off, int Lm, uint32_t flags,
+                            const double* qsrc = nullptr, const int64_t* starts_src = nullptr) {
   const int K = h->K, Kp = h->Kp, V = h->V, D = h->D;
   if (K > 256) return fail("Categorical statistics: K > 256 unsupported");
   CK(cat_uncentre(h));
   const int KpT = (K + 63) / 64 * 64;
   const int64_t n = (int64_t)B * Lm;
   hipStream_t stream = h->stream;
-  CK(ensure_q(h, h->curB, Lq, stream));
+  if (!qsrc) CK(ensure_q(h, h->curB, Lq, stream));
   CK(ensure_starts_pulled(h));
+  const double* qv = qsrc ? qsrc : (const double*)h->q.p;
+  const int64_t* sv = starts_src ? starts_src : (const int64_t*)h->starts.p;
   const StatsPlan plan = stats_plan(h, n);
+  if (qsrc && (int64_t)(Lq + plan.rpc) * KpT >= ((int64_t)1 << 31))
+    return fail("Categorical statistics: window too long for the GEMM's 32-bit row offsets");
   const int64_t rpcc = (n + 1023) / 1024 > 64 ? (n + 1023) / 1024 : 64;
   const int nchunkc = (int)((n + rpcc - 1) / rpcc);
   CK(ensure(h->part, (size_t)plan.nchunk * KpT * KpT * sizeof(double)));
@@ -361,8 +370,8 @@ static int launch_stats_cat(svihmm_ctx* h, int B, int Lq, int off, int Lm, uint3
                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     dim3 g2((unsigned)plan.nchunk, KpT / 64, KpT / 64);
     hipLaunchKernelGGL((k_stats_mfma4<1, 2, 2, 1, false, true>), g2, dim3(512), lds, stream,
-                       (const double*)h->obs.p, mk, (const int64_t*)h->starts.p, n, Lm, D, K, 0, 0,
-                       (const int*)nullptr, (const double*)h->q.p, plan.rpc, flags, Lq, off,
+                       (const double*)h->obs.p, mk, sv, n, Lm, D, K, 0, 0,
+                       (const int*)nullptr, qv, plan.rpc, flags, Lq, off,
                        (double*)h->part.p, KpT, 0, (const double*)nullptr, (const double*)nullptr,
                        (const double*)nullptr, (const double2*)nullptr, (double*)nullptr);
     const size_t ldsc = (size_t)V * Kp * sizeof(double);
@@ -370,7 +379,7 @@ static int launch_stats_cat(svihmm_ctx* h, int B, int Lq, int off, int Lm, uint3
     if (ldsc > 64 * 1024)
       hipFuncSetAttribute((const void*)k_stats_cat, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsc);
     hipLaunchKernelGGL(k_stats_cat, dim3((unsigned)nchunkc), dim3(64), ldsc, stream, (const double*)h->obs.p, mk,
-                       (const int64_t*)h->starts.p, n, Lm, K, Kp, V, (const double*)h->q.p, rpcc, Lq, off,
+                       sv, n, Lm, K, Kp, V, qv, rpcc, Lq, off,
                        (double*)h->partc.p);
     HIPCK(hipGetLastError());
   }
@@ -391,6 +400,27 @@ int launch_stats(svihmm_ctx* h, int B, int Lq, int off, int Lm, uint32_t flags) 
   CK(ensure_stats(h, plan.nchunk));
   CK(launch_stats_range(h, 0, B, Lq, off, Lm, flags, plan, 0, h->stream));
   return launch_stats_finalize(h, plan.nchunk, h->stream);
+}
+
+// svihmm_suffstats: statistics of caller-supplied posteriors q [B*Lm, K] of the windows starts_dev [B] (both
+// device buffers of their own) into h->packed, centred coordinates, lb slot 0.  The plain-posterior
+// instantiations only: the caller has the fp32 format off and nothing of the last E-step is read.
+int launch_stats_posteriors(svihmm_ctx* h, const double* q, const int64_t* starts_dev, int B, int Lm,
+                            uint32_t flags) {
+  CK(flush_lb(h, h->stream));       // (a deferred ELBO total lands in the slot overwritten below)
+  if (h->emis_cat) {
+    CK(launch_stats_cat(h, B, Lm, 0, Lm, flags, q, starts_dev));
+  } else {
+    const StatsPlan plan = stats_plan(h, (int64_t)B * Lm, h->variant[8]);
+    // (the pipelined GEMM addresses a chunk's q rows with 32-bit element offsets)
+    if ((int64_t)(Lm + plan.rpc) * h->Kp >= ((int64_t)1 << 31))
+      return fail("svihmm_suffstats: window too long for the statistics GEMM's 32-bit row offsets");
+    CK(ensure_stats(h, plan.nchunk));
+    CK(launch_stats_range(h, 0, B, Lm, 0, Lm, flags, plan, 0, h->stream, q, starts_dev));
+    CK(launch_stats_finalize(h, plan.nchunk, h->stream));
+  }
+  HIPCK(hipMemsetAsync((double*)h->packed.p + packed_len(h) - 1, 0, sizeof(double), h->stream));
+  return 0;
 }
 
 }  // extern "C"

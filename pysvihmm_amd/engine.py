@@ -327,6 +327,28 @@ class HipEngine(object):
                 "svihmm_estep_minibatch")
         return self._wrap_packed(out) if read else None
 
+    def suffstats(self, starts, Lm, var_x, flags=L.TRANS_WRAP, read=True):
+        """Expected sufficient statistics of posteriors the caller supplies (no E-step):
+        ``var_x[b, t]`` is the posterior of observation row ``starts[b] + t``, used as given.
+        ``TRANS_WRAP``: the metaobs transition form (reference hmmsgd_metaobs.py:876-878),
+        without it the batch form (hmmbatchcd.py:182-184).  Returns the view ``estep`` returns
+        (``lb`` = 0), or None with read=False (statistics stay in HBM).  The intermediates of the
+        last E-step are left as they were."""
+        self._pre_mutate()
+        st = self._starts(starts)
+        Lm = int(Lm)
+        if len(st) < 1 or Lm < 1:
+            raise ValueError("suffstats: need at least one window of positive length")
+        q = np.asarray(var_x, dtype=np.float64)
+        if q.shape != (len(st), Lm, self.K):
+            raise ValueError("suffstats: var_x has shape %s, expected %s"
+                             % (q.shape, (len(st), Lm, self.K)))
+        q = np.ascontiguousarray(q)
+        out = np.empty(self._packed_len()) if read else None
+        L.check(self._lib.svihmm_suffstats(self._h, L.i64ptr(st), len(st), Lm, int(flags), L.dptr(q),
+                                           L.dptr(out)), "svihmm_suffstats")
+        return self._wrap_packed(out) if read else None
+
     def _packed_len(self):
         if self.V:
             return PackedCatStats.size(self.K, self.V)

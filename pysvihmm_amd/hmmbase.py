@@ -418,6 +418,29 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         self._q0 = self.engine.read_rows("var_x", 0, 1)[0]
         return st
 
+    def _batch_stats_route(self, literal_global_update, families=("niw", "diag", "cat")):
+        """Whether the host loop of a batch class (a ``local_update`` override, or
+        ``infer(fused=False)``) may take the statistics of ``self.var_x`` on the device instead of
+        the literal ``global_update``: only where that method is the class's own and the engine and
+        the emission family have device statistics."""
+        if "global_update" in self.__dict__ or type(self).global_update is not literal_global_update:
+            return False
+        if not hasattr(self.engine, "suffstats"):
+            return False
+        fam = {"niw": self._niw_fastpath, "diag": self._diag_fastpath, "cat": self._cat_fastpath}
+        return any(fam[f]() for f in families)
+
+    def _batch_suffstats(self):
+        """Statistics of the host posteriors ``self.var_x`` (whatever ``local_update`` left there)
+        over the whole chain on the device, batch transition form (hmmbatchcd.py:182-184): what
+        ``_batch_estep_stats`` returns, for the same ``_global_update_from_stats``."""
+        self._upload_obs()
+        self._push_globals()
+        self._push_emission()
+        q = np.asarray(self.var_x, dtype=np.float64)
+        self._q0 = q[0].copy()
+        return self.engine.suffstats([0], self.T, q[None], flags=0)
+
     def _fetch_local(self):
         """Pull the per-time-step arrays of the last device E-step to the host
         attributes (documented reference attributes)."""

@@ -51,6 +51,7 @@ class VBHMM(VariationalHMMBase):
         if type(self).local_update is not VariationalHMMBase.local_update \
                 or type(self).global_update is not VBHMM.global_update:
             fused = False
+        route = not fused and self._batch_stats_route(VBHMM.global_update)
         # the reference's "self.obs[self.mask,:]" is a no-op (quirk Q9): masked rows
         # still enter lliks, but are excluded from the emission update
         self.obs_full = self.obs.copy()
@@ -69,6 +70,11 @@ class VBHMM(VariationalHMMBase):
             if fused:
                 st = self._batch_estep_stats()
                 self._global_update_from_stats(st)
+            elif route:
+                # a local_update override: its posteriors' statistics on the device, then the same
+                # update the fused path applies
+                self.local_update()
+                self._global_update_from_stats(self._batch_suffstats())
             else:
                 self.local_update()
                 self.global_update()

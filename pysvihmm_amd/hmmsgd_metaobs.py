@@ -320,6 +320,8 @@ class VBHMM(VariationalHMMBase):
                     minibatch, miniL, (bufferL, L_) if growBuffer else None)
             else:
                 lb = 0.
+                route = self._suffstats_route()
+                segs = []
                 A_inter = np.zeros_like(self.var_tran)
                 if type(self.var_emit[0]) is Categorical:
                     # the reference calls util.NIW_zero_nat_pars here for every family
@@ -333,14 +335,25 @@ class VBHMM(VariationalHMMBase):
                     self.cur_mo = data
                     self._stationary_init()
                     self.local_update(metaobs=data)
-                    if growBuffer:
-                        A_i, e_i = self.intermediate_pars_buffer(data, bufferL, L_)
+                    if route:
+                        # the posteriors intermediate_pars(_buffer) would read (reference :857-1008);
+                        # their statistics are taken for the whole minibatch below
+                        if growBuffer:
+                            segs.append((data.i1 + bufferL - L_, data.i2 - bufferL + L_,
+                                         np.array(self.var_x[bufferL - L_:bufferL + L_ + 1, :], dtype=np.float64)))
+                        else:
+                            segs.append((data.i1, data.i2, np.array(self.var_x, dtype=np.float64)))
                     else:
-                        A_i, e_i = self.intermediate_pars(data)
-                    A_inter += A_i
-                    for k in range(K):
-                        emit_inter[k] += e_i[k]
+                        if growBuffer:
+                            A_i, e_i = self.intermediate_pars_buffer(data, bufferL, L_)
+                        else:
+                            A_i, e_i = self.intermediate_pars(data)
+                        A_inter += A_i
+                        for k in range(K):
+                            emit_inter[k] += e_i[k]
                     lb += self.local_lower_bound()
+                if segs:
+                    A_inter, emit_inter = self._segments_inter(segs, A_inter, emit_inter)
 
             self.global_update(A_inter, emit_inter)
             self.iter_time[it] = time.time() - start_time
@@ -588,6 +601,58 @@ class VBHMM(VariationalHMMBase):
                 getattr(self, name)
             self.__dict__.pop("_pending_rows", None)
 
+    def _suffstats_route(self):
+        """Whether the host loop takes the statistics of its windows' posteriors on the device
+        (one ``engine.suffstats`` call per minibatch) instead of ``intermediate_pars`` on the host:
+        only where that method, its buffered form and the arithmetic behind them are this class's,
+        the emission family has device statistics and no communicator shards the minibatch."""
+        for name in ("intermediate_pars", "intermediate_pars_buffer", "_intermediate"):
+            if name in self.__dict__ or getattr(type(self), name) is not getattr(VBHMM, name):
+                return False
+        if self.comm is not None or not hasattr(self.engine, "suffstats"):
+            return False
+        return self._niw_fastpath() or self._diag_fastpath() or self._cat_fastpath()
+
+    def _segments_inter(self, segs, A_inter, emit_inter):
+        """``(A_inter, emit_inter)`` of the windows ``segs = [(loff, uoff, var_x), ...]``: what the
+        serial accumulation of ``_intermediate(var_x, loff, uoff)`` gives (:398-436, quirk Q1 wrap),
+        from one device call.  Posteriors whose shape is not that of their segment (a
+        ``local_update`` override may leave anything behind) go the host way for the whole batch."""
+        K = self.K
+        Lm = segs[0][1] - segs[0][0] + 1
+        if all(u - l + 1 == Lm and q.shape == (Lm, K) for l, u, q in segs):
+            q = np.stack([q for _, _, q in segs])
+            # (what local_update left on the engine, made sure of: all three uploads are idempotent)
+            self._upload_obs()
+            self._push_globals()
+            self._push_emission()
+            st = self.engine.suffstats(np.array([l for l, _, _ in segs], dtype=np.int64), Lm, q,
+                                       flags=L.TRANS_WRAP)
+            return self._stats_to_inter(st, len(segs))
+        for l, u, q in segs:
+            A_i, e_i = self._intermediate(q, l, u)
+            A_inter += A_i
+            for k in range(K):
+                emit_inter[k] += e_i[k]
+        return A_inter, emit_inter
+
+    def _stats_to_inter(self, st, nwin):
+        """Packed device statistics of ``nwin`` windows -> ``(A_inter, emit_inter)`` exactly as the
+        serial accumulation of the reference (:398-436) would hold them."""
+        K, D = self.K, self.D
+        # quirk Q2: prior_tran - 1 is part of every window's A_i
+        A_inter = st.A_raw + nwin * (self.prior_tran - 1.)
+        if hasattr(st, "counts"):
+            # Categorical (reference :907-926): every window contributes alpha_0 + counts - 1
+            emit_inter = [nwin * (G.alphav_0 - 1.) + st.counts[k] for k, G in enumerate(self.var_emit)]
+        elif hasattr(st, "xsq"):
+            # diagonal family: expected sufficient statistics [sum q x, n, sum q x^2, n] per state
+            emit_inter = [np.stack([st.xbar[k], np.full(D, st.neff[k]), st.xsq[k], np.full(D, st.neff[k])])
+                          for k in range(K)]
+        else:
+            emit_inter = _StackedStats(st.xbar.copy(), st.neff.copy(), st.S.copy())
+        return A_inter, emit_inter
+
     def _minibatch_estep(self, minibatch, miniL, buffer=None):
         """All windows of the minibatch in one device E-step; returns
         ``(A_inter, emit_inter, lb)`` exactly as the serial accumulation of the
@@ -622,17 +687,7 @@ class VBHMM(VariationalHMMBase):
         st = self.engine.estep(starts, Lm, flags=flags, read=(comm is None), inner=inner)
         if comm is not None:
             st = comm.allreduce_stats(self.engine, K, D)
-        # quirk Q2: prior_tran - 1 is part of every window's A_i
-        A_inter = st.A_raw + nwin * (self.prior_tran - 1.)
-        if hasattr(st, "counts"):
-            # Categorical (reference :907-926): every window contributes alpha_0 + counts - 1
-            emit_inter = [nwin * (G.alphav_0 - 1.) + st.counts[k] for k, G in enumerate(self.var_emit)]
-        elif hasattr(st, "xsq"):
-            # diagonal family: expected sufficient statistics [sum q x, n, sum q x^2, n] per state
-            emit_inter = [np.stack([st.xbar[k], np.full(D, st.neff[k]), st.xsq[k], np.full(D, st.neff[k])])
-                          for k in range(K)]
-        else:
-            emit_inter = _StackedStats(st.xbar.copy(), st.neff.copy(), st.S.copy())
+        A_inter, emit_inter = self._stats_to_inter(st, nwin)
         lb = float(st.lb[0])
         # leave the object as the reference does after the loop: state of the last window
         self.cur_mo = minibatch[-1]
