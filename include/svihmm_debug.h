@@ -76,6 +76,8 @@ const char* svihmm_last_kernel_name(svihmm_ctx* h, int32_t slot);
  *      below its batch-size floor of 32 768 rows)
  * | 7 = 3: the LDS-broadcast one-wave minibatch sweep k_wave_lin instead of the register-resident k_wave_linr (fp64)
  *      / the four-wave k_wave_lin4 (fp32 mode)
+ * | 17 message layout of the tiled fp64 epoch at K = 64 (1: Eh / ah / bh row-major as on every other path instead of
+ *      step-major inside each 16-window group, csrc/kernels_msg_layout.h -- same results bit for bit)
  * Codes that make results INVALID exist only in a -DSVIHMM_MEASURE build of the library (make measure):
  * | 7 = 9: the scaled sweeps are skipped, the statistics read stale messages (tools/r4_overlap_probe.py);
  *   a product build rejects them with an error. */

@@ -1,6 +1,7 @@
 // device_helpers.h -- wave / row reductions, fp64 exp/log, DPP helpers shared by the kernels.
 // Part of libsvihmm_hip.so; included by every translation unit (host.h lists them).
 #pragma once
+#include "kernels_msg_layout.h"
 
 // ------------------------------------------------------------------------------------
 //  device helpers

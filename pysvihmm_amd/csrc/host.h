@@ -158,6 +158,7 @@ struct svihmm_ctx {
   bool lin_stale = false;          // parameters changed since: logs can no longer be rebuilt
   bool last_host_ll = false;       // the last sweep ran on host-supplied lliks
   bool eh_in_llE = false;          // scaled emission lives in llE (h->ll holds the plain lliks)
+  bool step_major = false;         // Eh / ah / bh of the batch in flight lie in the step-major layout (kernels_msg_layout.h)
   uint32_t last_flags = 0;
   int m_b0 = 0, m_nb = 0;          // window range currently materialised in m_*
   int lastB = 0, lastLm = 0;       // shape of the intermediates currently held
@@ -332,6 +333,8 @@ int launch_diag_to_theta(svihmm_ctx* h, int K, int D);
 int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled = false, const int64_t* starts_dev = nullptr, double* out = nullptr, double* kexp_out = nullptr, hipStream_t stream = nullptr, size_t min_lds = 0, double* ll0_out = nullptr);
 int launch_fb(svihmm_ctx* h, int B, int Lm, int dir0, int ndir, const double* ll = nullptr, double* la = nullptr, double* lb = nullptr);
 int launch_fb_fused(svihmm_ctx* h, int B, int Lm, bool want_lb, bool total);
+bool emission_row_tile_orbit(const svihmm_ctx* h, int64_t n);
+bool step_major_ok(const svihmm_ctx* h, int B, int Lm, uint32_t flags, bool lin);
 int launch_fb_lin(svihmm_ctx* h, int B, int Lm, bool total);
 int launch_fb_lin_range(svihmm_ctx* h, int b0, int nb, int Lm, hipStream_t stream);
 int launch_niw_to_theta(svihmm_ctx* h, int K, int D, double* logdet_out, const SviStepArgs* step = nullptr);

@@ -51,7 +51,8 @@ template <int NT, int MT>
 __device__ __forceinline__ void emission_scaled_epilogue(
     const double (&outv)[MT][NT][4], const unsigned char* bad_s, int wave, int li, int lg,
     int64_t g0, int64_t nrows, int K, int n0, double* __restrict__ ll, double* __restrict__ kexp,
-    int st32, double* __restrict__ ll0, int Lm) {
+    int st32, double* __restrict__ ll0, int Lm, const long long* omap = nullptr) {
+    // omap (LDS, step-major epoch layout -- kernels_msg_layout.h): storage row of each of the workgroup's rows
     // One exp per (row, state) is the algorithmic minimum of transcendental work on the
     // whole E-step; keep it lean: constants pinned in VGPRs, branch-free NaN/inf handling.
     ExpConsts ek;
@@ -79,7 +80,8 @@ __device__ __forceinline__ void emission_scaled_epilogue(
         }
         mx = row16_max(mx);   // all lanes: the DPP reduction stays outside the store guards
         const double kx = (mx > -1e300 && mx < 1e300) ? ceil(mx * l2e) : 0.0;
-        double* orow = ll + g * K + n0 + li;
+        const int64_t go = omap ? (int64_t)omap[rl] : g;
+        double* orow = ll + go * K + n0 + li;
         float* orow32 = reinterpret_cast<float*>(ll) + g * K + n0 + li;   // fp32 mode: Eh stored as float
 #pragma unroll
         for (int n = 0; n < NT; ++n) {
@@ -304,7 +306,8 @@ __global__ __launch_bounds__(256) void k_emission_orbit(
     const int64_t* __restrict__ starts, int64_t nrows, int Lm, int D, int K,
     const double* __restrict__ orb, uint32_t flags, double* __restrict__ ll,
     double* __restrict__ kexp, double* __restrict__ ll0,
-    int64_t* __restrict__ starts_copy = nullptr, int nstarts = 0) {
+    int64_t* __restrict__ starts_copy = nullptr, int nstarts = 0, int smB = 0) {
+  // smB: window count of the batch whose Eh rows leave in the step-major layout (kernels_msg_layout.h), 0 = row-major
   constexpr int ROWS = 64 * MT, KP = 16 * NT;
   // SVI loop (round 5): `starts` is the host's pinned, device-visible slot -- the window starts are read over
   // PCIe here once (a separate k_pull launch in front of this kernel cost 6 us + a 7 us dispatch gap on the
@@ -333,6 +336,7 @@ __global__ __launch_bounds__(256) void k_emission_orbit(
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t g0 = (int64_t)blockIdx.x * ROWS;
   double* xs1 = (double*)xs2;
+  long long omap_r = 0;
   // row r of the tile -> wave r >> 5, row tile (r >> 4) & 1, lane row r & 15
   auto slot = [&](int r, int idx) {
     return MT == 2 ? ((((r >> 5) * 16 + (r & 15)) * LEN + EO_SHIFT((r >> 5) * 16 + (r & 15)) + idx + 1) << 1) + ((r >> 4) & 1)
@@ -346,6 +350,7 @@ __global__ __launch_bounds__(256) void k_emission_orbit(
       const unsigned x = t0 + (unsigned)(valid ? r : 0);
       const unsigned bwr = x / (unsigned)Lm;
       const int64_t orow = starts[bw0 + bwr] + (x - bwr * (unsigned)Lm);
+      omap_r = msg_row(smB, Lm, bw0 + bwr, x - bwr * (unsigned)Lm);     // (ROWS <= 256: one row per thread)
       unsigned char bd = 0;
       if (valid && (flags & SVIHMM_MASK_AS_NAN) && mask) bd = mask[orow] != 0;
       rowoff[r] = valid ? orow * D : -1;
@@ -381,6 +386,8 @@ __global__ __launch_bounds__(256) void k_emission_orbit(
     }
   }
   __syncthreads();
+  // the observation offsets are consumed: their slots carry the rows' storage rows to the epilogue
+  if (smB && tid < ROWS) rowoff[tid] = omap_r;
 
   const int li = lane & 15, lg = lane >> 4;
   double4_t acc[MT][NT];
@@ -467,7 +474,9 @@ __global__ __launch_bounds__(256) void k_emission_orbit(
 #pragma unroll
       for (int r = 0; r < 4; ++r) outv[m][n][r] = acc[m][n][r];
   __builtin_amdgcn_sched_barrier(0);
-  emission_scaled_epilogue<NT, MT>(outv, bad_s, wave, li, lg, g0, nrows, K, 0, ll, kexp, (flags >> 16) & 1, ll0, Lm);
+  if (smB) __syncthreads();     // (uniform) the map rows of the other waves' threads
+  emission_scaled_epilogue<NT, MT>(outv, bad_s, wave, li, lg, g0, nrows, K, 0, ll, kexp, (flags >> 16) & 1, ll0, Lm,
+                                   smB ? rowoff : (const long long*)nullptr);
 }
 
 // ------------------------------------------------------------------------------------

@@ -701,7 +701,10 @@ struct LinLane {
   bool vj;
   unsigned oE[4], oR[4], oRw;   // 32-bit element offsets of (window lg+4r, state j) / row; oRw: window lg+4*wave
   int gwc[4];
-  __device__ __forceinline__ void init(int bfirst, int B, int wstride, int K, bool shared_rows) {
+  size_t tsK;                   // elements between two steps of a window in Eh / ah / bh
+  // smaj: step-major messages (kernels_msg_layout.h) -- the group's windows of one step adjacent (element offset
+  // (w - b0) K + j), its steps nw K apart; the per-row scalars (oR, oRw) keep the row-major order
+  __device__ __forceinline__ void init(int bfirst, int B, int wstride, int K, bool shared_rows, bool smaj = false) {
     lane = threadIdx.x & 63; wave = threadIdx.x >> 6;
     li = lane & 15; lg = lane >> 4;
     j = wave * 16 + li;
@@ -713,8 +716,9 @@ struct LinLane {
       const int gw = b0 + LV<CT>::crow(lg, r);
       gwc[r] = gw < B ? gw : B - 1;
       oR[r] = shared_rows ? 0u : (unsigned)(gwc[r] - b0) * (unsigned)wstride;
-      oE[r] = oR[r] * (unsigned)K + (unsigned)jc;
+      oE[r] = (smaj ? (unsigned)(gwc[r] - b0) : oR[r]) * (unsigned)K + (unsigned)jc;
     }
+    tsK = smaj ? (size_t)msg_group_windows(B, b0) * K : (size_t)K;
     const int gww = b0 + LV<CT>::crow(lg, wave & 3);
     oRw = shared_rows ? 0u : (unsigned)((gww < B ? gww : B - 1) - b0) * (unsigned)wstride;
   }
@@ -743,6 +747,7 @@ struct LinChain {
   double* Mout;             // MODE 2: [chunks][16*NW][K] chunk matrix, MoutT its transpose
   double* MoutT;
   double* Mh;               // MODE 2: [chunks][16*NW] per-row exponents
+  int smaj;                 // MODE 0, four full state tiles: Eh / ah / bh in the step-major layout (kernels_msg_layout.h)
 };
 
 // MODE 0: windows start from the initial distribution.  MODE 1: from chain.init_vec.
@@ -765,7 +770,9 @@ __device__ __forceinline__ void fwd_lin_body(
   typedef typename LV<CT>::v4 cv4;
   LinLane<NW, FULL, CT> L;
   const int chunk = MODE == 2 ? blockIdx.x / NW : 0, rgrp = MODE == 2 ? blockIdx.x % NW : 0;
-  L.init(MODE == 2 ? chunk : blockIdx.x * 16, MODE == 2 ? chunk + 1 : B, wstride, K, MODE == 2);
+  constexpr bool SMOK = NW == 4 && FULL && MODE == 0 && !BS && std::is_same<ST, double>::value;
+  L.init(MODE == 2 ? chunk : blockIdx.x * 16, MODE == 2 ? chunk + 1 : B, wstride, K, MODE == 2, SMOK && ch.smaj);
+  const size_t tsK = SMOK ? L.tsK : (size_t)K;
   const int li = L.li, lg = L.lg, j = L.j, jc = L.jc, wave = L.wave;
   const bool vj = L.vj;
   CT Bv[BS ? 1 : KS];
@@ -805,9 +812,9 @@ __device__ __forceinline__ void fwd_lin_body(
       for (int r = 0; r < 4; ++r) { a0[r] = (vj && j == rgrp * 16 + LV<CT>::crow(lg, r)) ? (CT)1 : (CT)0; h[r] = 0.0; }
     }
 #pragma unroll
-    for (int r = 0; r < 4; ++r) ea[r] = (Eb + (size_t)i1 * K)[L.oE[r]];
+    for (int r = 0; r < 4; ++r) ea[r] = (Eb + (size_t)i1 * tsK)[L.oE[r]];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) eb[r] = (Eb + (size_t)i2 * K)[L.oE[r]];
+    for (int r = 0; r < 4; ++r) eb[r] = (Eb + (size_t)i2 * tsK)[L.oE[r]];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       if (MODE != 2) {
@@ -827,9 +834,9 @@ __device__ __forceinline__ void fwd_lin_body(
     cv4 acc, tot;
     if constexpr (BS) lin_matmul_stream<NW, FULL>(sh, CUR, li, lg, Bcol, K, acc, tot);
     else lin_matmul<NW, CT>(sh, CUR, li, lg, Bv, acc, tot);
-    ST* __restrict__ at = ab + (size_t)t * K;
+    ST* __restrict__ at = ab + (size_t)t * tsK;
     double* __restrict__ ht = hb + t;
-    const ST* __restrict__ E2 = Eb + (size_t)t2 * K;
+    const ST* __restrict__ E2 = Eb + (size_t)t2 * tsK;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int e2 = LV<CT>::fexp(tot[r]);
@@ -931,7 +938,9 @@ __device__ __forceinline__ void bwd_lin_body(
   typedef typename LinCT<MODE, BS, ST>::t CT;
   typedef typename LV<CT>::v4 cv4;
   LinLane<NW, FULL, CT> L;
-  L.init(blockIdx.x * 16, B, wstride, K, false);
+  constexpr bool SMOK = NW == 4 && FULL && MODE == 0 && !BS && std::is_same<ST, double>::value;
+  L.init(blockIdx.x * 16, B, wstride, K, false, SMOK && ch.smaj);
+  const size_t tsK = SMOK ? L.tsK : (size_t)K;
   const int li = L.li, lg = L.lg, j = L.j, jc = L.jc, wave = L.wave;
   const bool vj = L.vj;
   CT Bv[BS ? 1 : KS];
@@ -954,11 +963,11 @@ __device__ __forceinline__ void bwd_lin_body(
   {
     CT e0[4], b0v[4];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) e0[r] = (Eb + (size_t)top * K)[L.oE[r]];
+    for (int r = 0; r < 4; ++r) e0[r] = (Eb + (size_t)top * tsK)[L.oE[r]];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) ea[r] = (Eb + (size_t)i1 * K)[L.oE[r]];
+    for (int r = 0; r < 4; ++r) ea[r] = (Eb + (size_t)i1 * tsK)[L.oE[r]];
 #pragma unroll
-    for (int r = 0; r < 4; ++r) eb[r] = (Eb + (size_t)i2 * K)[L.oE[r]];
+    for (int r = 0; r < 4; ++r) eb[r] = (Eb + (size_t)i2 * tsK)[L.oE[r]];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       if (MODE == 1) {
@@ -968,7 +977,7 @@ __device__ __forceinline__ void bwd_lin_body(
         b0v[r] = (CT)1;
         g[r] = 0.0;
         if (NW % 4 != 0) (gb + top)[L.oR[r]] = 0.0;
-        if (FULL || vj) (bb + (size_t)top * K)[L.oE[r]] = 1.0;
+        if (FULL || vj) (bb + (size_t)top * tsK)[L.oE[r]] = 1.0;
       }
       sh.P[0][LV<CT>::crow(lg, r)][j] = vj ? e0[r] * b0v[r] : (CT)0;
     }
@@ -982,9 +991,9 @@ __device__ __forceinline__ void bwd_lin_body(
     cv4 acc, tot;
     if constexpr (BS) lin_matmul_stream<NW, FULL>(sh, CUR, li, lg, Bcol, K, acc, tot);
     else lin_matmul<NW, CT>(sh, CUR, li, lg, Bv, acc, tot);
-    ST* __restrict__ bt = bb + (size_t)t * K;
+    ST* __restrict__ bt = bb + (size_t)t * tsK;
     double* __restrict__ gt = gb + t;
-    const ST* __restrict__ E2 = Eb + (size_t)t2 * K;
+    const ST* __restrict__ E2 = Eb + (size_t)t2 * tsK;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int e2 = LV<CT>::fexp(tot[r]);
@@ -1906,16 +1915,19 @@ template <int KT, typename ST = double>
 __global__ __launch_bounds__(256) void k_lin_posterior(
     const ST* __restrict__ ah, const ST* __restrict__ bh, const double* __restrict__ hx,
     const double* __restrict__ gx, const double2* __restrict__ zfac, int64_t nrows, int Lm,
-    int K, double* __restrict__ q) {
+    int K, double* __restrict__ q, int smB = 0) {
+  // smB: ah / bh in the step-major layout of a batch of smB windows (kernels_msg_layout.h); q leaves row-major
   const int li = threadIdx.x & 15;
   const int64_t g = (int64_t)blockIdx.x * 16 + (threadIdx.x >> 4);
   if (g >= nrows) return;
-  const double2 zf = zfac[g / Lm];
+  const int64_t w = g / Lm;
+  const double2 zf = zfac[w];
   const double s = ldexp(zf.x, (int)(hx[g] + gx[g] - zf.y));
+  const int64_t m = msg_row(smB, Lm, w, g - w * Lm);
 #pragma unroll
   for (int c = 0; c < KT; ++c) {
     const int k = li + 16 * c;
-    if (k < K) q[g * K + k] = ((double)ah[g * K + k] * (double)bh[g * K + k]) * s;
+    if (k < K) q[g * K + k] = ((double)ah[m * K + k] * (double)bh[m * K + k]) * s;
   }
 }
 

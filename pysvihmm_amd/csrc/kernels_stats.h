@@ -219,7 +219,11 @@ __global__ __launch_bounds__(256 * NSPLIT) void k_stats_mfma4(
     const int* __restrict__ fab, const ST* __restrict__ q, int64_t rows_per_chunk,
     uint32_t flags, int Lq, int off, double* __restrict__ part, int KpTot, int mt_limit,
     const ST* __restrict__ bh, const double* __restrict__ hx, const double* __restrict__ gx,
-    const double2* __restrict__ zfac, double* __restrict__ qout) {
+    const double2* __restrict__ zfac, double* __restrict__ qout, int smB = 0) {
+  // smB (LIN, whole batches only: q / bh start at window 0): window count of the batch whose ah / bh rows lie in the
+  // step-major layout (kernels_msg_layout.h), 0 = row-major.  Only the message rows' offsets change: they are taken
+  // relative to the first row of the 16-window group the chunk starts in (QM), hx / gx stay row-major behind Q0.
+  // Host guarantees (rows_per_chunk / Lm + 18) * Lq * K < 2^31.
   // qout (LIN, wide models): the first feature group's workgroups also write the posteriors
   // q = ah bh scale they form while staging, for the transition-block launch that follows
   static_assert(ST_RB == 32, "row permutation assumes 32-row stages");
@@ -286,11 +290,12 @@ __global__ __launch_bounds__(256 * NSPLIT) void k_stats_mfma4(
   const int64_t bw0 = c0 / Lm;
   const unsigned t0 = (unsigned)(c0 - bw0 * Lm);
   const int64_t Q0 = bw0 * Lq + off;
-  const ST* __restrict__ qthr = q + Q0 * K + kbase + sc;   // per-thread bases
-  const ST* __restrict__ bthr = LIN ? bh + Q0 * K + kbase + sc : nullptr;
+  const int64_t QM = (LIN && smB) ? (bw0 & ~(int64_t)15) * Lq : Q0;     // first message row the offsets count from
+  const ST* __restrict__ qthr = q + QM * K + kbase + sc;   // per-thread bases
+  const ST* __restrict__ bthr = LIN ? bh + QM * K + kbase + sc : nullptr;
   double* __restrict__ qothr = (LIN && qout && blockIdx.y == 0) ? qout + Q0 * K + kbase + sc : nullptr;
-  const ST* __restrict__ pthr = q + Q0 * K + pbase + sc;
-  const ST* __restrict__ bpthr = LIN ? bh + Q0 * K + pbase + sc : nullptr;
+  const ST* __restrict__ pthr = q + QM * K + pbase + sc;
+  const ST* __restrict__ bpthr = LIN ? bh + QM * K + pbase + sc : nullptr;
 
   // ---- row bookkeeping, three stages ahead, in phases; threads 0..31
   unsigned ri_bwr = 0, ri_t = 0;
@@ -317,6 +322,12 @@ __global__ __launch_bounds__(256 * NSPLIT) void k_stats_mfma4(
         ri_hq = hx[Q0 + ri_qr]; ri_gq = gx[Q0 + ri_qr];
         const int pr = ri_pok ? ri_pr : ri_qr;
         ri_hp = hx[Q0 + pr]; ri_gp = gx[Q0 + pr];
+        if (smB) {      // the rows' scalars are addressed: from here on ri_qr / ri_pr are message rows relative to QM
+          const int64_t mr = msg_row(smB, Lq, bw, (int64_t)off + ri_t) - QM;
+          const int nw = msg_group_windows(smB, bw);
+          ri_qr = (int)mr;
+          ri_pr = ri_t > 0 ? (int)mr - nw : (int)mr + (Lm - 1) * nw;
+        }
       }
     }
   };

@@ -905,6 +905,19 @@ int64_t svihmm_packed_size(int32_t K, int32_t D) {
 }
 
 
+// Step-major message layout (kernels_msg_layout.h): exactly the batches whose sweeps are k_sweeps_lin<4, true, 0> on
+// double messages behind the row-tile orbit emission kernel -- the tiled fp64 epoch at K = 64.  Thresholds, from the
+// dispatch: B >= lin_wave_max (4 CUs' worth of windows + 1: below it the wave-per-window / fused kernels run) and at
+// least one 128-row emission workgroup per CU.  Everything else keeps row-major; variant 17 = 1 forces row-major here
+// too (A/B runs, the bit-identity test).  (B + 18) Lm K < 2^31: the statistics GEMM's 32-bit message offsets.
+bool step_major_ok(const svihmm_ctx* h, int B, int Lm, uint32_t flags, bool lin) {
+  if (!lin || h->variant[17] == 1 || h->K != 64 || h->Kp != 64) return false;
+  if ((flags & SVIHMM_USE_HOST_LLIKS) || h->emis_cat || (h->prec == 1 && h->f32_ok)) return false;
+  if (use_chain(h, B, Lm) || B < lin_wave_max(h)) return false;
+  if ((int64_t)(B + 18) * Lm * h->K >= ((int64_t)1 << 31)) return false;
+  return emission_row_tile_orbit(h, (int64_t)B * Lm);
+}
+
 // lin: the batch goes through the scaled linear-domain sweeps (pick_fb == 3)
 int prepare_ll(svihmm_ctx* h, const int64_t* starts, int B, int Lm, uint32_t flags,
                       bool need_obs_for_stats, bool lin) {
@@ -914,6 +927,7 @@ int prepare_ll(svihmm_ctx* h, const int64_t* starts, int B, int Lm, uint32_t fla
   if (starts) CK(upload_starts(h, starts, B));
   h->cur_f32 = false;
   h->eh_float = false;
+  h->step_major = false;
   if (host_ll) {
     if (!h->have_host_ll || h->hostB != B || h->hostLm != Lm)
       return fail("SVIHMM_USE_HOST_LLIKS: no uploaded lliks of shape [B,Lm,K]");
@@ -928,6 +942,8 @@ int prepare_ll(svihmm_ctx* h, const int64_t* starts, int B, int Lm, uint32_t fla
     const bool wide32 = two_pass && lin && h->prec == 1 && h->f32_ok && !use_chain(h, B, Lm) &&
                         f32_wide_ok(h, (int64_t)B * Lm);
     h->cur_f32 = lin && h->prec == 1 && h->f32_ok && (!two_pass || wide32) && !use_chain(h, B, Lm);
+    h->step_major = !two_pass && !h->cur_f32 && step_major_ok(h, B, Lm, flags, lin);
+    h->curB = B;
     CK(launch_emission(h, B, Lm, flags, lin && !two_pass));
     if (h->cur_f32 && !two_pass && h->f32_fused_req) {     // (float Eh is written; from here on the batch is an fp64 one)
       h->eh_float = true;
@@ -1091,7 +1107,7 @@ static int estep_pipelined(svihmm_ctx* h, const int64_t* starts, int B, int Lm, 
   CK(ensure_stats(h, plan[0].nchunk + plan[1].nchunk));
   h->have_host_ll = false;
   h->lin_mode = true; h->lin_stale = false; h->last_host_ll = false; h->eh_in_llE = false; h->last_flags = flags;
-  h->cur_f32 = false;
+  h->cur_f32 = false; h->step_major = false;
   h->q_valid = false; h->curB = B;
   h->m_nb = 0; h->have_lb = true;
   hipStream_t A = h->stream, Bs = h->stream2;

@@ -187,6 +187,13 @@ int launch_emission_deferred(svihmm_ctx* h) {
 }
 
 
+// Does a scaled fp64 emission of n rows into the handle's own buffers take the row-tile orbit kernel
+// (k_emission_orbit: the only producer of the step-major layout)?  The same tests as in launch_emission below.
+bool emission_row_tile_orbit(const svihmm_ctx* h, int64_t n) {
+  const int D = h->D;
+  if (h->emis_cat || h->emis_diag || h->K > 64 || D < 8 || D > 40 || D % 8 != 0 || h->variant[5] == 1) return false;
+  return !((n + 127) / 128 < h->ncu && h->variant[5] != 2 && h->variant[5] != 5);
+}
 // scaled: write (Eh, kexp) for the linear-domain sweeps instead of ll (K <= 64 only).
 // starts_dev / out: window starts and destination (default: the handle's buffers).
 int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
@@ -198,10 +205,15 @@ int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
   if (!h->have_globals || h->eK != h->K) return fail("emission K does not match globals K");
   const int64_t n = (int64_t)B * Lm;
   const int D = h->D, K = h->K, Kp = h->Kp;
+  const bool own_out = !out;
   if (!out) {
     CK(ensure(h->ll, (size_t)n * K * sizeof(double)));
     out = (double*)h->ll.p;
   }
+  // the batch's sweeps will read step-major rows: only the row-tile orbit launch below writes them
+  if (scaled && own_out && h->step_major &&
+      (starts_dev || kexp_out || stream || min_lds || ll0_out || !emission_row_tile_orbit(h, n) || B != h->curB))
+    return fail("internal: step-major messages without their emission kernel");
   // window starts whose pull is still owed (SVI loop, upload_starts): the orbit kernel below takes them from
   // the pinned slot itself and leaves the device copy behind; every other kernel gets the device copy first
   const bool own_starts = starts_dev == nullptr;
@@ -371,13 +383,15 @@ int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
     // fewer than one 128-row workgroup per CU: 64-row workgroups
     const int MTo = ((n + 127) / 128 < h->ncu && h->variant[5] != 2) ? 1 : 2;
     const int rows = 64 * MTo;
+    // step-major Eh rows (prepare_ll: step_major_ok) leave only from here, for the whole batch into the handle's buffer
+    const int smB = (h->step_major && own_out && own_starts) ? B : 0;
     // (+ 1 KB at D = 32 with two row tiles per wave: every second block of eight rows starts eight slots later, EO_SHIFT)
     const size_t lds = (size_t)rows * LEN * 8 + rows * 9 + ((MTo == 2 && D == 32) ? 1024 : 0);
     dim3 grid((unsigned)((n + rows - 1) / rows));
 #define EMO(NTV, UV, MTV) hipLaunchKernelGGL((k_emission_orbit<NTV, UV, MTV>), grid, dim3(256), lds, stream,  \
                                         (const double*)h->obs.p, mk, starts_dev, n, Lm, D, K,               \
                                         (const double*)h->theta_orb.p, flags, out, kexp_out, ll0_out,               \
-                                        pend ? (int64_t*)h->starts.p : (int64_t*)nullptr, pend_n)
+                                        pend ? (int64_t*)h->starts.p : (int64_t*)nullptr, pend_n, smB)
 #define EMOM(NTV, UV) do { if (MTo == 1) EMO(NTV, UV, 1); else EMO(NTV, UV, 2); } while (0)
     if (D % 16 == 0) { if (NT == 4) EMOM(4, 4); else if (NT == 3) EMOM(3, 4); else if (NT == 2) EMOM(2, 4); else EMOM(1, 4); }
     else             { if (NT == 4) EMOM(4, 2); else if (NT == 3) EMOM(3, 2); else if (NT == 2) EMOM(2, 2); else EMOM(1, 2); }

@@ -326,7 +326,11 @@ int launch_fb_lin_range(svihmm_ctx* h, int b0, int nb, int Lm, hipStream_t strea
     return 0;
   }
   CK(launch_lin_init(h, b0, nb, Lm, stream));
-  const LinChain none = {};
+  LinChain none = {};
+  if (h->step_major) {      // (prepare_ll chose it for exactly the launch below: step_major_ok)
+    if (!(NW == 4 && full && b0 == 0 && nb == h->curB)) return fail("internal: step-major messages without their sweep kernel");
+    none.smaj = 1;
+  }
 #define SWPX(NWV, F, BSV)                                                                                  \
   do {                                                                                                     \
     const size_t lds = sizeof(LinShared<NWV>);                                                             \
@@ -382,7 +386,7 @@ int ensure_q(svihmm_ctx* h, int B, int Lm, hipStream_t stream) {
   dim3 grid((unsigned)((n + 15) / 16));
 #define PQ(KT) hipLaunchKernelGGL(k_lin_posterior<KT>, grid, dim3(256), 0, stream, (const double*)h->la.p, \
                                   (const double*)h->lb.p, (const double*)h->hx.p, (const double*)h->gx.p,   \
-                                  (const double2*)h->zfac.p, n, Lm, K, (double*)h->q.p)
+                                  (const double2*)h->zfac.p, n, Lm, K, (double*)h->q.p, h->step_major ? B : 0)
 #define PQF(KT) hipLaunchKernelGGL((k_lin_posterior<KT, float>), grid, dim3(256), 0, stream, (const float*)h->la.p, \
                                    (const float*)h->lb.p, (const double*)h->hx.p, (const double*)h->gx.p,          \
                                    (const double2*)h->zfac.p, n, Lm, K, (double*)h->q.p)

@@ -136,6 +136,11 @@ int launch_stats_range(svihmm_ctx* h, int b0, int nb, int Lq, int off, int Lm, u
   const double* hxv = lin ? (const double*)h->hx.p + (size_t)b0 * Lq : nullptr;
   const double* gxv = lin ? (const double*)h->gx.p + (size_t)b0 * Lq : nullptr;
   const double2* zfv = lin ? (const double2*)h->zfac.p + b0 : nullptr;
+  // step-major messages (kernels_msg_layout.h): read in place by the pipelined fp64 kernel, whole batches only
+  const int smB = (lin && h->step_major) ? h->curB : 0;
+  if (smB && (b0 != 0 || nb != h->curB || h->cur_f32 || Kp != 64 ||
+              ((int64_t)(rpc / Lm + 18) * Lq) * K >= ((int64_t)1 << 31)))
+    return fail("internal: step-major messages without their statistics kernel");
   double* partv = (double*)h->part.p + (size_t)chunk_base * Ftot * Kp;
   {
     ProfScope ps(h, KS_STATS, stream);
@@ -227,7 +232,7 @@ int launch_stats_range(svihmm_ctx* h, int b0, int nb, int Lq, int off, int Lm, u
                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);                                \
     hipLaunchKernelGGL((k_stats_mfma4<5, 2, 2, XKV, LN, false, double, double, 3>), grid, dim3(512), lds3,     \
                        stream, (const double*)h->obs.p, mk, starts_dev, n, Lm, D, K, Fp, F,                    \
-                       (const int*)h->fab.p, qv, rpc, flags, Lq, off, partv, Kp, mt_limit, bhv, hxv, gxv, zfv, qoutv); \
+                       (const int*)h->fab.p, qv, rpc, flags, Lq, off, partv, Kp, mt_limit, bhv, hxv, gxv, zfv, qoutv, smB); \
   } while (0)
 #define ST3T(XKV) do { if (lin) ST3TL(XKV, true); else ST3TL(XKV, false); } while (0)
           if (xk <= 1) ST3T(1); else if (xk <= 3) ST3T(3); else if (xk <= 5) ST3T(5); else ST3T(9);
@@ -243,7 +248,7 @@ int launch_stats_range(svihmm_ctx* h, int b0, int nb, int Lq, int off, int Lm, u
     hipLaunchKernelGGL((k_stats_mfma4<MTV, NTW, NS, XKV, LN>), grid, dim3(256 * NS), lds, stream, \
                        (const double*)h->obs.p, mk, starts_dev, n, Lm, D, K, Fp,                  \
                        F, (const int*)h->fab.p, qv, rpc, flags, Lq, off,                          \
-                       partv, Kp, mt_limit, bhv, hxv, gxv, zfv, qoutv);                           \
+                       partv, Kp, mt_limit, bhv, hxv, gxv, zfv, qoutv, smB);                      \
   } while (0)
 #define ST3(MTV, NTW, NS, XKV) do { if (lin) ST3L(MTV, NTW, NS, XKV, true); else ST3L(MTV, NTW, NS, XKV, false); } while (0)
 #define ST3X(NTW, NS) do { if (xk <= 1) ST3(5, NTW, NS, 1); else if (xk <= 3) ST3(5, NTW, NS, 3); else if (xk <= 5) ST3(5, NTW, NS, 5); else ST3(5, NTW, NS, 9); } while (0)
