@@ -35,7 +35,8 @@
 extern "C" {
 #endif
 
-/* 3: svihmm_export_packed / svihmm_import_packed, svihmm_svi_set_adagrad / _read_adagrad,
+/* 3 (addition, nothing else changed meaning): svihmm_viterbi.
+ * 3: svihmm_export_packed / svihmm_import_packed, svihmm_svi_set_adagrad / _read_adagrad,
  *    svihmm_svi_begin_diag / _begin_cat / _read_factors added, slot mask
  *    of svihmm_profile_enable (round 4; nothing else changed meaning).
  * 2: svihmm_get_shift added, svihmm_shift_obs no longer changes what later calls mean (the shift is
@@ -368,6 +369,38 @@ int svihmm_pred_logprob(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t
  * [0, K) are skipped).  out_z (host int32[n]) and out_conf (host int64[K*K]) are optional. */
 int svihmm_state_argmax(svihmm_ctx* h, const int32_t* true_sts, int32_t* out_z,
                         int64_t* out_conf);
+
+/* Viterbi / MAP state paths: the most probable state SEQUENCE of every window (svihmm_state_argmax
+ * decodes the marginals row by row -- right for the Hamming metric, hmmbase.py:346-355, but its rows can
+ * be joined by transitions of (near-)zero probability).  For each window b of Lm rows starting at
+ * starts[b], with the globals currently set (mod_init, ltran) and the current emission family:
+ *     delta[0][j] = mod_init[j] + ll[0][j]
+ *     delta[t][j] = max_i (delta[t-1][i] + ltran[i][j]) + ll[t][j]       psi[t][j] = the first maximising i
+ *     z[Lm-1] = first argmax_j delta[Lm-1][j];  z[t-1] = psi[t][z[t]];   score[b] = max_j delta[Lm-1][j]
+ * ll is exactly what svihmm_loglik returns for the windows with the same flags: NIW, diagonal and
+ * Categorical families, svihmm_set_lliks data with SVIHMM_USE_HOST_LLIKS (starts is then not used and may
+ * be NULL), SVIHMM_MASK_AS_NAN gives masked rows ll = 0.
+ * Operation order (part of the contract): ONE add per (i, j); a max over i in ascending order in which only
+ * a strictly larger value replaces the incumbent, so the lowest index wins ties like np.argmax and an
+ * all -inf column decodes to predecessor 0; then ONE add of ll[t][j].  There is no multiplication, hence no
+ * fused multiply-add: given identical ll, delta, score and the path are bit-identical to the same three
+ * steps in NumPy ((delta[:, None] + ltran) -> argmax / max over axis 0 -> + ll[t]).
+ * The recursion lives in the log domain and has none of the dynamic-range limits of the scaled sweeps:
+ * ltran entries below SVIHMM_LTRAN_LINEAR_MIN, or -inf, take the same kernels.  Always fp64 (the precision
+ * mode and what svihmm_get_precision reports are unchanged).  K <= 256 (one-byte back-pointers).
+ * out_z: host int32[B*Lm], window-major like svihmm_state_argmax; out_score: host double[B]; either may be
+ * NULL (not both).  Windows whose back-pointers fit in LDS are decoded in one launch; longer ones -- the
+ * whole chain B = 1, Lm = T included -- keep psi in HBM and backtrack without a sequential pass, by
+ * composing per-chunk state maps as svihmm_ffbs does.  The forward pass over one window is sequential.
+ * Fails with a message, before any device work, without globals, without an emission family or
+ * observations (unless host lliks), on a K mismatch between globals and emission family, B < 1 or
+ * Lm < 1, a window outside [0, T), K > 256, or host lliks of another shape.
+ * Intermediates: like svihmm_loglik the call writes the handle's lliks buffer -- afterwards the lliks of
+ * THESE windows are readable (svihmm_read_intermediate / _read_rows, what = 0) and lalpha / lbeta / var_x of
+ * an earlier E-step are not; the packed statistics held in HBM (svihmm_read_packed / _allreduce_packed /
+ * _export_packed) are not touched. */
+int svihmm_viterbi(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t Lm, uint32_t flags,
+                   int32_t* out_z, double* out_score);
 
 /* Readback of the intermediates of the last estep/forward_backward call
  * (what 0: lliks, 1: lalpha, 2: lbeta, 3: var_x; each [B,Lm,K]).

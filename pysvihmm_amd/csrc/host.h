@@ -149,6 +149,7 @@ struct svihmm_ctx {
   // work
   Buf starts, ll, la, lb, q, lse_part, local_lb, logz, part, packed, scratch;
   Buf user_q, user_starts;         // svihmm_suffstats: the caller's posteriors and windows (never the E-step's q / starts)
+  Buf vit;                         // svihmm_viterbi: score | z | final argmax | psi | path | chunk maps (launch_viterbi)
   // scaled linear-domain sweeps: per-row binary exponents, (na, k) records, 1/Z factors,
   // Eh of host-supplied lliks; log-domain intermediates materialised on demand (m_*)
   Buf kexp, hx, gx, zfac, llE, m_ll, m_la, m_lb, chain, chain2;
@@ -361,6 +362,7 @@ int ensure_starts_pulled(svihmm_ctx* h);
 int cat_uncentre(svihmm_ctx* h);
 int launch_fb_chain(svihmm_ctx* h, int Lm, bool total);
 int launch_emission_deferred(svihmm_ctx* h);
+int launch_viterbi(svihmm_ctx* h, int B, int Lm, const double* ll, bool want_z, int32_t** dz_out, double** dscore_out);
 bool sweep_emission_ok(const svihmm_ctx* h, int B, int Lq, int off, int Lm, uint32_t flags);
 bool sweep_mixed_ok(const svihmm_ctx* h, int B, int Lq, int off, int Lm, uint32_t flags);
 bool sweep_stats_ok(const svihmm_ctx* h, int B, int Lq, int off, int Lm, uint32_t flags);

@@ -76,7 +76,7 @@ int svihmm_destroy(svihmm_ctx* h) {
   for (auto& p : h->pending) { hipEventDestroy(p.e0); hipEventDestroy(p.e1); }
   for (auto e : h->pool) hipEventDestroy(e);
   Buf* bufs[] = {&h->obs, &h->mask, &h->mod_init, &h->ltran, &h->Aexp, &h->AexpT, &h->theta, &h->niw,
-                 &h->fab, &h->starts, &h->user_q, &h->user_starts, &h->ll, &h->la, &h->lb, &h->q, &h->lse_part,
+                 &h->fab, &h->starts, &h->user_q, &h->user_starts, &h->vit, &h->ll, &h->la, &h->lb, &h->q, &h->lse_part,
                  &h->local_lb, &h->logz, &h->part, &h->packed, &h->scratch, &h->kexp, &h->hx, &h->gx,
                  &h->zfac, &h->llE, &h->m_ll, &h->m_la, &h->m_lb, &h->chain, &h->chain2, &h->cat_table, &h->partc, &h->theta_orb, &h->prior, &h->vlb_aux, &h->gen_z,
                  &h->svi_state, &h->svi_prior, &h->svi_work, &h->commtmp, &h->ll0, &h->a0v, &h->a0e,
@@ -2206,6 +2206,49 @@ int svihmm_state_argmax(svihmm_ctx* h, const int32_t* true_sts, int32_t* out_z,
   if (out_z) CK(d2h(h, out_z, dz, (size_t)n * sizeof(int32_t)));
   if (out_conf) CK(d2h(h, out_conf, dconf, cb));
   HIPCK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+
+// ---- Viterbi / MAP state paths (kernels_viterbi.h) -------------------------------------------
+// Everything that can be wrong with the call is found here, before any device work; the lliks are then
+// produced exactly as svihmm_loglik produces them (prepare_ll) and decoded by launch_viterbi.
+int svihmm_viterbi(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t Lm, uint32_t flags,
+                   int32_t* out_z, double* out_score) {
+  if (!h) return fail("svihmm_viterbi: NULL handle");
+  if (!out_z && !out_score) return fail("svihmm_viterbi: neither out_z nor out_score given");
+  if (!h->have_globals) return fail("svihmm_viterbi: no globals: call svihmm_set_globals first");
+  if (h->K > 256)
+    return fail("svihmm_viterbi: K = " + std::to_string(h->K) + " > 256 not supported (one-byte back-pointers)");
+  if (B < 1 || Lm < 1) return fail("svihmm_viterbi: B and Lm must be positive");
+  const bool host_ll = (flags & SVIHMM_USE_HOST_LLIKS) != 0;
+  if (host_ll) {
+    if (!h->have_host_ll || h->hostB != B || h->hostLm != Lm)
+      return fail("svihmm_viterbi: SVIHMM_USE_HOST_LLIKS without uploaded lliks of shape [B, Lm, K] (svihmm_set_lliks)");
+  } else {
+    if (h->T <= 0 || !h->obs.p) return fail("svihmm_viterbi: no observations: call svihmm_set_obs first");
+    if (!h->have_emission)
+      return fail("svihmm_viterbi: no emission family: call svihmm_set_emission_niw / _diag / _cat first");
+    if (h->K != h->eK)
+      return fail("svihmm_viterbi: K of the globals (" + std::to_string(h->K) + ") differs from the emission "
+                  "family's K (" + std::to_string(h->eK) + ")");
+    if (h->eD != h->D) return fail("svihmm_viterbi: emission D does not match obs D");
+    if (!starts) return fail("svihmm_viterbi: starts is NULL");
+    for (int b = 0; b < B; ++b)
+      if (starts[b] < 0 || starts[b] + Lm > h->T)
+        return fail("svihmm_viterbi: window " + std::to_string(b) + " reaches outside [0, T)");
+  }
+  CK(set_device(h));
+  CK(wait_side_streams(h));
+  CK(prepare_ll(h, starts, B, Lm, flags & (SVIHMM_MASK_AS_NAN | SVIHMM_USE_HOST_LLIKS), false));
+  h->lastB = B; h->lastLm = Lm;
+  int32_t* dz = nullptr;
+  double* dscore = nullptr;
+  CK(launch_viterbi(h, B, Lm, (const double*)h->ll.p, out_z != nullptr, &dz, &dscore));
+  if (out_z) CK(d2h(h, out_z, dz, (size_t)B * Lm * sizeof(int32_t)));
+  if (out_score) CK(d2h(h, out_score, dscore, (size_t)B * sizeof(double)));
+  HIPCK(hipStreamSynchronize(h->stream));
+  CK(check_emission_status(h));
   return 0;
 }
 

@@ -3,6 +3,7 @@
 #include "host.h"
 #include "device_helpers.h"
 #include "kernels_recursion.h"
+#include "kernels_viterbi.h"
 
 extern "C" {
 
@@ -768,6 +769,75 @@ int svihmm_ffbs_sample(svihmm_ctx* h, int64_t T, int32_t K, const double* lalpha
   CK(ffbs_draw(h, (const double*)h->m_la.p, T, K, logA, uniforms, &dz));
   CK(d2h(h, out_z, dz, (size_t)T * sizeof(int64_t)));
   HIPCK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// svihmm_viterbi: max-plus forward sweep + backtrack over the lliks ll [B*Lm, K] with the globals currently set.
+// Windows whose psi fits the LDS budget (kernels_viterbi.h: Lm <= vit_lds_rows(KS)) are decoded in one launch;
+// longer ones write psi to HBM and backtrack by composing chunk maps (k_vit_paths, k_ffbs_compose, k_vit_gather).
+// *dz_out (int32 [B*Lm], only when want_z) and *dscore_out (double [B]) live in h->vit until the next call.
+int launch_viterbi(svihmm_ctx* h, int B, int Lm, const double* ll, bool want_z, int32_t** dz_out,
+                   double** dscore_out) {
+  const int K = h->K;
+  if (K > 256) return fail("svihmm_viterbi: K > 256 not supported (one-byte back-pointers)");
+  const int KS = K <= 64 ? 64 : 256;
+  const int Ls = vit_lds_rows(KS);
+  const bool in_lds = Lm <= Ls;
+  const int Cw = (Lm + Ls - 1) / Ls;
+  const int64_t Lpad = (int64_t)Cw * Ls;
+  const int64_t C = (int64_t)B * Cw;
+  if (!in_lds && C * KS >= ((int64_t)1 << 31)) return fail("svihmm_viterbi: too many row chunks for the map composition");
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t n = (size_t)B * Lm;
+  const size_t o_score = 0, o_z = up((size_t)B * sizeof(double)), o_zlast = o_z + up(n * sizeof(int32_t));
+  const size_t o_psi = o_zlast + up((size_t)B * sizeof(int32_t));
+  const size_t nps = in_lds ? 0 : up((size_t)B * Lpad * KS);
+  const size_t o_path = o_psi + nps, o_mA = o_path + nps;
+  const size_t nmap = in_lds ? 0 : up((size_t)C * KS);
+  const size_t o_mB = o_mA + nmap, o_entry = o_mB + nmap;
+  CK(ensure(h->vit, o_entry + (in_lds ? 0 : up((size_t)C)) + 256));
+  char* base = (char*)h->vit.p;
+  double* dscore = (double*)(base + o_score);
+  int32_t* dz = (int32_t*)(base + o_z);
+  int32_t* zlast = (int32_t*)(base + o_zlast);
+  unsigned char* psi = (unsigned char*)(base + o_psi);
+  unsigned char* path = (unsigned char*)(base + o_path);
+  unsigned char* mA = (unsigned char*)(base + o_mA);
+  unsigned char* mB = (unsigned char*)(base + o_mB);
+  unsigned char* entry = (unsigned char*)(base + o_entry);
+  *dz_out = want_z ? dz : nullptr;
+  *dscore_out = dscore;
+  const double* lt = (const double*)h->ltran.p;
+  const double* mi = (const double*)h->mod_init.p;
+  ProfScope ps(h, KS_MISC);
+  const size_t lds = (size_t)2 * KS * 8 + (in_lds && want_z ? (size_t)Lm * KS : 0);
+#define VITW(KM)                                                                                                  \
+  do {                                                                                                            \
+    if (in_lds)                                                                                                   \
+      hipLaunchKernelGGL((k_vit_wave<KM, true>), dim3(B), dim3(64), lds, h->stream, ll, lt, mi, Lm, K, Lpad,      \
+                         (unsigned char*)nullptr, want_z ? dz : (int32_t*)nullptr, (int32_t*)nullptr, dscore);    \
+    else                                                                                                          \
+      hipLaunchKernelGGL((k_vit_wave<KM, false>), dim3(B), dim3(64), lds, h->stream, ll, lt, mi, Lm, K, Lpad,     \
+                         psi, (int32_t*)nullptr, zlast, dscore);                                                  \
+  } while (0)
+  if (K <= 16) VITW(16); else if (K <= 32) VITW(32); else if (K <= 64) VITW(64);
+  else if (in_lds)
+    hipLaunchKernelGGL(k_vit_wide<true>, dim3(B), dim3(256), lds, h->stream, ll, lt, mi, Lm, K, Lpad,
+                       (unsigned char*)nullptr, want_z ? dz : (int32_t*)nullptr, (int32_t*)nullptr, dscore);
+  else
+    hipLaunchKernelGGL(k_vit_wide<false>, dim3(B), dim3(256), lds, h->stream, ll, lt, mi, Lm, K, Lpad, psi,
+                       (int32_t*)nullptr, zlast, dscore);
+#undef VITW
+  HIPCK(hipGetLastError());
+  if (!in_lds && want_z) {
+    hipLaunchKernelGGL(k_vit_paths, dim3((unsigned)C), dim3(KS), (size_t)Ls * KS, h->stream, (const unsigned char*)psi,
+                       (const int32_t*)zlast, Lm, Ls, Cw, Lpad, KS, K, path);
+    hipLaunchKernelGGL(k_ffbs_compose, dim3(1), dim3(1024), 0, h->stream, (const unsigned char*)path, (int64_t)B * Lpad,
+                       KS, Ls, (int)C, mA, mB, entry);
+    hipLaunchKernelGGL(k_vit_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
+                       (const unsigned char*)path, (const unsigned char*)entry, Lm, Ls, Cw, Lpad, KS, (int64_t)n, dz);
+    HIPCK(hipGetLastError());
+  }
   return 0;
 }
 

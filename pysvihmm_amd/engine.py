@@ -399,6 +399,24 @@ class HipEngine(object):
         L.check(self._lib.svihmm_state_argmax(self._h, vp(ts), vp(z), vp(conf)), "svihmm_state_argmax")
         return z, conf
 
+    def viterbi(self, starts, Lm, flags=0, want_z=True):
+        """Viterbi / MAP state path of every window under the globals and the emission family
+        currently set (``svihmm_viterbi``): ``(z int32[B, Lm], score float64[B])`` with
+        ``score[b] = max_z log p(z, x_window)`` in the expectations' log domain.  The lliks are those
+        ``loglik(starts, Lm, flags)`` returns; with ``USE_HOST_LLIKS`` the batch uploaded by
+        ``set_lliks`` is decoded (``starts`` then only gives the number of windows).  Given the same
+        lliks the result is bit-identical to the NumPy recursion stated in ``include/svihmm.h``.
+        ``want_z=False`` skips the backtrack and returns ``(None, score)``."""
+        self._pre_mutate()
+        st = self._starts(starts)
+        Lm = int(Lm)
+        z = np.empty((len(st), max(Lm, 0)), dtype=np.int32) if want_z else None
+        score = np.empty(len(st))
+        L.check(self._lib.svihmm_viterbi(self._h, L.i64ptr(st), len(st), Lm, int(flags),
+                                         None if z is None else z.ctypes.data_as(C.c_void_p),
+                                         L.dptr(score)), "svihmm_viterbi")
+        return z, score
+
     def read_packed(self):
         out = np.empty(self._packed_len())
         L.check(self._lib.svihmm_read_packed(self._h, L.dptr(out)), "svihmm_read_packed")

@@ -477,6 +477,26 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         flags = self._push_emission()
         self.engine.forward_backward([0], self.T, flags=flags, want=())
 
+    # -- Viterbi / MAP path -------------------------------------------------------------
+    def viterbi(self, metaobs=None):
+        """Most probable state sequence of the whole chain (or of one meta-observation
+        ``metaobs``: rows ``i1 .. i2``) under the current variational parameters, decoded on the
+        device: ``(z int32[Lm], score)``.  Same psi-expectations and missing-data convention as
+        ``full_local_update`` (masked rows contribute ``lliks = 0``); emission plugins without a
+        device family are evaluated on the host and uploaded (``set_lliks``).  No attribute of the
+        model changes.  ``argmax(var_x, axis=1)`` remains the decode of ``hamming_dist``; for the
+        same metric on the MAP path: ``util.munkres_match(true_sts, z, K)``."""
+        loff, uoff = (0, self.T - 1) if metaobs is None else (metaobs.i1, metaobs.i2)
+        Lm = uoff - loff + 1
+        mod_init = digamma(self.var_init + eps) - digamma(np.sum(self.var_init) + eps)
+        tran_sum = np.sum(self.var_tran, axis=1)
+        mod_tran = digamma(self.var_tran + eps) - digamma(tran_sum[:, npa] + eps)
+        self._upload_obs()
+        self.engine.set_globals(mod_init, mod_tran)
+        flags = self._push_emission(windows=[loff], Lm=Lm, nan_mask=True)
+        z, score = self.engine.viterbi([loff], Lm, flags=flags)
+        return z[0], float(score[0])
+
     # -- FFBS (reference hmm_fast.pyx:43-124, bound at hmmbase.py:409-411) ---------------
     def ffbs_fast(self, var_init, lalpha_init=None, uniforms=None):
         """Forward-filter backward-sample.  Returns ``(z int64[T], lalpha[T,K])``.
