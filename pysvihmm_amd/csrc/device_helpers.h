@@ -256,6 +256,7 @@ __device__ __forceinline__ void svi_arrive(const SviSync& sy) {
 __device__ __forceinline__ void svi_tran_step(int e, int K, const double* __restrict__ packed,
                                               const double* __restrict__ prior_tran, double* __restrict__ var_tran,
                                               double rho, double bA, double nwin, double* __restrict__ ada_G) {
+#pragma clang fp contract(off)     // (see svi_niw_* below: the same roundings in whichever kernel this is inlined into)
   if (e >= K * K) return;
   const double a_inter = packed[e] + nwin * (prior_tran[e] - 1.0);
   const double nat_old = var_tran[e] - 1.0;
@@ -269,4 +270,36 @@ __device__ __forceinline__ void svi_tran_step(int e, int K, const double* __rest
   } else {
     var_tran[e] = ((1.0 - rho) * nat_old + rho * (bA * a_inter)) + 1.0;
   }
+}
+
+// The NIW factor's natural-parameter blend (hmmsgd_metaobs.py:1048-1069, util.py:28-60), one scalar at a time, for the
+// two kernels that run it: k_svi_global_step (kernels_svi.h) and the merged step + theta builder k_svi_step_theta32s
+// (kernels_emission.h).  Contraction is off inside: left to itself the compiler fuses the multiply-adds of these
+// expressions differently in the two kernels (fma(bE, x, ka0 p) in one, fma(ka0, p, bE x) in the other), and the same
+// loop then took a different rounding path through D = 17 .. 32 than through every other D -- mu' of 12 % of the
+// entries one ulp apart at K = 64, D = 32, rho = 1 (tests/test_gpu_svi_globals.py).  Every product and sum below is
+// rounded on its own, which is also what the reference's NumPy does.
+__device__ __forceinline__ double svi_niw_kappa(double rho, double bE, double ka, double ka0, double neff) {
+#pragma clang fp contract(off)
+  return (1.0 - rho) * ka + rho * (ka0 + bE * neff);                                    // kappa' = e2
+}
+__device__ __forceinline__ double svi_niw_nu(double rho, double bE, double nuo, double nu0, double neff, int D) {
+#pragma clang fp contract(off)
+  const double e4 = (1.0 - rho) * (nuo + 2 + D) + rho * ((nu0 + 2 + D) + bE * neff);
+  return e4 - 2 - D;
+}
+__device__ __forceinline__ double svi_niw_mu(double rho, double bE, double ka, double ka0, double e2, double m,
+                                             double p, double xbar) {
+#pragma clang fp contract(off)
+  return ((1.0 - rho) * (ka * m) + rho * (ka0 * p + bE * xbar)) / e2;                   // mu' = e1 / e2
+}
+// sigma'_ab from the old / prior / new means' components a and b
+__device__ __forceinline__ double svi_niw_sigma(double rho, double bE, double ka, double ka0, double e2, double sg,
+                                                double sg0, double S, double moa, double mob, double m0a, double m0b,
+                                                double mna, double mnb) {
+#pragma clang fp contract(off)
+  const double e3o = sg + (moa * mob) * ka;
+  const double e3p = sg0 + (m0a * m0b) * ka0;
+  const double e3 = (1.0 - rho) * e3o + rho * (e3p + bE * S);
+  return e3 - (mna * mnb) * e2;
 }

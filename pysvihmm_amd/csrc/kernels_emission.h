@@ -1678,12 +1678,13 @@ __global__ __launch_bounds__(64) void k_svi_step_theta32s(
     const double ka = kap[k], nuo = nu[k];
     const int ac = a < D ? a : 0;
     const double m_ld = mu[ac], p_ld = mu0[ac], x_ld = xbar[ac];
-    const double e2 = (1.0 - rho) * ka + rho * (ka0 + bE * neff);                        // kappa'
-    const double e4 = (1.0 - rho) * (nuo + 2 + D) + rho * ((nu0 + 2 + D) + bE * neff);
+    // (the blend's expressions: svi_niw_* in device_helpers.h, shared with k_svi_global_step -- the two kernels round alike)
+    const double e2 = svi_niw_kappa(rho, bE, ka, ka0, neff);                             // kappa'
+    const double nun = svi_niw_nu(rho, bE, nuo, nu0, neff, D);
     if (a < D) {
       const double m = m_ld, p = p_ld;
       mo[a] = m; m0[a] = p;
-      mn[a] = ((1.0 - rho) * (ka * m) + rho * (ka0 * p + bE * x_ld)) / e2;               // mu' = e1 / e2
+      mn[a] = svi_niw_mu(rho, bE, ka, ka0, e2, m, p, x_ld);                              // mu' = e1 / e2
     }
     __syncthreads();
     {
@@ -1699,15 +1700,13 @@ __global__ __launch_bounds__(64) void k_svi_step_theta32s(
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
         const int b = 2 * i + hh, bc = b < D ? b : 0;
-        const double e3o = vs[i] + (mo[rr] * mo[bc]) * ka;
-        const double e3p = v0[i] + (m0[rr] * m0[bc]) * ka0;
-        const double e3 = (1.0 - rho) * e3o + rho * (e3p + bE * vS[i]);
-        if (r_ < D && b < D) sg[rr * D + b] = e3 - (mn[rr] * mn[bc]) * e2;                  // sigma'
+        const double sn = svi_niw_sigma(rho, bE, ka, ka0, e2, vs[i], v0[i], vS[i], mo[rr], mo[bc], m0[rr], m0[bc], mn[rr], mn[bc]);
+        if (r_ < D && b < D) sg[rr * D + b] = sn;                                           // sigma'
       }
     }
     __syncthreads();
     if (a < D) mu[a] = mn[a];
-    if (a == 0) { kap[k] = e2; nu[k] = e4 - 2 - D; }
+    if (a == 0) { kap[k] = e2; nu[k] = nun; }
   }
   // (only the transition workgroups arrive on the step counter: what waits on it -- the side stream's globals kernel, 60 us
   //  that must be over before the next sweeps -- needs var_tran alone and should not wait for the K factor updates)

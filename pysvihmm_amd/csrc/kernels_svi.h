@@ -289,23 +289,21 @@ __device__ __forceinline__ void k_svi_global_step_body(
   const double neff = packed[(size_t)K * K + nmu + k];
   const double* S = packed + (size_t)K * K + nmu + K + (size_t)k * D * D;
   const double ka = kap[k], nuo = nu[k];
-  const double e2 = (1.0 - rho) * ka + rho * (ka0 + bE * neff);                        // kappa'
-  const double e4 = (1.0 - rho) * (nuo + 2 + D) + rho * ((nu0 + 2 + D) + bE * neff);
+  // (the blend's expressions: svi_niw_* in device_helpers.h, shared with k_svi_step_theta32s)
+  const double e2 = svi_niw_kappa(rho, bE, ka, ka0, neff);                             // kappa'
+  const double nun = svi_niw_nu(rho, bE, nuo, nu0, neff, D);
   for (int a = tid; a < D; a += 256) {
     const double m = mu[a], p = mu0[a];
     mo[a] = m; m0[a] = p;
-    mn[a] = ((1.0 - rho) * (ka * m) + rho * (ka0 * p + bE * xbar[a])) / e2;            // mu' = e1 / e2
+    mn[a] = svi_niw_mu(rho, bE, ka, ka0, e2, m, p, xbar[a]);                           // mu' = e1 / e2
   }
   __syncthreads();
   for (int e = tid; e < D * D; e += 256) {
     const int a = e / D, b = e - a * D;
-    const double e3o = sg[e] + (mo[a] * mo[b]) * ka;
-    const double e3p = sg0[e] + (m0[a] * m0[b]) * ka0;
-    const double e3 = (1.0 - rho) * e3o + rho * (e3p + bE * S[e]);
-    sg[e] = e3 - (mn[a] * mn[b]) * e2;                                                 // sigma'
+    sg[e] = svi_niw_sigma(rho, bE, ka, ka0, e2, sg[e], sg0[e], S[e], mo[a], mo[b], m0[a], m0[b], mn[a], mn[b]);   // sigma'
   }
   for (int a = tid; a < D; a += 256) mu[a] = mn[a];
-  if (tid == 0) { kap[k] = e2; nu[k] = e4 - 2 - D; }
+  if (tid == 0) { kap[k] = e2; nu[k] = nun; }
 }
 __global__ __launch_bounds__(256) void k_svi_global_step(
     const double* __restrict__ packed, const double* __restrict__ prior_tran, double* __restrict__ var_tran,

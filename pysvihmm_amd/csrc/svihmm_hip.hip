@@ -1704,7 +1704,9 @@ static int svi_begin_finish(svihmm_ctx* h) {
   HIPCK(hipStreamSynchronize(h->stream));          // (the rings below are keyed to this loop's events)
   for (auto& ss : h->svi_starts) ss.used_it = -1;
   CK(svi_refresh_emission(h, -1, 0));   // theta / table of the initial factors (their vlb is not used)
-  h->svi_vi_cur = 1;
+  // (the slot svihmm_svi_read_state / _read_factors hand out: before the first iteration it is the one the
+  //  globals below write -- it used to be 1, and a read right after begin returned the never-written second slot)
+  h->svi_vi_cur = 0;
   CK(svi_globals(h, 0, 0));          // globals of iteration 0
   h->svi_active = true;
   return 0;
