@@ -35,7 +35,8 @@
 extern "C" {
 #endif
 
-/* 3 (addition, nothing else changed meaning): svihmm_viterbi.
+/* 3 (addition, nothing else changed meaning): svihmm_ffbs_windows.
+ * 3 (addition, nothing else changed meaning): svihmm_viterbi.
  * 3: svihmm_export_packed / svihmm_import_packed, svihmm_svi_set_adagrad / _read_adagrad,
  *    svihmm_svi_begin_diag / _begin_cat / _read_factors added, slot mask
  *    of svihmm_profile_enable (round 4; nothing else changed meaning).
@@ -401,6 +402,45 @@ int svihmm_state_argmax(svihmm_ctx* h, const int32_t* true_sts, int32_t* out_z,
  * _export_packed) are not touched. */
 int svihmm_viterbi(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t Lm, uint32_t flags,
                    int32_t* out_z, double* out_score);
+
+/* Forward-filter backward-sample for window batches, many draws from ONE forward filter (hmm_fast.pyx:43-124;
+ * its lalpha_init branch, :80-95, exists so that a filter can serve repeated draws): S state paths of every
+ * window b of Lm rows starting at starts[b].
+ * Forward filter: runs once, in the log domain, with the globals currently set (mod_init, ltran) and the current
+ *   emission family; lalpha[b] is what svihmm_forward_backward returns for these windows and `flags` (the same
+ *   kernels: the per-window log-domain recursion, for B = 1 and Lm >= 2048 the blocked scan with the log-domain
+ *   repair of svihmm_ffbs).  NIW, diagonal and Categorical families, svihmm_set_lliks data with
+ *   SVIHMM_USE_HOST_LLIKS (starts is then not used and may be NULL), SVIHMM_MASK_AS_NAN gives masked rows ll = 0.
+ *   Always fp64: the precision mode and what svihmm_get_precision reports are unchanged.
+ * Draws: for every draw s < S and window b
+ *     z[s][b][Lm-1] ~ softmax_k( lalpha[b][Lm-1][k] )
+ *     z[s][b][t]    ~ softmax_k( lalpha[b][t][k] + logA[k][ z[s][b][t+1] ] )
+ * Draw rule (part of the contract): lp_k the sum above, m = max_k lp_k, p_k = exp(lp_k - m), c_k the running sum
+ *   of p in ascending state order, tot = c_{K-1}; the draw is the smallest k with u * tot <= c_k, K - 1 if there is
+ *   none.  Where u * tot lies within rounding of some c_k either neighbouring state may be returned (the caveat
+ *   of svihmm_ffbs).  A (window, draw) pair gives the same path whatever S, B or the other windows are.
+ * Uniform source: `uniforms` non-NULL is host double[S][B][Lm], u of (s, b, t) is entry g = (s*B + b)*Lm + t.
+ *   uniforms == NULL: u is generated on the device, nothing is uploaded: Philox4x32-10 with key `seed`, counter
+ *   row g, stream 0, the first two words through the 53-bit mapping svihmm_generate uses for its transition
+ *   uniform.
+ * logA: host double[K][K], used as logA[k][z_next] like svihmm_ffbs (need not be the filter's ltran).  -inf entries
+ *   mean probability zero; +inf, NaN or a column without a finite entry fail.
+ * out_z: host int32[S][B][Lm], window-major inside a draw like svihmm_viterbi; out_lalpha: host double[B][Lm][K]
+ *   or NULL.
+ * Fails with a message, before any device work: NULL logA or out_z; S < 1, B < 1 or Lm < 1 (or S*B >= 2^31); a
+ *   window outside [0, T); no globals, no emission family or no observations (unless host lliks), host lliks of
+ *   another shape; a K mismatch between globals and emission family; K > 256; a bad logA.  The handle stays
+ *   usable after a failed call.
+ * Windows below 2048 rows are sampled in one launch, one lane per (window, draw); longer ones -- the whole chain
+ *   B = 1, Lm = T included -- compose per-chunk state maps once per (window, draw) as svihmm_ffbs does (for
+ *   B = 1, S = 1, Lm = T the path is svihmm_ffbs's).  No device buffer scales with S*Lm*K: lalpha is held once,
+ *   only z and the caller's uniforms scale with S*B*Lm.
+ * Intermediates: the call writes the handle's lliks / lalpha buffers -- afterwards lliks and lalpha of THESE
+ *   windows are readable (svihmm_read_intermediate / _read_rows), lbeta / var_x of an earlier E-step are not; the
+ *   packed statistics held in HBM (svihmm_read_packed / _allreduce_packed / _export_packed) are not touched. */
+int svihmm_ffbs_windows(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t Lm, uint32_t flags,
+                        const double* logA, int32_t S, const double* uniforms, uint64_t seed,
+                        int32_t* out_z, double* out_lalpha);
 
 /* Readback of the intermediates of the last estep/forward_backward call
  * (what 0: lliks, 1: lalpha, 2: lbeta, 3: var_x; each [B,Lm,K]).

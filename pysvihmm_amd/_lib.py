@@ -89,6 +89,8 @@ SIGNATURES = {
     "svihmm_state_argmax": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "svihmm_viterbi": (C.c_int, [C.c_void_p, _c_int64_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p,
                                  _c_double_p]),
+    "svihmm_ffbs_windows": (C.c_int, [C.c_void_p, _c_int64_p, C.c_int32, C.c_int32, C.c_uint32, _c_double_p,
+                                      C.c_int32, _c_double_p, C.c_uint64, C.c_void_p, _c_double_p]),
     "svihmm_read_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, _c_double_p]),
     "svihmm_read_intermediate": (C.c_int, [C.c_void_p, C.c_int32, _c_double_p]),
     "svihmm_ffbs": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_uint32, _c_int64_p,

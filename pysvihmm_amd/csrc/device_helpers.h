@@ -174,6 +174,28 @@ __device__ __forceinline__ int feat_index_d(int a, int b, int D) {
   return a * (D + 1) - a * (a - 1) / 2 + (b - a);
 }
 
+// Counter-based randomness of svihmm_generate (kernels_misc.h) and svihmm_ffbs_windows
+// (kernels_ffbs_windows.h): Philox4x32-10, key = seed, counter = (row, stream); u53 maps two words to
+// a double in [0, 1) with 53 bits.  oracle/ref_numpy.py restates both.
+__device__ __forceinline__ void philox4x32_10(unsigned long long seed, unsigned long long row,
+                                              unsigned stream, unsigned (&o)[4]) {
+  unsigned c0 = (unsigned)row, c1 = (unsigned)(row >> 32), c2 = stream, c3 = 0u;
+  unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned long long p0 = (unsigned long long)0xD2511F53u * c0;
+    const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c2;
+    const unsigned n0 = (unsigned)(p1 >> 32) ^ c1 ^ k0, n1 = (unsigned)p1;
+    const unsigned n2 = (unsigned)(p0 >> 32) ^ c3 ^ k1, n3 = (unsigned)p0;
+    c0 = n0; c1 = n1; c2 = n2; c3 = n3;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  o[0] = c0; o[1] = c1; o[2] = c2; o[3] = c3;
+}
+__device__ __forceinline__ double u53(unsigned hi, unsigned lo) {   // [0, 1), 53 bits
+  return ((double)(hi >> 5) * 67108864.0 + (double)(lo >> 6)) * (1.0 / 9007199254740992.0);
+}
+
 // ------------------------------------------------------------------------------------
 //  Device-side dependencies of the resident SVI loop (round 5).  A stream-order event between two kernels
 //  of an iteration's chain costs ~7 us of dispatch (record) or 4-10 us (a wait that was satisfied long

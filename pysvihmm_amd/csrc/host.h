@@ -149,7 +149,8 @@ struct svihmm_ctx {
   // work
   Buf starts, ll, la, lb, q, lse_part, local_lb, logz, part, packed, scratch;
   Buf user_q, user_starts;         // svihmm_suffstats: the caller's posteriors and windows (never the E-step's q / starts)
-  Buf vit;                         // svihmm_viterbi: score | z | final argmax | psi | path | chunk maps (launch_viterbi)
+  Buf vit;                         // svihmm_viterbi: score | z | final argmax | psi | path | chunk maps (launch_viterbi);
+                                   // svihmm_ffbs_windows: logA | z | the caller's uniforms (launch_ffbs_windows)
   // scaled linear-domain sweeps: per-row binary exponents, (na, k) records, 1/Z factors,
   // Eh of host-supplied lliks; log-domain intermediates materialised on demand (m_*)
   Buf kexp, hx, gx, zfac, llE, m_ll, m_la, m_lb, chain, chain2;
@@ -161,6 +162,10 @@ struct svihmm_ctx {
   bool eh_in_llE = false;          // scaled emission lives in llE (h->ll holds the plain lliks)
   bool step_major = false;         // Eh / ah / bh of the batch in flight lie in the step-major layout (kernels_msg_layout.h)
   uint32_t last_flags = 0;
+  // svihmm_get_precision's last-batch report while the batch in flight is not an E-step's: svihmm_ffbs_windows runs its
+  // filter through prepare_ll (cur_f32 / eh_float describe ITS buffers, always fp64) and holds the report of the
+  // E-step before it here (-1: none held; prepare_ll drops it)
+  int f32_report_hold = -1;
   int m_b0 = 0, m_nb = 0;          // window range currently materialised in m_*
   int lastB = 0, lastLm = 0;       // shape of the intermediates currently held
   int curB = 0;                    // windows of the batch being processed
@@ -363,6 +368,8 @@ int cat_uncentre(svihmm_ctx* h);
 int launch_fb_chain(svihmm_ctx* h, int Lm, bool total);
 int launch_emission_deferred(svihmm_ctx* h);
 int launch_viterbi(svihmm_ctx* h, int B, int Lm, const double* ll, bool want_z, int32_t** dz_out, double** dscore_out);
+int launch_ffbs_windows(svihmm_ctx* h, const int64_t* starts, int B, int Lm, uint32_t flags, const double* logA, int S,
+                        const double* uniforms, uint64_t seed, bool want_lalpha, int32_t** dz_out, const double** dla_out);
 bool sweep_emission_ok(const svihmm_ctx* h, int B, int Lq, int off, int Lm, uint32_t flags);
 bool sweep_mixed_ok(const svihmm_ctx* h, int B, int Lq, int off, int Lm, uint32_t flags);
 bool sweep_stats_ok(const svihmm_ctx* h, int B, int Lq, int off, int Lm, uint32_t flags);

@@ -129,7 +129,8 @@ int svihmm_set_precision(svihmm_ctx* h, int32_t mode) {
 int svihmm_get_precision(svihmm_ctx* h, int32_t* mode_out, int32_t* last_batch_f32_out) {
   if (!h) return fail("svihmm_get_precision: NULL handle");
   if (mode_out) *mode_out = h->prec;
-  if (last_batch_f32_out) *last_batch_f32_out = (h->cur_f32 || h->eh_float) ? 1 : 0;
+  if (last_batch_f32_out)
+    *last_batch_f32_out = h->f32_report_hold >= 0 ? h->f32_report_hold : (h->cur_f32 || h->eh_float) ? 1 : 0;
   return 0;
 }
 int svihmm_sync(svihmm_ctx* h) {
@@ -925,6 +926,7 @@ int prepare_ll(svihmm_ctx* h, const int64_t* starts, int B, int Lm, uint32_t fla
   const bool host_ll = flags & SVIHMM_USE_HOST_LLIKS;
   CK(check_windows(h, starts, B, Lm, !host_ll || need_obs_for_stats));
   if (starts) CK(upload_starts(h, starts, B));
+  h->f32_report_hold = -1;
   h->cur_f32 = false;
   h->eh_float = false;
   h->step_major = false;
@@ -2249,6 +2251,65 @@ int svihmm_viterbi(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t Lm, 
   CK(launch_viterbi(h, B, Lm, (const double*)h->ll.p, out_z != nullptr, &dz, &dscore));
   if (out_z) CK(d2h(h, out_z, dz, (size_t)B * Lm * sizeof(int32_t)));
   if (out_score) CK(d2h(h, out_score, dscore, (size_t)B * sizeof(double)));
+  HIPCK(hipStreamSynchronize(h->stream));
+  CK(check_emission_status(h));
+  return 0;
+}
+
+
+// ---- FFBS for window batches x draws (kernels_ffbs_windows.h) ---------------------------------
+// Everything that can be wrong with the call is found here, before any device work; the filter and the draws
+// are launch_ffbs_windows' (tu_recursion.hip).
+int svihmm_ffbs_windows(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t Lm, uint32_t flags,
+                        const double* logA, int32_t S, const double* uniforms, uint64_t seed,
+                        int32_t* out_z, double* out_lalpha) {
+  if (!h) return fail("svihmm_ffbs_windows: NULL handle");
+  if (!logA || !out_z) return fail("svihmm_ffbs_windows: logA and out_z must be given");
+  if (S < 1 || B < 1 || Lm < 1) return fail("svihmm_ffbs_windows: S, B and Lm must be positive");
+  if ((int64_t)S * B >= ((int64_t)1 << 31)) return fail("svihmm_ffbs_windows: S * B too large");
+  if (!h->have_globals) return fail("svihmm_ffbs_windows: no globals: call svihmm_set_globals first");
+  const int K = h->K;
+  if (K > 256) return fail("svihmm_ffbs_windows: K = " + std::to_string(K) + " > 256 not supported");
+  const bool host_ll = (flags & SVIHMM_USE_HOST_LLIKS) != 0;
+  if (host_ll) {
+    if (!h->have_host_ll || h->hostB != B || h->hostLm != Lm)
+      return fail("svihmm_ffbs_windows: SVIHMM_USE_HOST_LLIKS without uploaded lliks of shape [B, Lm, K] (svihmm_set_lliks)");
+  } else {
+    if (h->T <= 0 || !h->obs.p) return fail("svihmm_ffbs_windows: no observations: call svihmm_set_obs first");
+    if (!h->have_emission)
+      return fail("svihmm_ffbs_windows: no emission family: call svihmm_set_emission_niw / _diag / _cat first");
+    if (K != h->eK)
+      return fail("svihmm_ffbs_windows: K of the globals (" + std::to_string(K) + ") differs from the emission "
+                  "family's K (" + std::to_string(h->eK) + ")");
+    if (h->eD != h->D) return fail("svihmm_ffbs_windows: emission D does not match obs D");
+    if (!starts) return fail("svihmm_ffbs_windows: starts is NULL");
+    for (int b = 0; b < B; ++b)
+      if (starts[b] < 0 || starts[b] + Lm > h->T)
+        return fail("svihmm_ffbs_windows: window " + std::to_string(b) + " reaches outside [0, T)");
+  }
+  // logA[k][z_next]: -inf is probability zero; every column needs one finite entry to draw from
+  for (int j = 0; j < K; ++j) {
+    bool any = false;
+    for (int k = 0; k < K; ++k) {
+      const double v = logA[(size_t)k * K + j];
+      if (v != v || v == INFINITY)
+        return fail("svihmm_ffbs_windows: logA[" + std::to_string(k) + "][" + std::to_string(j) + "] is NaN or +inf");
+      any = any || v > -INFINITY;
+    }
+    if (!any) return fail("svihmm_ffbs_windows: column " + std::to_string(j) + " of logA has no finite entry");
+  }
+  CK(set_device(h));
+  CK(wait_side_streams(h));
+  int32_t* dz = nullptr;
+  const double* dla = nullptr;
+  // (not an E-step batch: what svihmm_get_precision reports about the last one stays)
+  const int report = h->f32_report_hold >= 0 ? h->f32_report_hold : (h->cur_f32 || h->eh_float) ? 1 : 0;
+  const int rc = launch_ffbs_windows(h, starts, B, Lm, flags & (SVIHMM_MASK_AS_NAN | SVIHMM_USE_HOST_LLIKS), logA, S,
+                                     uniforms, seed, out_lalpha != nullptr, &dz, &dla);
+  h->f32_report_hold = report;
+  if (rc) return rc;
+  CK(d2h(h, out_z, dz, (size_t)S * B * Lm * sizeof(int32_t)));
+  if (out_lalpha) CK(d2h(h, out_lalpha, dla, (size_t)B * Lm * K * sizeof(double)));
   HIPCK(hipStreamSynchronize(h->stream));
   CK(check_emission_status(h));
   return 0;

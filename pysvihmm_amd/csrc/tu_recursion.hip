@@ -4,6 +4,7 @@
 #include "device_helpers.h"
 #include "kernels_recursion.h"
 #include "kernels_viterbi.h"
+#include "kernels_ffbs_windows.h"
 
 extern "C" {
 
@@ -648,47 +649,107 @@ int materialise(svihmm_ctx* h, int b0, int nb) {
 }
 
 // backward sampling from the device-resident lalpha[T,K] (hmm_fast.pyx:97-122): blocked
-// composition of the per-row draw maps (K <= 64, T >= 1024), else the sequential single-wave
-// sampler.  *dz_out: device int64[T] (in h->scratch), valid until the next call.
+// composition of the per-row draw maps (K <= 256, T >= 1024), else the sequential single-wave
+// sampler.  ffbs_plan: which of the two and the bytes of path / chunk-map scratch it needs;
+// ffbs_launch: the launches alone, on device operands (lalpha rows, logA, one uniform per row) ->
+// dz (device int64[T]); ffbs_draw: upload of logA and the uniforms + the launches, *dz_out in
+// h->scratch, valid until the next call.
+struct FfbsPlan { bool blocked; int KS, Ls, Cs; size_t extra; };
+static FfbsPlan ffbs_plan(const svihmm_ctx* h, int64_t T, int K) {
+  FfbsPlan pl;
+  pl.blocked = K <= 256 && T >= 1024 && h->variant[6] != 1;
+  pl.KS = K <= 16 ? 16 : K <= 32 ? 32 : K <= 64 ? 64 : 256;      // path entries per row
+  pl.Ls = T >= 65536 ? 512 : 256;
+  pl.Cs = (int)((T + pl.Ls - 1) / pl.Ls);
+  pl.extra = pl.blocked ? (size_t)T * pl.KS + 2 * (size_t)pl.Cs * pl.KS + (size_t)pl.Cs + 64 : 0;
+  return pl;
+}
+static int ffbs_launch(svihmm_ctx* h, const FfbsPlan& pl, const double* la, int64_t T, int K, const double* dlogA,
+                       const double* dun, int64_t* dz, unsigned char* path) {
+  const int KS = pl.KS, Ls = pl.Ls, Cs = pl.Cs;
+  unsigned char* mA = path + (size_t)T * KS;
+  unsigned char* mB = mA + (size_t)Cs * KS;
+  unsigned char* entry = mB + (size_t)Cs * KS;
+  ProfScope ps(h, KS_FFBS);
+  if (pl.blocked) {
+#define FPATH(KM)                                                                                          \
+  hipLaunchKernelGGL(k_ffbs_paths<KM>, dim3(Cs), dim3(64), ((size_t)K * (KM + 1) + 2 * KM) * sizeof(double), \
+                     h->stream, la, dlogA, dun, T, K, Ls, path)
+    if (KS == 16) FPATH(16); else if (KS == 32) FPATH(32); else if (KS == 64) FPATH(64);
+    else
+      hipLaunchKernelGGL(k_ffbs_paths_wide, dim3(Cs), dim3(256), 0, h->stream, la, dlogA, dun, T, K, Ls, path);
+#undef FPATH
+    hipLaunchKernelGGL(k_ffbs_compose, dim3(1), dim3(1024), 0, h->stream, (const unsigned char*)path, T, KS,
+                       Ls, Cs, mA, mB, entry);
+    hipLaunchKernelGGL(k_ffbs_gather, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, h->stream,
+                       (const unsigned char*)path, (const unsigned char*)entry, T, KS, Ls, dz);
+  } else {
+    hipLaunchKernelGGL(k_ffbs_sample, dim3(1), dim3(64), K > 64 ? (size_t)K * 8 : 0, h->stream,
+                       la, dlogA, dun, T, K, dz);
+  }
+  HIPCK(hipGetLastError());
+  return 0;
+}
 static int ffbs_draw(svihmm_ctx* h, const double* la, int64_t T, int K, const double* logA,
                      const double* uniforms, int64_t** dz_out) {
-  const bool blocked = K <= 256 && T >= 1024 && h->variant[6] != 1;
-  const int KS = K <= 16 ? 16 : K <= 32 ? 32 : K <= 64 ? 64 : 256;      // path entries per row
-  const int Ls = T >= 65536 ? 512 : 256;
-  const int Cs = (int)((T + Ls - 1) / Ls);
+  const FfbsPlan pl = ffbs_plan(h, T, K);
   const size_t base = ((size_t)K * K + (size_t)T) * sizeof(double) + (size_t)T * sizeof(int64_t);
-  const size_t extra = blocked ? (size_t)T * KS + 2 * (size_t)Cs * KS + (size_t)Cs + 64 : 0;
-  CK(ensure(h->scratch, base + extra));
+  CK(ensure(h->scratch, base + pl.extra));
   double* dlogA = (double*)h->scratch.p;
   double* dun = dlogA + (size_t)K * K;
   int64_t* dz = (int64_t*)(dun + T);
   *dz_out = dz;
-  unsigned char* path = (unsigned char*)(dz + T);
-  unsigned char* mA = path + (size_t)T * KS;
-  unsigned char* mB = mA + (size_t)Cs * KS;
-  unsigned char* entry = mB + (size_t)Cs * KS;
   HIPCK(hipMemcpyAsync(dlogA, logA, (size_t)K * K * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCK(hipMemcpyAsync(dun, uniforms, (size_t)T * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  {
-    ProfScope ps(h, KS_FFBS);
-    if (blocked) {
-#define FPATH(KM)                                                                                          \
-  hipLaunchKernelGGL(k_ffbs_paths<KM>, dim3(Cs), dim3(64), ((size_t)K * (KM + 1) + 2 * KM) * sizeof(double), \
-                     h->stream, la, (const double*)dlogA, (const double*)dun, T, K, Ls, path)
-      if (KS == 16) FPATH(16); else if (KS == 32) FPATH(32); else if (KS == 64) FPATH(64);
-      else
-        hipLaunchKernelGGL(k_ffbs_paths_wide, dim3(Cs), dim3(256), 0, h->stream, la, (const double*)dlogA,
-                           (const double*)dun, T, K, Ls, path);
-#undef FPATH
-      hipLaunchKernelGGL(k_ffbs_compose, dim3(1), dim3(1024), 0, h->stream, (const unsigned char*)path, T, KS,
-                         Ls, Cs, mA, mB, entry);
-      hipLaunchKernelGGL(k_ffbs_gather, dim3((unsigned)((T + 255) / 256)), dim3(256), 0, h->stream,
-                         (const unsigned char*)path, (const unsigned char*)entry, T, KS, Ls, dz);
-    } else {
-      hipLaunchKernelGGL(k_ffbs_sample, dim3(1), dim3(64), K > 64 ? (size_t)K * 8 : 0, h->stream,
-                         la, (const double*)dlogA, (const double*)dun, T, K, dz);
-    }
+  return ffbs_launch(h, pl, la, T, K, dlogA, dun, dz, (unsigned char*)(dz + T));
+}
+
+// The forward filter of the FFBS entry points: lalpha [B][Lm][K] of the windows, resident until the next
+// call (*la_out).  One long chain (use_chain) through the exact blocked scan (scaled sweeps), then lalpha
+// from (ah, h, K); everything else with the per-window log-domain kernel.  want_exact: the caller hands
+// lalpha itself back, so the entries the scaled messages lost to underflow are repaired too.
+static int ffbs_filter(svihmm_ctx* h, const int64_t* starts, int B, int Lm, uint32_t flags, bool want_exact,
+                       const double** la_out) {
+  const int K = h->K;
+  const int64_t T = Lm;
+  if (B == 1 && K <= 256 && use_chain(h, 1, Lm)) {
+    CK(prepare_ll(h, starts, 1, Lm, flags, false, true));
+    CK(launch_fb_chain(h, Lm, false));
+    CK(ensure(h->m_la, (size_t)T * K * sizeof(double)));
+    h->m_nb = 0;
+    ProfScope ps(h, KS_FB);
+    hipLaunchKernelGGL(k_chain_lalpha, dim3(h->chain_C), dim3(256), 0, h->stream, (const double*)h->la.p,
+                       (const double*)h->hx.p, (const double*)h->kexp.p, h->chain_kbef, h->chain_L,
+                       h->chain_C, T, K, (double*)h->m_la.p);
     HIPCK(hipGetLastError());
+    const double* la = (const double*)h->m_la.p;
+    if (want_exact) {
+      // the caller wants lalpha itself: entries the scaled messages lost to underflow are
+      // recomputed in the log domain (plain lliks into m_ll, corrected copy into m_lb)
+      CK(ensure(h->m_lb, (size_t)T * K * sizeof(double)));
+      const double* llp = (const double*)h->ll.p;     // host-supplied / two-pass lliks are still there
+      if (!h->eh_in_llE) {
+        CK(ensure(h->m_ll, (size_t)T * K * sizeof(double)));
+        CK(launch_emission(h, 1, Lm, flags, false, nullptr, (double*)h->m_ll.p));
+        llp = (const double*)h->m_ll.p;
+      }
+      const unsigned nblk = (unsigned)((T + 63) / 64);
+#define LFIX(KM) hipLaunchKernelGGL(k_lalpha_fix<KM>, dim3(nblk), dim3(256), 0, h->stream, la, (const double*)h->la.p, \
+                                    llp, (const double*)h->ltran.p,                                              \
+                                    (const double*)h->mod_init.p, T, K, (double*)h->m_lb.p)
+      if (K <= 16) LFIX(16); else if (K <= 32) LFIX(32); else if (K <= 64) LFIX(64);
+      else
+        hipLaunchKernelGGL(k_lalpha_fix_wide, dim3(nblk), dim3(256), 0, h->stream, la, (const double*)h->la.p, llp,
+                           (const double*)h->ltran.p, (const double*)h->mod_init.p, T, K, (double*)h->m_lb.p);
+#undef LFIX
+      HIPCK(hipGetLastError());
+      la = (const double*)h->m_lb.p;
+    }
+    *la_out = la;
+  } else {
+    CK(prepare_ll(h, starts, B, Lm, flags, false));
+    CK(launch_fb(h, B, Lm, 0, 1));
+    *la_out = (const double*)h->la.p;
   }
   return 0;
 }
@@ -704,53 +765,91 @@ int svihmm_ffbs(svihmm_ctx* h, const double* logA, const double* uniforms, uint3
   const int K = h->K;
   if (!h->have_globals) return fail("no globals: call svihmm_set_globals");
   CK(wait_globals(h));
-  // forward filter: long chains through the exact blocked scan (scaled sweeps), then lalpha
-  // from (ah, h, K); short ones with the per-window log-domain kernel
   const double* la = nullptr;
-  if (K <= 256 && use_chain(h, 1, (int)T)) {
-    CK(prepare_ll(h, &st0, 1, (int)T, flags, false, true));
-    CK(launch_fb_chain(h, (int)T, false));
-    CK(ensure(h->m_la, (size_t)T * K * sizeof(double)));
-    h->m_nb = 0;
-    ProfScope ps(h, KS_FB);
-    hipLaunchKernelGGL(k_chain_lalpha, dim3(h->chain_C), dim3(256), 0, h->stream, (const double*)h->la.p,
-                       (const double*)h->hx.p, (const double*)h->kexp.p, h->chain_kbef, h->chain_L,
-                       h->chain_C, T, K, (double*)h->m_la.p);
-    HIPCK(hipGetLastError());
-    la = (const double*)h->m_la.p;
-    if (out_lalpha) {
-      // the caller wants lalpha itself: entries the scaled messages lost to underflow are
-      // recomputed in the log domain (plain lliks into m_ll, corrected copy into m_lb)
-      CK(ensure(h->m_lb, (size_t)T * K * sizeof(double)));
-      const double* llp = (const double*)h->ll.p;     // host-supplied / two-pass lliks are still there
-      if (!h->eh_in_llE) {
-        CK(ensure(h->m_ll, (size_t)T * K * sizeof(double)));
-        CK(launch_emission(h, 1, (int)T, flags, false, nullptr, (double*)h->m_ll.p));
-        llp = (const double*)h->m_ll.p;
-      }
-      const unsigned nblk = (unsigned)((T + 63) / 64);
-#define LFIX(KM) hipLaunchKernelGGL(k_lalpha_fix<KM>, dim3(nblk), dim3(256), 0, h->stream, la, (const double*)h->la.p, \
-                                    llp, (const double*)h->ltran.p,                                              \
-                                    (const double*)h->mod_init.p, T, K, (double*)h->m_lb.p)
-      if (K <= 16) LFIX(16); else if (K <= 32) LFIX(32); else if (K <= 64) LFIX(64);
-      else
-        hipLaunchKernelGGL(k_lalpha_fix_wide, dim3(nblk), dim3(256), 0, h->stream, la, (const double*)h->la.p, llp,
-                           (const double*)h->ltran.p, (const double*)h->mod_init.p, T, K, (double*)h->m_lb.p);
-#undef LFIX
-      HIPCK(hipGetLastError());
-      la = (const double*)h->m_lb.p;
-    }
-  } else {
-    CK(prepare_ll(h, &st0, 1, (int)T, flags, false));
-    CK(launch_fb(h, 1, (int)T, 0, 1));
-    la = (const double*)h->la.p;
-  }
+  CK(ffbs_filter(h, &st0, 1, (int)T, flags, out_lalpha != nullptr, &la));
   int64_t* dz = nullptr;
   CK(ffbs_draw(h, la, T, K, logA, uniforms, &dz));
   CK(d2h(h, out_z, dz, (size_t)T * sizeof(int64_t)));
   if (out_lalpha) CK(d2h(h, out_lalpha, la, (size_t)T * K * sizeof(double)));
   HIPCK(hipStreamSynchronize(h->stream));
   h->lastB = 1; h->lastLm = (int)T;
+  return 0;
+}
+
+// svihmm_ffbs_windows: one forward filter over the windows (ffbs_filter), then S backward draws of every window
+// from the resident lalpha.  Windows below FFW_SWITCH rows: one launch, a lane per (window, draw) pair
+// (kernels_ffbs_windows.h).  Longer ones -- the whole chain included -- run the blocked composition of ffbs_launch
+// once per (window, draw) on la + b Lm K; the path / chunk-map scratch is reused by every draw.
+// h->vit: logA | z int32 [S][B][Lm] | the caller's uniforms [S][B][Lm]; nothing scales with S T K.
+// *dz_out / *dla_out (lalpha [B][Lm][K]) stay valid until the next call.
+int launch_ffbs_windows(svihmm_ctx* h, const int64_t* starts, int B, int Lm, uint32_t flags, const double* logA,
+                        int S, const double* uniforms, uint64_t seed, bool want_lalpha, int32_t** dz_out,
+                        const double** dla_out) {
+  const int K = h->K;
+  if (K > 256) return fail("svihmm_ffbs_windows: K > 256 not supported");
+  CK(wait_globals(h));
+  const double* la = nullptr;
+  CK(ffbs_filter(h, starts, B, Lm, flags, want_lalpha, &la));
+  h->have_lb = false;
+  h->lastB = B; h->lastLm = Lm;
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t n = (size_t)S * B * Lm;
+  const size_t o_z = up((size_t)K * K * sizeof(double)), o_u = o_z + up(n * sizeof(int32_t));
+  CK(ensure(h->vit, o_u + (uniforms ? n * sizeof(double) : 0) + 256));
+  char* base = (char*)h->vit.p;
+  double* dlogA = (double*)base;
+  int32_t* dz = (int32_t*)(base + o_z);
+  double* dun = uniforms ? (double*)(base + o_u) : nullptr;
+  HIPCK(hipMemcpyAsync(dlogA, logA, (size_t)K * K * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (uniforms) HIPCK(hipMemcpyAsync(dun, uniforms, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  *dz_out = dz;
+  *dla_out = la;
+  if (Lm < FFW_SWITCH) {
+    const unsigned nblk = (unsigned)(((int64_t)B * S + 63) / 64);
+    ProfScope ps(h, KS_FFBS);
+    if (K <= 64) {
+      const int KM = K <= 16 ? 16 : K <= 32 ? 32 : 64;
+      const int nwmax = ffw_windows_per_wave(B, S), RT = ffw_row_tile(nwmax, KM, Lm);
+      const size_t lds = ffw_lds_bytes(K, KM, nwmax, RT);
+#define FWIN(KMAX)                                                                                                  \
+  do {                                                                                                              \
+    if (lds > 64 * 1024)                                                                                            \
+      hipFuncSetAttribute((const void*)k_ffbs_win<KMAX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);     \
+    hipLaunchKernelGGL(k_ffbs_win<KMAX>, dim3(nblk), dim3(64), lds, h->stream, la, (const double*)dlogA,            \
+                       (const double*)dun, (unsigned long long)seed, B, S, Lm, K, nwmax, RT, dz);                   \
+  } while (0)
+      if (KM == 16) FWIN(16); else if (KM == 32) FWIN(32); else FWIN(64);
+#undef FWIN
+    } else {
+      hipLaunchKernelGGL(k_ffbs_win_wide, dim3(nblk), dim3(64), 0, h->stream, la, (const double*)dlogA,
+                         (const double*)dun, (unsigned long long)seed, B, S, Lm, K, dz);
+    }
+    HIPCK(hipGetLastError());
+    return 0;
+  }
+  // long windows: per-draw scratch in h->scratch = (Philox: uniforms [Lm]) | z int64 [Lm] | path, chunk maps
+  const FfbsPlan pl = ffbs_plan(h, Lm, K);
+  const size_t o_zl = uniforms ? 0 : up((size_t)Lm * sizeof(double));
+  const size_t o_path = o_zl + up((size_t)Lm * sizeof(int64_t));
+  CK(ensure(h->scratch, o_path + pl.extra));
+  char* sb = (char*)h->scratch.p;
+  int64_t* dzl = (int64_t*)(sb + o_zl);
+  const unsigned nb256 = (unsigned)((Lm + 255) / 256);
+  for (int s = 0; s < S; ++s)
+    for (int b = 0; b < B; ++b) {
+      const int64_t g0 = ((int64_t)s * B + b) * Lm;
+      const double* du = dun ? dun + g0 : (const double*)sb;
+      if (!dun) {
+        ProfScope ps(h, KS_FFBS);
+        hipLaunchKernelGGL(k_ffw_fill_uniforms, dim3(nb256), dim3(256), 0, h->stream, (unsigned long long)seed, g0,
+                           (int64_t)Lm, (double*)sb);
+      }
+      CK(ffbs_launch(h, pl, la + (size_t)b * Lm * K, Lm, K, dlogA, du, dzl, (unsigned char*)(sb + o_path)));
+      ProfScope ps(h, KS_FFBS);
+      hipLaunchKernelGGL(k_ffw_store_path, dim3(nb256), dim3(256), 0, h->stream, (const int64_t*)dzl, (int64_t)Lm,
+                         dz + g0);
+    }
+  HIPCK(hipGetLastError());
   return 0;
 }
 

@@ -279,6 +279,7 @@ class HipEngine(object):
         lliks = L.as_f64(lliks)
         B, Lm, K = lliks.shape
         L.check(self._lib.svihmm_set_lliks(self._h, L.dptr(lliks), B, Lm), "svihmm_set_lliks")
+        self._host_ll_windows = B
 
     # -- compute -----------------------------------------------------------------------
     @staticmethod
@@ -458,6 +459,35 @@ class HipEngine(object):
         L.check(self._lib.svihmm_ffbs_sample(self._h, T, K, L.dptr(lalpha), L.dptr(logA), L.dptr(u),
                                              L.i64ptr(z)), "svihmm_ffbs_sample")
         return z
+
+    def ffbs_windows(self, starts, Lm, logA, n_draws=1, uniforms=None, seed=0, flags=0, want_lalpha=False):
+        """``n_draws`` state paths of every window from ONE forward filter (``svihmm_ffbs_windows``):
+        ``(z int32[S, B, Lm], lalpha float64[B, Lm, K] or None)``.  The filter uses the globals and
+        the emission family currently set (with ``USE_HOST_LLIKS`` the batch uploaded by
+        ``set_lliks``; ``starts`` then only gives the number of windows and may be None); the draws
+        use ``logA[k, z_next]`` like ``ffbs``.  ``uniforms`` [S, B, Lm] are consumed one per state;
+        without them the device draws its own (Philox4x32-10 keyed by ``seed``, nothing uploaded).
+        The draw rule is stated in ``include/svihmm.h``."""
+        self._pre_mutate()
+        if starts is None:
+            if not int(flags) & L.USE_HOST_LLIKS:
+                raise RuntimeError("ffbs_windows: starts=None needs USE_HOST_LLIKS (the windows of set_lliks)")
+            st, B = None, int(getattr(self, "_host_ll_windows", 0))
+        else:
+            st = self._starts(starts)
+            B = len(st)
+        Lm, S = int(Lm), int(n_draws)
+        logA = L.as_f64(logA, (self.K, self.K))
+        u = None
+        if uniforms is not None:
+            u = L.as_f64(uniforms, (max(S, 0), B, max(Lm, 0)))
+        z = np.empty((max(S, 0), B, max(Lm, 0)), dtype=np.int32)
+        la = np.empty((B, max(Lm, 0), self.K)) if want_lalpha else None
+        self._rows = B * max(Lm, 0)
+        L.check(self._lib.svihmm_ffbs_windows(self._h, L.i64ptr(st), B, Lm, int(flags), L.dptr(logA), S,
+                                              L.dptr(u), int(seed) & 0xFFFFFFFFFFFFFFFF,
+                                              z.ctypes.data_as(C.c_void_p), L.dptr(la)), "svihmm_ffbs_windows")
+        return z, la
 
     # -- SVI loop with the variational state resident in HBM ---------------------------------
     def svi_begin(self, prior_tran, var_tran, prior, factors, prior_logpart, maxit, zsign=1.0):

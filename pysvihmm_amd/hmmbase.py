@@ -524,6 +524,40 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         z, lalpha = self.engine.ffbs(logA, uniforms, flags=flags)
         return z, lalpha
 
+    def ffbs_windows(self, metaobs=None, n_draws=1, var_init=None, uniforms=None, seed=None):
+        """``n_draws`` FFBS state paths of one meta-observation, of a list of equal-length ones, or
+        (``metaobs=None``) of the whole chain, all from ONE forward filter on the device:
+        ``z int32[n_draws, B, Lm]``.  Conventions of ``ffbs_fast`` (quirk Q6): ``var_init`` (default
+        ``self.var_init``) through digamma with ``DBL_EPSILON``, ``log(var_tran + DBL_EPSILON)`` as
+        the filter's transition and the sampler's; emission plugins without a device family are
+        evaluated on the host (``set_lliks``), as in ``viterbi()``.  ``uniforms`` [n_draws, B, Lm]
+        replace the device's counter-based generator, whose ``seed`` otherwise comes from
+        ``np.random`` (so ``np.random.seed`` makes the draws reproducible).  No attribute of the
+        model changes."""
+        if metaobs is None:
+            wins = [(0, self.T - 1)]
+        elif isinstance(metaobs, (list, tuple)):
+            wins = [(m.i1, m.i2) for m in metaobs]
+        else:
+            wins = [(metaobs.i1, metaobs.i2)]
+        if not wins:
+            raise RuntimeError("ffbs_windows: no meta-observation given")
+        Lm = wins[0][1] - wins[0][0] + 1
+        if any(u - l + 1 != Lm for l, u in wins):
+            raise RuntimeError("ffbs_windows: the meta-observations must have equal lengths")
+        starts = [l for l, _ in wins]
+        var_init = np.asarray(self.var_init if var_init is None else var_init, dtype=np.float64)
+        mod_init = digamma(var_init + DBL_EPSILON) - digamma(np.sum(var_init) + DBL_EPSILON)
+        logA = np.log(self.var_tran + DBL_EPSILON)
+        if uniforms is None and seed is None:
+            seed = int(np.random.randint(0, 2 ** 31 - 1)) * 2 ** 31 + int(np.random.randint(0, 2 ** 31 - 1))
+        self._upload_obs()
+        self.engine.set_globals(mod_init, logA)
+        flags = self._push_emission(windows=starts, Lm=Lm)
+        z, _ = self.engine.ffbs_windows(starts, Lm, logA, n_draws=n_draws, uniforms=uniforms,
+                                        seed=0 if seed is None else seed, flags=flags)
+        return z
+
     # -- metrics (host) ----------------------------------------------------------------
     def hamming_dist(self, full_var_x, true_sts):
         """Hamming distance after the best label permutation (reference hmmbase.py:346-365).
