@@ -25,6 +25,14 @@ NIW_MAX_D = 96                    # wider observations: host-evaluated lliks (ge
 DIAG_MAX_D = 128                  # diagonal family on the device up to this width
 LTRAN_F32_MIN = -60.0
 F64, F32 = 0, 1
+# svihmm_set_variant's slots: the SVIHMM_VAR_* enumerators of include/svihmm_debug.h, lower-cased (their codes are
+# documented there)
+VARIANT = {
+    "svi_loop": 0, "stats": 1, "fb": 2, "emission_mt": 3, "pipeline": 4, "emission_orbit": 5, "chain": 6,
+    "sweep_family": 7, "stats_chunks": 8, "centring": 9, "stats_tiling": 10, "allreduce_coords": 11,
+    "stats_lds3": 12, "wide_sweeps": 13, "wide_tran_block": 14, "wide_posterior": 15, "renorm4": 16,
+    "msg_layout": 17,
+}
 
 _lib = None
 

@@ -5,6 +5,7 @@
 //   tu_emission.hip    emission kernels (kernels_emission.h) and their launchers
 //   tu_recursion.hip   sweeps / scans / FFBS (kernels_recursion.h) and their launchers
 //   tu_stats.hip       statistics GEMMs + finalize (kernels_stats.h) and their launchers
+//   tu_fused.hip       fused sweep + statistics launch of the minibatch E-step (kernels_fused.h) and its plan
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
@@ -173,11 +174,8 @@ struct svihmm_ctx {
   bool have_host_ll = false;
   bool have_packed = false;
   bool have_lb = false;           // lbeta materialised by the last call
-  // variants: [0] emission (0 auto,1 outer,2 mfma) [1] stats (0 auto,1 outer,2 mfma,3 pipelined)
-  // [2] sweeps (0 auto,1 wave,2 log-MFMA,3 scaled) [3] emission row tiles
-  // [4] two-stream E-step pipeline (0 auto,1 off,2 on)
-  // [8] row chunks of the statistics GEMM (0 = automatic)
-  int variant[24] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  // kernel-selection knobs (svihmm_set_variant), indexed by SVIHMM_VAR_*: the table in include/svihmm_debug.h
+  int variant[SVIHMM_NVARIANT] = {0};
   // second stream + events of the pipelined E-step (created on first use)
   hipStream_t stream2 = nullptr;
   hipEvent_t ev_em[2] = {nullptr, nullptr}, ev_sw[2] = {nullptr, nullptr};
@@ -310,6 +308,10 @@ inline int set_device(svihmm_ctx* h) {
 inline int64_t cu_scaled(const svihmm_ctx* h, int64_t v) {
   const int64_t r = (v * h->ncu + 128) / 256;
   return r < 1 ? 1 : r;
+}
+// the large-batch floor of the fp32 mode's bf16 kernels (emission for D > 32 / wide models, both statistics GEMMs)
+inline bool bf16_batch_floor_ok(const svihmm_ctx* h, int64_t n) {
+  return n >= cu_scaled(h, 32768) || h->variant[SVIHMM_VAR_STATS_TILING] == SVIHMM_STATS_TILING_BF16_SMALL;
 }
 struct StatsPlan { int64_t rpc, nchunk; };
 // the natural-gradient step's arguments when it rides in the theta builder's launch (k_svi_step_theta32s, kernels_svi_theta.h)

@@ -172,7 +172,7 @@ int svihmm_set_obs(svihmm_ctx* h, const double* obs, int64_t T, int32_t D,
 static void sample_center(const svihmm_ctx* h, const double* obs, int64_t T, int D, std::vector<double>& c) {
   c.assign((size_t)D, 0.0);
   const_cast<svihmm_ctx*>(h)->center_deferred = false;
-  if (h->variant[9] == 1 || !obs || T <= 0) return;      // variant 9 = 1: no automatic centring
+  if (h->variant[SVIHMM_VAR_CENTRING] == SVIHMM_CENTRING_OFF || !obs || T <= 0) return;      // (no automatic centring)
   // a Categorical table is the active emission: the column holds symbol indices, which the lookup
   // kernels truncate to int -- it stays exactly as uploaded (round-3 advisor finding: set_emission_cat
   // followed by set_obs centred the symbols)
@@ -504,7 +504,7 @@ static void from_centred(const svihmm_ctx* h, double* mu, int K, int D) {
 static int centre_deferred(svihmm_ctx* h) {
   if (!h->center_deferred) return 0;
   h->center_deferred = false;
-  if (h->T <= 0 || !h->obs.p || h->shifted || h->variant[9] == 1) return 0;
+  if (h->T <= 0 || !h->obs.p || h->shifted || h->variant[SVIHMM_VAR_CENTRING] == SVIHMM_CENTRING_OFF) return 0;
   const int D = h->D;
   int64_t nsamp = ((int64_t)4 << 20) / D;
   if (nsamp > 65536) nsamp = 65536;
@@ -817,25 +817,31 @@ static int upload_starts(svihmm_ctx* h, const int64_t* starts, int B) {
 
 
 
-// Which sweep implementation a batch uses: 1 wave-per-window (log domain; small batches,
-// K > 64), 2 log-domain MFMA (callers that want lalpha / lbeta back), 3 scaled
-// linear-domain MFMA (the E-step fast path; logs are materialised on demand).
+// Which sweep implementation a batch uses, as a code of the FB knob: SVIHMM_FB_WAVE wave-per-window (log domain;
+// small batches, K > 64), SVIHMM_FB_LOG_MFMA log-domain MFMA (callers that want lalpha / lbeta back),
+// SVIHMM_FB_SCALED scaled linear-domain MFMA (the E-step fast path; logs are materialised on demand).
 static int pick_fb(const svihmm_ctx* h, int B, int Lm, bool want_logs) {
-  int var = h->variant[2];
-  if (h->K > 256 || h->exact_log) return 1;
+  int var = h->variant[SVIHMM_VAR_FB];
+  if (h->K > 256 || h->exact_log) return SVIHMM_FB_WAVE;
   if (h->K > 64) {   // no log-domain MFMA sweep beyond 64 states: scaled (streamed B) or per-window
-    if (var == 2) var = 1;
+    if (var == SVIHMM_FB_LOG_MFMA) var = SVIHMM_FB_WAVE;
     // one long chain: blocked scan (its messages convert to logs row by row, see materialise);
     // large batches: scaled sweeps unless the logs themselves are wanted
-    if (var == 0) var = (use_chain(h, B, Lm) || (B >= cu_scaled(h, 192) && !want_logs)) ? 3 : 1;
-    if (var == 3 && !use_chain(h, B, Lm) && (size_t)16 * Lm * h->K * sizeof(double) >= ((size_t)1 << 32)) var = 1;
+    if (var == 0) var = (use_chain(h, B, Lm) || (B >= cu_scaled(h, 192) && !want_logs)) ? SVIHMM_FB_SCALED : SVIHMM_FB_WAVE;
+    if (var == SVIHMM_FB_SCALED && !use_chain(h, B, Lm) && (size_t)16 * Lm * h->K * sizeof(double) >= ((size_t)1 << 32))
+      var = SVIHMM_FB_WAVE;
     return var;
   }
-  if (var == 0) var = want_logs ? (use_chain(h, B, Lm) ? 3 : B >= cu_scaled(h, 192) ? 2 : 1) : 3;   // no logs wanted: scaled sweeps at any batch size; logs of one long chain: blocked scan + conversion
+  // no logs wanted: scaled sweeps at any batch size; logs of one long chain: blocked scan + conversion
+  if (var == 0)
+    var = want_logs ? (use_chain(h, B, Lm) ? SVIHMM_FB_SCALED : B >= cu_scaled(h, 192) ? SVIHMM_FB_LOG_MFMA : SVIHMM_FB_WAVE)
+                    : SVIHMM_FB_SCALED;
   // the scaled sweeps address a workgroup's 16 windows with 32-bit byte offsets
   // (the wave-per-window kernel of small batches uses 64-bit row offsets)
-  if (var == 3 && !use_chain(h, B, Lm) && !(B < lin_wave_max(h) && h->variant[7] != 2) &&
-      (size_t)16 * Lm * h->K * sizeof(double) >= ((size_t)1 << 32)) var = 2;
+  if (var == SVIHMM_FB_SCALED && !use_chain(h, B, Lm) &&
+      !(B < lin_wave_max(h) && h->variant[SVIHMM_VAR_SWEEP_FAMILY] != SVIHMM_SWEEP_FAMILY_TILES) &&
+      (size_t)16 * Lm * h->K * sizeof(double) >= ((size_t)1 << 32))
+    var = SVIHMM_FB_LOG_MFMA;
   return var;
 }
 
@@ -867,13 +873,13 @@ static int run_fb(svihmm_ctx* h, int B, int Lm, int var, bool want_lb, bool tota
   // taken at the same place: every stream-order event between two kernels of the iteration's chain
   // costs a few microseconds of dispatch, two in a row less than two apart
   CK(wait_side_streams(h));
-  if (var == 3) {
+  if (var == SVIHMM_FB_SCALED) {
     h->have_lb = true;   // materialised lazily
     return launch_fb_lin(h, B, Lm, total);
   }
-  h->have_lb = (var != 2) || want_lb;
+  h->have_lb = (var != SVIHMM_FB_LOG_MFMA) || want_lb;
   if (h->svi_flags && h->in_svi_estep) CK(wait_globals(h));    // (the log-domain kernels take no gate)
-  if (var == 2) return launch_fb_fused(h, B, Lm, want_lb, total);
+  if (var == SVIHMM_FB_LOG_MFMA) return launch_fb_fused(h, B, Lm, want_lb, total);
   CK(launch_fb(h, B, Lm, 0, 2));
   return launch_posterior(h, B, Lm, total);
 }
@@ -909,17 +915,18 @@ int64_t svihmm_packed_size(int32_t K, int32_t D) {
 // Step-major message layout (kernels_msg_layout.h): exactly the batches whose sweeps are k_sweeps_lin<4, true, 0> on
 // double messages behind the row-tile orbit emission kernel -- the tiled fp64 epoch at K = 64.  Thresholds, from the
 // dispatch: B >= lin_wave_max (4 CUs' worth of windows + 1: below it the wave-per-window / fused kernels run) and at
-// least one 128-row emission workgroup per CU.  Everything else keeps row-major; variant 17 = 1 forces row-major here
+// least one 128-row emission workgroup per CU.  Everything else keeps row-major; SVIHMM_MSG_LAYOUT_ROW_MAJOR forces
+// row-major here
 // too (A/B runs, the bit-identity test).  (B + 18) Lm K < 2^31: the statistics GEMM's 32-bit message offsets.
 bool step_major_ok(const svihmm_ctx* h, int B, int Lm, uint32_t flags, bool lin) {
-  if (!lin || h->variant[17] == 1 || h->K != 64 || h->Kp != 64) return false;
+  if (!lin || h->variant[SVIHMM_VAR_MSG_LAYOUT] == SVIHMM_MSG_LAYOUT_ROW_MAJOR || h->K != 64 || h->Kp != 64) return false;
   if ((flags & SVIHMM_USE_HOST_LLIKS) || h->emis_cat || (h->prec == 1 && h->f32_ok)) return false;
   if (use_chain(h, B, Lm) || B < lin_wave_max(h)) return false;
   if ((int64_t)(B + 18) * Lm * h->K >= ((int64_t)1 << 31)) return false;
   return emission_row_tile_orbit(h, (int64_t)B * Lm);
 }
 
-// lin: the batch goes through the scaled linear-domain sweeps (pick_fb == 3)
+// lin: the batch goes through the scaled linear-domain sweeps (pick_fb == SVIHMM_FB_SCALED)
 int prepare_ll(svihmm_ctx* h, const int64_t* starts, int B, int Lm, uint32_t flags,
                       bool need_obs_for_stats, bool lin) {
   if (!h->have_globals) return fail("no globals: call svihmm_set_globals");
@@ -1031,7 +1038,9 @@ static int read_packed_host(svihmm_ctx* h, double* out) {
 // back into this handle's centred coordinates.  The RCCL all-reduce and the host-mediated exchange
 // (svihmm_export_packed / svihmm_import_packed) run between the same two halves.
 static bool common_needs_shift(const svihmm_ctx* h, bool always) {
-  return h->shifted && !h->emis_cat && (always || h->nranks > 1 || h->variant[11] == 1);   // (variant 11: rehearsal at one rank)
+  // (the knob: rehearsal at one rank)
+  return h->shifted && !h->emis_cat &&
+         (always || h->nranks > 1 || h->variant[SVIHMM_VAR_ALLREDUCE_COORDS] == SVIHMM_ALLREDUCE_COORDS_ON);
 }
 static int packed_to_common(svihmm_ctx* h, bool always, double** buf_out) {
   const size_t n = (size_t)packed_len(h);
@@ -1072,14 +1081,14 @@ static int allreduce_packed_dev(svihmm_ctx* h) {
 // a CU; the sweep kernels raise their wave priority.  Partials stay deterministic (fixed
 // chunking per half, one finalize over all slots).
 static bool use_pipeline(const svihmm_ctx* h, int B, int Lm, int fbvar, uint32_t flags) {
-  const int v = h->variant[4];
-  if (v == 1 || fbvar != 3 || (flags & SVIHMM_USE_HOST_LLIKS)) return false;
+  const int v = h->variant[SVIHMM_VAR_PIPELINE];
+  if (v == SVIHMM_PIPELINE_UNFUSED || fbvar != SVIHMM_FB_SCALED || (flags & SVIHMM_USE_HOST_LLIKS)) return false;
   if (h->Kp > 64 || h->D > 64 || h->emis_cat) return false;
-  const int sv = h->variant[1];
-  if (sv != 0 && sv != 3) return false;
+  const int sv = h->variant[SVIHMM_VAR_STATS];
+  if (sv != 0 && sv != SVIHMM_STATS_PIPELINED) return false;
   // opt-in only: on MI355X the sweeps' fp64 VALU work queues behind the GEMMs' MFMAs on a
   // shared SIMD and both sides lose more than the overlap wins (experiments)
-  return v == 2 && B >= 32;
+  return v == SVIHMM_PIPELINE_TWO_STREAM && B >= 32;
 }
 static int estep_pipelined(svihmm_ctx* h, const int64_t* starts, int B, int Lm, int inner_off,
                            int inner_len, uint32_t flags) {
@@ -1155,14 +1164,14 @@ int svihmm_forward_backward(svihmm_ctx* h, const int64_t* starts, int32_t B, int
   if (!h) return fail("svihmm_forward_backward: NULL handle");
   CK(set_device(h));
   const int var = pick_fb(h, B, Lm, out_lalpha != nullptr || out_lbeta != nullptr);
-  CK(prepare_ll(h, starts, B, Lm, flags, false, var == 3));
+  CK(prepare_ll(h, starts, B, Lm, flags, false, var == SVIHMM_FB_SCALED));
   CK(run_fb(h, B, Lm, var, out_lbeta != nullptr, false));
   h->lastB = B; h->lastLm = Lm;
-  if (var == 3 && (out_lalpha || out_lbeta)) CK(materialise(h, 0, B));   // forced variant
-  if (var == 3 && out_var_x) CK(ensure_q(h, B, Lm, h->stream));
+  if (var == SVIHMM_FB_SCALED && (out_lalpha || out_lbeta)) CK(materialise(h, 0, B));   // forced variant
+  if (var == SVIHMM_FB_SCALED && out_var_x) CK(ensure_q(h, B, Lm, h->stream));
   const size_t n = (size_t)B * Lm * h->K * sizeof(double);
-  if (out_lalpha) CK(d2h(h, out_lalpha, var == 3 ? h->m_la.p : h->la.p, n));
-  if (out_lbeta) CK(d2h(h, out_lbeta, var == 3 ? h->m_lb.p : h->lb.p, n));
+  if (out_lalpha) CK(d2h(h, out_lalpha, var == SVIHMM_FB_SCALED ? h->m_la.p : h->la.p, n));
+  if (out_lbeta) CK(d2h(h, out_lbeta, var == SVIHMM_FB_SCALED ? h->m_lb.p : h->lb.p, n));
   if (out_var_x) CK(d2h(h, out_var_x, h->q.p, n));
   if (out_local_lb) CK(d2h(h, out_local_lb, h->local_lb.p, (size_t)B * sizeof(double)));
   HIPCK(hipStreamSynchronize(h->stream));
@@ -1178,7 +1187,7 @@ int svihmm_pred_logprob(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t
   CK(set_device(h));
   if (!h->have_mask) { out2[0] = NAN; out2[1] = 0.0; return 0; }
   const int var = pick_fb(h, B, Lm, false);
-  CK(prepare_ll(h, starts, B, Lm, flags, false, var == 3));
+  CK(prepare_ll(h, starts, B, Lm, flags, false, var == SVIHMM_FB_SCALED));
   CK(run_fb(h, B, Lm, var, false, false));
   h->lastB = B; h->lastLm = Lm;
   CK(ensure_q(h, B, Lm, h->stream));
@@ -1220,13 +1229,13 @@ static int estep_core(svihmm_ctx* h, const int64_t* starts, int B, int Lm, int i
   } else {
     // (the fused launch below can compute the emission tiles itself: launch_emission then does everything but launch)
     h->em_def.active = false;
-    h->em_defer_req = var == 3 && sweep_emission_ok(h, B, Lm, inner_off, inner_len, flags);
-    h->f32_fused_req = var == 3 && sweep_mixed_ok(h, B, Lm, inner_off, inner_len, flags);
-    const int prc = prepare_ll(h, starts, B, Lm, flags, true, var == 3);
+    h->em_defer_req = var == SVIHMM_FB_SCALED && sweep_emission_ok(h, B, Lm, inner_off, inner_len, flags);
+    h->f32_fused_req = var == SVIHMM_FB_SCALED && sweep_mixed_ok(h, B, Lm, inner_off, inner_len, flags);
+    const int prc = prepare_ll(h, starts, B, Lm, flags, true, var == SVIHMM_FB_SCALED);
     h->em_defer_req = false;
     h->f32_fused_req = false;
     if (prc) { h->em_def.active = false; return prc; }
-    const bool fused = var == 3 && sweep_stats_ok(h, B, Lm, inner_off, inner_len, flags);
+    const bool fused = var == SVIHMM_FB_SCALED && sweep_stats_ok(h, B, Lm, inner_off, inner_len, flags);
     if (h->eh_float && !fused) return fail("internal: float emission rows without the fused launch that reads them");
     if (!fused) CK(launch_emission_deferred(h));
     if (fused) {
@@ -1269,7 +1278,8 @@ int svihmm_estep_minibatch_ex(svihmm_ctx* h, const int64_t* starts, int32_t B, i
     }
     return 0;
   }
-  h->starts_sync_call = out_packed != nullptr && h->variant[9] != 2;    // (variant 9 = 2: the k_pull route)
+  // (SVIHMM_CENTRING_PULL_STARTS: the k_pull route)
+  h->starts_sync_call = out_packed != nullptr && h->variant[SVIHMM_VAR_CENTRING] != SVIHMM_CENTRING_PULL_STARTS;
   const int rc = estep_core(h, starts, B, Lm, inner_off, inner_len, flags);
   h->starts_sync_call = false;
   if (rc) return rc;
@@ -1302,21 +1312,46 @@ static int upload_staged(svihmm_ctx* h, void* dst, const void* src, size_t bytes
   return 0;
 }
 
+// ---- argument checks of the entry points that take windows of the resident observations ------
+// (svihmm_suffstats, svihmm_viterbi, svihmm_ffbs_windows; `fn`: the entry point's name.  Host work only: every one of
+//  them is through with these before its first device call.  The older entry points keep check_windows / prepare_ll.)
+// the model side: observations and an emission family of the globals' K and the observations' D
+static int check_window_model(const svihmm_ctx* h, const char* fn) {
+  const auto bad = [fn](const std::string& what) { return fail(std::string(fn) + ": " + what); };
+  if (h->T <= 0 || !h->obs.p) return bad("no observations: call svihmm_set_obs first");
+  if (!h->have_emission) return bad("no emission family: call svihmm_set_emission_niw / _diag / _cat first");
+  if (h->K != h->eK)
+    return bad("K of the globals (" + std::to_string(h->K) + ") differs from the emission family's K (" +
+               std::to_string(h->eK) + ")");
+  if (h->eD != h->D) return bad("emission D does not match obs D");
+  return 0;
+}
+// every window [starts[b], starts[b] + Lm) inside [0, T)
+static int check_window_range(const svihmm_ctx* h, const char* fn, const int64_t* starts, int B, int Lm) {
+  for (int b = 0; b < B; ++b)
+    if (starts[b] < 0 || starts[b] + Lm > h->T)
+      return fail(std::string(fn) + ": window " + std::to_string(b) + " reaches outside [0, T)");
+  return 0;
+}
+// a decoder's window batch (B, Lm positive): host lliks of exactly its shape, or the model side and the windows
+static int check_window_call(const svihmm_ctx* h, const char* fn, const int64_t* starts, int B, int Lm, uint32_t flags) {
+  if (flags & SVIHMM_USE_HOST_LLIKS) {
+    if (!h->have_host_ll || h->hostB != B || h->hostLm != Lm)
+      return fail(std::string(fn) + ": SVIHMM_USE_HOST_LLIKS without uploaded lliks of shape [B, Lm, K] (svihmm_set_lliks)");
+    return 0;
+  }
+  CK(check_window_model(h, fn));
+  if (!starts) return fail(std::string(fn) + ": starts is NULL");
+  return check_window_range(h, fn, starts, B, Lm);
+}
+
 int svihmm_suffstats(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t Lm, uint32_t flags,
                      const double* var_x, double* out_packed) {
   if (!h) return fail("svihmm_suffstats: NULL handle");
-  if (h->T <= 0 || !h->obs.p) return fail("svihmm_suffstats: no observations: call svihmm_set_obs first");
-  if (!h->have_emission)
-    return fail("svihmm_suffstats: no emission family: call svihmm_set_emission_niw / _diag / _cat first");
-  if (h->K != h->eK)
-    return fail("svihmm_suffstats: K of the globals (" + std::to_string(h->K) + ") differs from the emission "
-                "family's K (" + std::to_string(h->eK) + ")");
-  if (h->eD != h->D) return fail("svihmm_suffstats: emission D does not match obs D");
+  CK(check_window_model(h, "svihmm_suffstats"));
   if (B < 1 || Lm < 1) return fail("svihmm_suffstats: B and Lm must be positive");
   if (!starts || !var_x) return fail("svihmm_suffstats: starts / var_x is NULL");
-  for (int b = 0; b < B; ++b)
-    if (starts[b] < 0 || starts[b] + Lm > h->T)
-      return fail("svihmm_suffstats: window " + std::to_string(b) + " reaches outside [0, T)");
+  CK(check_window_range(h, "svihmm_suffstats", starts, B, Lm));
   CK(set_device(h));
   CK(wait_side_streams(h));
   const int K = h->K;
@@ -1532,7 +1567,7 @@ static int svi_refresh_emission(svihmm_ctx* h, int elbo_it, int lb_slot, hipEven
   h->theta_sy = SviSync{};
   h->lin_stale = true;
 #ifdef SVIHMM_MEASURE
-  if (h->variant[0] == 9) return 0;    // measurement only: no ELBO kernels at all
+  if (h->variant[SVIHMM_VAR_SVI_LOOP] == SVIHMM_SVI_LOOP_NO_ELBO) return 0;    // measurement only: no ELBO kernels at all
 #endif
   if (h->svi_flags && defer_elbo && elbo_it >= 0) {
     // launched by the next svihmm_svi_iteration behind its sweeps (svi_launch_elbo), or by whoever needs them first
@@ -1654,8 +1689,8 @@ static int svi_begin_common(svihmm_ctx* h, int K, int D, const double* prior_tra
     h->svi_elbo_cap = maxit;
   }
   for (int i = 0; i < maxit; ++i) h->svi_elbo[i] = NAN;
-  // device-side dependencies (variant[0] = 1: the stream-event choreography of rounds 2-4 instead)
-  h->svi_flags = h->variant[0] != 1;
+  // device-side dependencies (SVI_LOOP = SVIHMM_SVI_LOOP_EVENTS: the stream-event choreography of rounds 2-4 instead)
+  h->svi_flags = h->variant[SVIHMM_VAR_SVI_LOOP] != SVIHMM_SVI_LOOP_EVENTS;
   h->tgt_step = h->tgt_glob = h->tgt_theta = h->tgt_side = h->tgt_early = 0;
   h->elbo_pending = false;
   h->svi_period_ticks = 0; h->svi_cur_it = -1; h->svi_replaying = false; h->svi_recoveries = 0;
@@ -1809,7 +1844,7 @@ static int svi_iteration_impl(svihmm_ctx* h, int32_t it, const int64_t* starts, 
 // Leave the counters in the middle of a loop and carry on with the stream-event choreography (round 6).  Two
 // callers: a gate of the loop gave up (the status word is set: a tool that serialises kernels attached after
 // svihmm_svi_begin's probe, another process time-slicing the device, a partition too small for the loop's
-// kernels side by side), or the host decides to (`clean`: debug variant 0 = 2).  When a gate gave up the loop is
+// kernels side by side), or the host decides to (`clean`: SVIHMM_SVI_LOOP_LOSE_CONCURRENCY).  When a gate gave up the loop is
 // dead on the device: every later gate returned at once, the E-steps whose inputs were missing poisoned their
 // iteration and the global steps from that iteration on did not run (device_helpers.h) -- the loop's state is the
 // one after iteration p - 1, whole.  The iterations from p on are replayed from the host's log (the host runs at
@@ -1874,7 +1909,8 @@ int svihmm_svi_iteration(svihmm_ctx* h, int32_t it, const int64_t* starts, int32
   if (h->svi_flags) {
     // a gate of the loop gave up since the last call (mapped status word: a plain host read)
     if (h->pin_status && *(volatile int*)&h->pin_status[1] != 0) CK(svi_recover(h, false));
-    else if (h->variant[0] == 2 && it == 3) CK(svi_recover(h, true));     // (debug: "concurrency lost" between two iterations)
+    // (debug: "concurrency lost" between two iterations)
+    else if (h->variant[SVIHMM_VAR_SVI_LOOP] == SVIHMM_SVI_LOOP_LOSE_CONCURRENCY && it == 3) CK(svi_recover(h, true));
   }
   if (h->svi_flags) {
     // the iteration period, from the device stamps of an iteration that is certainly complete (eight back)
@@ -2225,23 +2261,7 @@ int svihmm_viterbi(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t Lm, 
   if (h->K > 256)
     return fail("svihmm_viterbi: K = " + std::to_string(h->K) + " > 256 not supported (one-byte back-pointers)");
   if (B < 1 || Lm < 1) return fail("svihmm_viterbi: B and Lm must be positive");
-  const bool host_ll = (flags & SVIHMM_USE_HOST_LLIKS) != 0;
-  if (host_ll) {
-    if (!h->have_host_ll || h->hostB != B || h->hostLm != Lm)
-      return fail("svihmm_viterbi: SVIHMM_USE_HOST_LLIKS without uploaded lliks of shape [B, Lm, K] (svihmm_set_lliks)");
-  } else {
-    if (h->T <= 0 || !h->obs.p) return fail("svihmm_viterbi: no observations: call svihmm_set_obs first");
-    if (!h->have_emission)
-      return fail("svihmm_viterbi: no emission family: call svihmm_set_emission_niw / _diag / _cat first");
-    if (h->K != h->eK)
-      return fail("svihmm_viterbi: K of the globals (" + std::to_string(h->K) + ") differs from the emission "
-                  "family's K (" + std::to_string(h->eK) + ")");
-    if (h->eD != h->D) return fail("svihmm_viterbi: emission D does not match obs D");
-    if (!starts) return fail("svihmm_viterbi: starts is NULL");
-    for (int b = 0; b < B; ++b)
-      if (starts[b] < 0 || starts[b] + Lm > h->T)
-        return fail("svihmm_viterbi: window " + std::to_string(b) + " reaches outside [0, T)");
-  }
+  CK(check_window_call(h, "svihmm_viterbi", starts, B, Lm, flags));
   CK(set_device(h));
   CK(wait_side_streams(h));
   CK(prepare_ll(h, starts, B, Lm, flags & (SVIHMM_MASK_AS_NAN | SVIHMM_USE_HOST_LLIKS), false));
@@ -2270,23 +2290,7 @@ int svihmm_ffbs_windows(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t
   if (!h->have_globals) return fail("svihmm_ffbs_windows: no globals: call svihmm_set_globals first");
   const int K = h->K;
   if (K > 256) return fail("svihmm_ffbs_windows: K = " + std::to_string(K) + " > 256 not supported");
-  const bool host_ll = (flags & SVIHMM_USE_HOST_LLIKS) != 0;
-  if (host_ll) {
-    if (!h->have_host_ll || h->hostB != B || h->hostLm != Lm)
-      return fail("svihmm_ffbs_windows: SVIHMM_USE_HOST_LLIKS without uploaded lliks of shape [B, Lm, K] (svihmm_set_lliks)");
-  } else {
-    if (h->T <= 0 || !h->obs.p) return fail("svihmm_ffbs_windows: no observations: call svihmm_set_obs first");
-    if (!h->have_emission)
-      return fail("svihmm_ffbs_windows: no emission family: call svihmm_set_emission_niw / _diag / _cat first");
-    if (K != h->eK)
-      return fail("svihmm_ffbs_windows: K of the globals (" + std::to_string(K) + ") differs from the emission "
-                  "family's K (" + std::to_string(h->eK) + ")");
-    if (h->eD != h->D) return fail("svihmm_ffbs_windows: emission D does not match obs D");
-    if (!starts) return fail("svihmm_ffbs_windows: starts is NULL");
-    for (int b = 0; b < B; ++b)
-      if (starts[b] < 0 || starts[b] + Lm > h->T)
-        return fail("svihmm_ffbs_windows: window " + std::to_string(b) + " reaches outside [0, T)");
-  }
+  CK(check_window_call(h, "svihmm_ffbs_windows", starts, B, Lm, flags));
   // logA[k][z_next]: -inf is probability zero; every column needs one finite entry to draw from
   for (int j = 0; j < K; ++j) {
     bool any = false;
@@ -2365,7 +2369,7 @@ int svihmm_generate(svihmm_ctx* h, int64_t T, int32_t K, int32_t D, const double
   {   // centre: the plain average of the state means (a point inside the data)
     std::vector<double> c((size_t)D, 0.0);
     h->center_deferred = h->have_emission && h->emis_cat;
-    if (h->variant[9] != 1 && !(h->have_emission && h->emis_cat)) {
+    if (h->variant[SVIHMM_VAR_CENTRING] != SVIHMM_CENTRING_OFF && !(h->have_emission && h->emis_cat)) {
       for (int k = 0; k < K; ++k)
         for (int d = 0; d < D; ++d) c[d] += means[(size_t)k * D + d] / K;
       for (int d = 0; d < D; ++d) if (!(c[d] > -1.7e308 && c[d] < 1.7e308)) c[d] = 0.0;
@@ -2531,10 +2535,10 @@ const char* svihmm_last_kernel_name(svihmm_ctx* h, int32_t slot) {
   return h->last_kernel[slot];
 }
 int svihmm_set_variant(svihmm_ctx* h, int32_t which, int32_t value) {
-  if (!h || which < 0 || which >= 24) return fail("svihmm_set_variant: bad arguments");
+  if (!h || which < 0 || which >= SVIHMM_NVARIANT) return fail("svihmm_set_variant: bad arguments");
 #ifndef SVIHMM_MEASURE
   // codes under which a call's results are invalid exist in the measurement build only
-  if (which == 7 && value == 9)
+  if (which == SVIHMM_VAR_SWEEP_FAMILY && value == SVIHMM_SWEEP_FAMILY_SKIP)
     return fail("svihmm_set_variant: measurement-only code (build with -DSVIHMM_MEASURE: make measure)");
 #endif
   h->variant[which] = value;

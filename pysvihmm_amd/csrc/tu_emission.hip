@@ -45,12 +45,15 @@ static int emd_buffers(svihmm_ctx* h, int K, uint4** uwp) {
 //  only when BOTH ends have their kernel -- otherwise it runs fp64, as the header promises)
 bool f32_wide_ok(const svihmm_ctx* h, int64_t n) {
   return !h->emis_diag && !h->emis_cat && h->K > 64 && h->K <= 256 && h->D <= 64 && h->niw.p != nullptr &&
-         h->variant[5] != 3 && h->variant[10] != 2 && (n >= cu_scaled(h, 32768) || h->variant[10] == 3) &&
+         h->variant[SVIHMM_VAR_EMISSION_ORBIT] != SVIHMM_EMISSION_ORBIT_F64 &&
+         h->variant[SVIHMM_VAR_STATS_TILING] != SVIHMM_STATS_TILING_F32_MFMA && bf16_batch_floor_ok(h, n) &&
          stats_bf16w_shape_ok(h, n);
 }
 // the step may ride in the theta builder's launch: NIW family, the split builder's widths, plain fp64 / fp32 records alike
 bool step_theta_ok(const svihmm_ctx* h, int K, int D) {
-  return D > 16 && D <= 32 && h->variant[13] != 2 && h->variant[13] != 3 && !(h->prec == 1 && emd_shape_ok(K, D) && !h->svi_active);
+  return D > 16 && D <= 32 && h->variant[SVIHMM_VAR_WIDE_SWEEPS] != SVIHMM_WIDE_SWEEPS_THETA_OLD &&
+         h->variant[SVIHMM_VAR_WIDE_SWEEPS] != SVIHMM_WIDE_SWEEPS_THETA_OWN_STEP &&
+         !(h->prec == 1 && emd_shape_ok(K, D) && !h->svi_active);
 }
 int launch_niw_to_theta(svihmm_ctx* h, int K, int D, double* logdet_out, const SviStepArgs* step) {
   CK(upload_feature_table(h, D, K));
@@ -111,7 +114,8 @@ int launch_niw_to_theta(svihmm_ctx* h, int K, int D, double* logdet_out, const S
     else if (emd) NIWW(64);
     else if (D <= 8) NIWW(8);
     else if (D <= 16) NIWW(16);
-    else if (D > 16 && D <= 32 && h->variant[13] != 2)     // (both halves of the wave at work: round 6; variant 13 = 2: the older builder)
+    // (both halves of the wave at work: round 6)
+    else if (D > 16 && D <= 32 && h->variant[SVIHMM_VAR_WIDE_SWEEPS] != SVIHMM_WIDE_SWEEPS_THETA_OLD)
       hipLaunchKernelGGL(k_niw_to_theta_wave32s, dim3(K), dim3(64), 0, h->stream, (const double*)dmu, (const double*)dsg,
                          (const double*)dka, (const double*)dnu, K, D, Kp, (double*)h->theta.p, dstatus, orbp, logdet_out,
                          uwp, h->theta_sy);
@@ -191,8 +195,11 @@ int launch_emission_deferred(svihmm_ctx* h) {
 // (k_emission_orbit: the only producer of the step-major layout)?  The same tests as in launch_emission below.
 bool emission_row_tile_orbit(const svihmm_ctx* h, int64_t n) {
   const int D = h->D;
-  if (h->emis_cat || h->emis_diag || h->K > 64 || D < 8 || D > 40 || D % 8 != 0 || h->variant[5] == 1) return false;
-  return !((n + 127) / 128 < h->ncu && h->variant[5] != 2 && h->variant[5] != 5);
+  if (h->emis_cat || h->emis_diag || h->K > 64 || D < 8 || D > 40 || D % 8 != 0 ||
+      h->variant[SVIHMM_VAR_EMISSION_ORBIT] == SVIHMM_EMISSION_ORBIT_OFF)
+    return false;
+  return !((n + 127) / 128 < h->ncu && h->variant[SVIHMM_VAR_EMISSION_ORBIT] != SVIHMM_EMISSION_ORBIT_128 &&
+           h->variant[SVIHMM_VAR_EMISSION_ORBIT] != SVIHMM_EMISSION_ORBIT_64);
 }
 // scaled: write (Eh, kexp) for the linear-domain sweeps instead of ll (K <= 64 only).
 // starts_dev / out: window starts and destination (default: the handle's buffers).
@@ -248,9 +255,10 @@ int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
     return 0;
   }
   // fp32 mode, large batches of a NIW model with K <= 64, D <= 32: the centred bf16 x 3 kernel
-  // (variant[5] = 3: the fp64 feature GEMM also in this mode)
+  // (SVIHMM_EMISSION_ORBIT_F64: the fp64 feature GEMM also in this mode)
   if (!h->emis_diag && scaled && (flags & SVIHMM_INT_ST32) && emb_shape_ok(K, D) && h->niw.p &&
-      h->variant[5] != 3 && min_lds == 0 && (n >= 8192 || h->variant[5] == 4)) {
+      h->variant[SVIHMM_VAR_EMISSION_ORBIT] != SVIHMM_EMISSION_ORBIT_F64 && min_lds == 0 &&
+      (n >= 8192 || h->variant[SVIHMM_VAR_EMISSION_ORBIT] == SVIHMM_EMISSION_ORBIT_BF16_SMALL)) {
     uint4* uwp = nullptr;
     const int64_t* pend = nullptr;
     int pend_n = 0;
@@ -285,7 +293,8 @@ int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
       hipLaunchKernelGGL(k_emission_bf16x3<2>, dim3((unsigned)((n + 255) / 256)), dim3(256), lds, stream,
                          (const double*)h->obs.p, mk, starts_dev, n, Lm, D, K, (const char*)uwp,
                          flags, (float*)out, kexp_out, ll0_out, pend ? (int64_t*)h->starts.p : (int64_t*)nullptr, pend_n);
-    else if (h->variant[5] == 8)        // (one group of four waves: the form of the round's first half)
+    // (one group of four waves: the form of the round's first half)
+    else if (h->variant[SVIHMM_VAR_EMISSION_ORBIT] == SVIHMM_EMISSION_ORBIT_BF16_128)
       hipLaunchKernelGGL(k_emission_bf16x3<1>, dim3((unsigned)((n + 127) / 128)), dim3(256), lds, stream,
                          (const double*)h->obs.p, mk, starts_dev, n, Lm, D, K, (const char*)uwp,
                          flags, (float*)out, kexp_out, ll0_out, pend ? (int64_t*)h->starts.p : (int64_t*)nullptr, pend_n);
@@ -308,7 +317,7 @@ int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
   // scaling pass follows): the centred bf16 x 3 kernel with 64-dimension pair records (round 5)
   const bool wide32 = !scaled && h->cur_f32 && K > 64;
   if (!h->emis_diag && ((scaled && (flags & SVIHMM_INT_ST32) && K <= 64) || wide32) && emd_shape_ok(K, D) && h->niw.p &&
-      h->variant[5] != 3 && min_lds == 0 && (n >= cu_scaled(h, 32768) || h->variant[10] == 3)) {
+      h->variant[SVIHMM_VAR_EMISSION_ORBIT] != SVIHMM_EMISSION_ORBIT_F64 && min_lds == 0 && bf16_batch_floor_ok(h, n)) {
     uint4* uwp = nullptr;
     CK(device_starts());
     CK(emd_buffers(h, K, &uwp));
@@ -339,9 +348,10 @@ int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
     HIPCK(hipGetLastError());
     return 0;
   }
-  int var = 2;      // (the VALU outer-product generation of round 1 is gone: variant[0] is ignored)
-  // scaled output, D % 8 == 0: the address-free orbit schedule (variant[5] = 1 keeps K1b)
-  if (!h->emis_diag && scaled && K <= 64 && D >= 8 && D <= 40 && D % 8 == 0 && h->variant[5] != 1 && min_lds == 0) {
+  int var = 2;      // (the VALU outer-product generation of round 1 is gone, and with it the knob that chose it)
+  // scaled output, D % 8 == 0: the address-free orbit schedule (SVIHMM_EMISSION_ORBIT_OFF keeps K1b)
+  if (!h->emis_diag && scaled && K <= 64 && D >= 8 && D <= 40 && D % 8 == 0 &&
+      h->variant[SVIHMM_VAR_EMISSION_ORBIT] != SVIHMM_EMISSION_ORBIT_OFF && min_lds == 0) {
     const int NT = Kp / 16, LEN = D + D / 2 + 1;
     const int nks = (D / 4) * (D / 2 + 1) + (D / 2 + 1 + 3) / 4;
     const int64_t* pend = nullptr;
@@ -358,8 +368,9 @@ int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
       h->orb_valid = true;
     }
     // minibatches (fewer than 32768 rows): 16-row workgroups, the four waves split the k-steps
-    // (k_emission_orbit_ks; variant[5] = 5: the 64-row form of round 3, 2: always 128 rows)
-    if ((n + 127) / 128 < h->ncu && h->variant[5] != 2 && h->variant[5] != 5) {
+    // (k_emission_orbit_ks; SVIHMM_EMISSION_ORBIT_64: the 64-row form of round 3, _128: always 128 rows)
+    if ((n + 127) / 128 < h->ncu && h->variant[SVIHMM_VAR_EMISSION_ORBIT] != SVIHMM_EMISSION_ORBIT_128 &&
+        h->variant[SVIHMM_VAR_EMISSION_ORBIT] != SVIHMM_EMISSION_ORBIT_64) {
       const int R0 = 3 * NT * 256 > 16 * LEN + 1 ? 3 * NT * 256 : ((16 * LEN + 1) & ~1);
       const size_t lds = (size_t)(R0 + 16 * NT + 16) * 8 + 16;
       dim3 grid((unsigned)((n + 15) / 16));
@@ -381,7 +392,7 @@ int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
       return 0;
     }
     // fewer than one 128-row workgroup per CU: 64-row workgroups
-    const int MTo = ((n + 127) / 128 < h->ncu && h->variant[5] != 2) ? 1 : 2;
+    const int MTo = ((n + 127) / 128 < h->ncu && h->variant[SVIHMM_VAR_EMISSION_ORBIT] != SVIHMM_EMISSION_ORBIT_128) ? 1 : 2;
     const int rows = 64 * MTo;
     // step-major Eh rows (prepare_ll: step_major_ok) leave only from here, for the whole batch into the handle's buffer
     const int smB = (h->step_major && own_out && own_starts) ? B : 0;
@@ -403,7 +414,7 @@ int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
   CK(device_starts());
   if (var == 2) {
     const int DS = (D + 2) | 1;
-    int MT = h->variant[3] > 0 ? h->variant[3] : 2;
+    int MT = h->variant[SVIHMM_VAR_EMISSION_MT] > 0 ? h->variant[SVIHMM_VAR_EMISSION_MT] : 2;
     if (MT != 2 && MT != 4) MT = 2;
     size_t lds = (size_t)(64 * MT) * DS * 8 + (size_t)h->Fp * 4 + (size_t)(64 * MT) * 9;
     if (lds > 150 * 1024 && MT == 4) { MT = 2; lds = (size_t)128 * DS * 8 + (size_t)h->Fp * 4 + 128 * 9; }
@@ -415,8 +426,8 @@ int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
       const int ntile = Kp / 16;
       int NT = (ntile % 4 == 0) ? 4 : (ntile % 2 == 0) ? 2 : 1;
       // wide models: eight state tiles per wave -- every generated A operand feeds 8 instead of 4
-      // MFMAs (variant[3] = 1: four)
-      if (!scaled && MT == 2 && ntile % 8 == 0 && h->variant[3] != 1) NT = 8;
+      // MFMAs (SVIHMM_EMISSION_MT_NT4: four)
+      if (!scaled && MT == 2 && ntile % 8 == 0 && h->variant[SVIHMM_VAR_EMISSION_MT] != SVIHMM_EMISSION_MT_NT4) NT = 8;
       if (scaled) { NT = ntile; MT = 2; }   // the workgroup must own whole rows (K <= 64)
       const int rows = 64 * MT;
       dim3 grid((unsigned)((n + rows - 1) / rows), ntile / NT);

@@ -13,7 +13,7 @@ extern "C" {
 // in groups of 20 than in groups of 16)
 static bool five_tile_shape(const svihmm_ctx* h) {
   const int Kp = h->Kp, Fp = h->Fp, D = h->D;
-  if (Kp != 64 || h->variant[10] != 0) return false;
+  if (Kp != 64 || h->variant[SVIHMM_VAR_STATS_TILING] != 0) return false;
   const int xk = (D + 1 + 15) / 16, mt = (Fp + Kp) / 16;
   if ((D + 1 + 7) / 8 > 9) return false;         // (the fused kernel's statistics stage: eight threads per row, <= 9 x columns each)
   if (xk > 3) return true;
@@ -46,8 +46,10 @@ static int pipe_stages(const svihmm_ctx* h, int B, int Lm, int ngrp, int* nchunk
 // the part of the test that does not depend on what prepare_ll decides for the batch
 static bool fused_shape_ok(const svihmm_ctx* h, int B, int Lq, int off, int Lm, uint32_t flags, int* nst_out) {
   const int K = h->K;
-  if (h->variant[4] == 1 || h->variant[1] != 0 || h->variant[2] == 1 || h->variant[2] == 2 || h->variant[7] != 0 ||
-      h->variant[8] != 0 || h->variant[15] != 0)
+  if (h->variant[SVIHMM_VAR_PIPELINE] == SVIHMM_PIPELINE_UNFUSED || h->variant[SVIHMM_VAR_STATS] != 0 ||
+      h->variant[SVIHMM_VAR_FB] == SVIHMM_FB_WAVE || h->variant[SVIHMM_VAR_FB] == SVIHMM_FB_LOG_MFMA ||
+      h->variant[SVIHMM_VAR_SWEEP_FAMILY] != 0 || h->variant[SVIHMM_VAR_STATS_CHUNKS] != 0 ||
+      h->variant[SVIHMM_VAR_WIDE_POSTERIOR] != 0)
     return false;
   if ((flags & SVIHMM_USE_HOST_LLIKS) || h->emis_cat || h->emis_diag) return false;
   if (K != 64 || h->Fp <= 0 || !five_tile_shape(h)) return false;      // (the sweep workgroups run the all-lanes-valid body)
@@ -68,22 +70,25 @@ bool sweep_stats_ok(const svihmm_ctx* h, int B, int Lq, int off, int Lm, uint32_
   // (measured, tools/r6_fused_check.py: from ~16 windows on the fused launch is ahead of sweeps + statistics one after the
   //  other -- 161 against 171 us at 64 windows --, below that the statistics launch is too short to be worth hiding;
   //  float MESSAGES (cur_f32) keep the mode's own sweep + bf16 statistics kernels -- the fp32 mode's minibatches come
-  //  here as fp64 batches behind float emission rows (sweep_mixed_ok); variant 4 = 3 forces the fused launch for every
-  //  batch it can take -- tests)
-  if (h->variant[4] != 3 && (B < 16 || h->cur_f32)) return false;
+  //  here as fp64 batches behind float emission rows (sweep_mixed_ok); SVIHMM_PIPELINE_FUSED_ALL forces the fused
+  //  launch for every batch it can take -- tests)
+  if (h->variant[SVIHMM_VAR_PIPELINE] != SVIHMM_PIPELINE_FUSED_ALL && (B < 16 || h->cur_f32)) return false;
   return true;
 }
 // fp32 mode: will this batch take the fused launch with float emission rows and fp64 messages (asked BEFORE prepare_ll)?
-// The same thresholds as the fp64 batch's; variant 4 = 6: never (the mode's own sweep + bf16 statistics kernels).
+// The same thresholds as the fp64 batch's; SVIHMM_PIPELINE_F32_OWN: never (the mode's own sweep + bf16 statistics kernels).
 bool sweep_mixed_ok(const svihmm_ctx* h, int B, int Lq, int off, int Lm, uint32_t flags) {
   int nst = 0;
-  if (h->prec != 1 || !h->f32_ok || h->variant[4] == 6 || h->variant[4] == 3) return false;
+  if (h->prec != 1 || !h->f32_ok || h->variant[SVIHMM_VAR_PIPELINE] == SVIHMM_PIPELINE_F32_OWN ||
+      h->variant[SVIHMM_VAR_PIPELINE] == SVIHMM_PIPELINE_FUSED_ALL)
+    return false;
   if (!fused_shape_ok(h, B, Lq, off, Lm, flags, &nst)) return false;
   return B >= 16;
 }
 // Will the fused launch of this batch also compute the emission tiles (asked BEFORE prepare_ll; launch_emission holds
 // its launch back only on the fp64 minibatch path whose tile the fused kernel carries)?
-// OFF unless asked for (variant 4 = 3: everything the kernel can take, tests; 5: the automatic thresholds + emission).
+// OFF unless asked for (SVIHMM_PIPELINE_FUSED_ALL: everything the kernel can take, tests; _FUSED_EMISSION: the automatic
+// thresholds + emission).
 // Measured at 64 windows (tools/r6_fused_trace.py, r6_fused_check.py, r4_svi_probe.py; profiles/r06g_*): the statistics
 // workgroups finish the 1028 tiles 46 - 55 us into the launch (first tile 15 us: 295 KB of theta operands per workgroup,
 // 61 MB through the L2s; then 8.5 us a tile against 3.9 us of matrix work -- one wave per SIMD hides nothing) and the
@@ -92,10 +97,13 @@ bool sweep_mixed_ok(const svihmm_ctx* h, int B, int Lq, int off, int Lm, uint32_
 // the same L2 traffic (every tile re-reads the 270 KB orbit: 277 MB in 39 us = 7.1 TB/s), not by latency.
 bool sweep_emission_ok(const svihmm_ctx* h, int B, int Lq, int off, int Lm, uint32_t flags) {
   int nst = 0;
-  if ((h->variant[4] != 3 && h->variant[4] != 5) || h->variant[5] != 0 || !fused_shape_ok(h, B, Lq, off, Lm, flags, &nst)) return false;
+  if ((h->variant[SVIHMM_VAR_PIPELINE] != SVIHMM_PIPELINE_FUSED_ALL &&
+       h->variant[SVIHMM_VAR_PIPELINE] != SVIHMM_PIPELINE_FUSED_EMISSION) ||
+      h->variant[SVIHMM_VAR_EMISSION_ORBIT] != 0 || !fused_shape_ok(h, B, Lq, off, Lm, flags, &nst))
+    return false;
   if (h->prec == 1 && h->f32_ok) return false;           // (fp32 mode: its own emission kernel on the bf16 pipe)
   if (h->D > 32 || h->D % 8 != 0) return false;          // (the resident theta operands of the tile: <= 144 k-steps)
-  if (h->variant[4] != 3 && B < 16) return false;
+  if (h->variant[SVIHMM_VAR_PIPELINE] != SVIHMM_PIPELINE_FUSED_ALL && B < 16) return false;
   const int64_t ntile = ((int64_t)B * Lq + 15) / 16;
   return (ntile + nst - 1) / nst <= WLR_MAX_BANDS;
 }
@@ -264,8 +272,8 @@ int launch_sweep_stats(svihmm_ctx* h, int B, int Lq, int off, int Lm, uint32_t f
   } while (0)
 #define FZXM(RNV) do { if (xk <= 5) FZM(5, RNV); else FZM(9, RNV); } while (0)
     // (fp64 messages, transition expectations inside a float's range: the sweeps re-normalise every fourth step --
-    //  kernels_wave_linr.h, RN; variant 16 = 1 keeps every step)
-    const bool rn4 = !h->cur_f32 && h->f32_ok && h->variant[16] != 1;
+    //  kernels_wave_linr.h, RN; SVIHMM_RENORM4_OFF keeps every step)
+    const bool rn4 = !h->cur_f32 && h->f32_ok && h->variant[SVIHMM_VAR_RENORM4] != SVIHMM_RENORM4_OFF;
     if (h->eh_float) {       // fp32 mode: float emission rows, fp64 messages and statistics
       if (emw || h->cur_f32) return fail("internal: mixed-format fused launch in the wrong state");
       if (rn4) FZXM(4); else FZXM(1);

@@ -165,7 +165,9 @@ static int launch_lin_init(svihmm_ctx* h, int b0, int nb, int Lm, hipStream_t st
 // minibatch-sized batches, 16 < K <= 64: the kernels that split one window over one wave's registers (fp64,
 // k_wave_linr) or four waves (fp32 storage, k_wave_lin4)
 static bool minibatch_wave_kernel(const svihmm_ctx* h, int K, int nb, int Lm) {
-  if (K <= 16 || K > 64 || nb >= lin_wave_max(h) || h->variant[7] == 2 || h->variant[7] == 3) return false;
+  if (K <= 16 || K > 64 || nb >= lin_wave_max(h) || h->variant[SVIHMM_VAR_SWEEP_FAMILY] == SVIHMM_SWEEP_FAMILY_TILES ||
+      h->variant[SVIHMM_VAR_SWEEP_FAMILY] == SVIHMM_SWEEP_FAMILY_WAVE_LIN)
+    return false;
   return h->cur_f32 ? nb <= lin_wave4_max(h) : (nb <= lin_waver_max(h) && Lm <= (1 << 20));
 }
 // SVI loop on counters (svihmm_hip.hip, svi_globals): those two kernels wait for the side stream's globals
@@ -181,7 +183,8 @@ SviSync sweep_gate(svihmm_ctx* h, hipStream_t stream) {
     sy.ticks = h->svi_ticks;
     sy.poison = (unsigned*)h->svi_sync.p + 16 * 5;
     sy.poison_val = SVI_POISON_BASE - (unsigned)(h->svi_cur_it < 0 ? 0 : h->svi_cur_it);
-    if (h->variant[0] == 3 && h->svi_cur_it == 3) {      // (debug: a count that never comes, 2 ms bound -- svi_recover's test)
+    // (debug: a count that never comes, 2 ms bound -- svi_recover's test)
+    if (h->variant[SVIHMM_VAR_SVI_LOOP] == SVIHMM_SVI_LOOP_STUCK_GATE && h->svi_cur_it == 3) {
       sy.gate_tgt += 1000u;
       sy.ticks = (unsigned long long)(2.0 * (h->wall_clock_khz > 0.0 ? h->wall_clock_khz : 100000.0));
     }
@@ -201,10 +204,10 @@ int launch_fb_lin_range(svihmm_ctx* h, int b0, int nb, int Lm, hipStream_t strea
   const int K = h->K;
   const bool wave_kernel = minibatch_wave_kernel(h, K, nb, Lm);
   if (h->svi_flags && h->in_svi_estep && stream == h->stream && !wave_kernel) CK(wait_globals(h));
-  // measurement only (tools/r4_overlap_probe.py): variant[7] = 9 skips the sweep launch -- the
+  // measurement only (tools/r4_overlap_probe.py): SVIHMM_SWEEP_FAMILY_SKIP skips the sweep launch -- the
   // statistics then read the previous step's messages; bounds what hiding the sweeps could give
 #ifdef SVIHMM_MEASURE
-  if (h->variant[7] == 9) return 0;
+  if (h->variant[SVIHMM_VAR_SWEEP_FAMILY] == SVIHMM_SWEEP_FAMILY_SKIP) return 0;
 #endif
   const int NW = (K + 15) / 16;
   const bool full = (K == 16 * NW);
@@ -260,7 +263,7 @@ int launch_fb_lin_range(svihmm_ctx* h, int b0, int nb, int Lm, hipStream_t strea
       HIPCK(hipGetLastError());
       return 0;
     }
-    if (nb < lin_wave_max(h) && h->variant[7] != 2) {
+    if (nb < lin_wave_max(h) && h->variant[SVIHMM_VAR_SWEEP_FAMILY] != SVIHMM_SWEEP_FAMILY_TILES) {
       dim3 gw((unsigned)nb, 2);
 #define WLF(KM, FK) hipLaunchKernelGGL((k_wave_lin<KM, FK, float>), gw, dim3(64), 0, stream, Ef, kx, (const double*)h->Aexp.p, \
                                        (const double*)h->AexpT.p, mi, l0, l0s, Lm, K, af, bf, hx,   \
@@ -272,7 +275,8 @@ int launch_fb_lin_range(svihmm_ctx* h, int b0, int nb, int Lm, hipStream_t strea
       //  arithmetic: 278 against 303 ns per step, but over 257 steps the statistics drift to 1.2e-4 of the fp64
       //  oracle -- inside the mode's 1e-3, above this suite's 1e-4 canary; the fp32 mode keeps the four-wave
       //  kernel, which computes in fp64 on float storage)
-      if (wave_kernel && nb <= lin_waver_max(h) && Lm <= (1 << 20) && h->variant[7] != 4) {
+      if (wave_kernel && nb <= lin_waver_max(h) && Lm <= (1 << 20) &&
+          h->variant[SVIHMM_VAR_SWEEP_FAMILY] != SVIHMM_SWEEP_FAMILY_WAVE_LIN4) {
         // (round 5, second half: the one-wave register-resident kernel with fp64 arithmetic on the float storage)
         const SviSync gsy = sweep_gate(h, stream);
         hipLaunchKernelGGL((k_wave_linr<float, double>), gw, dim3(64), 0, stream, Ef, kx, (const double*)h->Aexp.p,
@@ -299,22 +303,22 @@ int launch_fb_lin_range(svihmm_ctx* h, int b0, int nb, int Lm, hipStream_t strea
     HIPCK(hipGetLastError());
     return 0;
   }
-  if (K <= 64 && nb < lin_wave_max(h) && h->variant[7] != 2) {
+  if (K <= 64 && nb < lin_wave_max(h) && h->variant[SVIHMM_VAR_SWEEP_FAMILY] != SVIHMM_SWEEP_FAMILY_TILES) {
     // small batches: one wavefront per (window, direction)
     dim3 gw((unsigned)nb, 2);
 #define WL(KM, FK) hipLaunchKernelGGL((k_wave_lin<KM, FK>), gw, dim3(64), 0, stream, Eh, kx, (const double*)h->Aexp.p, \
                                       (const double*)h->AexpT.p, mi, l0, l0s, Lm, K, ah, bh, hx,  \
                                       gx, llb, lz, zf)
     // up to a few hundred windows the chip is far from full with one wave per (window,
-    // direction): split each window's source states over four waves (variant[7] = 3: off)
+    // direction): split each window's source states over four waves (SVIHMM_SWEEP_FAMILY_WAVE_LIN: off)
     // minibatch-sized batches, K > 16 (round 5): one wave per (window, direction) with the mat-vec in registers
     // (k_wave_linr; it replaces round 3's four-wave k_wave_lin4<64, double>: 316 against 319 ns per step with a
-    // quarter of the waves and no LDS exchange; variant[7] = 3: the LDS-broadcast one-wave kernel below)
+    // quarter of the waves and no LDS exchange; SVIHMM_SWEEP_FAMILY_WAVE_LIN: the LDS-broadcast one-wave kernel below)
     if (wave_kernel) {
       const SviSync gsy = sweep_gate(h, stream);
       // (transition expectations inside a float's range: re-normalised every fourth step -- kernels_wave_linr.h, RN;
-      //  variant 16 = 1: every step)
-      if (h->f32_ok && h->variant[16] != 1)
+      //  SVIHMM_RENORM4_OFF: every step)
+      if (h->f32_ok && h->variant[SVIHMM_VAR_RENORM4] != SVIHMM_RENORM4_OFF)
         hipLaunchKernelGGL((k_wave_linr<double, double, 4>), gw, dim3(64), 0, stream, Eh, kx, (const double*)h->Aexp.p,
                            (const double*)h->AexpT.p, mi, l0, l0s, Lm, K, ah, bh, hx, gx, llb, lz, zf, gsy);
       else
@@ -362,13 +366,18 @@ int launch_fb_lin_range(svihmm_ctx* h, int b0, int nb, int Lm, hipStream_t strea
                        nb, Lm, K, ah, bh, hx, gx, llb, lz, zf);                                            \
   } while (0)
     // more 16-window workgroups than CUs: 32 windows per workgroup share the streamed transition
-    // tile (variant[13] = 1: off)
-    const bool w32 = 2 * ((nb + 15) / 16) > h->ncu && h->variant[13] != 1;     // more workgroups than CUs
+    // tile (SVIHMM_WIDE_SWEEPS_16: off)
+    // (more workgroups than CUs)
+    const bool w32 = 2 * ((nb + 15) / 16) > h->ncu && h->variant[SVIHMM_VAR_WIDE_SWEEPS] != SVIHMM_WIDE_SWEEPS_16;
     // 128 < K <= 192: twelve waves of one state tile (three per SIMD; the eight two-tile waves would
-    // run four empty tiles: 4.85 against 6.1 ms at K = 192, D = 32, T = 1e6).  variant[7] = 1: one
-    // tile per wave for every K, 2: two tiles per wave for every K
-    if (NW <= 12 && h->variant[7] != 2) { if (K == 192) SWPX(12, true, true); else SWPX(12, false, true); }
-    else if (h->variant[7] == 1) { if (K == 256) SWPX(16, true, true); else SWPX(16, false, true); }
+    // run four empty tiles: 4.85 against 6.1 ms at K = 192, D = 32, T = 1e6).  SVIHMM_SWEEP_FAMILY_ONE_TILE:
+    // one tile per wave for every K, _TILES: two tiles per wave for every K
+    if (NW <= 12 && h->variant[SVIHMM_VAR_SWEEP_FAMILY] != SVIHMM_SWEEP_FAMILY_TILES) {
+      if (K == 192) SWPX(12, true, true); else SWPX(12, false, true);
+    }
+    else if (h->variant[SVIHMM_VAR_SWEEP_FAMILY] == SVIHMM_SWEEP_FAMILY_ONE_TILE) {
+      if (K == 256) SWPX(16, true, true); else SWPX(16, false, true);
+    }
     else if (w32) { if (K == 256) SWP2(true, 2); else SWP2(false, 2); }
     else if (K == 256) SWP2(true, 1); else SWP2(false, 1);
 #undef SWP2
@@ -416,7 +425,7 @@ int launch_sum_lb(svihmm_ctx* h, int B, hipStream_t stream) {
 // that the sequential boundary scan (S2) stays short (S1's work does not depend on it)
 static int chain_len(int Lm) { return Lm >= 512 * 1024 ? 1024 : 256; }
 bool use_chain(const svihmm_ctx* h, int B, int Lm) {
-  return B == 1 && h->K <= 256 && Lm >= 2048 && h->variant[6] != 1 && !h->exact_log;
+  return B == 1 && h->K <= 256 && Lm >= 2048 && h->variant[SVIHMM_VAR_CHAIN] != SVIHMM_CHAIN_OFF && !h->exact_log;
 }
 int launch_fb_chain(svihmm_ctx* h, int Lm, bool total) {
   const int K = h->K, T = Lm, L = chain_len(Lm);
@@ -657,7 +666,7 @@ int materialise(svihmm_ctx* h, int b0, int nb) {
 struct FfbsPlan { bool blocked; int KS, Ls, Cs; size_t extra; };
 static FfbsPlan ffbs_plan(const svihmm_ctx* h, int64_t T, int K) {
   FfbsPlan pl;
-  pl.blocked = K <= 256 && T >= 1024 && h->variant[6] != 1;
+  pl.blocked = K <= 256 && T >= 1024 && h->variant[SVIHMM_VAR_CHAIN] != SVIHMM_CHAIN_OFF;
   pl.KS = K <= 16 ? 16 : K <= 32 ? 32 : K <= 64 ? 64 : 256;      // path entries per row
   pl.Ls = T >= 65536 ? 512 : 256;
   pl.Cs = (int)((T + pl.Ls - 1) / pl.Ls);

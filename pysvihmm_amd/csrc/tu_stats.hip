@@ -12,7 +12,7 @@ extern "C" {
 // The small instances exist for the staging widths narrow observations need (xk <= 3) only.
 static int stats_mt(const svihmm_ctx* h) {
   const int Kp = h->Kp, Fp = h->Fp, D = h->D;
-  if (Kp > 64 || h->variant[10] == 1) return 5;
+  if (Kp > 64 || h->variant[SVIHMM_VAR_STATS_TILING] == SVIHMM_STATS_TILING_FIVE) return 5;
   const int NSPLIT = (Kp / 16 == 4) ? 2 : 1;
   const int xk = (D + 1 + 8 * NSPLIT - 1) / (8 * NSPLIT);
   const int mt = (Fp + Kp) / 16;
@@ -25,13 +25,14 @@ static int stats_mt(const svihmm_ctx* h) {
 // 128 chunks x 2 feature groups at the bench shape; more chunks only add partial-sum traffic
 // (64 windows: statistics + finalize 74 -> 56 us, tools/chunk_sweep.py).  chunk = multiple of ST_RB.
 // fp32 mode, K = 64 / D <= 32 / whole 32-feature tiles: the statistics GEMM on the bf16 matrix pipe
-// (k_stats_bf16x3; variant[10] = 2: the fp32-input MFMA kernel instead)
+// (k_stats_bf16x3; SVIHMM_STATS_TILING_F32_MFMA: the fp32-input MFMA kernel instead)
 static bool stats_bf16_ok(const svihmm_ctx* h, int64_t n) {
   // (batches below 32 768 rows -- the 64-window minibatch -- keep the fp32-input kernel's many small
   //  workgroups: one 8-wave workgroup per chunk would leave most CUs idle)
   return h->cur_f32 && h->lin_mode && !h->q_valid && h->K == 64 && h->Kp == 64 && h->D <= 32 && h->Fp > 0 &&
-         h->Fp % 32 == 0 && !h->emis_cat && !h->emis_diag && h->variant[10] != 2 && h->variant[1] == 0 &&
-         (n >= cu_scaled(h, 32768) || h->variant[10] == 3);     // (variant[10] = 3: tests force it on small batches)
+         h->Fp % 32 == 0 && !h->emis_cat && !h->emis_diag &&
+         h->variant[SVIHMM_VAR_STATS_TILING] != SVIHMM_STATS_TILING_F32_MFMA && h->variant[SVIHMM_VAR_STATS] == 0 &&
+         bf16_batch_floor_ok(h, n);     // (SVIHMM_STATS_TILING_BF16_SMALL: tests force it on small batches)
 }
 // ... and k_stats_bf16x3w (round 5) for what that kernel does not take: wide models (64 < K <= 256) and more
 // than 22 feature tiles (D > 32); D <= 64 (two stage buffers of x^T + six planes in 160 KB of LDS)
@@ -59,9 +60,12 @@ bool stats_bf16w_shape_ok(const svihmm_ctx* h, int64_t n) {
   // (D <= 64: the kernel stages x columns 0..63 from the observations and treats columns 64, 65 as the ones / zero
   //  columns -- found by the fuzz at K = 64, D = 79 with the floors lifted)
   return h->K <= 256 && h->D <= 64 && h->Kp % 64 == 0 && h->Fp > 0 && !h->emis_cat &&
-         !h->emis_diag && h->variant[10] != 2 && h->variant[1] == 0 && bw_lds(h) <= 160 * 1024 &&
-         (h->K > 64 || ((h->Fp + 31) / 32 + 2 > 24 && (n >= cu_scaled(h, 32768) || h->variant[10] == 3)) ||
-          (n >= cu_scaled(h, 8192) && n < cu_scaled(h, 32768) && h->variant[10] != 3));      // (minibatch-sized batches at K = 64: the six-tile groups)
+         !h->emis_diag && h->variant[SVIHMM_VAR_STATS_TILING] != SVIHMM_STATS_TILING_F32_MFMA &&
+         h->variant[SVIHMM_VAR_STATS] == 0 && bw_lds(h) <= 160 * 1024 &&
+         (h->K > 64 || ((h->Fp + 31) / 32 + 2 > 24 && bf16_batch_floor_ok(h, n)) ||
+          // (minibatch-sized batches at K = 64: the six-tile groups)
+          (n >= cu_scaled(h, 8192) && n < cu_scaled(h, 32768) &&
+           h->variant[SVIHMM_VAR_STATS_TILING] != SVIHMM_STATS_TILING_BF16_SMALL));
 }
 static bool stats_bf16w_ok(const svihmm_ctx* h, int64_t n) {
   return h->cur_f32 && h->lin_mode && !h->q_valid && stats_bf16w_shape_ok(h, n);
@@ -115,20 +119,21 @@ int launch_stats_range(svihmm_ctx* h, int b0, int nb, int Lq, int off, int Lm, u
   const uint8_t* mk = h->have_mask ? (const uint8_t*)h->mask.p : nullptr;
   CK(ensure_starts_pulled(h));    // (an E-step without an emission launch -- host lliks -- still owes the device copy)
   const int64_t* starts_dev = (starts_src ? starts_src : (const int64_t*)h->starts.p) + b0;
-  int var = h->variant[1];
-  if (var != 2) var = 3;      // (2: the double-buffered generation; the VALU generation of round 1 is gone)
-  if (var == 3) {   // feasibility of the pipelined kernel (same test as below)
+  int var = h->variant[SVIHMM_VAR_STATS];
+  if (var != SVIHMM_STATS_DBUF) var = SVIHMM_STATS_PIPELINED;      // (the VALU generation of round 1 is gone)
+  if (var == SVIHMM_STATS_PIPELINED) {   // feasibility of the pipelined kernel (same test as below)
     const int KpW = Kp > 64 ? 64 : Kp;
     const int TPR = 8 * ((KpW / 16 == 4) ? 2 : 1);
     const size_t lds = ((size_t)(D + 3 + KpW) * ST_CC + 2 * (size_t)ST_RB * ST_QS(KpW)) * 8 + 4 * ST_RB * sizeof(StRow4);
-    if (lds > 150 * 1024 || (D + 1 + TPR - 1) / TPR > 9 || (Kp > 64 && Kp % 64 != 0)) var = 2;
+    if (lds > 150 * 1024 || (D + 1 + TPR - 1) / TPR > 9 || (Kp > 64 && Kp % 64 != 0)) var = SVIHMM_STATS_DBUF;
   }
   // scaled sweeps: the pipelined kernel forms q = ah * bh * scale itself; the others read var_x
   // (wide models too, round 3: the separate posterior pass costs more than the second operand's loads;
-  //  variant[15] = 1: K > 64 through q as before)
-  // (variant[15] = 2, measurement only: posteriors by their own pass + the GEMM on plain q for every K)
-  const bool lin = !qsrc && h->lin_mode && !h->q_valid && var == 3 && (Kp <= 64 || h->variant[15] != 1) &&
-                   h->variant[15] != 2;
+  //  SVIHMM_WIDE_POSTERIOR_PASS: K > 64 through q as before)
+  // (SVIHMM_WIDE_POSTERIOR_PASS_ALL, measurement only: posteriors by their own pass + the GEMM on plain q for every K)
+  const bool lin = !qsrc && h->lin_mode && !h->q_valid && var == SVIHMM_STATS_PIPELINED &&
+                   (Kp <= 64 || h->variant[SVIHMM_VAR_WIDE_POSTERIOR] != SVIHMM_WIDE_POSTERIOR_PASS) &&
+                   h->variant[SVIHMM_VAR_WIDE_POSTERIOR] != SVIHMM_WIDE_POSTERIOR_PASS_ALL;
   if (h->lin_mode && !lin && !qsrc) CK(ensure_q(h, h->curB, Lq, stream));
   const size_t qo = (size_t)b0 * Lq * K;
   const double* qv = (qsrc ? qsrc : (const double*)(lin ? h->la.p : h->q.p)) + qo;   // (reassigned: see the transition blocks)
@@ -144,7 +149,7 @@ int launch_stats_range(svihmm_ctx* h, int b0, int nb, int Lq, int off, int Lm, u
   double* partv = (double*)h->part.p + (size_t)chunk_base * Ftot * Kp;
   {
     ProfScope ps(h, KS_STATS, stream);
-    if (var == 3) {
+    if (var == SVIHMM_STATS_PIPELINED) {
       // pipelined VGPR-form GEMM.  K <= 64: all tiles (statistics + transition) in one launch.
       // K > 64: state groups of 64 in grid.z for the emission-statistics tiles; the K x K
       // transition tiles (which need q[t-1] of ALL states as operand rows) go to k_stats_mfma.
@@ -178,7 +183,7 @@ int launch_stats_range(svihmm_ctx* h, int b0, int nb, int Lq, int off, int Lm, u
                            starts_dev, n, Lm, D, K, KpF, Fp, F, (const int*)h->fab.p, (const float*)h->la.p + qo,
                            (const float*)h->lb.p + qo, rpc, flags, Lq, off, partv, hxv, gxv, zfv, TPG);
       }
-      else if (lds > 150 * 1024 || xk > 9 || (big && Kp % 64 != 0)) var = 2;
+      else if (lds > 150 * 1024 || xk > 9 || (big && Kp % 64 != 0)) var = SVIHMM_STATS_DBUF;
       else if (lin && h->cur_f32 && !big && stats_bf16_ok(h, n) && rpc % SB_ROWS == 0 && nchunk * rpc >= n) {
         const size_t xb = (((size_t)(D + 2) * SB_XRS * 4) + 15) & ~(size_t)15;
         const size_t ldsb = 2 * (xb + 6 * (size_t)64 * SB_QRS * 2) + 3 * SB_ROWS * sizeof(SbRow);
@@ -223,7 +228,7 @@ int launch_stats_range(svihmm_ctx* h, int b0, int nb, int Lq, int off, int Lm, u
         const int xk3 = xk <= 1 ? 1 : xk <= 3 ? 3 : xk <= 5 ? 5 : 9;      // (the XK instance ST3T picks below)
         const size_t lds3 = ((size_t)(D + 3 + KpW) * (3 * ST_CS + 2) + 3 * (size_t)ST_RB * ST_QS3(KpW, xk3)) * 8 +
                             4 * ST_RB * sizeof(StRow4) + 16;
-        const bool tb = NTt == 4 && MTs == 5 && lds3 <= 160 * 1024 && h->variant[12] != 1;
+        const bool tb = NTt == 4 && MTs == 5 && lds3 <= 160 * 1024 && h->variant[SVIHMM_VAR_STATS_LDS3] != SVIHMM_STATS_LDS3_OFF;
         if (tb) {
 #define ST3TL(XKV, LN)                                                                                         \
   do {                                                                                                         \
@@ -264,8 +269,8 @@ int launch_stats_range(svihmm_ctx* h, int b0, int nb, int Lq, int off, int Lm, u
         if (big) {
           // transition tiles: one (64 MTt) x 64 (previous state, state) block per workgroup; two
           // m-tiles per wave where the state count allows (round 3: 4 MFMAs on 4 LDS reads per
-          // k-step instead of 2 on 4; variant[14] = 1: one)
-          const int MTt = (Kp % 128 == 0 && h->variant[14] != 1) ? 2 : 1;
+          // k-step instead of 2 on 4; SVIHMM_WIDE_TRAN_BLOCK_64: one)
+          const int MTt = (Kp % 128 == 0 && h->variant[SVIHMM_VAR_WIDE_TRAN_BLOCK] != SVIHMM_WIDE_TRAN_BLOCK_64) ? 2 : 1;
           dim3 g2((unsigned)nchunk, Kp / (64 * MTt), Kp / 64);
           const size_t ldt = ((size_t)(2 + 64 * MTt) * ST_CC + 2 * (size_t)ST_RB * ST_QS_TR(64, MTt)) * 8 + 4 * ST_RB * sizeof(StRow4);
           const size_t ldt3 = ((size_t)(2 + 64 * MTt) * (3 * ST_CS + 2) + 3 * (size_t)ST_RB * ST_QS_TR(64, MTt)) * 8 +
@@ -290,7 +295,7 @@ int launch_stats_range(svihmm_ctx* h, int b0, int nb, int Lq, int off, int Lm, u
   } while (0)
           // (no obs columns in these tiles: XK = 1 always, the three-buffer loop always fits)
           if (lin) qv = qoutv;      // written by the feature launch above
-          if (h->variant[12] != 1) { if (MTt == 2) STT3(2, false); else STT3(1, false); }
+          if (h->variant[SVIHMM_VAR_STATS_LDS3] != SVIHMM_STATS_LDS3_OFF) { if (MTt == 2) STT3(2, false); else STT3(1, false); }
           else { if (MTt == 2) STT(2, false); else STT(1, false); }
           if (lin && off == 0 && Lm == Lq && b0 == 0 && nb == h->curB) h->q_valid = true;
 #undef STT3
@@ -298,7 +303,7 @@ int launch_stats_range(svihmm_ctx* h, int b0, int nb, int Lq, int off, int Lm, u
         }
       }
     }
-    if (var == 2) {
+    if (var == SVIHMM_STATS_DBUF) {
       const int ntile = Kp / 16;
       const int NT = (ntile % 4 == 0) ? 4 : (ntile % 2 == 0) ? 2 : 1;
       const int MT = 3;
@@ -401,7 +406,7 @@ static int launch_stats_cat(svihmm_ctx* h, int B, int Lq, int off, int Lm, uint3
 
 int launch_stats(svihmm_ctx* h, int B, int Lq, int off, int Lm, uint32_t flags) {
   if (h->emis_cat) return launch_stats_cat(h, B, Lq, off, Lm, flags);
-  const StatsPlan plan = stats_plan(h, (int64_t)B * Lm, h->variant[8]);
+  const StatsPlan plan = stats_plan(h, (int64_t)B * Lm, h->variant[SVIHMM_VAR_STATS_CHUNKS]);
   CK(ensure_stats(h, plan.nchunk));
   CK(launch_stats_range(h, 0, B, Lq, off, Lm, flags, plan, 0, h->stream));
   return launch_stats_finalize(h, plan.nchunk, h->stream);
@@ -416,7 +421,7 @@ int launch_stats_posteriors(svihmm_ctx* h, const double* q, const int64_t* start
   if (h->emis_cat) {
     CK(launch_stats_cat(h, B, Lm, 0, Lm, flags, q, starts_dev));
   } else {
-    const StatsPlan plan = stats_plan(h, (int64_t)B * Lm, h->variant[8]);
+    const StatsPlan plan = stats_plan(h, (int64_t)B * Lm, h->variant[SVIHMM_VAR_STATS_CHUNKS]);
     // (the pipelined GEMM addresses a chunk's q rows with 32-bit element offsets)
     if ((int64_t)(Lm + plan.rpc) * h->Kp >= ((int64_t)1 << 31))
       return fail("svihmm_suffstats: window too long for the statistics GEMM's 32-bit row offsets");

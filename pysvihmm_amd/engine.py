@@ -677,9 +677,8 @@ class HipEngine(object):
         return self._lib.svihmm_last_kernel_name(self._h, names.index(slot_name)).decode()
 
     def set_variant(self, which, value):
-        # ("svi_loop", slot 0 -- 1: the resident SVI loop on stream events instead of device-side counters;
-        #  include/svihmm_debug.h lists every slot)
-        idx = {"svi_loop": 0, "stats": 1, "fb": 2, "emission_mt": 3, "pipeline": 4, "emission_orbit": 5, "chain": 6}[which] if isinstance(which, str) else which
+        """``which``: a slot name of ``_lib.VARIANT`` or its index; include/svihmm_debug.h lists every slot's codes."""
+        idx = L.VARIANT[which] if isinstance(which, str) else which
         L.check(self._lib.svihmm_set_variant(self._h, idx, int(value)), "set_variant")
 
     def selftest_mfma(self, A, B):

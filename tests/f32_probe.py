@@ -11,7 +11,7 @@ from pysvihmm_amd import _lib as L
 from oracle import ref_c
 
 K, D, B, Lm = [int(a) for a in sys.argv[1:5]]
-variants = [tuple(int(x) for x in a.split(":")) for a in sys.argv[5:]]
+variants = [(int(k) if k.isdigit() else k, int(v)) for k, v in (a.split(":") for a in sys.argv[5:])]   # slot: name (_lib.VARIANT) or index
 T = max(B * 3 + Lm, 6000)
 pb = make_problem(K, D, T, seed=K + D, miss=0.05, sep=4.0)
 starts = np.random.default_rng(B).integers(0, T - Lm + 1, size=B)

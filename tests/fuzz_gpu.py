@@ -125,11 +125,11 @@ def run_case(e, L, ref_c, case, seed):
     # the same with the bf16 kernels' batch-size floors lifted (round 5): the centred emission kernels
     # (k_emission_bf16x3 / k_emission_bf16x3d), the bf16 statistics kernels and -- from 192 windows -- the whole
     # wide-model path (k_scale_ll_f32, k_sweeps_lin2<float>, k_stats_bf16x3w) on this case's ragged shape
-    e.set_precision("f32"); e.set_variant(10, 3); e.set_variant(5, 4)
+    e.set_precision("f32"); e.set_variant("stats_tiling", 3); e.set_variant("emission_orbit", 4)
     try:
         st = e.estep(starts, Lm, flags=L.TRANS_WRAP)
     finally:
-        e.set_variant(10, 0); e.set_variant(5, 0); e.set_precision("f64")
+        e.set_variant("stats_tiling", 0); e.set_variant("emission_orbit", 0); e.set_precision("f64")
     assert np.all(np.isfinite(st.buf)), "f32 (bf16 kernels): non-finite statistics"
     g = unpack(st.buf, K, D)
     np.testing.assert_allclose(g[0], r[0], rtol=2e-3, atol=2e-4 * sc, err_msg="f32/bf16 A_raw")
@@ -809,7 +809,8 @@ def main(argv=None):
     nfail = ndone = 0
     for kv in args.variant.split(","):
         if kv:
-            e.set_variant(int(kv.split(":")[0]), int(kv.split(":")[1]))
+            k, v = kv.split(":")            # slot by name (_lib.VARIANT) or by index
+            e.set_variant(int(k) if k.isdigit() else k, int(v))
     if args.replay is not None:
         print(run_sequence(e, L, args.replay))
         return 0

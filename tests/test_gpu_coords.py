@@ -88,7 +88,7 @@ def test_guard_without_automatic_centring_and_its_cure():
                                 pb["nu"], flags=L.TRANS_WRAP)
     e = HipEngine(0)
     try:
-        e.set_variant(9, 1)
+        e.set_variant("centring", 1)
         e.set_obs(obs, None)
         assert np.all(e.get_shift() == 0.0)
         e.set_globals(pb["mod_init"], pb["ltran"])
@@ -98,7 +98,7 @@ def test_guard_without_automatic_centring_and_its_cure():
         e.shift_obs(np.full(D, off))
         e.set_emission_niw(mu, pb["sigma"], pb["kappa"], pb["nu"])
         _stats_close(e.estep(starts, 33, flags=L.TRANS_WRAP).buf, ref, K, D, 66, off)
-        e.set_variant(9, 0)
+        e.set_variant("centring", 0)
         e.set_obs(obs, None)                     # automatic again
         e.set_emission_niw(mu, pb["sigma"], pb["kappa"], pb["nu"])
         _stats_close(e.estep(starts, 33, flags=L.TRANS_WRAP).buf, ref, K, D, 66, off)

@@ -97,9 +97,9 @@ def test_diag_parameters_follow_the_centre():
         _close(e.estep(starts, Lm, flags=L.TRANS_WRAP), ref, K, D, 40 * Lm, 2e4)
         e.set_obs(obs, pb["mask"])                      # new centre chosen, factors stay
         _close(e.estep(starts, Lm, flags=L.TRANS_WRAP), ref, K, D, 40 * Lm, 2e4)
-        e.set_variant(9, 1)                             # ... also when the new centre is the origin
+        e.set_variant("centring", 1)                             # ... also when the new centre is the origin
         e.set_obs(obs[:, :], pb["mask"])
-        e.set_variant(9, 0)
+        e.set_variant("centring", 0)
         e.shift_obs(obs[~pb["mask"]].mean(0))
         _close(e.estep(starts, Lm, flags=L.TRANS_WRAP), ref, K, D, 40 * Lm, 2e4)
     finally:

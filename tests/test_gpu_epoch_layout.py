@@ -79,11 +79,11 @@ def test_epoch_layout(eng, Lm, wrap, masked, overlap):
     res = {}
     try:
         for name, v in (("step", 0), ("row", 1)):
-            eng.set_variant(17, v)
+            eng.set_variant("msg_layout", v)
             st = eng.estep(starts, Lm, flags=flags)
             res[name] = (st.buf.copy(), eng.read_intermediate("var_x", B, Lm))
     finally:
-        eng.set_variant(17, 0)
+        eng.set_variant("msg_layout", 0)
     # (b), (c): bit-identical statistics and posteriors under the two layouts
     assert np.array_equal(res["step"][0], res["row"][0])
     assert np.array_equal(res["step"][1], res["row"][1])

@@ -162,7 +162,7 @@ def test_f32_bf16x3_emission_large_batch(K, D, B, Lm, off, sep):
         q, _ = ref_c.posterior(ref_c.forward(ll, pb["mod_init"], pb["ltran"]), ref_c.backward(ll, pb["ltran"]))
         assert np.abs(e.read_rows("var_x", b * Lm, Lm) - q).max() < 2e-5
     # the same batch with the fp64 feature GEMM in front of the fp32 sweeps / statistics
-    e.set_variant(5, 3)
+    e.set_variant("emission_orbit", 3)
     st2 = e.estep(starts, Lm, flags=L.TRANS_WRAP)
     assert e.precision() == ("f32", True)
     np.testing.assert_allclose(st2.lb[0], lb, rtol=1e-5)
@@ -218,7 +218,7 @@ def test_f32_bf16x3_emission_nan_rows_and_outliers(flags_name, K, D):
         _close(st.xbar[ok], xbar[ok], sc * 1e6, "xbar")
     np.testing.assert_allclose(st.lb[0], lb, rtol=1e-5)
     # the same through the fp64 feature GEMM of the mode
-    e.set_variant(5, 3)
+    e.set_variant("emission_orbit", 3)
     st2 = e.estep(starts, Lm, flags=flags)
     np.testing.assert_allclose(st2.neff, st.neff, rtol=1e-3, atol=1e-6 * sc)
     e.close()
@@ -249,14 +249,14 @@ def test_f32_statistics_on_the_bf16_pipe(D, B, Lm, flags_wrap, inner):
         e.set_obs(pb["obs"], pb["mask"])
         e.set_globals(pb["mod_init"], pb["ltran"])
         e.set_emission_niw(pb["mu"], pb["sigma"], pb["kappa"], pb["nu"])
-        e.set_variant(10, 3)              # the bf16 kernel also below its batch-size floor of 32 768 rows
+        e.set_variant("stats_tiling", 3)              # the bf16 kernel also below its batch-size floor of 32 768 rows
         st = e.estep(starts, Lm, flags=flags, inner=inner)
         assert e.precision() == ("f32", True)
         got = st.buf.copy()
-        e.set_variant(10, 2)
+        e.set_variant("stats_tiling", 2)
         old = e.estep(starts, Lm, flags=flags, inner=inner).buf.copy()
         assert not np.array_equal(got, old)       # (two different kernels did run)
-        e.set_variant(10, 0)
+        e.set_variant("stats_tiling", 0)
         if B * Lm >= 32768:               # ... and by default above it
             np.testing.assert_array_equal(e.estep(starts, Lm, flags=flags, inner=inner).buf, got)
         if inner is None:

@@ -6,6 +6,8 @@ within 1e-11 tot of the boundary between the two states -- at most ONE such step
 tests/test_ffbs_windows_ref.py counts them for these sizes).  Windows below 2048 rows take the
 lane-per-(window, draw) kernel (K <= 64 in registers, wider models in three passes), longer ones the blocked
 composition of svihmm_ffbs once per (window, draw)."""
+import re
+
 import numpy as np
 import pytest
 from scipy.special import digamma
@@ -327,51 +329,58 @@ def test_errors_leave_the_engine_usable():
     logA = _logA(K, 1)
     e = _fresh()
     try:
-        def bad(*a, **k):
+        def bad_call(msg, fn):                            # the whole message, as the C ABI words it
             e.profile_reset()
-            with pytest.raises(RuntimeError, match="svihmm_ffbs_windows"):
-                e.ffbs_windows(*a, **k)
+            with pytest.raises(RuntimeError,
+                               match="^" + re.escape("svihmm_ffbs_windows failed: svihmm_ffbs_windows: " + msg) + "$"):
+                fn()
             assert not e.profile_read()                   # nothing was launched or copied
+        def bad(msg, *a, **k):
+            bad_call(msg, lambda: e.ffbs_windows(*a, **k))
+        def cabi(st_, la_, out_):
+            return lambda: L.check(e._lib.svihmm_ffbs_windows(e._h, st_, 1, 5, 0, la_, 1, None, 0, out_, None),
+                                   "svihmm_ffbs_windows")
+        host = "SVIHMM_USE_HOST_LLIKS without uploaded lliks of shape [B, Lm, K] (svihmm_set_lliks)"
+        outside = "window %d reaches outside [0, T)"
         e.profile(True)
         st0, out0 = np.zeros(1, np.int64), np.empty(5, dtype=np.int32)
-        with pytest.raises(RuntimeError, match="svihmm_ffbs_windows.*no globals"):      # (C ABI: the engine has no K yet)
-            L.check(e._lib.svihmm_ffbs_windows(e._h, L.i64ptr(st0), 1, 5, 0, L.dptr(logA), 1, None, 0,
-                                               out0.ctypes.data, None), "svihmm_ffbs_windows")
-        assert not e.profile_read()
+        bad_call("no globals: call svihmm_set_globals first",       # (C ABI: the engine has no K yet)
+                 cabi(L.i64ptr(st0), L.dptr(logA), out0.ctypes.data))
         mi = np.log(rng.dirichlet(np.ones(K)))
         lt = np.log(rng.dirichlet(np.ones(K), size=K))
         e.set_globals(mi, lt)
-        bad([0], 5, logA)                                 # no observations
-        bad([0], 5, logA, flags=L.USE_HOST_LLIKS)         # no host lliks either
+        bad("no observations: call svihmm_set_obs first", [0], 5, logA)
+        bad(host, [0], 5, logA, flags=L.USE_HOST_LLIKS)   # no host lliks either
         e.set_obs(obs)
-        bad([0], 5, logA)                                 # no emission family
+        bad("no emission family: call svihmm_set_emission_niw / _diag / _cat first", [0], 5, logA)
         A = rng.normal(size=(K, D, D))
-        e.set_emission_niw(rng.normal(size=(K, D)), np.einsum('kij,klj->kil', A, A) + D * np.eye(D), np.ones(K),
-                           D + 2.0 + np.zeros(K))
+        niw = (rng.normal(size=(K, D)), np.einsum('kij,klj->kil', A, A) + D * np.eye(D), np.ones(K), D + 2.0 + np.zeros(K))
+        e.set_emission_niw(*niw)
         u = rng.random((2, 2, 5))
         z, _ = e.ffbs_windows([0, 7], 5, logA, n_draws=2, uniforms=u)
-        bad([], 5, logA)                                  # B < 1
-        bad([0], 0, logA)                                 # Lm < 1
-        bad([0], 5, logA, n_draws=0)                      # S < 1
-        bad([T - 4], 5, logA)                             # window past the end
-        bad([-1], 5, logA)                                # ... and before the start
-        e.set_lliks(rng.normal(size=(2, 6, K)))
-        bad([0, 0], 5, logA, flags=L.USE_HOST_LLIKS)      # host lliks of another shape
-        bad([0], 6, logA, flags=L.USE_HOST_LLIKS)
+        bad("S, B and Lm must be positive", [], 5, logA)
+        bad("S, B and Lm must be positive", [0], 0, logA)
+        bad("S, B and Lm must be positive", [0], 5, logA, n_draws=0)
+        bad(outside % 0, [T - 4], 5, logA)                # window past the end
+        bad(outside % 1, [0, -1], 5, logA)                # ... and before the start
         st = np.zeros(1, np.int64)
         out = np.empty(5, dtype=np.int32)
+        bad_call("starts is NULL", cabi(None, L.dptr(logA), out.ctypes.data))      # (C ABI)
+        e.set_obs(rng.normal(size=(T, D + 1)))
+        bad("emission D does not match obs D", [0], 5, logA)
+        e.set_obs(obs)
+        e.set_emission_niw(*niw)
+        e.set_lliks(rng.normal(size=(2, 6, K)))
+        bad(host, [0, 0], 5, logA, flags=L.USE_HOST_LLIKS)      # host lliks of another shape
+        bad(host, [0], 6, logA, flags=L.USE_HOST_LLIKS)
         for la_, out_ in ((None, out.ctypes.data), (L.dptr(logA), None)):      # NULL logA / out_z (C ABI)
-            e.profile_reset()
-            with pytest.raises(RuntimeError, match="svihmm_ffbs_windows"):
-                L.check(e._lib.svihmm_ffbs_windows(e._h, L.i64ptr(st), 1, 5, 0, la_, 1, None, 0, out_, None),
-                        "svihmm_ffbs_windows")
-            assert not e.profile_read()
+            bad_call("logA and out_z must be given", cabi(L.i64ptr(st), la_, out_))
         e.set_globals(np.log(rng.dirichlet(np.ones(K + 1))), np.log(rng.dirichlet(np.ones(K + 1), size=K + 1)))
-        bad([0], 5, _logA(K + 1, 1))                      # K of the globals != the family's K
+        bad("K of the globals (%d) differs from the emission family's K (%d)" % (K + 1, K), [0], 5, _logA(K + 1, 1))
         Kw = 257
         e.set_globals(np.zeros(Kw), np.zeros((Kw, Kw)))
         e.set_lliks(np.zeros((1, 3, Kw)))
-        bad([0], 3, np.zeros((Kw, Kw)), flags=L.USE_HOST_LLIKS)    # K > 256
+        bad("K = 257 > 256 not supported", [0], 3, np.zeros((Kw, Kw)), flags=L.USE_HOST_LLIKS)
         # still usable
         e.profile(False)
         e.set_globals(mi, lt)

@@ -180,7 +180,7 @@ def test_renormalising_every_fourth_step_changes_nothing(B, Lm, pipeline):
         for every in (0, 1):
             eng = HipEngine(0)
             try:
-                eng.set_variant(16, every)
+                eng.set_variant("renorm4", every)
                 eng.set_variant("pipeline", pipeline)
                 eng.set_obs(pb["obs"], pb["mask"])
                 eng.set_globals(pb["mod_init"], ltran)

@@ -232,11 +232,11 @@ def test_wide_sweeps_32_windows_per_workgroup(eng, K, B):
     st = eng.estep(starts, Lm, flags=flags)
     post = eng.forward_backward(starts, Lm, want=("var_x", "local_lb"))
     try:
-        eng.set_variant(13, 1); eng.set_variant(14, 1)
+        eng.set_variant("wide_sweeps", 1); eng.set_variant("wide_tran_block", 1)
         st16 = eng.estep(starts, Lm, flags=flags)
         post16 = eng.forward_backward(starts, Lm, want=("var_x", "local_lb"))
     finally:
-        eng.set_variant(13, 0); eng.set_variant(14, 0)
+        eng.set_variant("wide_sweeps", 0); eng.set_variant("wide_tran_block", 0)
     assert np.array_equal(st.buf, st16.buf)
     assert np.array_equal(post["var_x"], post16["var_x"]) and np.array_equal(post["local_lb"], post16["local_lb"])
     ref = ref_c.estep_minibatch(pb["obs"], pb["mask"], starts, Lm, pb["mod_init"], pb["ltran"],

@@ -148,16 +148,16 @@ def test_allreduce_in_caller_coordinates_rehearsal(tmp_path):
             upload()
             ref = e.estep(starts, 33, flags=L.TRANS_WRAP).buf.copy()
             for v in (0, 1):
-                e.set_variant(11, v)
+                e.set_variant("allreduce_coords", v)
                 e.estep(starts, 33, flags=L.TRANS_WRAP, read=False)
                 e.allreduce_packed()
                 got = e.read_packed().buf
                 np.testing.assert_allclose(got, ref, rtol=1e-12, atol=1e-9 * np.abs(ref).max())
-            e.set_variant(11, 0)
+            e.set_variant("allreduce_coords", 0)
         # the loop with the all-reduce inside the iteration
         res = []
         for v in (0, 1):
-            e.set_variant(11, v)
+            e.set_variant("allreduce_coords", v)
             np.random.seed(2)
             prior = np.array([Gaussian(mu_0=obs.mean(0), sigma_0=0.75 * np.cov(obs.T), kappa_0=0.01, nu_0=D + 2)
                               for _ in range(K)])
@@ -171,7 +171,7 @@ def test_allreduce_in_caller_coordinates_rehearsal(tmp_path):
             np.testing.assert_allclose(res[1].var_emit[k].mu_mf, res[0].var_emit[k].mu_mf, rtol=1e-9, atol=1e-9)
             np.testing.assert_allclose(res[1].var_emit[k].sigma_mf, res[0].var_emit[k].sigma_mf, rtol=1e-8, atol=1e-9)
     finally:
-        e.set_variant(11, 0)
+        e.set_variant("allreduce_coords", 0)
         e.close()
 
 

@@ -3,6 +3,7 @@ the caller supplies, against NumPy (oracle/ref_numpy), against the E-step on the
 error cases, and the class routes that use it (a message or local-update override keeps the
 device statistics)."""
 import os
+import re
 
 import numpy as np
 import pytest
@@ -216,15 +217,20 @@ def test_errors():
     obs = rng.normal(size=(T, D))
     eng = _engine()
     try:
-        with pytest.raises(RuntimeError):          # no observations (straight to the C ABI: K is unknown yet)
-            L.check(eng._lib.svihmm_suffstats(eng._h, L.i64ptr(np.zeros(1, np.int64)), 1, 2, 0,
-                                              L.dptr(np.zeros(2 * K)), None), "svihmm_suffstats")
+        def bad(msg, fn, *a, **k):                 # the whole message, as the C ABI words it
+            with pytest.raises(RuntimeError, match="^" + re.escape("svihmm_suffstats failed: svihmm_suffstats: " + msg) + "$"):
+                fn(*a, **k)
+        def cabi(st_, B_, Lm_, q_):
+            return lambda: L.check(eng._lib.svihmm_suffstats(eng._h, st_, B_, Lm_, 0, q_, None), "svihmm_suffstats")
+        st1, q1 = L.i64ptr(np.zeros(1, np.int64)), L.dptr(np.zeros(2 * K))
+        # (straight to the C ABI: K is unknown yet)
+        bad("no observations: call svihmm_set_obs first", cabi(st1, 1, 2, q1))
         eng.set_obs(obs)
         _globals(eng, K, rng)
         q = _posteriors(rng, 2, 10, K)
-        with pytest.raises(RuntimeError):          # before any emission upload
-            eng.suffstats([0, 5], 10, q)
-        eng.set_emission_diag(rng.normal(size=(K, D)), np.ones((K, D)), 2 * np.ones((K, D)), np.ones((K, D)))
+        bad("no emission family: call svihmm_set_emission_niw / _diag / _cat first", eng.suffstats, [0, 5], 10, q)
+        diag = (rng.normal(size=(K, D)), np.ones((K, D)), 2 * np.ones((K, D)), np.ones((K, D)))
+        eng.set_emission_diag(*diag)
         eng.suffstats([0, 5], 10, q)
         with pytest.raises(ValueError):            # K mismatch (posteriors)
             eng.suffstats([0, 5], 10, _posteriors(rng, 2, 10, K + 1))
@@ -232,13 +238,21 @@ def test_errors():
             eng.suffstats([0, 5], 10, q[:, :9])
         with pytest.raises(ValueError):            # B = 0
             eng.suffstats([], 10, np.zeros((0, 10, K)))
-        with pytest.raises(RuntimeError):          # a window outside the sequence
-            eng.suffstats([0, T - 9], 10, q)
-        with pytest.raises(RuntimeError):
-            eng.suffstats([-1, 5], 10, q)
+        bad("window 1 reaches outside [0, T)", eng.suffstats, [0, T - 9], 10, q)      # a window outside the sequence
+        bad("window 0 reaches outside [0, T)", eng.suffstats, [-1, 5], 10, q)
+        # (what the Python layer refuses itself, at the C ABI)
+        bad("B and Lm must be positive", cabi(st1, 0, 2, q1))
+        bad("B and Lm must be positive", cabi(st1, 1, 0, q1))
+        bad("starts / var_x is NULL", cabi(None, 1, 2, q1))
+        bad("starts / var_x is NULL", cabi(st1, 1, 2, None))
+        eng.set_obs(rng.normal(size=(T, D + 1)))
+        bad("emission D does not match obs D", eng.suffstats, [0, 5], 10, q)
+        eng.set_obs(obs)
+        eng.set_emission_diag(*diag)
+        eng.suffstats([0, 5], 10, q)
         _globals(eng, K + 1, rng)                  # K of the globals != the family's K
-        with pytest.raises(RuntimeError):
-            eng.suffstats([0, 5], 10, _posteriors(rng, 2, 10, K + 1))
+        bad("K of the globals (%d) differs from the emission family's K (%d)" % (K + 1, K),
+            eng.suffstats, [0, 5], 10, _posteriors(rng, 2, 10, K + 1))
     finally:
         eng.close()
 

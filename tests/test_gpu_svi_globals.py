@@ -30,11 +30,11 @@ EPS = R.F64_EPS
 def _engine(events=0, theta=None):
     from pysvihmm_amd.engine import HipEngine
     eng = HipEngine(0)
-    eng.set_variant(9, 1)                    # no automatic centring of the resident observations
+    eng.set_variant("centring", 1)                    # no automatic centring of the resident observations
     if events:
         eng.set_variant("svi_loop", 1)       # stream events instead of device-side counters (k_svi_elbo forms the total)
     if theta is not None:
-        eng.set_variant(13, theta)
+        eng.set_variant("wide_sweeps", theta)
     return eng
 
 

@@ -21,7 +21,7 @@ def test_both_builders_give_identical_lliks(K, D):
         for old in (0, 2):
             eng = HipEngine(0)
             try:
-                eng.set_variant(13, old)
+                eng.set_variant("wide_sweeps", old)
                 eng.set_precision(prec)
                 eng.set_obs(pb["obs"], pb["mask"])
                 eng.set_globals(pb["mod_init"], pb["ltran"])
@@ -49,7 +49,7 @@ def test_resident_loop_trajectory_is_identical():
     for old in (3, 2, 0):
         eng = HipEngine(0)
         try:
-            eng.set_variant(13, old)
+            eng.set_variant("wide_sweeps", old)
             eng.set_obs(pb["obs"], pb["mask"])
             eng.svi_begin(prior_tran, pb["var_tran"], (mu0, sg0, ka0, nu0), (pb["mu"], pb["sigma"], pb["kappa"], pb["nu"]),
                           niw_prior_logpart(sg0, nu0), nit, 1.0)

@@ -6,6 +6,7 @@ demand exact equality.  Lengths: the kernels keep psi in LDS up to 1008 rows (K 
 (K > 64) and backtrack longer windows in chunks of that many rows (kernels_viterbi.h), hence the
 cases either side of 1008 / 240, at exact multiples, and with a ragged last chunk."""
 import os
+import re
 
 import numpy as np
 import pytest
@@ -315,38 +316,47 @@ def test_errors_leave_the_engine_usable():
     obs = rng.normal(size=(T, D))
     e = _fresh()
     try:
-        def bad(fn, *a, **k):
+        def bad(msg, fn, *a, **k):                        # the whole message, as the C ABI words it
             e.profile_reset()
-            with pytest.raises(RuntimeError, match="svihmm_viterbi"):
+            with pytest.raises(RuntimeError, match="^" + re.escape("svihmm_viterbi failed: svihmm_viterbi: " + msg) + "$"):
                 fn(*a, **k)
             assert not e.profile_read()                   # nothing was launched or copied
+        host = "SVIHMM_USE_HOST_LLIKS without uploaded lliks of shape [B, Lm, K] (svihmm_set_lliks)"
+        outside = "window %d reaches outside [0, T)"
         e.profile(True)
-        bad(e.viterbi, [0], 5)                            # no globals
+        bad("no globals: call svihmm_set_globals first", e.viterbi, [0], 5)
         mi, lt = np.log(rng.dirichlet(np.ones(K))), _tran(rng, K, "random")
         e.set_globals(mi, lt)
-        bad(e.viterbi, [0], 5)                            # no observations
-        bad(e.viterbi, [0], 5, flags=L.USE_HOST_LLIKS)    # no host lliks either
+        bad("no observations: call svihmm_set_obs first", e.viterbi, [0], 5)
+        bad(host, e.viterbi, [0], 5, flags=L.USE_HOST_LLIKS)    # no host lliks either
         e.set_obs(obs)
-        bad(e.viterbi, [0], 5)                            # no emission family
+        bad("no emission family: call svihmm_set_emission_niw / _diag / _cat first", e.viterbi, [0], 5)
         A = rng.normal(size=(K, D, D))
         niw = (rng.normal(size=(K, D)), np.einsum('kij,klj->kil', A, A) + D * np.eye(D), np.ones(K), D + 2.0 + np.zeros(K))
         e.set_emission_niw(*niw)
         z, s = e.viterbi([0, 7], 5)
-        bad(e.viterbi, [], 5)                             # B < 1
-        bad(e.viterbi, [0], 0)                            # Lm < 1
-        bad(e.viterbi, [T - 4], 5)                        # window past the end
-        bad(e.viterbi, [-1], 5)                           # ... and before the start
+        bad("B and Lm must be positive", e.viterbi, [], 5)
+        bad("B and Lm must be positive", e.viterbi, [0], 0)
+        bad(outside % 0, e.viterbi, [T - 4], 5)           # window past the end
+        bad(outside % 1, e.viterbi, [0, -1], 5)           # ... and before the start
+        score = np.empty(1)
+        bad("starts is NULL", lambda: L.check(                # (C ABI)
+            e._lib.svihmm_viterbi(e._h, None, 1, 5, 0, None, L.dptr(score)), "svihmm_viterbi"))
+        e.set_obs(rng.normal(size=(T, D + 1)))
+        bad("emission D does not match obs D", e.viterbi, [0], 5)
+        e.set_obs(obs)
+        e.set_emission_niw(*niw)
         e.set_lliks(rng.normal(size=(2, 6, K)))
-        bad(e.viterbi, [0, 0], 5, flags=L.USE_HOST_LLIKS)     # host lliks of another shape
-        bad(e.viterbi, [0], 6, flags=L.USE_HOST_LLIKS)
+        bad(host, e.viterbi, [0, 0], 5, flags=L.USE_HOST_LLIKS)     # host lliks of another shape
+        bad(host, e.viterbi, [0], 6, flags=L.USE_HOST_LLIKS)
         e.set_globals(np.log(rng.dirichlet(np.ones(K + 1))), _tran(rng, K + 1, "random"))
-        bad(e.viterbi, [0], 5)                            # K of the globals != the family's K
+        bad("K of the globals (%d) differs from the emission family's K (%d)" % (K + 1, K), e.viterbi, [0], 5)
         Kw = 257
         e.set_globals(np.zeros(Kw), np.zeros((Kw, Kw)))
         e.set_lliks(np.zeros((1, 3, Kw)))
-        bad(e.viterbi, [0], 3, flags=L.USE_HOST_LLIKS)    # K > 256
-        with pytest.raises(RuntimeError, match="svihmm_viterbi"):      # nothing to return (C ABI)
-            L.check(e._lib.svihmm_viterbi(e._h, L.i64ptr(np.zeros(1, np.int64)), 1, 3, 0, None, None), "svihmm_viterbi")
+        bad("K = 257 > 256 not supported (one-byte back-pointers)", e.viterbi, [0], 3, flags=L.USE_HOST_LLIKS)
+        bad("neither out_z nor out_score given", lambda: L.check(      # nothing to return (C ABI)
+            e._lib.svihmm_viterbi(e._h, L.i64ptr(np.zeros(1, np.int64)), 1, 3, 0, None, None), "svihmm_viterbi"))
         # still usable
         e.profile(False)
         e.set_globals(mi, lt)
