@@ -35,7 +35,8 @@
 extern "C" {
 #endif
 
-/* 3 (addition, nothing else changed meaning): svihmm_ffbs_windows.
+/* 3 (addition, nothing else changed meaning): svihmm_grow_windows.
+ * 3 (addition, nothing else changed meaning): svihmm_ffbs_windows.
  * 3 (addition, nothing else changed meaning): svihmm_viterbi.
  * 3: svihmm_export_packed / svihmm_import_packed, svihmm_svi_set_adagrad / _read_adagrad,
  *    svihmm_svi_begin_diag / _begin_cat / _read_factors added, slot mask
@@ -441,6 +442,55 @@ int svihmm_viterbi(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t Lm, 
 int svihmm_ffbs_windows(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t Lm, uint32_t flags,
                         const double* logA, int32_t S, const double* uniforms, uint64_t seed,
                         int32_t* out_z, double* out_lalpha);
+
+/* Adaptive window length and buffer growth on the device (hmmsgd_metaobs.py:521-569 select_L, :579-661
+ * select_buffer "GrowBuf"): for each of n centres the half-width at which the posterior of its probe rows stops moving.
+ * T = the resident rows; ll = what svihmm_loglik returns for them with `flags` (NIW, diagonal and Categorical
+ * families, SVIHMM_MASK_AS_NAN); q_b = the posterior of the window [c - b, c + b] under the globals currently set,
+ * started from mod_init at row c - b (get_local_messages, :663-700); the probes are its rows c - m and c + m,
+ * m = probe_off.  select_L is half0 = minHalfL, m = 0; select_buffer is half0 = m = halfL.
+ * Growth rule, per centre and independent of all other centres (eps = epsilon, inc = increment):
+ *     b = half0; q_old = probes(b); d_l = d_r = DBL_MAX; count = 0; run = old = (0, 0)
+ *     loop: if c - b < 1 + inc or c + b + inc + 1 > T or b > cutoff: stop
+ *           rule 0: if d_l < eps and d_r < eps: stop
+ *           rule 1: count += 1; if count > 1 and (run_l - old_l)/(count - 1) < eps and (run_r - old_r)/(count - 1) < eps: stop
+ *           b += inc; q_new = probes(b); d_x = sum_k |q_new_x[k] - q_old_x[k]|; old = run; run += d; q_old = q_new
+ * out_half[i] = the final b; out_steps[i] (may be NULL) = growth steps taken; out_trace (may be NULL):
+ *   out_trace[(i*trace_cap + s)*2 + {0, 1}] = (d_l, d_r) of step s, NaN past a centre's steps; steps beyond trace_cap
+ *   are counted, not stored; for m = 0 both entries are equal.
+ * method:
+ *   SVIHMM_GROW_PRODUCTS  one emission pass over the rows every centre can reach (n windows of ONE common length
+ *       W = min(2 R + 1, T), R = the largest half-width the sequence ends and the cutoff let any centre reach,
+ *       window i starting at clamp(c_i - R, 0, T - W)), then one launch, one workgroup per centre: the candidates are
+ *       nested, so with G_t = A diag(e_t), A = exp(ltran), e_t = exp(ll_t - max_k ll_t) the probe marginals are
+ *       q_left ~ (v' F_b) (.) (Mid R_b 1), q_right ~ (v' F_b Mid) (.) (R_b 1), v = exp(mod_init + ll_{c-b}), where
+ *       F_b = G_{c-b+1} .. G_{c-m} grows on the left, R_b = G_{c+m+1} .. G_{c+b} on the right and
+ *       Mid = G_{c-m+1} .. G_{c+m} is built once: two K x K x K products per added row (v_mfma_f64_16x16x4_f64)
+ *       instead of a whole forward / backward pass per candidate.  Matrices are rescaled by exact powers of two.
+ *       Needs K <= 64 and every ltran entry >= SVIHMM_LTRAN_LINEAR_MIN; fails with a message otherwise.  A centre's
+ *       result is bit-identical whatever n and the other centres are.
+ *   SVIHMM_GROW_LITERAL   the rule as written: per candidate the E-step of svihmm_forward_backward on the windows of
+ *       the centres still growing; the probe rows, residuals and the rule's state stay on the device, per candidate
+ *       only the n "grows again" flags come back.  Any K svihmm_forward_backward serves, any ltran.
+ *   SVIHMM_GROW_AUTO      PRODUCTS where it applies, LITERAL otherwise.
+ * Always fp64: the precision mode and what svihmm_get_precision reports are unchanged.
+ * Fails with a message, before any device work (the handle stays usable): NULL centers or out_half; n < 1,
+ *   increment < 1, half0 < 0, probe_off < 0 or probe_off > half0; rule not 0 or 1; epsilon not finite; trace_cap < 0;
+ *   an unknown method; a start window [c - half0, c + half0] outside [0, T); no observations, no globals or no
+ *   emission family; a K mismatch between globals and emission family; SVIHMM_USE_HOST_LLIKS (host lliks have no row
+ *   axis to grow along); method PRODUCTS where the kernel does not apply.
+ * Intermediates: like svihmm_loglik the call writes the handle's lliks buffer -- afterwards the lliks of the LAST
+ *   window batch it evaluated are readable (svihmm_read_intermediate / _read_rows, what = 0): the n reach windows of
+ *   length W (PRODUCTS), the last candidate's windows of the centres that grew longest (LITERAL); lalpha / lbeta /
+ *   var_x of an earlier E-step are not.  The packed statistics held in HBM are not touched. */
+#define SVIHMM_GROW_AUTO     0
+#define SVIHMM_GROW_LITERAL  1   /* one log-domain forward/backward per candidate, by the library */
+#define SVIHMM_GROW_PRODUCTS 2   /* the matrix-product kernel; fails where it does not apply */
+int svihmm_grow_windows(svihmm_ctx* h, const int64_t* centers, int32_t n,
+                        int32_t half0, int32_t probe_off, int32_t increment, int32_t cutoff,
+                        double epsilon, int32_t rule, uint32_t flags, int32_t method,
+                        int32_t* out_half, int32_t* out_steps,
+                        double* out_trace, int32_t trace_cap);
 
 /* Readback of the intermediates of the last estep/forward_backward call
  * (what 0: lliks, 1: lalpha, 2: lbeta, 3: var_x; each [B,Lm,K]).

@@ -25,6 +25,7 @@ NIW_MAX_D = 96                    # wider observations: host-evaluated lliks (ge
 DIAG_MAX_D = 128                  # diagonal family on the device up to this width
 LTRAN_F32_MIN = -60.0
 F64, F32 = 0, 1
+GROW_METHOD = {"auto": 0, "literal": 1, "products": 2}     # SVIHMM_GROW_* of include/svihmm.h
 # svihmm_set_variant's slots: the SVIHMM_VAR_* enumerators of include/svihmm_debug.h, lower-cased (their codes are
 # documented there)
 VARIANT = {
@@ -99,6 +100,9 @@ SIGNATURES = {
                                  _c_double_p]),
     "svihmm_ffbs_windows": (C.c_int, [C.c_void_p, _c_int64_p, C.c_int32, C.c_int32, C.c_uint32, _c_double_p,
                                       C.c_int32, _c_double_p, C.c_uint64, C.c_void_p, _c_double_p]),
+    "svihmm_grow_windows": (C.c_int, [C.c_void_p, _c_int64_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                      C.c_double, C.c_int32, C.c_uint32, C.c_int32, C.c_void_p, C.c_void_p,
+                                      _c_double_p, C.c_int32]),
     "svihmm_read_rows": (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, _c_double_p]),
     "svihmm_read_intermediate": (C.c_int, [C.c_void_p, C.c_int32, _c_double_p]),
     "svihmm_ffbs": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p, C.c_uint32, _c_int64_p,

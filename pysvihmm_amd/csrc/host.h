@@ -151,7 +151,8 @@ struct svihmm_ctx {
   Buf starts, ll, la, lb, q, lse_part, local_lb, logz, part, packed, scratch;
   Buf user_q, user_starts;         // svihmm_suffstats: the caller's posteriors and windows (never the E-step's q / starts)
   Buf vit;                         // svihmm_viterbi: score | z | final argmax | psi | path | chunk maps (launch_viterbi);
-                                   // svihmm_ffbs_windows: logA | z | the caller's uniforms (launch_ffbs_windows)
+                                   // svihmm_ffbs_windows: logA | z | the caller's uniforms (launch_ffbs_windows);
+                                   // svihmm_grow_windows: results / the rule's state (launch_grow_*)
   // scaled linear-domain sweeps: per-row binary exponents, (na, k) records, 1/Z factors,
   // Eh of host-supplied lliks; log-domain intermediates materialised on demand (m_*)
   Buf kexp, hx, gx, zfac, llE, m_ll, m_la, m_lb, chain, chain2;
@@ -372,6 +373,13 @@ int launch_emission_deferred(svihmm_ctx* h);
 int launch_viterbi(svihmm_ctx* h, int B, int Lm, const double* ll, bool want_z, int32_t** dz_out, double** dscore_out);
 int launch_ffbs_windows(svihmm_ctx* h, const int64_t* starts, int B, int Lm, uint32_t flags, const double* logA, int S,
                         const double* uniforms, uint64_t seed, bool want_lalpha, int32_t** dz_out, const double** dla_out);
+int launch_grow_products(svihmm_ctx* h, int n, int W, const double* ll, const int32_t* off, const int32_t* smax, int half0,
+                         int m, int inc, double eps, int rule, int trace_cap, int32_t** half_out, int32_t** steps_out,
+                         double** trace_out);
+int launch_grow_state(svihmm_ctx* h, int n, int trace_cap, const int64_t* centers, const double* init);
+int launch_grow_probe(svihmm_ctx* h, int n, int nact, const int32_t* idx, int b, int m, bool first, int inc, int cutoff,
+                      double eps, int rule, int trace_cap, int32_t* active_host);
+int grow_state_results(svihmm_ctx* h, int n, int trace_cap, const int32_t** ist_out, const double** trace_out);
 bool sweep_emission_ok(const svihmm_ctx* h, int B, int Lq, int off, int Lm, uint32_t flags);
 bool sweep_mixed_ok(const svihmm_ctx* h, int B, int Lq, int off, int Lm, uint32_t flags);
 bool sweep_stats_ok(const svihmm_ctx* h, int B, int Lq, int off, int Lm, uint32_t flags);

@@ -2320,6 +2320,138 @@ int svihmm_ffbs_windows(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t
 }
 
 
+// ---- growing adaptive windows / buffers (kernels_grow.h) ---------------------------------------
+// Everything that can be wrong with the call is found here, before any device work.
+//   product route: one emission pass over the rows every centre can reach (n windows of one common length W, clamped
+//     into [0, T)), then ONE launch of k_grow_products;
+//   literal route: per candidate half-width the E-step of svihmm_forward_backward (same dispatch, no outputs) on the
+//     windows of the centres still growing + k_grow_probe; only the n "grows again" flags come back per candidate.
+static int grow_literal(svihmm_ctx* h, const int64_t* centers, int n, int half0, int m, int inc, int cutoff, double eps,
+                        int rule, uint32_t flags, int trace_cap, int32_t* out_half, int32_t* out_steps, double* out_trace) {
+  std::vector<double> init((size_t)n * 6, 0.0);
+  for (int i = 0; i < n; ++i) init[(size_t)i * 6] = init[(size_t)i * 6 + 1] = 1.7976931348623157e308;
+  CK(launch_grow_state(h, n, trace_cap, centers, init.data()));
+  std::vector<int32_t> act(n), flag(n);
+  std::vector<int64_t> starts(n);
+  for (int i = 0; i < n; ++i) act[i] = i;
+  int b = half0;
+  bool first = true;
+  while (!act.empty()) {
+    const int nact = (int)act.size(), Lm = 2 * b + 1;
+    for (int j = 0; j < nact; ++j) starts[j] = centers[act[j]] - b;
+    const int var = pick_fb(h, nact, Lm, false);
+    CK(prepare_ll(h, starts.data(), nact, Lm, flags, false, var == SVIHMM_FB_SCALED));
+    CK(run_fb(h, nact, Lm, var, false, false));
+    h->lastB = nact; h->lastLm = Lm;
+    if (var == SVIHMM_FB_SCALED) CK(ensure_q(h, nact, Lm, h->stream));
+    CK(launch_grow_probe(h, n, nact, act.data(), b, m, first, inc, cutoff, eps, rule, trace_cap, flag.data()));
+    size_t keep = 0;
+    for (int j = 0; j < nact; ++j)
+      if (flag[act[j]]) act[keep++] = act[j];
+    act.resize(keep);
+    first = false;
+    if (keep && b > INT32_MAX / 2 - inc) return fail("svihmm_grow_windows: half-width overflow");
+    b += inc;
+  }
+  const int32_t* dist = nullptr;
+  const double* dtrace = nullptr;
+  CK(grow_state_results(h, n, trace_cap, &dist, &dtrace));
+  std::vector<int32_t> ist((size_t)n * 3);
+  CK(d2h(h, ist.data(), dist, ist.size() * sizeof(int32_t)));
+  if (out_trace && trace_cap > 0) CK(d2h(h, out_trace, dtrace, (size_t)n * trace_cap * 2 * sizeof(double)));
+  HIPCK(hipStreamSynchronize(h->stream));
+  for (int i = 0; i < n; ++i) {
+    out_half[i] = ist[(size_t)i * 3];
+    if (out_steps) out_steps[i] = ist[(size_t)i * 3 + 1];
+  }
+  return 0;
+}
+
+static int grow_products(svihmm_ctx* h, const int64_t* centers, int n, int half0, int m, int inc, int cutoff, double eps,
+                         int rule, uint32_t flags, int trace_cap, int32_t* out_half, int32_t* out_steps, double* out_trace) {
+  const int64_t T = h->T;
+  // steps the rule's first condition allows: it goes on from b while b <= min(c - 1 - inc, T - c - inc - 1, cutoff)
+  std::vector<int32_t> smax(n), off(n);
+  std::vector<int64_t> starts(n);
+  int64_t reach = half0;
+  for (int i = 0; i < n; ++i) {
+    const int64_t c = centers[i];
+    int64_t lim = c - 1 - inc;
+    if (T - c - inc - 1 < lim) lim = T - c - inc - 1;
+    if (cutoff < lim) lim = cutoff;
+    const int64_t s = lim >= half0 ? (lim - half0) / inc + 1 : 0;
+    smax[i] = (int32_t)s;
+    if (half0 + s * inc > reach) reach = half0 + s * inc;
+  }
+  const int64_t W64 = 2 * reach + 1 < T ? 2 * reach + 1 : T;
+  if (W64 * h->K >= ((int64_t)1 << 31)) return fail("svihmm_grow_windows: reach window too long for the product kernel");
+  const int W = (int)W64;
+  for (int i = 0; i < n; ++i) {
+    int64_t s0 = centers[i] - reach;
+    if (s0 > T - W) s0 = T - W;
+    if (s0 < 0) s0 = 0;
+    starts[i] = s0;
+    off[i] = (int32_t)(centers[i] - s0);
+  }
+  CK(prepare_ll(h, starts.data(), n, W, flags, false));
+  h->lastB = n; h->lastLm = W;
+  int32_t *dhalf = nullptr, *dsteps = nullptr;
+  double* dtrace = nullptr;
+  CK(launch_grow_products(h, n, W, (const double*)h->ll.p, off.data(), smax.data(), half0, m, inc, eps, rule,
+                          out_trace ? trace_cap : 0, &dhalf, &dsteps, &dtrace));
+  CK(d2h(h, out_half, dhalf, (size_t)n * sizeof(int32_t)));
+  if (out_steps) CK(d2h(h, out_steps, dsteps, (size_t)n * sizeof(int32_t)));
+  if (out_trace && trace_cap > 0) CK(d2h(h, out_trace, dtrace, (size_t)n * trace_cap * 2 * sizeof(double)));
+  HIPCK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int svihmm_grow_windows(svihmm_ctx* h, const int64_t* centers, int32_t n, int32_t half0, int32_t probe_off,
+                        int32_t increment, int32_t cutoff, double epsilon, int32_t rule, uint32_t flags, int32_t method,
+                        int32_t* out_half, int32_t* out_steps, double* out_trace, int32_t trace_cap) {
+  const char* fn = "svihmm_grow_windows";
+  const auto bad = [fn](const std::string& what) { return fail(std::string(fn) + ": " + what); };
+  if (!h) return bad("NULL handle");
+  if (!centers || !out_half) return bad("centers and out_half must be given");
+  if (n < 1) return bad("n must be positive");
+  if (increment < 1) return bad("increment must be positive");
+  if (half0 < 0 || probe_off < 0 || probe_off > half0) return bad("need 0 <= probe_off <= half0");
+  if (rule != 0 && rule != 1) return bad("rule must be 0 (last residual) or 1 (running average)");
+  if (!(epsilon > -1.7976931348623157e308 && epsilon < 1.7976931348623157e308)) return bad("epsilon must be finite");
+  if (trace_cap < 0) return bad("trace_cap must not be negative");
+  if (method != SVIHMM_GROW_AUTO && method != SVIHMM_GROW_LITERAL && method != SVIHMM_GROW_PRODUCTS)
+    return bad("unknown method");
+  if (flags & SVIHMM_USE_HOST_LLIKS) return bad("SVIHMM_USE_HOST_LLIKS is not supported (host lliks have no row axis to grow along)");
+  if (!h->have_globals) return bad("no globals: call svihmm_set_globals first");
+  CK(check_window_model(h, fn));
+  for (int i = 0; i < n; ++i)
+    if (centers[i] - half0 < 0 || centers[i] + half0 >= h->T)
+      return bad("start window of centre " + std::to_string(i) + " reaches outside [0, T)");
+  const bool products_ok = h->K <= 64 && !h->exact_log;
+  if (method == SVIHMM_GROW_PRODUCTS && !products_ok)
+    return bad("method PRODUCTS needs K <= 64 and every ltran entry >= SVIHMM_LTRAN_LINEAR_MIN (K = " +
+               std::to_string(h->K) + (h->exact_log ? ", ltran below the linear range)" : ")"));
+  const bool products = method == SVIHMM_GROW_PRODUCTS || (method == SVIHMM_GROW_AUTO && products_ok);
+  CK(set_device(h));
+  CK(wait_side_streams(h));
+  // always fp64, and not an E-step batch: the precision mode is set aside for the call and what
+  // svihmm_get_precision reports about the last E-step batch stays
+  const int report = h->f32_report_hold >= 0 ? h->f32_report_hold : (h->cur_f32 || h->eh_float) ? 1 : 0;
+  const int prec = h->prec;
+  h->prec = 0;
+  const uint32_t fl = flags & SVIHMM_MASK_AS_NAN;
+  const int cap = out_trace ? trace_cap : 0;
+  const int rc = products ? grow_products(h, centers, n, half0, probe_off, increment, cutoff, epsilon, rule, fl, cap,
+                                          out_half, out_steps, out_trace)
+                          : grow_literal(h, centers, n, half0, probe_off, increment, cutoff, epsilon, rule, fl, cap,
+                                         out_half, out_steps, out_trace);
+  h->prec = prec;
+  h->f32_report_hold = report;
+  if (rc) return rc;
+  CK(check_emission_status(h));
+  return 0;
+}
+
 // ---- synthetic sequences generated in HBM (gen_synthetic.py:27-44) --------------------------
 int svihmm_generate(svihmm_ctx* h, int64_t T, int32_t K, int32_t D, const double* cdf,
                     const double* means, const double* chols, uint64_t seed) {

@@ -5,6 +5,7 @@
 #include "kernels_recursion.h"
 #include "kernels_viterbi.h"
 #include "kernels_ffbs_windows.h"
+#include "kernels_grow.h"
 
 extern "C" {
 
@@ -946,6 +947,109 @@ int launch_viterbi(svihmm_ctx* h, int B, int Lm, const double* ll, bool want_z, 
                        (const unsigned char*)path, (const unsigned char*)entry, Lm, Ls, Cw, Lpad, KS, (int64_t)n, dz);
     HIPCK(hipGetLastError());
   }
+  return 0;
+}
+
+// svihmm_grow_windows, product route (kernels_grow.h): one workgroup per centre over the lliks ll [n][W][K] of the
+// centres' reach windows; off[i] = the centre's row inside its window, smax[i] = the growth steps the sequence ends
+// and the cutoff allow (host arrays, checked against the window here: the kernel reads rows off - bmax .. off + bmax).
+// Results live in h->vit until the next call: *half_out / *steps_out int32 [n], *trace_out double [n][trace_cap][2].
+int launch_grow_products(svihmm_ctx* h, int n, int W, const double* ll, const int32_t* off, const int32_t* smax,
+                         int half0, int m, int inc, double eps, int rule, int trace_cap, int32_t** half_out,
+                         int32_t** steps_out, double** trace_out) {
+  const int K = h->K;
+  if (K > 64 || h->exact_log) return fail("svihmm_grow_windows: the product kernel needs K <= 64 and linear-range globals");
+  for (int i = 0; i < n; ++i) {
+    const int64_t reach = (int64_t)half0 + (int64_t)inc * smax[i];
+    if (smax[i] < 0 || off[i] - reach < 0 || off[i] + reach >= W)
+      return fail("svihmm_grow_windows: internal error: centre " + std::to_string(i) + " reaches outside its lliks window");
+  }
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t o_trace = 0, o_off = up((size_t)n * trace_cap * 2 * sizeof(double));
+  const size_t o_smax = o_off + up((size_t)n * 4), o_half = o_smax + up((size_t)n * 4), o_steps = o_half + up((size_t)n * 4);
+  CK(ensure(h->vit, o_steps + up((size_t)n * 4)));
+  char* base = (char*)h->vit.p;
+  double* dtrace = trace_cap > 0 ? (double*)(base + o_trace) : nullptr;
+  int32_t* doff = (int32_t*)(base + o_off);
+  int32_t* dsmax = (int32_t*)(base + o_smax);
+  int32_t* dhalf = (int32_t*)(base + o_half);
+  int32_t* dsteps = (int32_t*)(base + o_steps);
+  HIPCK(hipMemcpyAsync(doff, off, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+  HIPCK(hipMemcpyAsync(dsmax, smax, (size_t)n * 4, hipMemcpyHostToDevice, h->stream));
+  // (pageable sources: the two host arrays must not change before the copies have left them)
+  HIPCK(hipStreamSynchronize(h->stream));
+  const double* A = (const double*)h->Aexp.p;
+  const double* mi = (const double*)h->mod_init.p;
+  ProfScope ps(h, KS_FB);
+#define GROWP(NT)                                                                                                  \
+  do {                                                                                                             \
+    const size_t lds = grow_lds_bytes(NT);                                                                         \
+    if (lds > 64 * 1024)                                                                                           \
+      HIPCK(hipFuncSetAttribute((const void*)k_grow_products<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
+    hipLaunchKernelGGL(k_grow_products<NT>, dim3(n), dim3(GROW_THREADS), lds, h->stream, ll, A, mi,                \
+                       (const int32_t*)doff, (const int32_t*)dsmax, W, K, half0, m, inc, eps, rule, dhalf, dsteps, \
+                       dtrace, trace_cap);                                                                         \
+  } while (0)
+  if (K <= 16) GROWP(1); else if (K <= 32) GROWP(2); else if (K <= 48) GROWP(3); else GROWP(4);
+#undef GROWP
+  HIPCK(hipGetLastError());
+  *half_out = dhalf; *steps_out = dsteps; *trace_out = dtrace;
+  return 0;
+}
+
+// svihmm_grow_windows, literal route: the rule's state on the device.  launch_grow_state lays it out in h->vit and
+// uploads its initial value (init: [n][6] doubles, centers: [n]); launch_grow_probe folds one candidate's posteriors
+// q [nact][2 b + 1][K] (window j = centre idx[j]) into it and leaves the centres' "grows again" flags in *active_out.
+struct GrowState { double *qold, *st, *trace; int64_t* centers; int32_t *ist, *active, *idx; };
+static GrowState grow_state(svihmm_ctx* h, int n, int trace_cap) {
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const int K = h->K;
+  char* base = (char*)h->vit.p;
+  GrowState g;
+  size_t o = 0;
+  g.trace = (double*)(base + o); o += up((size_t)n * trace_cap * 2 * sizeof(double));
+  g.qold = (double*)(base + o); o += up((size_t)n * 2 * K * sizeof(double));
+  g.st = (double*)(base + o); o += up((size_t)n * 6 * sizeof(double));
+  g.centers = (int64_t*)(base + o); o += up((size_t)n * sizeof(int64_t));
+  g.ist = (int32_t*)(base + o); o += up((size_t)n * 3 * 4);
+  g.active = (int32_t*)(base + o); o += up((size_t)n * 4);
+  g.idx = (int32_t*)(base + o);
+  return g;
+}
+int launch_grow_state(svihmm_ctx* h, int n, int trace_cap, const int64_t* centers, const double* init) {
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t bytes = up((size_t)n * trace_cap * 2 * 8) + up((size_t)n * 2 * h->K * 8) + up((size_t)n * 48) +
+                       up((size_t)n * 8) + up((size_t)n * 12) + 2 * up((size_t)n * 4);
+  CK(ensure(h->vit, bytes));
+  const GrowState g = grow_state(h, n, trace_cap);
+  // trace: NaN beyond a centre's steps (all bits set is a quiet NaN); everything else zero
+  if (trace_cap > 0) HIPCK(hipMemsetAsync(g.trace, 0xff, (size_t)n * trace_cap * 2 * 8, h->stream));
+  HIPCK(hipMemsetAsync(g.qold, 0, (size_t)n * 2 * h->K * 8, h->stream));
+  HIPCK(hipMemsetAsync(g.ist, 0, (size_t)n * 12, h->stream));
+  HIPCK(hipMemcpyAsync(g.st, init, (size_t)n * 48, hipMemcpyHostToDevice, h->stream));
+  HIPCK(hipMemcpyAsync(g.centers, centers, (size_t)n * 8, hipMemcpyHostToDevice, h->stream));
+  HIPCK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+int launch_grow_probe(svihmm_ctx* h, int n, int nact, const int32_t* idx, int b, int m, bool first, int inc, int cutoff,
+                      double eps, int rule, int trace_cap, int32_t* active_host) {
+  const GrowState g = grow_state(h, n, trace_cap);
+  HIPCK(hipMemcpyAsync(g.idx, idx, (size_t)nact * 4, hipMemcpyHostToDevice, h->stream));
+  {
+    ProfScope ps(h, KS_MISC);
+    hipLaunchKernelGGL(k_grow_probe, dim3(nact), dim3(64), 0, h->stream, (const double*)h->q.p, 2 * b + 1, h->K, b, m,
+                       (const int32_t*)g.idx, first ? 1 : 0, (const int64_t*)g.centers, (int64_t)h->T, inc, cutoff, eps,
+                       rule, g.qold, g.st, g.ist, g.active, trace_cap > 0 ? g.trace : (double*)nullptr, trace_cap);
+    HIPCK(hipGetLastError());
+  }
+  HIPCK(hipMemcpyAsync(active_host, g.active, (size_t)n * 4, hipMemcpyDeviceToHost, h->stream));
+  HIPCK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+// the literal route's results (device pointers into h->vit): ist [n][3] = half-width, steps, count; trace
+int grow_state_results(svihmm_ctx* h, int n, int trace_cap, const int32_t** ist_out, const double** trace_out) {
+  const GrowState g = grow_state(h, n, trace_cap);
+  *ist_out = g.ist; *trace_out = g.trace;
   return 0;
 }
 

@@ -418,6 +418,28 @@ class HipEngine(object):
                                          L.dptr(score)), "svihmm_viterbi")
         return z, score
 
+    def grow_windows(self, centers, half0, probe_off=0, increment=1, cutoff=1000, epsilon=1e-5, rule=0,
+                     flags=0, method="auto", trace_cap=0):
+        """Adaptive window length / buffer growth on the device (``svihmm_grow_windows``; reference
+        ``select_L`` with ``half0 = minHalfL, probe_off = 0``, ``select_buffer`` with ``half0 = probe_off =
+        halfL``): for every centre the half-width at which the posterior of its probe rows ``c - probe_off``,
+        ``c + probe_off`` stops moving, by the rule stated in ``include/svihmm.h`` (``rule`` 0: last
+        residual below ``epsilon``, 1: running average).  ``method``: "auto", "literal" or "products".
+        Returns ``(half int32[n], steps int32[n], trace float64[n, trace_cap, 2] or None)``; trace rows
+        past a centre's steps are NaN."""
+        self._pre_mutate()
+        c = np.ascontiguousarray(np.asarray(centers, dtype=np.int64).ravel())
+        n, cap = len(c), int(trace_cap)
+        half = np.empty(n, dtype=np.int32)
+        steps = np.empty(n, dtype=np.int32)
+        trace = np.empty((n, cap, 2)) if cap > 0 else None
+        vp = lambda a: a.ctypes.data_as(C.c_void_p)
+        L.check(self._lib.svihmm_grow_windows(self._h, L.i64ptr(c), n, int(half0), int(probe_off), int(increment),
+                                              int(cutoff), float(epsilon), int(rule), int(flags),
+                                              L.GROW_METHOD[method], vp(half), vp(steps), L.dptr(trace), cap),
+                "svihmm_grow_windows")
+        return half, steps, trace
+
     def read_packed(self):
         out = np.empty(self._packed_len())
         L.check(self._lib.svihmm_read_packed(self._h, L.dptr(out)), "svihmm_read_packed")

@@ -742,6 +742,31 @@ class VBHMM(VariationalHMMBase):
         self._psi_expectations()
         self._push_globals()
 
+    # the growth rules of select_L / select_buffer in one device call (``svihmm_grow_windows``); False: the
+    # lock-step host loops below, one device E-step per candidate
+    device_growth = True
+
+    def _device_growth_ok(self):
+        """The device route applies: the engine offers it, the emission family lives on the device (no
+        host-evaluated lliks) and the type overrides none of the per-window message hooks the host loop
+        would call."""
+        if not self.device_growth or not hasattr(self.engine, "grow_windows"):
+            return False
+        if not (self._niw_fastpath() or self._diag_fastpath() or self._cat_fastpath()):
+            return False
+        cls = type(self)
+        return all(getattr(cls, nm) is getattr(VBHMM, nm)
+                   for nm in ("get_local_messages", "get_marginal", "get_forward", "get_backward"))
+
+    def _grow_on_device(self, indices, half0, probe_off, Lincrement, Lcutoff, epsilon, rule):
+        if not len(indices):
+            return -1
+        self._upload_obs()
+        flags = self._push_emission()
+        half, _, _ = self.engine.grow_windows(indices, half0, probe_off=probe_off, increment=Lincrement,
+                                              cutoff=Lcutoff, epsilon=epsilon, rule=rule, flags=flags)
+        return int(np.max(half))
+
     def select_L(self, numIndices=1, epsilon=1e-5, minHalfL=1, avgResidual=False,
                  Lincrement=1, Lcutoff=1000):
         """reference :521-569; the per-index growth loops run in lock-step so every
@@ -749,6 +774,8 @@ class VBHMM(VariationalHMMBase):
         indices = npr.choice(self.T - 2 * minHalfL - 1, size=numIndices) + minHalfL
         self._prepare_messages()
         n = len(indices)
+        if self._device_growth_ok():
+            return self._grow_on_device(indices, minHalfL, 0, Lincrement, Lcutoff, epsilon, 1 if avgResidual else 0)
         Lcur = np.full(n, minHalfL, dtype=int)
         q_old = self._local_messages_batch(indices, minHalfL)[:, minHalfL, :]
         q_diff = np.full(n, np.finfo(np.float64).max)
@@ -797,6 +824,8 @@ class VBHMM(VariationalHMMBase):
         indices = npr.choice(self.T - 2 * halfL - 1, size=numIndices) + halfL
         self._prepare_messages()
         n = len(indices)
+        if self._device_growth_ok():
+            return self._grow_on_device(indices, halfL, halfL, Lincrement, Lcutoff, epsilon, 0)
         bufL = np.full(n, halfL, dtype=int)
         v0 = self._local_messages_batch(indices, halfL)
         q_old_left = v0[:, 0, :].copy()
