@@ -35,7 +35,8 @@
 extern "C" {
 #endif
 
-/* 3 (addition, nothing else changed meaning): svihmm_grow_windows.
+/* 3 (addition, nothing else changed meaning): svihmm_set_sequences, svihmm_estep_sequences.
+ * 3 (addition, nothing else changed meaning): svihmm_grow_windows.
  * 3 (addition, nothing else changed meaning): svihmm_ffbs_windows.
  * 3 (addition, nothing else changed meaning): svihmm_viterbi.
  * 3: svihmm_export_packed / svihmm_import_packed, svihmm_svi_set_adagrad / _read_adagrad,
@@ -256,6 +257,60 @@ int svihmm_estep_minibatch_ex(svihmm_ctx* h, const int64_t* starts, int32_t B,
  * emission family, on a K mismatch, B < 1 or Lm < 1, or a window outside [0, T). */
 int svihmm_suffstats(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t Lm, uint32_t flags,
                      const double* var_x, double* out_packed);
+
+/* ---- several sequences of unequal length on one handle ----------------------------------------
+ * Recordings, trials, chromosomes: the resident rows are N independent chains laid end to end.  The
+ * statistics of the whole are the sums over the sequences; no message and no transition pair crosses a join.
+ *
+ * svihmm_set_sequences declares that: sequence s is rows [seq_off[s], seq_off[s+1]).  seq_off has N + 1
+ *   entries, seq_off[0] = 0, strictly increasing, seq_off[N] = T; a length of 1 is allowed.  N = 0 (seq_off may
+ *   then be NULL) removes the declaration, and so does every call that replaces the resident rows
+ *   (svihmm_set_obs, svihmm_alloc_obs, svihmm_generate).  Fails with a message (the handle stays usable, an
+ *   earlier declaration stays in force): no observations, NULL seq_off with N > 0, N < 0, offsets that break
+ *   the rules above.
+ *   While a declaration is in force every entry point that checks windows against [0, T) (svihmm_loglik,
+ *   _forward_backward, _estep_minibatch(_ex), _suffstats, _pred_logprob, _viterbi, _ffbs_windows, the start
+ *   windows of _grow_windows, _svi_iteration) also rejects a window that holds rows of two sequences; the
+ *   message names the window.  (The candidate windows svihmm_grow_windows evaluates while it grows are checked
+ *   like any window batch: growth that would reach across a join fails with that message instead of reading a
+ *   neighbour's rows.)  A window inside one sequence gives exactly what it gives without a declaration, and
+ *   without a declaration nothing changes.
+ *
+ * svihmm_estep_sequences: the whole E-step of all N declared sequences under the globals currently set and
+ *   the current emission family (NIW, diagonal, Categorical).  For sequence s it computes what
+ *   svihmm_forward_backward(h, {seq_off[s]}, 1, len_s, flags, ..) computes: the chain starts from mod_init.
+ *   packed (the family's current layout, svihmm_packed_len):
+ *     emission statistics over the unmasked rows of all sequences;
+ *     A_raw = sum_s sum_{t=1}^{len_s-1} q[t-1] (x) q[t]  (batch form, hmmbatchcd.py:182-184); with
+ *       SVIHMM_TRANS_WRAP additionally, per sequence, the pair (last row of s, first row of s) -- the
+ *       per-window rule of quirk Q1;
+ *     lb = sum_s local_lb[s].
+ *   out_seq_lb[N]: local_lb of each sequence (sum_t LSE_k lalpha_t[k], quirk Q4).
+ *   out_q0[K] = sum_s var_x[seq_off[s]], added in ascending s (var_init = prior_init + out_q0).
+ *   Any of the three pointers may be NULL; the packed result stays in HBM for svihmm_read_packed /
+ *   _allreduce_packed / _export_packed.  SVIHMM_MASK_AS_NAN as elsewhere.
+ *   Routing: a sequence of at least 2048 rows goes through the whole-chain blocked scan
+ *   (svihmm_forward_backward's route for B = 1), one after the other; all shorter ones -- and every sequence
+ *   when an ltran entry lies below SVIHMM_LTRAN_LINEAR_MIN, which takes the literal logaddexp form as in
+ *   svihmm_forward_backward -- run in ONE launch of the ragged log-domain sweeps, one (sequence, direction)
+ *   pair per wavefront (K <= 64) or workgroup, longest first.  The statistics are one pass over all T rows.
+ *   A run is bit-reproducible, and the posterior rows and local_lb of a sequence do not depend on which other
+ *   sequences are declared or in what order (given the same resident rows).
+ *   Always fp64: the precision mode and what svihmm_get_precision reports are unchanged.  K <= 256.
+ *   Fails with a message before any device work (the handle stays usable): no declaration, no globals, no
+ *   emission family or no observations; a K mismatch between globals and emission family; K > 256;
+ *   SVIHMM_USE_HOST_LLIKS; T beyond the statistics GEMM's 32-bit row offsets.
+ *   Towards a running resident SVI loop it behaves as svihmm_suffstats does.
+ *   Intermediates afterwards: var_x of all T rows is readable as one [1, T, K] batch
+ *   (svihmm_read_intermediate / _read_rows, what = 3) and svihmm_state_argmax decodes all T rows; what = 0, 1, 2
+ *   fail with "... svihmm_estep_sequences keeps var_x only".
+ * Not covered: hmmsgd_metaobs.VBHMM on a list (its batch factors, quirk Q3, have no agreed multi-sequence
+ *   form; the boundary check above lets a caller sample windows safely), decoding all sequences in one
+ *   svihmm_viterbi / svihmm_ffbs_windows call (decode them one by one as windows {seq_off[s]}, B = 1,
+ *   Lm = len_s), the fp32 mode, host lliks, K > 256. */
+int svihmm_set_sequences(svihmm_ctx* h, const int64_t* seq_off, int32_t N);
+int svihmm_estep_sequences(svihmm_ctx* h, uint32_t flags, double* out_packed, double* out_seq_lb,
+                           double* out_q0);
 
 /* ---- the SVI loop with the variational state resident in HBM ----------------------------------
  * hmmsgd_metaobs.VBHMM.infer (:347-445) iterates  { stationary init :413-418, psi-expectations

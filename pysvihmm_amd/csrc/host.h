@@ -150,6 +150,13 @@ struct svihmm_ctx {
   // work
   Buf starts, ll, la, lb, q, lse_part, local_lb, logz, part, packed, scratch;
   Buf user_q, user_starts;         // svihmm_suffstats: the caller's posteriors and windows (never the E-step's q / starts)
+  // svihmm_set_sequences: the resident rows are seq_off.size() - 1 independent chains (empty: no declaration); the
+  // offsets' device copy.  svihmm_estep_sequences: concatenated posteriors [T][K] (swapped with `q` when the call
+  // ends), lalpha | lbeta | per-row LSE of the ragged sweeps, the ragged launch's sequence order, local_lb[N] | q0[K]
+  std::vector<int64_t> seq_off;
+  Buf seq_off_d, seq_q, seq_work, seq_ord, seq_out;
+  bool seq_internal = false;       // svihmm_estep_sequences is evaluating row ranges of its own (no boundary check)
+  bool seq_result = false;         // the intermediates held are svihmm_estep_sequences': var_x of all T rows only
   Buf vit;                         // svihmm_viterbi: score | z | final argmax | psi | path | chunk maps (launch_viterbi);
                                    // svihmm_ffbs_windows: logA | z | the caller's uniforms (launch_ffbs_windows);
                                    // svihmm_grow_windows: results / the rule's state (launch_grow_*)
@@ -385,6 +392,10 @@ bool sweep_mixed_ok(const svihmm_ctx* h, int B, int Lq, int off, int Lm, uint32_
 bool sweep_stats_ok(const svihmm_ctx* h, int B, int Lq, int off, int Lm, uint32_t flags);
 int launch_sweep_stats(svihmm_ctx* h, int B, int Lq, int off, int Lm, uint32_t flags);
 SviSync sweep_gate(svihmm_ctx* h, hipStream_t stream);
+int launch_fb_sequences(svihmm_ctx* h, int nseq, const int32_t* order, const int64_t* seq_off, int64_t row_base,
+                        int64_t span, int maxlen, const double* ll, double* q, double* seq_lb);
+int launch_seq_finish(svihmm_ctx* h, int N, const int64_t* seq_off, bool wrap, const double* q, const double* seq_lb,
+                      double* q0);
 int launch_niw_vlb(svihmm_ctx* h, int K, int D, const double* dmu, const double* dsg, const double* dka,
                    const double* dnu, double* th2, int* dstat, double* ld, const double* p0, double* dout);
 }

@@ -20,6 +20,7 @@
 // is algebraically the reference's LSE_i(la[t-1,i] + ltran[i,j]) + ll[t,j]
 // (hmmbase.py:295) with K exps + K logs per step instead of K^2.
 #include "host.h"
+#include <algorithm>
 #include "device_helpers.h"
 #include "kernels_misc.h"
 #include "kernels_svi.h"
@@ -82,7 +83,8 @@ int svihmm_destroy(svihmm_ctx* h) {
                  &h->svi_state, &h->svi_prior, &h->svi_work, &h->commtmp, &h->ll0, &h->a0v, &h->a0e,
                  &h->shift_d, &h->uwb, &h->uwd, &h->AexpF, &h->AexpTF, &h->svi_sync, &h->pipe_cnt,
                  &h->pipe_tabs[0].buf, &h->pipe_tabs[1].buf, &h->pipe_tabs[2].buf, &h->pipe_tabs[3].buf,
-                 &h->pipe_tabs[4].buf, &h->pipe_tabs[5].buf, &h->pipe_tabs[6].buf, &h->pipe_tabs[7].buf};
+                 &h->pipe_tabs[4].buf, &h->pipe_tabs[5].buf, &h->pipe_tabs[6].buf, &h->pipe_tabs[7].buf,
+                 &h->seq_off_d, &h->seq_q, &h->seq_work, &h->seq_ord, &h->seq_out};
   for (Buf* b : bufs) release(*b);
   if (h->vlb_host) { hipHostFree(h->vlb_host); h->vlb_host = nullptr; }
   if (h->svi_elbo) { hipHostFree(h->svi_elbo); h->svi_elbo = nullptr; }
@@ -156,6 +158,7 @@ int svihmm_set_obs(svihmm_ctx* h, const double* obs, int64_t T, int32_t D,
     HIPCK(hipMemcpyAsync(h->mask.p, mask, (size_t)T, hipMemcpyHostToDevice, h->stream));
   }
   h->T = T; h->D = D; h->gen_T = 0;
+  h->seq_off.clear();                  // (a declaration of sequences described the previous rows)
   h->svi_active = false;               // a resident SVI state belonged to the previous sequence
   h->center_pending = false;
   std::vector<double> c;
@@ -331,6 +334,7 @@ int svihmm_alloc_obs(svihmm_ctx* h, int64_t T, int32_t D, int32_t with_mask) {
     HIPCK(hipMemsetAsync(h->mask.p, 0, (size_t)T, h->stream));
   }
   h->T = T; h->D = D; h->gen_T = 0;
+  h->seq_off.clear();
   h->svi_active = false;
   CK(reset_shift(h, std::vector<double>((size_t)D, 0.0), 0, 0));
   h->center_pending = true;            // the first block that arrives fixes the shift
@@ -724,6 +728,21 @@ int svihmm_set_lliks(svihmm_ctx* h, const double* lliks, int32_t B, int32_t Lm) 
 }
 
 // ---- launch helpers -----------------------------------------------------------------
+// A declaration of sequences is in force (svihmm_set_sequences): every window [starts[b], starts[b] + Lm), already
+// known to lie inside [0, T), must lie inside ONE of them.  `fn`: prefix of the message ("" for none).
+static int check_window_sequences(const svihmm_ctx* h, const std::string& fn, const int64_t* starts, int B, int Lm) {
+  if (h->seq_off.empty() || h->seq_internal) return 0;
+  const std::vector<int64_t>& so = h->seq_off;
+  for (int b = 0; b < B; ++b) {
+    // the sequence that holds the window's first row: the last offset <= starts[b]
+    const size_t s = (size_t)(std::upper_bound(so.begin(), so.end(), starts[b]) - so.begin()) - 1;
+    if (starts[b] + Lm > so[s + 1])
+      return fail(fn + "window " + std::to_string(b) + " (rows " + std::to_string(starts[b]) + " .. " +
+                  std::to_string(starts[b] + Lm - 1) + ") holds rows of two sequences: sequence " + std::to_string(s) +
+                  " ends at row " + std::to_string(so[s + 1] - 1) + " (svihmm_set_sequences)");
+  }
+  return 0;
+}
 static int check_windows(svihmm_ctx* h, const int64_t* starts, int B, int Lm, bool need_obs) {
   if (B <= 0 || Lm <= 0) return fail("bad window batch (B, Lm must be positive)");
   if (need_obs) {
@@ -732,6 +751,7 @@ static int check_windows(svihmm_ctx* h, const int64_t* starts, int B, int Lm, bo
     for (int b = 0; b < B; ++b)
       if (starts[b] < 0 || starts[b] + Lm > h->T)
         return fail("window " + std::to_string(b) + " out of range");
+    CK(check_window_sequences(h, "", starts, B, Lm));
   }
   return 0;
 }
@@ -937,6 +957,7 @@ int prepare_ll(svihmm_ctx* h, const int64_t* starts, int B, int Lm, uint32_t fla
   h->cur_f32 = false;
   h->eh_float = false;
   h->step_major = false;
+  h->seq_result = false;
   if (host_ll) {
     if (!h->have_host_ll || h->hostB != B || h->hostLm != Lm)
       return fail("SVIHMM_USE_HOST_LLIKS: no uploaded lliks of shape [B,Lm,K]");
@@ -979,6 +1000,9 @@ int prepare_ll(svihmm_ctx* h, const int64_t* starts, int B, int Lm, uint32_t fla
 static int intermediate_ptr(svihmm_ctx* h, int what, int64_t row0, int64_t nrows, const double** out) {
   const int K = h->K, Lm = h->lastLm;
   Buf* src[] = {&h->ll, &h->la, &h->lb, &h->q};
+  if (h->seq_result && what != 3)
+    return fail("lliks / lalpha / lbeta are not available: svihmm_estep_sequences keeps var_x only (what = 3); "
+                "svihmm_forward_backward on a sequence's window returns its messages");
   if (!h->lin_mode || what == 3 || (what == 0 && h->eh_in_llE)) {
     if (what == 3) CK(ensure_q(h, h->lastB, Lm, h->stream));
     if (what == 2 && !h->have_lb) {
@@ -1118,7 +1142,7 @@ static int estep_pipelined(svihmm_ctx* h, const int64_t* starts, int B, int Lm, 
   CK(ensure_stats(h, plan[0].nchunk + plan[1].nchunk));
   h->have_host_ll = false;
   h->lin_mode = true; h->lin_stale = false; h->last_host_ll = false; h->eh_in_llE = false; h->last_flags = flags;
-  h->cur_f32 = false; h->step_major = false;
+  h->cur_f32 = false; h->step_major = false; h->seq_result = false;
   h->q_valid = false; h->curB = B;
   h->m_nb = 0; h->have_lb = true;
   hipStream_t A = h->stream, Bs = h->stream2;
@@ -1331,7 +1355,7 @@ static int check_window_range(const svihmm_ctx* h, const char* fn, const int64_t
   for (int b = 0; b < B; ++b)
     if (starts[b] < 0 || starts[b] + Lm > h->T)
       return fail(std::string(fn) + ": window " + std::to_string(b) + " reaches outside [0, T)");
-  return 0;
+  return check_window_sequences(h, std::string(fn) + ": ", starts, B, Lm);
 }
 // a decoder's window batch (B, Lm positive): host lliks of exactly its shape, or the model side and the windows
 static int check_window_call(const svihmm_ctx* h, const char* fn, const int64_t* starts, int B, int Lm, uint32_t flags) {
@@ -1374,6 +1398,122 @@ int svihmm_suffstats(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t Lm
   h->mirror_valid = false;
   CK(launch_mirror(h));
   if (out_packed) CK(read_packed_host(h, out_packed));
+  return 0;
+}
+
+// ---- several sequences of unequal length on one handle (include/svihmm.h) ---------------------
+int svihmm_set_sequences(svihmm_ctx* h, const int64_t* seq_off, int32_t N) {
+  const char* fn = "svihmm_set_sequences";
+  const auto bad = [fn](const std::string& what) { return fail(std::string(fn) + ": " + what); };
+  if (!h) return bad("NULL handle");
+  if (N < 0) return bad("N must not be negative");
+  if (N == 0) { h->seq_off.clear(); return 0; }
+  if (h->T <= 0 || !h->obs.p) return bad("no observations: call svihmm_set_obs first");
+  if (!seq_off) return bad("seq_off is NULL");
+  if (seq_off[0] != 0) return bad("seq_off[0] must be 0");
+  for (int s = 0; s < N; ++s)
+    if (seq_off[s + 1] <= seq_off[s])
+      return bad("offsets must be strictly increasing (seq_off[" + std::to_string(s + 1) + "] = " +
+                 std::to_string(seq_off[s + 1]) + " after " + std::to_string(seq_off[s]) + ")");
+  if (seq_off[N] != h->T)
+    return bad("seq_off[N] = " + std::to_string(seq_off[N]) + " must equal T = " + std::to_string(h->T));
+  CK(set_device(h));
+  const size_t nb = ((size_t)N + 1) * sizeof(int64_t);
+  CK(ensure(h->seq_off_d, nb));
+  CK(upload_staged(h, h->seq_off_d.p, seq_off, nb));
+  h->seq_off.assign(seq_off, seq_off + N + 1);
+  return 0;
+}
+
+// emission -> sweeps -> statistics of all declared sequences into h->packed, h->seq_out (local_lb[N] | q0[K]) and the
+// concatenated posteriors, asynchronous.  Long sequences (use_chain) one after the other through the whole-chain
+// scan, which writes the handle's ll / la / lb / q from row 0: their posteriors and local_lb are copied out before
+// the next starts.  All others in one ragged launch over the lliks of the smallest row range that covers them.
+static int estep_sequences_core(svihmm_ctx* h, uint32_t flags) {
+  const int N = (int)h->seq_off.size() - 1, K = h->K;
+  const int64_t T = h->T;
+  const std::vector<int64_t>& so = h->seq_off;
+  const uint32_t efl = flags & SVIHMM_MASK_AS_NAN;
+  std::vector<int32_t> ragged, longs;
+  for (int s = 0; s < N; ++s) (use_chain(h, 1, (int)(so[s + 1] - so[s])) ? longs : ragged).push_back(s);
+  // longest first: the launch's tail is short (ties in ascending s)
+  std::stable_sort(ragged.begin(), ragged.end(),
+                   [&so](int32_t a, int32_t b) { return so[a + 1] - so[a] > so[b + 1] - so[b]; });
+  CK(ensure(h->seq_q, (size_t)T * K * sizeof(double)));
+  CK(ensure(h->seq_out, ((size_t)N + K) * sizeof(double)));
+  double* seq_q = (double*)h->seq_q.p;
+  double* seq_lb = (double*)h->seq_out.p;
+  double* q0 = seq_lb + N;
+  const int64_t* sod = (const int64_t*)h->seq_off_d.p;
+  if (!ragged.empty()) {
+    int64_t r0 = T, r1 = 0;
+    for (int32_t s : ragged) { r0 = std::min(r0, so[s]); r1 = std::max(r1, so[s + 1]); }
+    CK(ensure(h->seq_ord, ragged.size() * sizeof(int32_t)));
+    CK(upload_staged(h, h->seq_ord.p, ragged.data(), ragged.size() * sizeof(int32_t)));
+    CK(prepare_ll(h, &r0, 1, (int)(r1 - r0), efl, false, false));
+    CK(launch_fb_sequences(h, (int)ragged.size(), (const int32_t*)h->seq_ord.p, sod, r0, r1 - r0,
+                           (int)(so[ragged[0] + 1] - so[ragged[0]]), (const double*)h->ll.p, seq_q, seq_lb));
+  }
+  for (int32_t s : longs) {
+    const int len = (int)(so[s + 1] - so[s]);
+    CK(prepare_ll(h, &so[s], 1, len, efl, false, true));
+    h->m_nb = 0;
+    CK(launch_fb_lin(h, 1, len, false));
+    CK(ensure_q(h, 1, len, h->stream));
+    HIPCK(hipMemcpyAsync(seq_q + (size_t)so[s] * K, h->q.p, (size_t)len * K * sizeof(double), hipMemcpyDeviceToDevice,
+                         h->stream));
+    HIPCK(hipMemcpyAsync(seq_lb + s, h->local_lb.p, sizeof(double), hipMemcpyDeviceToDevice, h->stream));
+  }
+  // statistics: the concatenated posteriors as ONE window of T rows without wrap, then the N boundaries
+  CK(ensure(h->user_starts, sizeof(int64_t)));
+  HIPCK(hipMemsetAsync(h->user_starts.p, 0, sizeof(int64_t), h->stream));
+  CK(launch_stats_posteriors(h, seq_q, (const int64_t*)h->user_starts.p, 1, (int)T, 0));
+  CK(launch_seq_finish(h, N, sod, (flags & SVIHMM_TRANS_WRAP) != 0, seq_q, seq_lb, q0));
+  // what is readable afterwards: var_x of all T rows as one [1, T, K] batch
+  std::swap(h->q, h->seq_q);
+  h->lin_mode = false; h->q_valid = true; h->lin_stale = true; h->m_nb = 0; h->have_lb = false;
+  h->lastB = 1; h->lastLm = (int)T;
+  h->seq_result = true;
+  return 0;
+}
+
+int svihmm_estep_sequences(svihmm_ctx* h, uint32_t flags, double* out_packed, double* out_seq_lb, double* out_q0) {
+  const char* fn = "svihmm_estep_sequences";
+  const auto bad = [fn](const std::string& what) { return fail(std::string(fn) + ": " + what); };
+  if (!h) return bad("NULL handle");
+  if (h->seq_off.empty()) return bad("no sequences declared: call svihmm_set_sequences first");
+  if (flags & SVIHMM_USE_HOST_LLIKS) return bad("SVIHMM_USE_HOST_LLIKS is not supported (host lliks carry no sequence offsets)");
+  if (!h->have_globals) return bad("no globals: call svihmm_set_globals first");
+  CK(check_window_model(h, fn));
+  if (h->K > 256) return bad("K = " + std::to_string(h->K) + " > 256 not supported");
+  {
+    // (the statistics pass addresses the T rows as one window: launch_stats_posteriors' limit, before any device work)
+    const int64_t rpc = h->emis_cat ? 0 : stats_plan(h, h->T, h->variant[SVIHMM_VAR_STATS_CHUNKS]).rpc;
+    if (h->T > 0x7fffffff || (h->T + rpc) * (int64_t)(h->emis_cat ? 1 : h->Kp) >= ((int64_t)1 << 31))
+      return bad("T = " + std::to_string(h->T) + " rows are too many for the statistics GEMM's 32-bit row offsets");
+  }
+  CK(set_device(h));
+  CK(wait_side_streams(h));
+  // always fp64, and the precision mode's report about the last E-step batch stays (as svihmm_grow_windows)
+  const int report = h->f32_report_hold >= 0 ? h->f32_report_hold : (h->cur_f32 || h->eh_float) ? 1 : 0;
+  const int prec = h->prec;
+  h->prec = 0;
+  h->seq_internal = true;
+  const int rc = estep_sequences_core(h, flags);
+  h->seq_internal = false;
+  h->prec = prec;
+  h->cur_f32 = false; h->eh_float = false;
+  h->f32_report_hold = report;
+  if (rc) return rc;
+  h->have_packed = true;
+  h->mirror_valid = false;
+  CK(launch_mirror(h));
+  const int N = (int)h->seq_off.size() - 1;
+  if (out_seq_lb) CK(d2h(h, out_seq_lb, h->seq_out.p, (size_t)N * sizeof(double)));
+  if (out_q0) CK(d2h(h, out_q0, (const double*)h->seq_out.p + N, (size_t)h->K * sizeof(double)));
+  if (out_packed) CK(read_packed_host(h, out_packed));
+  HIPCK(hipStreamSynchronize(h->stream));
+  CK(check_emission_status(h));
   return 0;
 }
 
@@ -2427,6 +2567,10 @@ int svihmm_grow_windows(svihmm_ctx* h, const int64_t* centers, int32_t n, int32_
   for (int i = 0; i < n; ++i)
     if (centers[i] - half0 < 0 || centers[i] + half0 >= h->T)
       return bad("start window of centre " + std::to_string(i) + " reaches outside [0, T)");
+  for (int i = 0; i < n; ++i) {
+    const int64_t st = centers[i] - half0;
+    CK(check_window_sequences(h, std::string(fn) + ": start ", &st, 1, 2 * half0 + 1));
+  }
   const bool products_ok = h->K <= 64 && !h->exact_log;
   if (method == SVIHMM_GROW_PRODUCTS && !products_ok)
     return bad("method PRODUCTS needs K <= 64 and every ltran entry >= SVIHMM_LTRAN_LINEAR_MIN (K = " +
@@ -2496,6 +2640,7 @@ int svihmm_generate(svihmm_ctx* h, int64_t T, int32_t K, int32_t D, const double
     HIPCK(hipGetLastError());
   }
   h->T = T; h->D = D; h->gen_T = T;
+  h->seq_off.clear();
   h->svi_active = false;
   h->center_pending = false;
   {   // centre: the plain average of the state means (a point inside the data)

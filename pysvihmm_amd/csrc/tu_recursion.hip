@@ -6,6 +6,7 @@
 #include "kernels_viterbi.h"
 #include "kernels_ffbs_windows.h"
 #include "kernels_grow.h"
+#include "kernels_sequences.h"
 
 extern "C" {
 
@@ -1050,6 +1051,82 @@ int launch_grow_probe(svihmm_ctx* h, int n, int nact, const int32_t* idx, int b,
 int grow_state_results(svihmm_ctx* h, int n, int trace_cap, const int32_t** ist_out, const double** trace_out) {
   const GrowState g = grow_state(h, n, trace_cap);
   *ist_out = g.ist; *trace_out = g.trace;
+  return 0;
+}
+
+// ---- svihmm_estep_sequences (kernels_sequences.h) ----------------------------------------------
+// The ragged sweeps over the nseq sequences listed in `order` (device, longest first): lliks `ll` whose row 0 is
+// global row row_base, span rows -> posterior rows at their global index in q [T][K] and seq_lb[s].  lalpha / lbeta /
+// the per-row LSE live in h->seq_work, which no other route touches.  maxlen: the longest of the sequences.
+int launch_fb_sequences(svihmm_ctx* h, int nseq, const int32_t* order, const int64_t* seq_off, int64_t row_base,
+                        int64_t span, int maxlen, const double* ll, double* q, double* seq_lb) {
+  if (!h->have_globals) return fail("no globals: call svihmm_set_globals");
+  const int K = h->K;
+  if (K > 256) return fail("svihmm_estep_sequences: K > 256 not supported");
+  const size_t ne = (size_t)span * K;
+  CK(ensure(h->seq_work, (2 * ne + (size_t)span) * sizeof(double)));
+  double* la = (double*)h->seq_work.p;
+  double* lb = la + ne;
+  double* row_lse = lb + ne;
+  const double* A = (const double*)h->Aexp.p;
+  const double* mi = (const double*)h->mod_init.p;
+  dim3 grid((unsigned)nseq, 2);
+  {
+    ProfScope ps(h, KS_FB);
+    if (h->exact_log) {
+      const int threads = (K + 63) / 64 * 64;
+      const int in_lds = ((size_t)K * (K + 1) + 2 * K) * 8 <= 150 * 1024;
+      const size_t lds = (2 * (size_t)K + (in_lds ? (size_t)K * (K + 1) : 0)) * 8;
+      if (lds > 64 * 1024)
+        hipFuncSetAttribute((const void*)k_seq_exact, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL(k_seq_exact, grid, dim3(threads), lds, h->stream, ll, row_base, seq_off, order,
+                         (const double*)h->ltran.p, mi, K, in_lds, la, lb);
+    } else if (K <= 16)
+      hipLaunchKernelGGL(k_seq_wave<16>, grid, dim3(64), 0, h->stream, ll, row_base, seq_off, order, A, mi, K, la, lb);
+    else if (K <= 32)
+      hipLaunchKernelGGL(k_seq_wave<32>, grid, dim3(64), 0, h->stream, ll, row_base, seq_off, order, A, mi, K, la, lb);
+    else if (K <= 64)
+      hipLaunchKernelGGL(k_seq_wave<64>, grid, dim3(64), 0, h->stream, ll, row_base, seq_off, order, A, mi, K, la, lb);
+    else {
+      const int threads = (K + 63) / 64 * 64;
+      const int in_lds = ((size_t)K * K * 8 + 2 * K * 8 + 128) <= 150 * 1024;
+      const size_t lds = (2 * (size_t)K + 16) * 8 + (in_lds ? (size_t)K * K * 8 : 0);
+      if (lds > 64 * 1024)
+        hipFuncSetAttribute((const void*)k_seq_block, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL(k_seq_block, grid, dim3(threads), lds, h->stream, ll, row_base, seq_off, order, A,
+                         (const double*)h->AexpT.p, mi, K, in_lds, la, lb);
+    }
+    HIPCK(hipGetLastError());
+  }
+  {
+    ProfScope ps(h, KS_POSTERIOR);
+    // 64 rows per posterior workgroup of the longest sequence, at most 1024 workgroups per sequence
+    int nseg = (maxlen + 63) / 64;
+    if (nseg > 1024) nseg = 1024;
+    if (nseg < 1) nseg = 1;
+    dim3 gp((unsigned)nseq, (unsigned)nseg);
+#define SEQ_POST(KPL)                                                                                        \
+  hipLaunchKernelGGL(k_seq_posterior<KPL>, gp, dim3(256), 0, h->stream, (const double*)la, (const double*)lb, \
+                     row_base, seq_off, order, K, q, row_lse)
+    if (K <= 64) SEQ_POST(1); else SEQ_POST(4);
+#undef SEQ_POST
+    hipLaunchKernelGGL(k_seq_lb, dim3((unsigned)nseq), dim3(64), 0, h->stream, (const double*)row_lse, row_base,
+                       seq_off, order, seq_lb);
+    HIPCK(hipGetLastError());
+  }
+  return 0;
+}
+// behind launch_stats_posteriors over the concatenated posteriors as ONE window: the boundary correction of A_raw
+// (join pairs out, with `wrap` each sequence's own wrap pair in), q0, and the ELBO total into the packed lb slot
+int launch_seq_finish(svihmm_ctx* h, int N, const int64_t* seq_off, bool wrap, const double* q, const double* seq_lb,
+                      double* q0) {
+  const int K = h->K;
+  ProfScope ps(h, KS_STATS);
+  hipLaunchKernelGGL(k_seq_fix, dim3((unsigned)((K * K + 255) / 256 + 1)), dim3(256), 0, h->stream, q, seq_off, N, K,
+                     wrap ? 1 : 0, (double*)h->packed.p, q0);
+  hipLaunchKernelGGL(k_sum_lb, dim3(1), dim3(256), 0, h->stream, seq_lb, N,
+                     (double*)h->packed.p + (packed_len(h) - 1));
+  HIPCK(hipGetLastError());
   return 0;
 }
 

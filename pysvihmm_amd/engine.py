@@ -85,6 +85,7 @@ class HipEngine(object):
         self.V = 0            # > 0: Categorical emission with V symbols is active
         self.diag = False     # diagonal-Gaussian emission is active (its own packed layout)
         self._comm = False
+        self.seq_off = None   # offsets declared with set_sequences (every upload of rows removes them)
 
     # -- lifecycle ------------------------------------------------------------------
     def close(self):
@@ -143,6 +144,7 @@ class HipEngine(object):
                 raise RuntimeError("mask must have shape (T,)")
         L.check(self._lib.svihmm_set_obs(self._h, L.dptr(obs), T, D, L.u8ptr(m)), "svihmm_set_obs")
         self.T, self.D = T, D
+        self.seq_off = None
         self._obs_owner = None        # whoever uploaded claims the resident copy afterwards
 
     def generate(self, tran, means, chols, T, seed=0):
@@ -160,6 +162,7 @@ class HipEngine(object):
         L.check(self._lib.svihmm_generate(self._h, int(T), K, D, L.dptr(cdf), L.dptr(means), L.dptr(chols),
                                           int(seed) & 0xFFFFFFFFFFFFFFFF), "svihmm_generate")
         self.T, self.D = int(T), D
+        self.seq_off = None
         self._obs_owner = None
 
     def read_generated(self, want_obs=True, want_sts=True):
@@ -198,6 +201,7 @@ class HipEngine(object):
                 raise RuntimeError("mask must have shape (T,)")
         L.check(self._lib.svihmm_alloc_obs(self._h, T, D, int(m is not None)), "svihmm_alloc_obs")
         self.T, self.D = T, D
+        self.seq_off = None
         self._obs_owner = None
         row = 0
         for blk in blocks:
@@ -349,6 +353,46 @@ class HipEngine(object):
         L.check(self._lib.svihmm_suffstats(self._h, L.i64ptr(st), len(st), Lm, int(flags), L.dptr(q),
                                            L.dptr(out)), "svihmm_suffstats")
         return self._wrap_packed(out) if read else None
+
+    def set_sequences(self, lengths):
+        """Declare the resident rows as consecutive independent sequences of the given lengths
+        (``svihmm_set_sequences``; their sum must be ``T``).  ``None`` / ``()`` removes the declaration,
+        as every upload of new rows does.  While it is in force, windows that hold rows of two
+        sequences are rejected by every call that takes windows."""
+        n = 0 if lengths is None else len(lengths)
+        if n == 0:
+            L.check(self._lib.svihmm_set_sequences(self._h, None, 0), "svihmm_set_sequences")
+            self.seq_off = None
+            return
+        off = np.zeros(n + 1, dtype=np.int64)
+        np.cumsum(np.asarray(lengths, dtype=np.int64).ravel(), out=off[1:])
+        self.set_sequence_offsets(off)
+
+    def set_sequence_offsets(self, seq_off):
+        """``set_sequences`` from the ``N + 1`` offsets themselves (``seq_off[0] = 0 .. seq_off[N] = T``)."""
+        off = np.ascontiguousarray(np.asarray(seq_off, dtype=np.int64).ravel())
+        if len(off) < 2:
+            raise RuntimeError("set_sequence_offsets: need at least two offsets")
+        L.check(self._lib.svihmm_set_sequences(self._h, L.i64ptr(off), len(off) - 1), "svihmm_set_sequences")
+        self.seq_off = off
+
+    def estep_sequences(self, flags=0, read=True):
+        """Whole E-step of all declared sequences in one device call (``svihmm_estep_sequences``):
+        ``(stats, seq_lb[N], q0[K])`` -- ``stats`` as ``estep`` wraps them (None with read=False: they
+        stay in HBM for ``allreduce_packed``), ``A_raw`` in the batch form summed over the sequences
+        (``TRANS_WRAP``: plus each sequence's own wrap pair), ``lb = seq_lb.sum()``, ``q0`` the sum of
+        the sequences' first posterior rows.  Afterwards ``var_x`` of all T rows is readable
+        (``read_rows("var_x", ..)``, ``read_intermediate("var_x", 1, T)``, ``state_argmax``)."""
+        self._pre_mutate()
+        off = getattr(self, "seq_off", None)
+        n = 0 if off is None else len(off) - 1      # (none declared: the library says so)
+        out = np.empty(self._packed_len()) if read else None
+        seq_lb = np.empty(max(n, 1))
+        q0 = np.empty(max(self.K, 1))
+        L.check(self._lib.svihmm_estep_sequences(self._h, int(flags), L.dptr(out), L.dptr(seq_lb), L.dptr(q0)),
+                "svihmm_estep_sequences")
+        self._rows = self.T
+        return (self._wrap_packed(out) if read else None), seq_lb[:n], q0[:self.K]
 
     def _packed_len(self):
         if self.V:

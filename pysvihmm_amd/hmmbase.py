@@ -57,6 +57,31 @@ def is_diag_gaussian(e):
             and t.expected_log_likelihood is DiagonalGaussian.expected_log_likelihood)
 
 
+def concat_sequences(obs, mask=None):
+    """``obs`` as a list / tuple of ``[T_s, D]`` arrays (several independent sequences) ->
+    ``(rows [sum T_s, D], mask or None, seq_off int64[N + 1])``; ``mask`` may be a matching list, one
+    concatenated array or None.  Anything else passes through with ``seq_off = None``.  A one-element
+    list gives that element itself (the model then behaves exactly as with the bare array)."""
+    if not isinstance(obs, (list, tuple)):
+        return obs, mask, None
+    if len(obs) == 0:
+        raise RuntimeError("obs is an empty list of sequences")
+    seqs = [np.asarray(o) for o in obs]
+    if any(o.ndim != seqs[0].ndim or o.ndim not in (1, 2) or o.shape[0] < 1 for o in seqs) or \
+            any(o.shape[1:] != seqs[0].shape[1:] for o in seqs):
+        raise RuntimeError("every sequence must be a non-empty [T_s, D] array of one common D")
+    seq_off = np.zeros(len(seqs) + 1, dtype=np.int64)
+    np.cumsum([o.shape[0] for o in seqs], out=seq_off[1:])
+    if isinstance(mask, (list, tuple)):
+        if len(mask) != len(seqs) or any(np.shape(m) != (o.shape[0],) for m, o in zip(mask, seqs)):
+            raise RuntimeError("mask must list one [T_s] array per sequence")
+        mask = mask[0] if len(seqs) == 1 else np.concatenate([np.asarray(m).astype('bool') for m in mask])
+    elif mask is not None and np.shape(mask) != (int(seq_off[-1]),):
+        raise RuntimeError("a concatenated mask must have one entry per row of all sequences")
+    rows = obs[0] if len(seqs) == 1 else np.concatenate(seqs, axis=0)
+    return rows, mask, seq_off
+
+
 def dirichlet_elbo(prior, var):
     """sum over rows of E_q[log Dir(.|prior_r)] + H[Dir(.|var_r)] for row-wise Dirichlet factors
     (the ``*_energy + *_entropy`` terms of reference hmmbase.py:150-181 and
@@ -119,6 +144,8 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         # copy: mean and covariance of the prior objects are the (random) initial values
         self.var_emit = deepcopy(prior_emit)
 
+        # several sequences (a list of [T_s, D] arrays): rows concatenated, offsets beside them
+        obs, mask, self.seq_off = concat_sequences(obs, mask)
         self.obs = obs
         self.K = self.prior_tran.shape[0]
         if obs.ndim == 1:
@@ -156,6 +183,7 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         d.pop('_prior_stack', None)
         d.pop('_host_lliks', None)
         d.pop('_obs_print', None)
+        d.pop('_seq_var_x', None)
         d['_engine'] = None       # device handles are not picklable
         d['_obs_dirty'] = True
         return d
@@ -164,7 +192,10 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         self.__dict__.update(d)
 
     def set_data(self, obs, mask=None):
+        obs, mask, self.seq_off = concat_sequences(obs, mask)
         self.obs = obs
+        if self._multi():
+            self.T = int(self.seq_off[-1])      # (several sequences state their own row count)
         if mask is None:
             self.mask = np.zeros(self.obs.shape[0], dtype='bool')
         else:
@@ -181,6 +212,9 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         eng = self.engine
         if force or self._obs_dirty or getattr(eng, "_obs_owner", None) != id(self):
             eng.set_obs(self.obs, self.mask)
+            if self._multi() and hasattr(eng, "set_sequences"):
+                # (from here on the engine rejects windows that hold rows of two sequences)
+                eng.set_sequences(np.diff(self.seq_off))
             eng._obs_owner = id(self)
             self._obs_dirty = False
             self._obs_print = self._obs_fingerprint()
@@ -207,6 +241,58 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
             return False                  # default: upload again (in-place edits of any size count)
         fp = self.__dict__.get("_obs_print")
         return fp is not None and fp == self._obs_fingerprint()
+
+    # -- several sequences ----------------------------------------------------------
+    def _multi(self):
+        """More than one sequence (``obs`` was a list of at least two): total statistics are the
+        sums over the sequences, nothing crosses a join."""
+        so = self.__dict__.get("seq_off")
+        return so is not None and len(so) > 2
+
+    def _require_fused_sequences(self, fused):
+        if self._multi() and not fused:
+            raise RuntimeError("several sequences: infer(fused=False) and local_update / global_update "
+                               "overrides are not supported (the literal global_update would walk "
+                               "across the joins)")
+
+    def _sequences_estep(self):
+        """E-step of all sequences under the current variational parameters: ``(stats, lb, q0)`` with
+        the statistics summed over the sequences (batch transition form), ``lb = sum_s local_lb[s]``
+        and ``q0 = sum_s var_x[first row of s]``.  One ``estep_sequences`` call where the engine has
+        it, else one ``estep([off], len)`` per sequence with the sums formed here."""
+        if not (self._niw_fastpath() or self._diag_fastpath() or self._cat_fastpath()):
+            raise RuntimeError("several sequences need an emission family the device evaluates "
+                               "(NIW / diagonal Gaussian, Categorical): host lliks are not supported")
+        self._psi_expectations()
+        self._upload_obs()
+        self._push_globals()
+        flags = self._push_emission()
+        self._seq_flags = flags
+        eng = self.engine
+        self._seq_var_x = None
+        if hasattr(eng, "estep_sequences"):
+            st, seq_lb, q0 = eng.estep_sequences(flags=flags)
+            return st, float(st.lb[0]), q0
+        so = self.seq_off
+        total, lb, q0 = None, 0., np.zeros(self.K)
+        var_x = np.empty((self.T, self.K))
+        for s in range(len(so) - 1):
+            off, ln = int(so[s]), int(so[s + 1] - so[s])
+            st = eng.estep([off], ln, flags=flags)
+            total = st.buf.copy() if total is None else total + st.buf
+            lb += float(st.lb[0])
+            var_x[off:off + ln] = eng.read_intermediate("var_x", 1, ln)[0]
+            q0 += var_x[off]
+        self._seq_var_x = var_x
+        st = type(st)(total, st.K, getattr(st, "V", None) if hasattr(st, "counts") else st.D)
+        st.lb[0] = lb
+        return st, lb, q0
+
+    def _read_var_x(self):
+        """``var_x`` [T, K] of the last fused E-step."""
+        if self._multi() and self.__dict__.get("_seq_var_x") is not None:
+            return self._seq_var_x
+        return self.engine.read_intermediate("var_x", 1, self.T)[0]
 
     def _psi_expectations(self):
         """reference hmmbase.py:214-216."""
@@ -350,6 +436,11 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         if obs is not None or mask is not None:
             self.set_data(self.obs if obs is None else obs,
                           self.mask if mask is None else mask)
+        if self._multi():
+            # every sequence from mod_init, nothing across a join: one device call, then the rows
+            _, self._lZ, _ = self._sequences_estep()
+            self._fetch_local()
+            return
         self._psi_expectations()
         self._upload_obs()
         self._push_globals()
@@ -409,6 +500,9 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         """Whole-chain E-step + expected sufficient statistics on the device, batch
         transition form (hmmbatchcd.py:182-184): used by the batch infer() loops so
         that only O(K^2 + K D^2) numbers cross PCIe per iteration."""
+        if self._multi():
+            st, self._lZ, self._q0 = self._sequences_estep()
+            return st
         self._psi_expectations()
         self._upload_obs()
         self._push_globals()
@@ -445,6 +539,19 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         """Pull the per-time-step arrays of the last device E-step to the host
         attributes (documented reference attributes)."""
         T = self.T
+        if self._multi():
+            # var_x from the concatenated read-back, the messages sequence by sequence (the engine
+            # still holds the globals and emission factors of the last E-step)
+            eng, so = self.engine, self.seq_off
+            self.var_x = self._read_var_x()
+            self.lliks, self.lalpha, self.lbeta = (np.empty((T, self.K)) for _ in range(3))
+            for s in range(len(so) - 1):
+                off, ln = int(so[s]), int(so[s + 1] - so[s])
+                r = eng.forward_backward([off], ln, flags=self._seq_flags, want=("lalpha", "lbeta"))
+                self.lalpha[off:off + ln] = r["lalpha"][0]
+                self.lbeta[off:off + ln] = r["lbeta"][0]
+                self.lliks[off:off + ln] = eng.read_intermediate("lliks", 1, ln)[0]
+            return
         self.lliks = self.engine.read_intermediate("lliks", 1, T)[0]
         self.lalpha = self.engine.read_intermediate("lalpha", 1, T)[0]
         self.lbeta = self.engine.read_intermediate("lbeta", 1, T)[0]
@@ -471,6 +578,9 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
 
     def _full_estep_device(self):
         """Whole-chain E-step whose per-row results stay in HBM (for hamming_dist(None, ...))."""
+        if self._multi():
+            self._sequences_estep()
+            return
         self._psi_expectations()
         self._upload_obs()
         self._push_globals()
@@ -564,6 +674,8 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         ``full_var_x=None``: the whole-chain E-step, the arg-max and the K x K count matrix
         run on the device and only the labels cross the bus (T = 1e6, K = 64: 4 MB instead
         of the 512 MB of var_x); the distance follows from the counts."""
+        if full_var_x is None and self._multi() and not hasattr(self.engine, "estep_sequences"):
+            full_var_x = self.full_local_update()      # (no device call that decodes all sequences)
         if full_var_x is None:
             true_sts = np.asarray(true_sts).ravel()
             self._full_estep_device()

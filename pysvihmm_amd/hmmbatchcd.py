@@ -51,6 +51,7 @@ class VBHMM(VariationalHMMBase):
         if type(self).local_update is not VariationalHMMBase.local_update \
                 or type(self).global_update is not VBHMM.global_update:
             fused = False
+        self._require_fused_sequences(fused)
         route = not fused and self._batch_stats_route(VBHMM.global_update)
         # the reference's "self.obs[self.mask,:]" is a no-op (quirk Q9): masked rows
         # still enter lliks, but are excluded from the emission update
@@ -91,7 +92,7 @@ class VBHMM(VariationalHMMBase):
                 self.elbo = lb
                 self.elbo_vec[it] = lb
                 if fused and np.any(self.mask):
-                    self.var_x = self.engine.read_intermediate("var_x", 1, self.T)[0]
+                    self.var_x = self._read_var_x()
                 tmp = self.pred_logprob()
                 if tmp is not None:
                     self.pred_logprob_mean[it] = np.mean(tmp)

@@ -56,6 +56,7 @@ class VBHMM(VariationalHMMBase):
         if type(self).local_update is not VariationalHMMBase.local_update \
                 or type(self).global_update is not VBHMM.global_update:
             fused = False
+        self._require_fused_sequences(fused)
         route = not fused and self._batch_stats_route(VBHMM.global_update, ("niw", "diag"))
         self.obs_full = self.obs.copy()
         self.obs[self.mask, :] = np.nan       # hmmbatchsgd.py:149 (NaN rows -> lliks 0)
@@ -92,7 +93,7 @@ class VBHMM(VariationalHMMBase):
             self.elbo_vec[it] = lb
             if np.any(self.mask):
                 if fused:
-                    self.var_x = self.engine.read_intermediate("var_x", 1, self.T)[0]
+                    self.var_x = self._read_var_x()
                 tmp = self.pred_logprob()
                 if tmp is not None:
                     self.pred_logprob_mean[it] = np.mean(tmp)

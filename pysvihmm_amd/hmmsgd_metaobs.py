@@ -121,6 +121,10 @@ class VBHMM(VariationalHMMBase):
                                     prior_emit, mask=mask, init_init=init_init,
                                     init_tran=init_tran, verbose=verbose,
                                     sts=sts, engine=engine, device=device, dtype=dtype)
+        if self._multi():
+            # (the batch factors (T - 2L - 1)/(2L S), quirk Q3, have no agreed multi-sequence form)
+            raise RuntimeError("hmmsgd_metaobs.VBHMM takes one sequence: a list of several is supported "
+                               "by the batch classes (hmmbatchcd, hmmbatchsgd) only")
 
         self.elbo = -np.inf
         self.tau = tau
