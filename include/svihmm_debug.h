@@ -39,7 +39,7 @@ int svihmm_profile_read(svihmm_ctx* h, double ms_out[SVIHMM_NKERN],
                         int64_t count_out[SVIHMM_NKERN]);
 const char* svihmm_kernel_name(int32_t slot);
 /* The kernel function the slot's LAST launch dispatched, as rocprofv3 prints it (e.g.
- * "k_stats_mfma4<5, 2, 2, 3, true, false, double, double, 3>"; "" when unknown): bench.py checks it against
+ * "k_stats_mfma4<5, 2, 2, 3, true, false, double, double, 3, 1>"; "" when unknown): bench.py checks it against
  * the kernel name in the committed profile before it quotes that profile's duration. */
 const char* svihmm_last_kernel_name(svihmm_ctx* h, int32_t slot);
 /* ---- kernel-selection knobs (svihmm_set_variant) ------------------------------------------ */
@@ -48,7 +48,7 @@ const char* svihmm_last_kernel_name(svihmm_ctx* h, int32_t slot);
  * This table is the only place where the slots and codes are written down: the host code under pysvihmm_amd/csrc
  * reads the knobs by these names, pysvihmm_amd/_lib.py's VARIANT mirrors the slot names (tests/test_variant_table.py).
  * The numbers are fixed: tools/ and the committed profiles refer to them.  Some slots carry two unrelated switches
- * (5, 7, 9, 10, 13); their entries say so. */
+ * (5, 7, 9, 10, 12, 13); their entries say so. */
 #define SVIHMM_NVARIANT 24      /* size of the handle's knob array: slots 18 .. 23 are accepted and read by nothing */
 enum {
   /* 0: the resident SVI loop's dependency mechanism (0: device-side counters where kernels of two streams run side
@@ -88,7 +88,8 @@ enum {
   SVIHMM_VAR_STATS_TILING = 10,
   /* 11: svihmm_allreduce_packed forms the sum in caller coordinates also at one rank */
   SVIHMM_VAR_ALLREDUCE_COORDS = 11,
-  /* 12: barrier-free statistics GEMM with three LDS buffers */
+  /* 12: barrier-free statistics GEMM with three LDS buffers (code 1), and how that kernel's staging threads address
+   *    obs / ah / bh (code 2) */
   SVIHMM_VAR_STATS_LDS3 = 12,
   /* 13: two switches: wide models' sweeps with 32 windows per workgroup (code 1), and the NIW -> theta builder
    *    for 16 < D <= 32 (codes 2 / 3) */
@@ -171,6 +172,9 @@ enum {
   SVIHMM_ALLREDUCE_COORDS_ON = 1,        /* the multi-rank path's coordinate round trip, exercised on a single GPU */
   /* STATS_LDS3 */
   SVIHMM_STATS_LDS3_OFF = 1,             /* the double-buffered kernel */
+  SVIHMM_STATS_LDS3_FLAT = 2,            /* the three-buffer kernel, but its staging loads stay flat loads from clamped
+                                            addresses behind value selects instead of buffer loads with 32-bit lane
+                                            offsets (csrc/kernels_stats.h, SG) -- same results bit for bit */
   /* WIDE_SWEEPS */
   SVIHMM_WIDE_SWEEPS_16 = 1,             /* 16 windows per workgroup */
   SVIHMM_WIDE_SWEEPS_THETA_OLD = 2,      /* NIW -> theta for 16 < D <= 32 by the builder that leaves half the wave idle

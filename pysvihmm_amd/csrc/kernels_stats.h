@@ -211,15 +211,29 @@ template <> struct MF<float> {
 // has committed in stage s - 1, i.e. has left stage s - 2.  The row-info slot of stage s + 3 is
 // committed by wave 0 BEFORE its data commit of the same stage, so the same counter covers it.
 // (Knock-out measurement on the bench shape: without the barrier the kernel runs 1.41 -> 1.31 ms.)
+// SG: how the staging threads address obs / ah / bh.  0: flat loads from 64-bit per-thread pointers, rows that are
+// invalid, masked or without predecessor read a clamped address and their values are replaced by selects.  1
+// (fp64 messages, K == Kp, no qout; the host checks the extents): raw buffer loads -- one descriptor per array, built
+// once per workgroup from uniform values (obs from its first element, ah / bh from message row QM, each ending with
+// its array or after 2^31 bytes), and a 32-bit byte offset per lane.  A row that contributes nothing carries the
+// offset ST_NOROW: beyond every descriptor's range, so the hardware returns 0.0 without touching memory and neither a
+// clamp nor a select is left in the stage loop; the ones column is OR-ed in from the row record.  The staged values
+// are the same bit for bit (0.0 instead of a finite value times a 0.0 scale).
+#define ST_NOROW 0x80000000u
+typedef unsigned st_u2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ st_u2 st_bload(__amdgpu_buffer_rsrc_t r, unsigned byteoff) {
+  return __builtin_amdgcn_raw_buffer_load_b64(r, (int)byteoff, 0, 0);
+}
 template <int MT, int NTW, int NSPLIT, int XK, bool LIN, bool TRONLY = false, typename CT = double,
-          typename ST = double, int NB = 2>
+          typename ST = double, int NB = 2, int SG = 0>
 __global__ __launch_bounds__(256 * NSPLIT) void k_stats_mfma4(
     const double* __restrict__ obs, const uint8_t* __restrict__ mask,
     const int64_t* __restrict__ starts, int64_t nrows, int Lm, int D, int K, int Fp, int F,
     const int* __restrict__ fab, const ST* __restrict__ q, int64_t rows_per_chunk,
     uint32_t flags, int Lq, int off, double* __restrict__ part, int KpTot, int mt_limit,
     const ST* __restrict__ bh, const double* __restrict__ hx, const double* __restrict__ gx,
-    const double2* __restrict__ zfac, double* __restrict__ qout, int smB = 0) {
+    const double2* __restrict__ zfac, double* __restrict__ qout, int smB = 0, int64_t obs_len = 0) {
+  // obs_len (SG == 1): elements of obs, at most 2^28; there off == 0, Lq == Lm and q / bh hold all nrows rows
   // smB (LIN, whole batches only: q / bh start at window 0): window count of the batch whose ah / bh rows lie in the
   // step-major layout (kernels_msg_layout.h), 0 = row-major.  Only the message rows' offsets change: they are taken
   // relative to the first row of the 16-window group the chunk starts in (QM), hx / gx stay row-major behind Q0.
@@ -228,6 +242,7 @@ __global__ __launch_bounds__(256 * NSPLIT) void k_stats_mfma4(
   // q = ah bh scale they form while staging, for the transition-block launch that follows
   static_assert(ST_RB == 32, "row permutation assumes 32-row stages");
   static_assert(NB == 2 || NB == 3, "double or triple buffering");
+  static_assert(SG == 0 || (!TRONLY && sizeof(ST) == 8 && sizeof(CT) == 8), "buffer-load staging: the fp64 feature instances");
   // column stride of the A-operand tile: NB buffers of 33 row slots + padding such that 16
   // consecutive columns fall on 16 different bank pairs (67 = 3 mod 32 doubles; 101 = 5 mod 32)
   constexpr int CC = NB == 2 ? ST_CC : 3 * ST_CS + 2;
@@ -293,9 +308,19 @@ __global__ __launch_bounds__(256 * NSPLIT) void k_stats_mfma4(
   const int64_t QM = (LIN && smB) ? (bw0 & ~(int64_t)15) * Lq : Q0;     // first message row the offsets count from
   const ST* __restrict__ qthr = q + QM * K + kbase + sc;   // per-thread bases
   const ST* __restrict__ bthr = LIN ? bh + QM * K + kbase + sc : nullptr;
-  double* __restrict__ qothr = (LIN && qout && blockIdx.y == 0) ? qout + Q0 * K + kbase + sc : nullptr;
+  double* __restrict__ qothr = (SG == 0 && LIN && qout && blockIdx.y == 0) ? qout + Q0 * K + kbase + sc : nullptr;
   const ST* __restrict__ pthr = q + QM * K + pbase + sc;
   const ST* __restrict__ bpthr = LIN ? bh + QM * K + pbase + sc : nullptr;
+  // SG == 1: the three descriptors (uniform), this thread's column as a byte offset
+  __amdgpu_buffer_rsrc_t dobs, dq, dbh;
+  if (SG == 1) {
+    auto range = [](int64_t bytes) { return (int)(bytes < 0 ? 0 : bytes < 0x7fffffff ? bytes : 0x7fffffff); };
+    const int ob = range(obs_len * 8), mb = range(((int64_t)nrows - QM) * K * 8);
+    dobs = __builtin_amdgcn_make_buffer_rsrc((void*)obs, 0, ob, 0x00020000);
+    dq = __builtin_amdgcn_make_buffer_rsrc((void*)(q + QM * K), 0, mb, 0x00020000);
+    if (LIN) dbh = __builtin_amdgcn_make_buffer_rsrc((void*)(bh + QM * K), 0, mb, 0x00020000);
+  }
+  const unsigned scb = (unsigned)(kbase + sc) * 8u;
 
   // ---- row bookkeeping, three stages ahead, in phases; threads 0..31
   unsigned ri_bwr = 0, ri_t = 0;
@@ -340,10 +365,17 @@ __global__ __launch_bounds__(256 * NSPLIT) void k_stats_mfma4(
   auto ri_commit = [&](int buf) {
     if (tid < ST_RB) {
       StRow4 ri;
-      ri.ooff = (ri_ok && !ri_m) ? ri_o * D : -1;
-      ri.qoff = ri_ok ? ri_qr * K : -1;
-      ri.poff = ri_pr * K;
       ri.pok = (ri_ok && ri_pok) ? 1 : 0;
+      if (SG == 1) {    // byte offsets into the descriptors; high half of ooff: high word of the ones column's value
+        const bool okx = ri_ok && !ri_m;
+        ri.ooff = (long long)(okx ? ((unsigned long long)0x3ff00000u << 32) | (unsigned)(ri_o * D * 8) : (unsigned long long)ST_NOROW);
+        ri.qoff = ri_ok ? ri_qr * K * 8 : (int)ST_NOROW;
+        ri.poff = ri.pok ? ri_pr * K * 8 : (int)ST_NOROW;
+      } else {
+        ri.ooff = (ri_ok && !ri_m) ? ri_o * D : -1;
+        ri.qoff = ri_ok ? ri_qr * K : -1;
+        ri.poff = ri_pr * K;
+      }
       ri.pad_ = 0;
       ri.sq = 0.0; ri.sp = 0.0;
       if (LIN) {   // invalid rows: scale 0 (their loads come from a clamped, finite row)
@@ -357,10 +389,12 @@ __global__ __launch_bounds__(256 * NSPLIT) void k_stats_mfma4(
 
   // ---- staging: unconditional loads from clamped addresses, selects at commit time
   int xcc[XK], xwi[XK];  // clamped obs column; LDS index (buffer 0) of the column this thread writes
+  unsigned xone[XK];     // SG == 1: xcc = byte offset of the column (ST_NOROW past the data), all ones on the ones column
 #pragma unroll
   for (int k = 0; k < XK; ++k) {
     const int c = sc + TPR * k;
-    xcc[k] = c < D ? c : D - 1;
+    xcc[k] = SG == 1 ? (int)(c < D ? (unsigned)c * 8u : ST_NOROW) : (c < D ? c : D - 1);
+    xone[k] = c == D ? 0xffffffffu : 0u;
     xwi[k] = (c <= D ? c : ZERO) * CC + psr;   // beyond the ones slot: rewrite ZERO with 0.0
   }
   const int qwi = sr * QS + sc;                 // q tile element of this thread (column 0)
@@ -370,8 +404,38 @@ __global__ __launch_bounds__(256 * NSPLIT) void k_stats_mfma4(
   double rq2[LIN ? QK : 1], rp2[LIN ? PK : 1], rsq = 0.0, rsp = 0.0;
   bool okx = false, okq = false, okp = false;
   int qo_row = 0;                            // q offset of the row fetched last (qout)
+  unsigned rone = 0;                         // SG == 1: high word of the row's ones-column value (0: masked / invalid)
   auto fetch = [&](int buf) {
     const StRow4 ri = rinfo[buf * ST_RB + sr];
+    if (SG == 1) {
+      if (LIN) { rsq = ri.sq; rsp = ri.sp; }
+      if (need_x) {
+        rone = (unsigned)((unsigned long long)ri.ooff >> 32);
+        const unsigned xo = (unsigned)ri.ooff;
+#pragma unroll     // (saturating: ST_NOROW + ST_NOROW stays out of range)
+        for (int k = 0; k < XK; ++k)
+          rx[k] = __builtin_bit_cast(double, st_bload(dobs, __builtin_elementwise_add_sat(xo, (unsigned)xcc[k])));
+      }
+      {
+        const unsigned o = (unsigned)ri.qoff + scb;
+#pragma unroll
+        for (int k = 0; k < QK; ++k) rq[k] = __builtin_bit_cast(double, st_bload(dq, o + 8u * TPR * k));
+        if (LIN) {
+#pragma unroll
+          for (int k = 0; k < QK; ++k) rq2[k] = __builtin_bit_cast(double, st_bload(dbh, o + 8u * TPR * k));
+        }
+      }
+      if (need_qp) {
+        const unsigned o = (unsigned)ri.poff + scb;
+#pragma unroll
+        for (int k = 0; k < PK; ++k) rp[k] = __builtin_bit_cast(double, st_bload(dq, o + 8u * TPR * k));
+        if (LIN) {
+#pragma unroll
+          for (int k = 0; k < PK; ++k) rp2[k] = __builtin_bit_cast(double, st_bload(dbh, o + 8u * TPR * k));
+        }
+      }
+      return;
+    }
     okx = ri.ooff >= 0; okq = ri.qoff >= 0; okp = ri.pok != 0;
     if (LIN) { rsq = ri.sq; rsp = ri.sp; }
     if (need_x) {
@@ -401,6 +465,25 @@ __global__ __launch_bounds__(256 * NSPLIT) void k_stats_mfma4(
   };
   auto commit = [&](auto bufc) {
     constexpr int U = decltype(bufc)::value;
+    if (SG == 1) {      // out-of-range loads came back as 0.0: no selects
+      if (need_x) {
+#pragma unroll
+        for (int k = 0; k < XK; ++k) {
+          st_u2 w = __builtin_bit_cast(st_u2, rx[k]);
+          w.y |= rone & xone[k];
+          rb0[xwi[k] + U * ST_CS] = (CT)__builtin_bit_cast(double, w);
+        }
+      }
+#pragma unroll
+      for (int k = 0; k < QK; ++k)
+        qs0[U * ST_RB * QS + qwi + TPR * k] = (CT)(LIN ? (rq[k] * rq2[k]) * rsq : rq[k]);
+      if (need_qp) {
+#pragma unroll
+        for (int k = 0; k < PK; ++k)
+          rb0[pwi + U * ST_CS + TPR * k * CC] = (CT)(LIN ? (rp[k] * rp2[k]) * rsp : rp[k]);
+      }
+      return;
+    }
     if (need_x) {
 #pragma unroll
       for (int k = 0; k < XK; ++k) {

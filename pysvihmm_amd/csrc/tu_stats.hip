@@ -201,7 +201,7 @@ int launch_stats_range(svihmm_ctx* h, int b0, int nb, int Lq, int off, int Lm, u
         dim3 grid((unsigned)nchunk, (mt_limit + 4 * MTs - 1) / (4 * MTs), 1);
 #define ST3F(MTV, NTW, NS, XKV)                                                                   \
   do {                                                                                           \
-    h->last_kernel[KS_STATS] = "k_stats_mfma4<" #MTV ", " #NTW ", " #NS ", " #XKV ", true, false, float, float, 2>"; \
+    h->last_kernel[KS_STATS] = "k_stats_mfma4<" #MTV ", " #NTW ", " #NS ", " #XKV ", true, false, float, float, 2, 0>"; \
     if (ldsf > 64 * 1024)                                                                        \
       hipFuncSetAttribute((const void*)k_stats_mfma4<MTV, NTW, NS, XKV, true, false, float, float>, \
                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsf);                \
@@ -229,24 +229,35 @@ int launch_stats_range(svihmm_ctx* h, int b0, int nb, int Lq, int off, int Lm, u
         const size_t lds3 = ((size_t)(D + 3 + KpW) * (3 * ST_CS + 2) + 3 * (size_t)ST_RB * ST_QS3(KpW, xk3)) * 8 +
                             4 * ST_RB * sizeof(StRow4) + 16;
         const bool tb = NTt == 4 && MTs == 5 && lds3 <= 160 * 1024 && h->variant[SVIHMM_VAR_STATS_LDS3] != SVIHMM_STATS_LDS3_OFF;
+        // ... and, for a whole batch of the scaled sweeps (ah / bh of all n rows, no padded state columns), the staging
+        // loads as buffer loads from three descriptors with 32-bit byte offsets per lane (kernels_stats.h, SG = 1).  An
+        // offset must stay below ST_NOROW = 2^31: the resident observations and a chunk's message extent in bytes
+        // (SVIHMM_STATS_LDS3_FLAT: the flat loads from clamped addresses -- same results bit for bit)
+        const bool sgb = tb && lin && !big && K == Kp && b0 == 0 && nb == h->curB && off == 0 && Lq == Lm &&
+                         h->variant[SVIHMM_VAR_STATS_LDS3] != SVIHMM_STATS_LDS3_FLAT &&
+                         (int64_t)h->T * D * 8 < ((int64_t)1 << 31) &&
+                         ((int64_t)(rpc / Lm + 18) * Lq) * K * 8 < ((int64_t)1 << 31);
         if (tb) {
-#define ST3TL(XKV, LN)                                                                                         \
+#define ST3TG(XKV, LN, SGV, SGN)                                                                               \
   do {                                                                                                         \
-    h->last_kernel[KS_STATS] = "k_stats_mfma4<5, 2, 2, " #XKV ", " #LN ", false, double, double, 3>";          \
-    hipFuncSetAttribute((const void*)k_stats_mfma4<5, 2, 2, XKV, LN, false, double, double, 3>,                \
+    h->last_kernel[KS_STATS] = "k_stats_mfma4<5, 2, 2, " #XKV ", " #LN ", false, double, double, 3" SGN ">";   \
+    hipFuncSetAttribute((const void*)k_stats_mfma4<5, 2, 2, XKV, LN, false, double, double, 3, SGV>,           \
                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3);                                \
-    hipLaunchKernelGGL((k_stats_mfma4<5, 2, 2, XKV, LN, false, double, double, 3>), grid, dim3(512), lds3,     \
+    hipLaunchKernelGGL((k_stats_mfma4<5, 2, 2, XKV, LN, false, double, double, 3, SGV>), grid, dim3(512), lds3, \
                        stream, (const double*)h->obs.p, mk, starts_dev, n, Lm, D, K, Fp, F,                    \
-                       (const int*)h->fab.p, qv, rpc, flags, Lq, off, partv, Kp, mt_limit, bhv, hxv, gxv, zfv, qoutv, smB); \
+                       (const int*)h->fab.p, qv, rpc, flags, Lq, off, partv, Kp, mt_limit, bhv, hxv, gxv, zfv, qoutv, smB, \
+                       (int64_t)h->T * D);                                                                     \
   } while (0)
-#define ST3T(XKV) do { if (lin) ST3TL(XKV, true); else ST3TL(XKV, false); } while (0)
+#define ST3TL(XKV, LN) ST3TG(XKV, LN, 0, ", 0")
+#define ST3T(XKV) do { if (sgb) ST3TG(XKV, true, 1, ", 1"); else if (lin) ST3TL(XKV, true); else ST3TL(XKV, false); } while (0)
           if (xk <= 1) ST3T(1); else if (xk <= 3) ST3T(3); else if (xk <= 5) ST3T(5); else ST3T(9);
 #undef ST3T
 #undef ST3TL
+#undef ST3TG
         } else {
 #define ST3L(MTV, NTW, NS, XKV, LN)                                                               \
   do {                                                                                           \
-    h->last_kernel[KS_STATS] = "k_stats_mfma4<" #MTV ", " #NTW ", " #NS ", " #XKV ", " #LN ", false, double, double, 2>"; \
+    h->last_kernel[KS_STATS] = "k_stats_mfma4<" #MTV ", " #NTW ", " #NS ", " #XKV ", " #LN ", false, double, double, 2, 0>"; \
     if (lds > 64 * 1024)                                                                         \
       hipFuncSetAttribute((const void*)k_stats_mfma4<MTV, NTW, NS, XKV, LN>,                     \
                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                 \

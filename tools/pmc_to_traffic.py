@@ -14,7 +14,7 @@ import sys
 # family -> (kernel-name regex, workgroups) of the fp64 headline step, and of the fp32-mode step
 HEADLINE = {"emission": (r"k_emission_orbit<4, 4(, 2)?>", 7813),
             "forward_backward": (r"k_sweeps_lin<4, true, 0, false(, double)?>", 488),
-            "stats": (r"k_stats_mfma4<5, 2, 2, 3, true, false(, double, double)?(, [23])?>", 256),
+            "stats": (r"k_stats_mfma4<5, 2, 2, 3, true, false(, double, double)?(, [23])?(, [01])?>", 256),
             "finalize": (r"k_finalize", 161)}
 F32 = {"emission": (r"k_emission_bf16x3", 3907),
        "forward_backward": (r"k_sweeps_lin<4, true, 0, false, float>", 488),
