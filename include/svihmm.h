@@ -35,7 +35,8 @@
 extern "C" {
 #endif
 
-/* 3 (addition, nothing else changed meaning): svihmm_set_sequences, svihmm_estep_sequences.
+/* 3 (addition, nothing else changed meaning): svihmm_viterbi_sequences, svihmm_ffbs_sequences.
+ * 3 (addition, nothing else changed meaning): svihmm_set_sequences, svihmm_estep_sequences.
  * 3 (addition, nothing else changed meaning): svihmm_grow_windows.
  * 3 (addition, nothing else changed meaning): svihmm_ffbs_windows.
  * 3 (addition, nothing else changed meaning): svihmm_viterbi.
@@ -304,13 +305,72 @@ int svihmm_suffstats(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t Lm
  *   Intermediates afterwards: var_x of all T rows is readable as one [1, T, K] batch
  *   (svihmm_read_intermediate / _read_rows, what = 3) and svihmm_state_argmax decodes all T rows; what = 0, 1, 2
  *   fail with "... svihmm_estep_sequences keeps var_x only".
+ * Decoding all declared sequences in one call: svihmm_viterbi_sequences / svihmm_ffbs_sequences below.
  * Not covered: hmmsgd_metaobs.VBHMM on a list (its batch factors, quirk Q3, have no agreed multi-sequence
- *   form; the boundary check above lets a caller sample windows safely), decoding all sequences in one
- *   svihmm_viterbi / svihmm_ffbs_windows call (decode them one by one as windows {seq_off[s]}, B = 1,
- *   Lm = len_s), the fp32 mode, host lliks, K > 256. */
+ *   form; the boundary check above lets a caller sample windows safely), the fp32 mode, host lliks in
+ *   svihmm_estep_sequences, K > 256. */
 int svihmm_set_sequences(svihmm_ctx* h, const int64_t* seq_off, int32_t N);
 int svihmm_estep_sequences(svihmm_ctx* h, uint32_t flags, double* out_packed, double* out_seq_lb,
                            double* out_q0);
+
+/* svihmm_viterbi_sequences: the MAP state path of EVERY declared sequence (svihmm_set_sequences) in one call, under
+ *   the globals currently set and the current emission family.
+ *   out_z: host int32[T], row r holds the state of resident row r (the sequences laid end to end, as declared);
+ *   out_score: host double[N].  Either pointer may be NULL, not both.
+ *   Contract: for sequence s the result is what svihmm_viterbi(h, {seq_off[s]}, 1, len_s, flags, ..) defines -- the
+ *   recursion and the operation order fixed there (one add per (i, j), a strict `>` scan over ascending i, one add of
+ *   ll), delta started from mod_init at the sequence's first row.  Given the lliks the call itself evaluated, z and
+ *   score are bit-identical to that recursion in NumPy on each sequence's rows, and a sequence's path and score are
+ *   the same bits whatever else is declared and in whatever order (given the same ll rows).
+ *   Lliks: ONE emission pass over all T rows (NIW, diagonal, Categorical; SVIHMM_MASK_AS_NAN as elsewhere).
+ *   SVIHMM_USE_HOST_LLIKS is accepted when the batch uploaded by svihmm_set_lliks has shape [1][T][K]: its rows are
+ *   the concatenated rows.  Always fp64; K <= 256 (one-byte back-pointers).
+ *   Routing: a sequence whose back-pointers fit the 64 KiB LDS budget (len <= 1008 at K <= 64, 240 above; every
+ *   sequence when out_z is NULL) is decoded inside ONE forward launch, longest first, its LDS sized by the longest
+ *   of them; all longer sequences share ONE more forward launch that writes psi to HBM, and are
+ *   backtracked together by composing per-chunk state maps as svihmm_viterbi does.  No atomics, no reductions
+ *   across sequences.
+ *   Fails with a message before any device work (the handle stays usable): NULL handle; both outputs NULL; no
+ *   declaration; no globals; no observations or no emission family (unless host lliks); a K mismatch between globals
+ *   and emission family; K > 256; host lliks of a shape other than [1][T][K]; T > 2^31 - 1; (number of row
+ *   chunks of the long sequences) x (64 or 256) >= 2^31.
+ *   Intermediates afterwards: the lliks of all T rows are readable as one [1, T, K] batch (svihmm_read_intermediate /
+ *   _read_rows, what = 0); what = 1, 2, 3 fail with a message that names this call.  The packed statistics held in
+ *   HBM and what svihmm_get_precision reports are untouched.
+ *
+ * svihmm_ffbs_sequences: S forward-filter backward-sample paths of EVERY declared sequence from ONE forward filter.
+ *   out_z: host int32[S][T] (draw-major, resident rows inside a draw); out_lalpha: host double[T][K] or NULL.
+ *   Forward filter: runs once; for sequence s it is the filter of svihmm_ffbs_windows on the window {seq_off[s]},
+ *   Lm = len_s: log domain, started from mod_init.  Routing mirrors svihmm_estep_sequences: sequences below 2048
+ *   rows -- and every sequence when an ltran entry lies below SVIHMM_LTRAN_LINEAR_MIN, or with host lliks -- in ONE
+ *   launch of the ragged log-domain forward sweep; longer ones one after the other through the whole-chain blocked
+ *   scan with the log-domain repair of svihmm_ffbs.  NIW, diagonal and Categorical families, SVIHMM_MASK_AS_NAN;
+ *   SVIHMM_USE_HOST_LLIKS with an uploaded batch of shape [1][T][K].  Always fp64; K <= 256.
+ *   Draws: for every draw s < S and sequence q with last row e
+ *       z[s][e] ~ softmax_k( lalpha[e][k] ),    z[s][r] ~ softmax_k( lalpha[r][k] + logA[k][ z[s][r+1] ] )
+ *   Draw rule (part of the contract): lp_k the sum above, m = max_k lp_k, p_k = exp(lp_k - m), c_k the running sum
+ *   of p in ascending state order, tot = c_{K-1}; the draw is the smallest k with u * tot <= c_k, K - 1 if there is
+ *   none.  Where u * tot lies within rounding of some c_k either neighbouring state may be returned (the caveat
+ *   of svihmm_ffbs).  A (sequence, draw) pair gives the same path whatever S, N, the other sequences and their
+ *   order are.
+ *   Uniform source: the uniform of (draw s, resident row r) is entry g = s*T + r.  `uniforms` non-NULL is host
+ *   double[S][T].  uniforms == NULL: u is generated on the device, nothing is uploaded: Philox4x32-10 with key
+ *   `seed`, counter row g, stream 0, the first two words through the 53-bit mapping svihmm_generate uses for its
+ *   transition uniform.
+ *   logA: host double[K][K], used as logA[k][z_next] like svihmm_ffbs (need not be the filter's ltran).  -inf entries
+ *   mean probability zero; +inf, NaN or a column without a finite entry fail.
+ *   Sequences below 2048 rows are sampled in one launch, one lane per (sequence, draw) pair, pairs ordered longest
+ *   sequence first; longer ones compose per-chunk state maps once per (sequence, draw) as svihmm_ffbs does.  No device
+ *   buffer scales with S*T*K: lalpha is held once, only z and the caller's uniforms scale with S*T.
+ *   Fails with a message before any device work (the handle stays usable): NULL handle; NULL logA or out_z; S < 1;
+ *   S*N >= 2^31; a bad logA; and the cases of svihmm_viterbi_sequences (no declaration, no globals, no observations
+ *   or emission family unless host lliks, K mismatch, K > 256, host lliks of another shape, T > 2^31 - 1).
+ *   Intermediates afterwards: the lliks of all T rows are readable (what = 0); lalpha is handed out through
+ *   out_lalpha only: what = 1, 2, 3 fail with a message that names this call.  The packed statistics held in HBM
+ *   and what svihmm_get_precision reports are untouched. */
+int svihmm_viterbi_sequences(svihmm_ctx* h, uint32_t flags, int32_t* out_z, double* out_score);
+int svihmm_ffbs_sequences(svihmm_ctx* h, uint32_t flags, const double* logA, int32_t S, const double* uniforms,
+                          uint64_t seed, int32_t* out_z, double* out_lalpha);
 
 /* ---- the SVI loop with the variational state resident in HBM ----------------------------------
  * hmmsgd_metaobs.VBHMM.infer (:347-445) iterates  { stationary init :413-418, psi-expectations

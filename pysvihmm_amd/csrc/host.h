@@ -157,6 +157,12 @@ struct svihmm_ctx {
   Buf seq_off_d, seq_q, seq_work, seq_ord, seq_out;
   bool seq_internal = false;       // svihmm_estep_sequences is evaluating row ranges of its own (no boundary check)
   bool seq_result = false;         // the intermediates held are svihmm_estep_sequences': var_x of all T rows only
+  // svihmm_viterbi_sequences / svihmm_ffbs_sequences: the launch tables (sequence orders, pad_off, chunk table) on the
+  // device and their host image (alive until the call's final synchronisation); dec_result: the intermediates held are
+  // such a call's -- the lliks of all T rows only (1: _viterbi_sequences, 2: _ffbs_sequences; prepare_ll drops it)
+  Buf dec_tab;
+  std::vector<char> dec_host;
+  int dec_result = 0;
   Buf vit;                         // svihmm_viterbi: score | z | final argmax | psi | path | chunk maps (launch_viterbi);
                                    // svihmm_ffbs_windows: logA | z | the caller's uniforms (launch_ffbs_windows);
                                    // svihmm_grow_windows: results / the rule's state (launch_grow_*)
@@ -396,6 +402,10 @@ int launch_fb_sequences(svihmm_ctx* h, int nseq, const int32_t* order, const int
                         int64_t span, int maxlen, const double* ll, double* q, double* seq_lb);
 int launch_seq_finish(svihmm_ctx* h, int N, const int64_t* seq_off, bool wrap, const double* q, const double* seq_lb,
                       double* q0);
+int64_t viterbi_sequences_chunks(const svihmm_ctx* h);
+int launch_viterbi_sequences(svihmm_ctx* h, const double* ll, bool want_z, int32_t** dz_out, double** dscore_out);
+int launch_ffbs_sequences(svihmm_ctx* h, uint32_t flags, const double* logA, int S, const double* uniforms, uint64_t seed,
+                          bool want_lalpha, int32_t** dz_out, const double** dla_out);
 int launch_niw_vlb(svihmm_ctx* h, int K, int D, const double* dmu, const double* dsg, const double* dka,
                    const double* dnu, double* th2, int* dstat, double* ld, const double* p0, double* dout);
 }

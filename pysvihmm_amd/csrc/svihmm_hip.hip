@@ -84,7 +84,7 @@ int svihmm_destroy(svihmm_ctx* h) {
                  &h->shift_d, &h->uwb, &h->uwd, &h->AexpF, &h->AexpTF, &h->svi_sync, &h->pipe_cnt,
                  &h->pipe_tabs[0].buf, &h->pipe_tabs[1].buf, &h->pipe_tabs[2].buf, &h->pipe_tabs[3].buf,
                  &h->pipe_tabs[4].buf, &h->pipe_tabs[5].buf, &h->pipe_tabs[6].buf, &h->pipe_tabs[7].buf,
-                 &h->seq_off_d, &h->seq_q, &h->seq_work, &h->seq_ord, &h->seq_out};
+                 &h->seq_off_d, &h->seq_q, &h->seq_work, &h->seq_ord, &h->seq_out, &h->dec_tab};
   for (Buf* b : bufs) release(*b);
   if (h->vlb_host) { hipHostFree(h->vlb_host); h->vlb_host = nullptr; }
   if (h->svi_elbo) { hipHostFree(h->svi_elbo); h->svi_elbo = nullptr; }
@@ -958,6 +958,7 @@ int prepare_ll(svihmm_ctx* h, const int64_t* starts, int B, int Lm, uint32_t fla
   h->eh_float = false;
   h->step_major = false;
   h->seq_result = false;
+  h->dec_result = 0;
   if (host_ll) {
     if (!h->have_host_ll || h->hostB != B || h->hostLm != Lm)
       return fail("SVIHMM_USE_HOST_LLIKS: no uploaded lliks of shape [B,Lm,K]");
@@ -1003,6 +1004,11 @@ static int intermediate_ptr(svihmm_ctx* h, int what, int64_t row0, int64_t nrows
   if (h->seq_result && what != 3)
     return fail("lliks / lalpha / lbeta are not available: svihmm_estep_sequences keeps var_x only (what = 3); "
                 "svihmm_forward_backward on a sequence's window returns its messages");
+  if (h->dec_result && what != 0)
+    return fail(std::string("lalpha / lbeta / var_x are not available: ") +
+                (h->dec_result == 1 ? "svihmm_viterbi_sequences" : "svihmm_ffbs_sequences") +
+                " keeps the lliks of all T rows only (what = 0)" +
+                (h->dec_result == 2 ? "; lalpha is handed out through out_lalpha" : ""));
   if (!h->lin_mode || what == 3 || (what == 0 && h->eh_in_llE)) {
     if (what == 3) CK(ensure_q(h, h->lastB, Lm, h->stream));
     if (what == 2 && !h->have_lb) {
@@ -1142,7 +1148,7 @@ static int estep_pipelined(svihmm_ctx* h, const int64_t* starts, int B, int Lm, 
   CK(ensure_stats(h, plan[0].nchunk + plan[1].nchunk));
   h->have_host_ll = false;
   h->lin_mode = true; h->lin_stale = false; h->last_host_ll = false; h->eh_in_llE = false; h->last_flags = flags;
-  h->cur_f32 = false; h->step_major = false; h->seq_result = false;
+  h->cur_f32 = false; h->step_major = false; h->seq_result = false; h->dec_result = 0;
   h->q_valid = false; h->curB = B;
   h->m_nb = 0; h->have_lb = true;
   hipStream_t A = h->stream, Bs = h->stream2;
@@ -2454,6 +2460,96 @@ int svihmm_ffbs_windows(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t
   if (rc) return rc;
   CK(d2h(h, out_z, dz, (size_t)S * B * Lm * sizeof(int32_t)));
   if (out_lalpha) CK(d2h(h, out_lalpha, dla, (size_t)B * Lm * K * sizeof(double)));
+  HIPCK(hipStreamSynchronize(h->stream));
+  CK(check_emission_status(h));
+  return 0;
+}
+
+
+// ---- decoding all declared sequences in one call (kernels_decode_sequences.h) --------------------
+// Everything that can be wrong with the call is found here, before any device work.  Both calls evaluate the lliks
+// of all T rows in one emission pass (prepare_ll over the window [0, T) with the boundary check lifted, as
+// estep_sequences_core lifts it for its row ranges); host lliks must be the [1][T][K] batch of the concatenated rows.
+static int check_decode_sequences(const svihmm_ctx* h, const char* fn, uint32_t flags) {
+  const auto bad = [fn](const std::string& what) { return fail(std::string(fn) + ": " + what); };
+  if (h->seq_off.empty()) return bad("no sequences declared: call svihmm_set_sequences first");
+  if (!h->have_globals) return bad("no globals: call svihmm_set_globals first");
+  if (flags & SVIHMM_USE_HOST_LLIKS) {
+    if (!h->have_host_ll || h->hostB != 1 || h->hostLm != h->T)
+      return bad("SVIHMM_USE_HOST_LLIKS without uploaded lliks of shape [1, T, K] (svihmm_set_lliks)");
+  } else {
+    CK(check_window_model(h, fn));
+  }
+  if (h->K > 256) return bad("K = " + std::to_string(h->K) + " > 256 not supported");
+  if (h->T > 2147483647LL) return bad("T = " + std::to_string(h->T) + " rows are too many (T <= 2^31 - 1)");
+  return 0;
+}
+
+int svihmm_viterbi_sequences(svihmm_ctx* h, uint32_t flags, int32_t* out_z, double* out_score) {
+  const char* fn = "svihmm_viterbi_sequences";
+  if (!h) return fail("svihmm_viterbi_sequences: NULL handle");
+  if (!out_z && !out_score) return fail("svihmm_viterbi_sequences: neither out_z nor out_score given");
+  CK(check_decode_sequences(h, fn, flags));
+  if (out_z && viterbi_sequences_chunks(h) * (h->K <= 64 ? 64 : 256) >= ((int64_t)1 << 31))
+    return fail("svihmm_viterbi_sequences: too many row chunks for the map composition");
+  CK(set_device(h));
+  CK(wait_side_streams(h));
+  const int N = (int)h->seq_off.size() - 1;
+  const int64_t T = h->T, st0 = 0;
+  // (not an E-step batch: what svihmm_get_precision reports about the last one stays)
+  const int report = h->f32_report_hold >= 0 ? h->f32_report_hold : (h->cur_f32 || h->eh_float) ? 1 : 0;
+  h->seq_internal = true;
+  int rc = prepare_ll(h, &st0, 1, (int)T, flags & (SVIHMM_MASK_AS_NAN | SVIHMM_USE_HOST_LLIKS), false);
+  h->seq_internal = false;
+  h->f32_report_hold = report;
+  if (rc) return rc;
+  h->lastB = 1; h->lastLm = (int)T;
+  h->dec_result = 1;
+  int32_t* dz = nullptr;
+  double* dscore = nullptr;
+  CK(launch_viterbi_sequences(h, (const double*)h->ll.p, out_z != nullptr, &dz, &dscore));
+  if (out_z) CK(d2h(h, out_z, dz, (size_t)T * sizeof(int32_t)));
+  if (out_score) CK(d2h(h, out_score, dscore, (size_t)N * sizeof(double)));
+  HIPCK(hipStreamSynchronize(h->stream));
+  CK(check_emission_status(h));
+  return 0;
+}
+
+int svihmm_ffbs_sequences(svihmm_ctx* h, uint32_t flags, const double* logA, int32_t S, const double* uniforms,
+                          uint64_t seed, int32_t* out_z, double* out_lalpha) {
+  const char* fn = "svihmm_ffbs_sequences";
+  if (!h) return fail("svihmm_ffbs_sequences: NULL handle");
+  if (!logA || !out_z) return fail("svihmm_ffbs_sequences: logA and out_z must be given");
+  if (S < 1) return fail("svihmm_ffbs_sequences: S must be positive");
+  CK(check_decode_sequences(h, fn, flags));
+  const int K = h->K, N = (int)h->seq_off.size() - 1;
+  if ((int64_t)S * N >= ((int64_t)1 << 31)) return fail("svihmm_ffbs_sequences: S * N too large");
+  // logA[k][z_next]: -inf is probability zero; every column needs one finite entry to draw from
+  for (int j = 0; j < K; ++j) {
+    bool any = false;
+    for (int k = 0; k < K; ++k) {
+      const double v = logA[(size_t)k * K + j];
+      if (v != v || v == INFINITY)
+        return fail("svihmm_ffbs_sequences: logA[" + std::to_string(k) + "][" + std::to_string(j) + "] is NaN or +inf");
+      any = any || v > -INFINITY;
+    }
+    if (!any) return fail("svihmm_ffbs_sequences: column " + std::to_string(j) + " of logA has no finite entry");
+  }
+  CK(set_device(h));
+  CK(wait_side_streams(h));
+  const int64_t T = h->T;
+  int32_t* dz = nullptr;
+  const double* dla = nullptr;
+  const int report = h->f32_report_hold >= 0 ? h->f32_report_hold : (h->cur_f32 || h->eh_float) ? 1 : 0;
+  h->seq_internal = true;
+  const int rc = launch_ffbs_sequences(h, flags & (SVIHMM_MASK_AS_NAN | SVIHMM_USE_HOST_LLIKS), logA, S, uniforms, seed,
+                                       out_lalpha != nullptr, &dz, &dla);
+  h->seq_internal = false;
+  h->f32_report_hold = report;
+  if (rc) return rc;
+  h->dec_result = 2;
+  CK(d2h(h, out_z, dz, (size_t)S * T * sizeof(int32_t)));
+  if (out_lalpha) CK(d2h(h, out_lalpha, dla, (size_t)T * K * sizeof(double)));
   HIPCK(hipStreamSynchronize(h->stream));
   CK(check_emission_status(h));
   return 0;

@@ -1,5 +1,6 @@
 // tu_recursion.hip -- forward / backward recursions, blocked scan, FFBS: kernels and launchers
 // One of the translation units of libsvihmm_hip.so (see host.h).
+#include <algorithm>
 #include "host.h"
 #include "device_helpers.h"
 #include "kernels_recursion.h"
@@ -7,6 +8,7 @@
 #include "kernels_ffbs_windows.h"
 #include "kernels_grow.h"
 #include "kernels_sequences.h"
+#include "kernels_decode_sequences.h"
 
 extern "C" {
 
@@ -1126,6 +1128,276 @@ int launch_seq_finish(svihmm_ctx* h, int N, const int64_t* seq_off, bool wrap, c
                      wrap ? 1 : 0, (double*)h->packed.p, q0);
   hipLaunchKernelGGL(k_sum_lb, dim3(1), dim3(256), 0, h->stream, seq_lb, N,
                      (double*)h->packed.p + (packed_len(h) - 1));
+  HIPCK(hipGetLastError());
+  return 0;
+}
+
+// ---- decoding all declared sequences in one call (kernels_decode_sequences.h) -------------------
+// svihmm_viterbi_sequences.  Sequences whose psi fits the LDS budget (len <= vit_lds_rows(KS); all of them when no
+// path is wanted) are decoded inside the forward launch; all longer ones go in ONE forward launch that writes psi
+// to a common run of padded chunks, backtracked by k_vitseq_paths / k_ffbs_compose / k_vitseq_gather.
+// A launch's dynamic LDS is one number: the short sequences go in ONE launch sized by the longest of them.  Cutting
+// them (longest first) into up to three launches by LDS request -- 64 / 40 / 20 KiB, i.e. 2 / 4 / 8 workgroups per CU --
+// measured slower ("Decoding several sequences": the launches run one after the other and each
+// ends in its own tail); SVIHMM_DECODE_LDS_BINS=1 (measurement only) selects that form.
+// h->vit: score [N] | z int32 [T] | final argmax [long] | psi | path | chunk maps.
+// h->dec_tab: pad_off int64 [long] | order (short) | order (long) | chunk table.
+static const int VITSEQ_BINS[3] = {65536, 40960, 20480};
+int64_t viterbi_sequences_chunks(const svihmm_ctx* h) {
+  const int Ls = vit_lds_rows(h->K <= 64 ? 64 : 256);
+  int64_t C = 0;
+  for (size_t s = 0; s + 1 < h->seq_off.size(); ++s) {
+    const int64_t len = h->seq_off[s + 1] - h->seq_off[s];
+    if (len > Ls) C += (len + Ls - 1) / Ls;
+  }
+  return C;
+}
+int launch_viterbi_sequences(svihmm_ctx* h, const double* ll, bool want_z, int32_t** dz_out, double** dscore_out) {
+  const int K = h->K, N = (int)h->seq_off.size() - 1;
+  const int64_t T = h->T;
+  const std::vector<int64_t>& so = h->seq_off;
+  const int KS = K <= 64 ? 64 : 256, Ls = vit_lds_rows(KS);
+  std::vector<int32_t> shorts, longs;
+  for (int s = 0; s < N; ++s) ((!want_z || so[s + 1] - so[s] <= Ls) ? shorts : longs).push_back(s);
+  const auto longer = [&so](int32_t a, int32_t b) { return so[a + 1] - so[a] > so[b + 1] - so[b]; };
+  std::stable_sort(shorts.begin(), shorts.end(), longer);     // longest first (ties in ascending s)
+  std::stable_sort(longs.begin(), longs.end(), longer);
+  const size_t ns = shorts.size(), nl = longs.size();
+  std::vector<int64_t> pad(nl);
+  std::vector<int32_t> ctab;
+  int64_t P = 0;
+  for (size_t u = 0; u < nl; ++u) {
+    const int Cw = (int)((so[longs[u] + 1] - so[longs[u]] + Ls - 1) / Ls);
+    pad[u] = P;
+    for (int cw = 0; cw < Cw; ++cw) { ctab.push_back((int32_t)u); ctab.push_back(cw); }
+    P += (int64_t)Cw * Ls;
+  }
+  const int64_t C = (int64_t)ctab.size() / 2;
+  const size_t t_os = nl * sizeof(int64_t), t_ol = t_os + ns * sizeof(int32_t), t_ct = t_ol + nl * sizeof(int32_t);
+  const size_t t_end = t_ct + ctab.size() * sizeof(int32_t);
+  h->dec_host.resize(t_end);
+  if (nl) {
+    std::memcpy(h->dec_host.data(), pad.data(), nl * sizeof(int64_t));
+    std::memcpy(h->dec_host.data() + t_ol, longs.data(), nl * sizeof(int32_t));
+    std::memcpy(h->dec_host.data() + t_ct, ctab.data(), ctab.size() * sizeof(int32_t));
+  }
+  if (ns) std::memcpy(h->dec_host.data() + t_os, shorts.data(), ns * sizeof(int32_t));
+  CK(ensure(h->dec_tab, t_end + 256));
+  HIPCK(hipMemcpyAsync(h->dec_tab.p, h->dec_host.data(), t_end, hipMemcpyHostToDevice, h->stream));
+  const char* tb = (const char*)h->dec_tab.p;
+  const int64_t* dpad = (const int64_t*)tb;
+  const int32_t* dos = (const int32_t*)(tb + t_os);
+  const int32_t* dol = (const int32_t*)(tb + t_ol);
+  const int32_t* dct = (const int32_t*)(tb + t_ct);
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t o_z = up((size_t)N * sizeof(double)), o_zlast = o_z + up((size_t)T * sizeof(int32_t));
+  const size_t o_psi = o_zlast + up(nl * sizeof(int32_t));
+  const size_t nps = up((size_t)P * KS);
+  const size_t o_path = o_psi + nps, o_mA = o_path + nps;
+  const size_t nmap = up((size_t)C * KS);
+  const size_t o_mB = o_mA + nmap, o_entry = o_mB + nmap;
+  CK(ensure(h->vit, o_entry + up((size_t)C) + 256));
+  char* base = (char*)h->vit.p;
+  double* dscore = (double*)base;
+  int32_t* dz = (int32_t*)(base + o_z);
+  int32_t* zlast = (int32_t*)(base + o_zlast);
+  unsigned char* psi = (unsigned char*)(base + o_psi);
+  unsigned char* path = (unsigned char*)(base + o_path);
+  unsigned char* mA = (unsigned char*)(base + o_mA);
+  unsigned char* mB = (unsigned char*)(base + o_mB);
+  unsigned char* entry = (unsigned char*)(base + o_entry);
+  *dz_out = want_z ? dz : nullptr;
+  *dscore_out = dscore;
+  const double* lt = (const double*)h->ltran.p;
+  const double* mi = (const double*)h->mod_init.p;
+  const int64_t* sod = (const int64_t*)h->seq_off_d.p;
+  int32_t* zw = want_z ? dz : (int32_t*)nullptr;
+  ProfScope ps(h, KS_MISC);
+  static const bool binned = [] { const char* e = std::getenv("SVIHMM_DECODE_LDS_BINS"); return e && std::atoi(e) != 0; }();
+  // the short sequences: ranges [a, b) of the order array that share an LDS bin
+  for (size_t a = 0; a < ns;) {
+    size_t b = ns;
+    const int64_t la = so[shorts[a] + 1] - so[shorts[a]];
+    const size_t lds = (size_t)2 * KS * 8 + (want_z ? (size_t)la * KS : 0);
+    if (want_z && binned) {
+      int bin = 0;
+      while (bin + 1 < 3 && lds <= (size_t)VITSEQ_BINS[bin + 1]) ++bin;
+      if (bin + 1 < 3) {     // the range ends where the next smaller bin begins
+        const size_t rows_next = ((size_t)VITSEQ_BINS[bin + 1] - (size_t)2 * KS * 8) / KS;
+        for (b = a; b < ns && (size_t)(so[shorts[b] + 1] - so[shorts[b]]) > rows_next; ++b) {}
+      }
+    }
+    const unsigned n = (unsigned)(b - a);
+#define VSW(KM)                                                                                                    \
+  hipLaunchKernelGGL((k_vitseq_wave<KM, true>), dim3(n), dim3(64), lds, h->stream, ll, lt, mi, sod, dos + a,       \
+                     (const int64_t*)nullptr, K, (unsigned char*)nullptr, zw, (int32_t*)nullptr, dscore)
+    if (K <= 16) VSW(16); else if (K <= 32) VSW(32); else if (K <= 64) VSW(64);
+    else
+      hipLaunchKernelGGL(k_vitseq_wide<true>, dim3(n), dim3(256), lds, h->stream, ll, lt, mi, sod, dos + a,
+                         (const int64_t*)nullptr, K, (unsigned char*)nullptr, zw, (int32_t*)nullptr, dscore);
+#undef VSW
+    a = b;
+  }
+  HIPCK(hipGetLastError());
+  if (nl) {
+    const size_t lds = (size_t)2 * KS * 8;
+#define VSW(KM)                                                                                                    \
+  hipLaunchKernelGGL((k_vitseq_wave<KM, false>), dim3((unsigned)nl), dim3(64), lds, h->stream, ll, lt, mi, sod,    \
+                     dol, dpad, K, psi, (int32_t*)nullptr, zlast, dscore)
+    if (K <= 16) VSW(16); else if (K <= 32) VSW(32); else if (K <= 64) VSW(64);
+    else
+      hipLaunchKernelGGL(k_vitseq_wide<false>, dim3((unsigned)nl), dim3(256), lds, h->stream, ll, lt, mi, sod, dol,
+                         dpad, K, psi, (int32_t*)nullptr, zlast, dscore);
+#undef VSW
+    hipLaunchKernelGGL(k_vitseq_paths, dim3((unsigned)C), dim3(KS), (size_t)Ls * KS, h->stream,
+                       (const unsigned char*)psi, (const int32_t*)zlast, sod, dol, dpad, dct, Ls, KS, K, path);
+    hipLaunchKernelGGL(k_ffbs_compose, dim3(1), dim3(1024), 0, h->stream, (const unsigned char*)path, P, KS, Ls,
+                       (int)C, mA, mB, entry);
+    hipLaunchKernelGGL(k_vitseq_gather, dim3((unsigned)C), dim3(256), 0, h->stream, (const unsigned char*)path,
+                       (const unsigned char*)entry, sod, dol, dpad, dct, Ls, KS, dz);
+    HIPCK(hipGetLastError());
+  }
+  return 0;
+}
+
+// svihmm_ffbs_sequences: ONE forward filter over all sequences into lalpha [T][K] (h->seq_work), then S backward
+// draws of every sequence.  Filter routing as estep_sequences_core: whole-chain sequences (use_chain) one after the
+// other through ffbs_filter's chain route, copied to their rows; all others -- every sequence under sparse globals or
+// host lliks -- in one launch of the ragged sweeps' forward direction (grid (n, 1): the kernels take the direction
+// from blockIdx.y).  The emission pass over all T rows comes last, so the lliks of all rows stay readable.
+// Draws: sequences below FFW_SWITCH rows in one launch, a lane per (sequence, draw) pair; longer ones through the
+// blocked composition once per (sequence, draw), as launch_ffbs_windows does.
+// h->vit: logA | z int32 [S][T] | the caller's uniforms [S][T]; h->dec_tab: order (filter) | order (sampler).
+int launch_ffbs_sequences(svihmm_ctx* h, uint32_t flags, const double* logA, int S, const double* uniforms, uint64_t seed,
+                          bool want_lalpha, int32_t** dz_out, const double** dla_out) {
+  const int K = h->K, N = (int)h->seq_off.size() - 1;
+  const int64_t T = h->T;
+  const std::vector<int64_t>& so = h->seq_off;
+  const bool host_ll = flags & SVIHMM_USE_HOST_LLIKS;
+  CK(wait_globals(h));
+  std::vector<int32_t> ragged, chains, lanes, blocked;
+  for (int s = 0; s < N; ++s) {
+    const int len = (int)(so[s + 1] - so[s]);
+    (!host_ll && use_chain(h, 1, len) ? chains : ragged).push_back(s);
+    (len < FFW_SWITCH ? lanes : blocked).push_back(s);
+  }
+  const auto longer = [&so](int32_t a, int32_t b) { return so[a + 1] - so[a] > so[b + 1] - so[b]; };
+  std::stable_sort(ragged.begin(), ragged.end(), longer);
+  std::stable_sort(lanes.begin(), lanes.end(), longer);
+  CK(ensure(h->seq_work, (size_t)T * K * sizeof(double)));
+  double* la_all = (double*)h->seq_work.p;
+  for (int32_t s : chains) {
+    const int len = (int)(so[s + 1] - so[s]);
+    const double* la = nullptr;
+    CK(ffbs_filter(h, &so[s], 1, len, flags, want_lalpha, &la));
+    HIPCK(hipMemcpyAsync(la_all + (size_t)so[s] * K, la, (size_t)len * K * sizeof(double), hipMemcpyDeviceToDevice,
+                         h->stream));
+  }
+  const int64_t st0 = 0;
+  CK(prepare_ll(h, &st0, 1, (int)T, flags, false, false));
+  h->have_lb = false;
+  h->lastB = 1; h->lastLm = (int)T;
+  const size_t nr = ragged.size(), nlane = lanes.size();
+  h->dec_host.resize((nr + nlane) * sizeof(int32_t));
+  if (nr) std::memcpy(h->dec_host.data(), ragged.data(), nr * sizeof(int32_t));
+  if (nlane) std::memcpy(h->dec_host.data() + nr * sizeof(int32_t), lanes.data(), nlane * sizeof(int32_t));
+  CK(ensure(h->dec_tab, (nr + nlane) * sizeof(int32_t) + 256));
+  HIPCK(hipMemcpyAsync(h->dec_tab.p, h->dec_host.data(), (nr + nlane) * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  const int32_t* dor = (const int32_t*)h->dec_tab.p;
+  const int32_t* dlanes = dor + nr;
+  const int64_t* sod = (const int64_t*)h->seq_off_d.p;
+  const double* ll = (const double*)h->ll.p;
+  if (nr) {
+    const double* A = (const double*)h->Aexp.p;
+    const double* mi = (const double*)h->mod_init.p;
+    double* nolb = nullptr;
+    dim3 grid((unsigned)nr, 1);
+    ProfScope ps(h, KS_FB);
+    if (h->exact_log) {
+      const int threads = (K + 63) / 64 * 64;
+      const int in_lds = ((size_t)K * (K + 1) + 2 * K) * 8 <= 150 * 1024;
+      const size_t lds = (2 * (size_t)K + (in_lds ? (size_t)K * (K + 1) : 0)) * 8;
+      if (lds > 64 * 1024)
+        hipFuncSetAttribute((const void*)k_seq_exact, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL(k_seq_exact, grid, dim3(threads), lds, h->stream, ll, (int64_t)0, sod, dor,
+                         (const double*)h->ltran.p, mi, K, in_lds, la_all, nolb);
+    } else if (K <= 16)
+      hipLaunchKernelGGL(k_seq_wave<16>, grid, dim3(64), 0, h->stream, ll, (int64_t)0, sod, dor, A, mi, K, la_all, nolb);
+    else if (K <= 32)
+      hipLaunchKernelGGL(k_seq_wave<32>, grid, dim3(64), 0, h->stream, ll, (int64_t)0, sod, dor, A, mi, K, la_all, nolb);
+    else if (K <= 64)
+      hipLaunchKernelGGL(k_seq_wave<64>, grid, dim3(64), 0, h->stream, ll, (int64_t)0, sod, dor, A, mi, K, la_all, nolb);
+    else {
+      const int threads = (K + 63) / 64 * 64;
+      const int in_lds = ((size_t)K * K * 8 + 2 * K * 8 + 128) <= 150 * 1024;
+      const size_t lds = (2 * (size_t)K + 16) * 8 + (in_lds ? (size_t)K * K * 8 : 0);
+      if (lds > 64 * 1024)
+        hipFuncSetAttribute((const void*)k_seq_block, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      hipLaunchKernelGGL(k_seq_block, grid, dim3(threads), lds, h->stream, ll, (int64_t)0, sod, dor, A,
+                         (const double*)h->AexpT.p, mi, K, in_lds, la_all, nolb);
+    }
+    HIPCK(hipGetLastError());
+  }
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t n = (size_t)S * T;
+  const size_t o_z = up((size_t)K * K * sizeof(double)), o_u = o_z + up(n * sizeof(int32_t));
+  CK(ensure(h->vit, o_u + (uniforms ? n * sizeof(double) : 0) + 256));
+  char* base = (char*)h->vit.p;
+  double* dlogA = (double*)base;
+  int32_t* dz = (int32_t*)(base + o_z);
+  double* dun = uniforms ? (double*)(base + o_u) : nullptr;
+  HIPCK(hipMemcpyAsync(dlogA, logA, (size_t)K * K * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (uniforms) HIPCK(hipMemcpyAsync(dun, uniforms, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  *dz_out = dz;
+  *dla_out = la_all;
+  if (nlane) {
+    const unsigned nblk = (unsigned)(((int64_t)nlane * S + 63) / 64);
+    ProfScope ps(h, KS_FFBS);
+    if (K <= 64) {
+      const int KM = K <= 16 ? 16 : K <= 32 ? 32 : 64;
+      const size_t lds = ffs_lds_bytes(K, KM);
+#define FSEQ(KMAX)                                                                                                 \
+  hipLaunchKernelGGL(k_ffbs_seq<KMAX>, dim3(nblk), dim3(64), lds, h->stream, (const double*)la_all,                \
+                     (const double*)dlogA, (const double*)dun, (unsigned long long)seed, sod, dlanes, (int)nlane,  \
+                     S, T, K, dz)
+      if (KM == 16) FSEQ(16); else if (KM == 32) FSEQ(32); else FSEQ(64);
+#undef FSEQ
+    } else {
+      hipLaunchKernelGGL(k_ffbs_seq_wide, dim3(nblk), dim3(64), 0, h->stream, (const double*)la_all,
+                         (const double*)dlogA, (const double*)dun, (unsigned long long)seed, sod, dlanes, (int)nlane,
+                         S, T, K, dz);
+    }
+    HIPCK(hipGetLastError());
+  }
+  if (blocked.empty()) return 0;
+  // long sequences: per-draw scratch in h->scratch = (Philox: uniforms [len]) | z int64 [len] | path, chunk maps
+  int64_t maxlen = 0;
+  size_t extra = 0;
+  for (int32_t s : blocked) {
+    maxlen = std::max(maxlen, so[s + 1] - so[s]);
+    extra = std::max(extra, ffbs_plan(h, so[s + 1] - so[s], K).extra);
+  }
+  const size_t o_zl = uniforms ? 0 : up((size_t)maxlen * sizeof(double));
+  const size_t o_path = o_zl + up((size_t)maxlen * sizeof(int64_t));
+  CK(ensure(h->scratch, o_path + extra));
+  char* sb = (char*)h->scratch.p;
+  int64_t* dzl = (int64_t*)(sb + o_zl);
+  for (int d = 0; d < S; ++d)
+    for (int32_t s : blocked) {
+      const int64_t len = so[s + 1] - so[s];
+      const FfbsPlan pl = ffbs_plan(h, len, K);
+      const unsigned nb256 = (unsigned)((len + 255) / 256);
+      const int64_t g0 = (int64_t)d * T + so[s];
+      const double* du = dun ? dun + g0 : (const double*)sb;
+      if (!dun) {
+        ProfScope ps(h, KS_FFBS);
+        hipLaunchKernelGGL(k_ffw_fill_uniforms, dim3(nb256), dim3(256), 0, h->stream, (unsigned long long)seed, g0,
+                           len, (double*)sb);
+      }
+      CK(ffbs_launch(h, pl, la_all + (size_t)so[s] * K, len, K, dlogA, du, dzl, (unsigned char*)(sb + o_path)));
+      ProfScope ps(h, KS_FFBS);
+      hipLaunchKernelGGL(k_ffw_store_path, dim3(nb256), dim3(256), 0, h->stream, (const int64_t*)dzl, len, dz + g0);
+    }
   HIPCK(hipGetLastError());
   return 0;
 }

@@ -462,6 +462,47 @@ class HipEngine(object):
                                          L.dptr(score)), "svihmm_viterbi")
         return z, score
 
+    def viterbi_sequences(self, flags=0, want_z=True):
+        """MAP state path of every declared sequence (``set_sequences``) in one device call
+        (``svihmm_viterbi_sequences``): ``(z int32[T] or None, score float64[N])``; row ``r`` of ``z`` is the
+        state of resident row ``r``, so sequence ``s`` is ``z[seq_off[s]:seq_off[s + 1]]``.  Each sequence is
+        decoded as ``viterbi([seq_off[s]], len_s, flags)`` decodes it (the chain starts from ``mod_init``),
+        bit for bit given the same lliks.  With ``USE_HOST_LLIKS`` the ``[1, T, K]`` batch uploaded by
+        ``set_lliks`` holds the lliks of the concatenated rows.  Afterwards ``read_rows("lliks", ..)`` covers
+        all T rows."""
+        self._pre_mutate()
+        off = getattr(self, "seq_off", None)
+        n = 0 if off is None else len(off) - 1      # (none declared: the library says so)
+        T = max(int(self.T or 0), 0)
+        z = np.empty(max(T, 1), dtype=np.int32) if want_z else None
+        score = np.empty(max(n, 1))
+        L.check(self._lib.svihmm_viterbi_sequences(self._h, int(flags),
+                                                   None if z is None else z.ctypes.data_as(C.c_void_p),
+                                                   L.dptr(score)), "svihmm_viterbi_sequences")
+        self._rows = T
+        return (None if z is None else z[:T]), score[:n]
+
+    def ffbs_sequences(self, logA, n_draws=1, uniforms=None, seed=0, flags=0, want_lalpha=False):
+        """``n_draws`` FFBS state paths of every declared sequence from ONE forward filter
+        (``svihmm_ffbs_sequences``): ``(z int32[S, T], lalpha float64[T, K] or None)``.  ``uniforms`` [S, T]
+        holds the uniform of (draw, resident row); without them the device draws its own (Philox4x32-10
+        keyed by ``seed``, counter row ``draw * T + row``).  Filter, draw rule and ``logA`` as in
+        ``ffbs_windows``; every sequence starts from ``mod_init`` and is sampled back from its own last row."""
+        self._pre_mutate()
+        S = int(n_draws)
+        T = max(int(self.T or 0), 0)
+        logA = L.as_f64(logA, (self.K, self.K))
+        u = None
+        if uniforms is not None:
+            u = L.as_f64(uniforms, (max(S, 0), T))
+        z = np.empty((max(S, 0), max(T, 1)), dtype=np.int32)
+        la = np.empty((max(T, 1), self.K)) if want_lalpha else None
+        L.check(self._lib.svihmm_ffbs_sequences(self._h, int(flags), L.dptr(logA), S, L.dptr(u),
+                                                int(seed) & 0xFFFFFFFFFFFFFFFF, z.ctypes.data_as(C.c_void_p),
+                                                L.dptr(la)), "svihmm_ffbs_sequences")
+        self._rows = T
+        return z[:, :T], (None if la is None else la[:T])
+
     def grow_windows(self, centers, half0, probe_off=0, increment=1, cutoff=1000, epsilon=1e-5, rule=0,
                      flags=0, method="auto", trace_cap=0):
         """Adaptive window length / buffer growth on the device (``svihmm_grow_windows``; reference

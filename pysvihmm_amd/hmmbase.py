@@ -595,7 +595,13 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         ``full_local_update`` (masked rows contribute ``lliks = 0``); emission plugins without a
         device family are evaluated on the host and uploaded (``set_lliks``).  No attribute of the
         model changes.  ``argmax(var_x, axis=1)`` remains the decode of ``hamming_dist``; for the
-        same metric on the MAP path: ``util.munkres_match(true_sts, z, K)``."""
+        same metric on the MAP path: ``util.munkres_match(true_sts, z, K)``.
+
+        Several sequences (``obs`` was a list) and ``metaobs=None``: every sequence is decoded on its
+        own, from ``mod_init`` at its first row, all in ONE device call (``viterbi_sequences``):
+        ``(list of z_s int32[T_s], score float64[N])``."""
+        if metaobs is None and self._multi():
+            return self._viterbi_sequences()
         loff, uoff = (0, self.T - 1) if metaobs is None else (metaobs.i1, metaobs.i2)
         Lm = uoff - loff + 1
         mod_init = digamma(self.var_init + eps) - digamma(np.sum(self.var_init) + eps)
@@ -606,6 +612,33 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         flags = self._push_emission(windows=[loff], Lm=Lm, nan_mask=True)
         z, score = self.engine.viterbi([loff], Lm, flags=flags)
         return z[0], float(score[0])
+
+    def _split_sequences(self, a):
+        """Views of the last axis of ``a`` (resident rows) per sequence."""
+        so = self.seq_off
+        return [a[..., int(so[s]):int(so[s + 1])] for s in range(len(so) - 1)]
+
+    def _viterbi_sequences(self):
+        mod_init = digamma(self.var_init + eps) - digamma(np.sum(self.var_init) + eps)
+        tran_sum = np.sum(self.var_tran, axis=1)
+        mod_tran = digamma(self.var_tran + eps) - digamma(tran_sum[:, npa] + eps)
+        self._upload_obs()
+        eng = self.engine
+        eng.set_globals(mod_init, mod_tran)
+        # (a plugin without a device family: its lliks of the concatenated rows as one [1, T, K] batch)
+        flags = self._push_emission(windows=[0], Lm=self.T, nan_mask=True)
+        if hasattr(eng, "viterbi_sequences"):
+            z, score = eng.viterbi_sequences(flags=flags)
+            return [np.array(v) for v in self._split_sequences(z)], np.array(score, dtype=np.float64)
+        zs, score = [], np.empty(len(self.seq_off) - 1)
+        for s, (off, end) in enumerate(zip(self.seq_off[:-1], self.seq_off[1:])):
+            off, ln = int(off), int(end - off)
+            if flags & L.USE_HOST_LLIKS:
+                eng.set_lliks(self._host_lliks[:, off:off + ln])
+            z, sc = eng.viterbi([off], ln, flags=flags)
+            zs.append(z[0])
+            score[s] = sc[0]
+        return zs, score
 
     # -- FFBS (reference hmm_fast.pyx:43-124, bound at hmmbase.py:409-411) ---------------
     def ffbs_fast(self, var_init, lalpha_init=None, uniforms=None):
@@ -643,7 +676,14 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         evaluated on the host (``set_lliks``), as in ``viterbi()``.  ``uniforms`` [n_draws, B, Lm]
         replace the device's counter-based generator, whose ``seed`` otherwise comes from
         ``np.random`` (so ``np.random.seed`` makes the draws reproducible).  No attribute of the
-        model changes."""
+        model changes.
+
+        Several sequences (``obs`` was a list) and ``metaobs=None``: ``n_draws`` paths of every
+        sequence, each filtered from ``mod_init`` at its own first row, all from ONE device call
+        (``ffbs_sequences``): a list of ``int32[n_draws, T_s]`` arrays.  ``uniforms`` is then
+        ``[n_draws, T]`` over the concatenated rows."""
+        if metaobs is None and self._multi():
+            return self._ffbs_sequences(n_draws, var_init, uniforms, seed)
         if metaobs is None:
             wins = [(0, self.T - 1)]
         elif isinstance(metaobs, (list, tuple)):
@@ -667,6 +707,33 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         z, _ = self.engine.ffbs_windows(starts, Lm, logA, n_draws=n_draws, uniforms=uniforms,
                                         seed=0 if seed is None else seed, flags=flags)
         return z
+
+    def _ffbs_sequences(self, n_draws, var_init, uniforms, seed):
+        var_init = np.asarray(self.var_init if var_init is None else var_init, dtype=np.float64)
+        mod_init = digamma(var_init + DBL_EPSILON) - digamma(np.sum(var_init) + DBL_EPSILON)
+        logA = np.log(self.var_tran + DBL_EPSILON)
+        if uniforms is None and seed is None:
+            seed = int(np.random.randint(0, 2 ** 31 - 1)) * 2 ** 31 + int(np.random.randint(0, 2 ** 31 - 1))
+        self._upload_obs()
+        eng = self.engine
+        eng.set_globals(mod_init, logA)
+        flags = self._push_emission(windows=[0], Lm=self.T)
+        seed = 0 if seed is None else seed
+        if hasattr(eng, "ffbs_sequences"):
+            z, _ = eng.ffbs_sequences(logA, n_draws=n_draws, uniforms=uniforms, seed=seed, flags=flags)
+            return [np.array(v) for v in self._split_sequences(z)]
+        if uniforms is None:
+            raise RuntimeError("ffbs_windows on several sequences: this engine has no ffbs_sequences; "
+                               "pass uniforms [n_draws, T] to sample sequence by sequence")
+        u = np.asarray(uniforms, dtype=np.float64).reshape(int(n_draws), self.T)
+        out = []
+        for off, end in zip(self.seq_off[:-1], self.seq_off[1:]):
+            off, ln = int(off), int(end - off)
+            if flags & L.USE_HOST_LLIKS:
+                eng.set_lliks(self._host_lliks[:, off:off + ln])
+            z, _ = eng.ffbs_windows([off], ln, logA, n_draws=n_draws, uniforms=u[:, None, off:off + ln], flags=flags)
+            out.append(z[:, 0])
+        return out
 
     # -- metrics (host) ----------------------------------------------------------------
     def hamming_dist(self, full_var_x, true_sts):
