@@ -35,7 +35,8 @@
 extern "C" {
 #endif
 
-/* 3 (addition, nothing else changed meaning): svihmm_viterbi_sequences, svihmm_ffbs_sequences.
+/* 3 (addition, nothing else changed meaning): svihmm_estep_sequence_subset.
+ * 3 (addition, nothing else changed meaning): svihmm_viterbi_sequences, svihmm_ffbs_sequences.
  * 3 (addition, nothing else changed meaning): svihmm_set_sequences, svihmm_estep_sequences.
  * 3 (addition, nothing else changed meaning): svihmm_grow_windows.
  * 3 (addition, nothing else changed meaning): svihmm_ffbs_windows.
@@ -305,6 +306,7 @@ int svihmm_suffstats(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t Lm
  *   Intermediates afterwards: var_x of all T rows is readable as one [1, T, K] batch
  *   (svihmm_read_intermediate / _read_rows, what = 3) and svihmm_state_argmax decodes all T rows; what = 0, 1, 2
  *   fail with "... svihmm_estep_sequences keeps var_x only".
+ * The E-step of a chosen subset of the declared sequences: svihmm_estep_sequence_subset below.
  * Decoding all declared sequences in one call: svihmm_viterbi_sequences / svihmm_ffbs_sequences below.
  * Not covered: hmmsgd_metaobs.VBHMM on a list (its batch factors, quirk Q3, have no agreed multi-sequence
  *   form; the boundary check above lets a caller sample windows safely), the fp32 mode, host lliks in
@@ -312,6 +314,46 @@ int svihmm_suffstats(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t Lm
 int svihmm_set_sequences(svihmm_ctx* h, const int64_t* seq_off, int32_t N);
 int svihmm_estep_sequences(svihmm_ctx* h, uint32_t flags, double* out_packed, double* out_seq_lb,
                            double* out_q0);
+
+/* svihmm_estep_sequence_subset: the E-step of a minibatch of WHOLE sequences -- what svihmm_estep_sequences defines,
+ *   restricted to the M listed ones, under the globals currently set and the current emission family (NIW, diagonal,
+ *   Categorical).  Stochastic variational inference over sequences draws M of the N, scales these statistics by N / M
+ *   and takes a Robbins-Monro step.
+ *   idx[M]: declared sequences, each entry in [0, N), M >= 1, in any order.  Duplicates are allowed and every
+ *   occurrence counts once (sampling with replacement).
+ *   For occurrence m it computes what svihmm_forward_backward(h, {seq_off[idx[m]]}, 1, len, flags, ..) computes.
+ *   packed (the family's current layout): emission statistics over the unmasked rows of all occurrences; A_raw in the
+ *   batch form summed over the occurrences, with SVIHMM_TRANS_WRAP additionally each occurrence's own (last row,
+ *   first row) pair; lb = sum_m local_lb.
+ *   out_seq_lb[M]: local_lb of each occurrence, in the order of idx.
+ *   out_q0[K]: the sum of the occurrences' first posterior rows, added in ascending m.
+ *   Any of the three pointers may be NULL; the packed result stays in HBM for svihmm_read_packed /
+ *   _allreduce_packed / _export_packed.  SVIHMM_MASK_AS_NAN as elsewhere.
+ *   Reproducibility: with idx = 0, 1, .., N - 1 the packed buffer, out_seq_lb, out_q0 and the posterior rows are
+ *   bit-identical to svihmm_estep_sequences on the same handle; the posterior rows and local_lb of a listed sequence
+ *   are the same bits as in the full call, whatever else is listed and wherever it stands in idx; two identical
+ *   calls are bit-identical.
+ *   Cost follows R = sum_m len(idx[m]): the listed rows (and mask bytes) are gathered bit for bit into a compact copy
+ *   that belongs to the handle (one launch, 2 R D 8 bytes moved), and emission, sweeps and statistics run on that
+ *   copy.  No kernel is launched over T rows and no buffer of T K or T D elements is written.  (Once, where a
+ *   Categorical table reads a resident copy that is still centred, the copy is brought back to exact symbol
+ *   indices first, as in front of every lookup launch.)
+ *   Routing as in svihmm_estep_sequences: listed sequences of at least 2048 rows through the whole-chain scan, one
+ *   after the other; all others -- every one when an ltran entry lies below SVIHMM_LTRAN_LINEAR_MIN -- in ONE
+ *   ragged launch, longest first.  Always fp64: the precision mode and what svihmm_get_precision reports are
+ *   unchanged.  K <= 256.
+ *   Afterwards: var_x of the R listed rows is readable as one [1, R, K] batch (what = 3), in the order of idx, and
+ *   svihmm_state_argmax decodes those R rows; what = 0, 1, 2 fail with "... svihmm_estep_sequence_subset keeps var_x
+ *   of the listed rows only".  The resident rows, the mask, T, the handle's centre and the declaration are exactly
+ *   as before -- after a failed call too -- and a following svihmm_estep_sequences returns the bits it returned
+ *   before.
+ *   Fails with a message before any device work (the handle stays usable): NULL handle; no declaration; idx NULL or
+ *   M < 1; an entry outside [0, N) (the message gives its position and value); no globals, no emission family or no
+ *   observations; a K mismatch between globals and emission family; K > 256; SVIHMM_USE_HOST_LLIKS; R beyond the
+ *   statistics GEMM's 32-bit row offsets.
+ *   Towards a running resident SVI loop it behaves as svihmm_suffstats does. */
+int svihmm_estep_sequence_subset(svihmm_ctx* h, const int32_t* idx, int32_t M, uint32_t flags,
+                                 double* out_packed, double* out_seq_lb, double* out_q0);
 
 /* svihmm_viterbi_sequences: the MAP state path of EVERY declared sequence (svihmm_set_sequences) in one call, under
  *   the globals currently set and the current emission family.

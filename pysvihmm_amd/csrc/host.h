@@ -157,6 +157,11 @@ struct svihmm_ctx {
   Buf seq_off_d, seq_q, seq_work, seq_ord, seq_out;
   bool seq_internal = false;       // svihmm_estep_sequences is evaluating row ranges of its own (no boundary check)
   bool seq_result = false;         // the intermediates held are svihmm_estep_sequences': var_x of all T rows only
+  // svihmm_estep_sequence_subset: the listed sequences' rows / mask bytes gathered end to end (sized by the listed
+  // rows R, reused), compact offsets [M + 1] | source offsets [M] on the device.  The call swaps them with obs / mask /
+  // seq_off_d for its duration (SubsetView).  seq_subset: seq_result describes such a call (var_x of its R rows)
+  Buf sub_obs, sub_mask, sub_tab;
+  bool seq_subset = false;
   // svihmm_viterbi_sequences / svihmm_ffbs_sequences: the launch tables (sequence orders, pad_off, chunk table) on the
   // device and their host image (alive until the call's final synchronisation); dec_result: the intermediates held are
   // such a call's -- the lliks of all T rows only (1: _viterbi_sequences, 2: _ffbs_sequences; prepare_ll drops it)
@@ -402,6 +407,7 @@ int launch_fb_sequences(svihmm_ctx* h, int nseq, const int32_t* order, const int
                         int64_t span, int maxlen, const double* ll, double* q, double* seq_lb);
 int launch_seq_finish(svihmm_ctx* h, int N, const int64_t* seq_off, bool wrap, const double* q, const double* seq_lb,
                       double* q0);
+int launch_seq_gather(svihmm_ctx* h, int M, const int64_t* tab, int maxlen, double* obs_out, uint8_t* mask_out);
 int64_t viterbi_sequences_chunks(const svihmm_ctx* h);
 int launch_viterbi_sequences(svihmm_ctx* h, const double* ll, bool want_z, int32_t** dz_out, double** dscore_out);
 int launch_ffbs_sequences(svihmm_ctx* h, uint32_t flags, const double* logA, int S, const double* uniforms, uint64_t seed,

@@ -23,6 +23,9 @@
 //                      (last row of s, first row of s + 1) come out, under SVIHMM_TRANS_WRAP each sequence's own
 //                      (last row, first row) pair goes in; q0 = sum_s q[seq_off[s]].  One thread per entry,
 //                      ascending s: no atomics, one fixed order.
+//   k_seq_gather       svihmm_estep_sequence_subset: the listed sequences' rows (and mask bytes) copied bit for
+//                      bit into a compact copy laid end to end in the order of the list; everything above then
+//                      runs on that copy with the compact offsets, so its cost follows the listed rows.
 #pragma once
 
 #define SEQ_PREFETCH 8
@@ -342,4 +345,43 @@ __global__ __launch_bounds__(256) void k_seq_fix(const double* __restrict__ q, c
     if (wrap) acc += ql * q[(size_t)seq_off[s] * K + j];
   }
   A_raw[e] = acc;
+}
+
+// svihmm_estep_sequence_subset's gather.  grid (M occurrences, segments), block 256: occurrence m is rows
+// [src_off[m], src_off[m] + len) of the resident copy, len = dst_off[m + 1] - dst_off[m], and becomes rows
+// [dst_off[m], dst_off[m + 1]) of the compact one.  A sequence's rows are one contiguous run of len * D doubles on
+// both sides; they travel as 64-bit words (a NaN keeps its payload), two per lane where source and destination
+// share their 16-byte phase, dealt round-robin to the gridDim.y workgroups that serve the occurrence.  64-bit
+// element offsets throughout.  mask / mask_out may be NULL (no mask resident).
+__global__ __launch_bounds__(256) void k_seq_gather(
+    const unsigned long long* __restrict__ obs, const uint8_t* __restrict__ mask,
+    const int64_t* __restrict__ dst_off, const int64_t* __restrict__ src_off, int D,
+    unsigned long long* __restrict__ obs_out, uint8_t* __restrict__ mask_out) {
+  const int m = blockIdx.x;
+  const int64_t d0 = dst_off[m], len = dst_off[m + 1] - d0, s0 = src_off[m];
+  const int64_t n = len * (int64_t)D;
+  const int64_t tid = (int64_t)blockIdx.y * 256 + threadIdx.x, nthr = (int64_t)gridDim.y * 256;
+  const unsigned long long* __restrict__ src = obs + s0 * (int64_t)D;
+  unsigned long long* __restrict__ dst = obs_out + d0 * (int64_t)D;
+  if ((((s0 ^ d0) * (int64_t)D) & 1) == 0) {
+    // the same phase: one leading word where the runs start on an odd element, then pairs, then the odd tail
+    const int64_t lead = (s0 * (int64_t)D) & 1;
+    const int64_t n2 = (n - lead) >> 1;
+    const ulonglong2* __restrict__ s2 = reinterpret_cast<const ulonglong2*>(src + lead);
+    ulonglong2* __restrict__ d2 = reinterpret_cast<ulonglong2*>(dst + lead);
+    int64_t i = tid;
+    for (; i + 3 * nthr < n2; i += 4 * nthr) {
+      const ulonglong2 a = s2[i], b = s2[i + nthr], c = s2[i + 2 * nthr], d = s2[i + 3 * nthr];
+      d2[i] = a; d2[i + nthr] = b; d2[i + 2 * nthr] = c; d2[i + 3 * nthr] = d;
+    }
+    for (; i < n2; i += nthr) d2[i] = s2[i];
+    if (tid == 0) {
+      if (lead) dst[0] = src[0];
+      if ((n - lead) & 1) dst[n - 1] = src[n - 1];
+    }
+  } else {
+    for (int64_t i = tid; i < n; i += nthr) dst[i] = src[i];
+  }
+  if (mask != nullptr)
+    for (int64_t i = tid; i < len; i += nthr) mask_out[d0 + i] = mask[s0 + i];
 }

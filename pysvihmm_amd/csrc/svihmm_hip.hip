@@ -84,7 +84,8 @@ int svihmm_destroy(svihmm_ctx* h) {
                  &h->shift_d, &h->uwb, &h->uwd, &h->AexpF, &h->AexpTF, &h->svi_sync, &h->pipe_cnt,
                  &h->pipe_tabs[0].buf, &h->pipe_tabs[1].buf, &h->pipe_tabs[2].buf, &h->pipe_tabs[3].buf,
                  &h->pipe_tabs[4].buf, &h->pipe_tabs[5].buf, &h->pipe_tabs[6].buf, &h->pipe_tabs[7].buf,
-                 &h->seq_off_d, &h->seq_q, &h->seq_work, &h->seq_ord, &h->seq_out, &h->dec_tab};
+                 &h->seq_off_d, &h->seq_q, &h->seq_work, &h->seq_ord, &h->seq_out, &h->dec_tab,
+                 &h->sub_obs, &h->sub_mask, &h->sub_tab};
   for (Buf* b : bufs) release(*b);
   if (h->vlb_host) { hipHostFree(h->vlb_host); h->vlb_host = nullptr; }
   if (h->svi_elbo) { hipHostFree(h->svi_elbo); h->svi_elbo = nullptr; }
@@ -1001,6 +1002,9 @@ int prepare_ll(svihmm_ctx* h, const int64_t* starts, int B, int Lm, uint32_t fla
 static int intermediate_ptr(svihmm_ctx* h, int what, int64_t row0, int64_t nrows, const double** out) {
   const int K = h->K, Lm = h->lastLm;
   Buf* src[] = {&h->ll, &h->la, &h->lb, &h->q};
+  if (h->seq_result && h->seq_subset && what != 3)
+    return fail("lliks / lalpha / lbeta are not available: svihmm_estep_sequence_subset keeps var_x of the listed "
+                "rows only (what = 3); svihmm_forward_backward on a sequence's window returns its messages");
   if (h->seq_result && what != 3)
     return fail("lliks / lalpha / lbeta are not available: svihmm_estep_sequences keeps var_x only (what = 3); "
                 "svihmm_forward_backward on a sequence's window returns its messages");
@@ -1435,7 +1439,7 @@ int svihmm_set_sequences(svihmm_ctx* h, const int64_t* seq_off, int32_t N) {
 // concatenated posteriors, asynchronous.  Long sequences (use_chain) one after the other through the whole-chain
 // scan, which writes the handle's ll / la / lb / q from row 0: their posteriors and local_lb are copied out before
 // the next starts.  All others in one ragged launch over the lliks of the smallest row range that covers them.
-static int estep_sequences_core(svihmm_ctx* h, uint32_t flags) {
+static int estep_sequences_core(svihmm_ctx* h, uint32_t flags, bool subset = false) {
   const int N = (int)h->seq_off.size() - 1, K = h->K;
   const int64_t T = h->T;
   const std::vector<int64_t>& so = h->seq_off;
@@ -1480,7 +1484,26 @@ static int estep_sequences_core(svihmm_ctx* h, uint32_t flags) {
   h->lin_mode = false; h->q_valid = true; h->lin_stale = true; h->m_nb = 0; h->have_lb = false;
   h->lastB = 1; h->lastLm = (int)T;
   h->seq_result = true;
+  h->seq_subset = subset;
   return 0;
+}
+
+// estep_sequences_core always in fp64, the precision mode's report about the last E-step batch held (as
+// svihmm_grow_windows), then the packed result's host-visible mirror
+static int estep_sequences_fp64(svihmm_ctx* h, uint32_t flags, bool subset) {
+  const int report = h->f32_report_hold >= 0 ? h->f32_report_hold : (h->cur_f32 || h->eh_float) ? 1 : 0;
+  const int prec = h->prec;
+  h->prec = 0;
+  h->seq_internal = true;
+  const int rc = estep_sequences_core(h, flags, subset);
+  h->seq_internal = false;
+  h->prec = prec;
+  h->cur_f32 = false; h->eh_float = false;
+  h->f32_report_hold = report;
+  if (rc) return rc;
+  h->have_packed = true;
+  h->mirror_valid = false;
+  return launch_mirror(h);
 }
 
 int svihmm_estep_sequences(svihmm_ctx* h, uint32_t flags, double* out_packed, double* out_seq_lb, double* out_q0) {
@@ -1500,23 +1523,87 @@ int svihmm_estep_sequences(svihmm_ctx* h, uint32_t flags, double* out_packed, do
   }
   CK(set_device(h));
   CK(wait_side_streams(h));
-  // always fp64, and the precision mode's report about the last E-step batch stays (as svihmm_grow_windows)
-  const int report = h->f32_report_hold >= 0 ? h->f32_report_hold : (h->cur_f32 || h->eh_float) ? 1 : 0;
-  const int prec = h->prec;
-  h->prec = 0;
-  h->seq_internal = true;
-  const int rc = estep_sequences_core(h, flags);
-  h->seq_internal = false;
-  h->prec = prec;
-  h->cur_f32 = false; h->eh_float = false;
-  h->f32_report_hold = report;
-  if (rc) return rc;
-  h->have_packed = true;
-  h->mirror_valid = false;
-  CK(launch_mirror(h));
+  CK(estep_sequences_fp64(h, flags, false));
   const int N = (int)h->seq_off.size() - 1;
   if (out_seq_lb) CK(d2h(h, out_seq_lb, h->seq_out.p, (size_t)N * sizeof(double)));
   if (out_q0) CK(d2h(h, out_q0, (const double*)h->seq_out.p + N, (size_t)h->K * sizeof(double)));
+  if (out_packed) CK(read_packed_host(h, out_packed));
+  HIPCK(hipStreamSynchronize(h->stream));
+  CK(check_emission_status(h));
+  return 0;
+}
+
+// ---- a minibatch of whole sequences (svihmm_estep_sequence_subset) ------------------------------
+// For the call's duration the handle's resident rows ARE the gathered copy: obs / mask / T / the declaration and its
+// device offsets stand for the R listed rows laid end to end, so estep_sequences_core and everything below it
+// (emission, ragged sweeps / chain scan, the statistics GEMM as one window, k_seq_fix) run unchanged and touch R
+// rows only.  The destructor puts the handle's own back on every return path.
+struct SubsetView {
+  svihmm_ctx* h; int64_t T; std::vector<int64_t> seq_off;
+  SubsetView(svihmm_ctx* h_, int64_t R, std::vector<int64_t>& compact) : h(h_), T(h_->T) {
+    std::swap(h->obs, h->sub_obs); std::swap(h->mask, h->sub_mask); std::swap(h->seq_off_d, h->sub_tab);
+    seq_off.swap(h->seq_off);
+    h->seq_off.swap(compact);
+    h->T = R;
+  }
+  ~SubsetView() {
+    std::swap(h->obs, h->sub_obs); std::swap(h->mask, h->sub_mask); std::swap(h->seq_off_d, h->sub_tab);
+    h->seq_off.swap(seq_off);
+    h->T = T;
+  }
+};
+
+int svihmm_estep_sequence_subset(svihmm_ctx* h, const int32_t* idx, int32_t M, uint32_t flags, double* out_packed,
+                                 double* out_seq_lb, double* out_q0) {
+  const char* fn = "svihmm_estep_sequence_subset";
+  const auto bad = [fn](const std::string& what) { return fail(std::string(fn) + ": " + what); };
+  if (!h) return bad("NULL handle");
+  if (h->seq_off.empty()) return bad("no sequences declared: call svihmm_set_sequences first");
+  if (!idx) return bad("idx is NULL");
+  if (M < 1) return bad("M = " + std::to_string(M) + ": at least one sequence must be listed");
+  const int N = (int)h->seq_off.size() - 1, D = h->D;
+  const std::vector<int64_t>& so = h->seq_off;
+  // dst_off [M + 1] | src_off [M]: the compact copy's offsets (its declaration) and where each occurrence comes from
+  std::vector<int64_t> tab((size_t)2 * M + 1);
+  int64_t R = 0, maxlen = 0;
+  for (int m = 0; m < M; ++m) {
+    const int32_t s = idx[m];
+    if (s < 0 || s >= N)
+      return bad("idx[" + std::to_string(m) + "] = " + std::to_string(s) + " is outside [0, N = " + std::to_string(N) + ")");
+    tab[m] = R;
+    tab[(size_t)M + 1 + m] = so[s];
+    R += so[s + 1] - so[s];
+    maxlen = std::max(maxlen, so[s + 1] - so[s]);
+  }
+  tab[M] = R;
+  if (flags & SVIHMM_USE_HOST_LLIKS) return bad("SVIHMM_USE_HOST_LLIKS is not supported (host lliks carry no sequence offsets)");
+  if (!h->have_globals) return bad("no globals: call svihmm_set_globals first");
+  CK(check_window_model(h, fn));
+  if (h->K > 256) return bad("K = " + std::to_string(h->K) + " > 256 not supported");
+  {
+    // (the statistics pass addresses the R listed rows as one window: svihmm_estep_sequences' check on T)
+    const int64_t rpc = h->emis_cat ? 0 : stats_plan(h, R, h->variant[SVIHMM_VAR_STATS_CHUNKS]).rpc;
+    if (R > 0x7fffffff || (R + rpc) * (int64_t)(h->emis_cat ? 1 : h->Kp) >= ((int64_t)1 << 31))
+      return bad("R = " + std::to_string(R) + " listed rows are too many for the statistics GEMM's 32-bit row offsets");
+  }
+  CK(set_device(h));
+  CK(wait_side_streams(h));
+  // the resident copy's lazily applied state first: symbol indices go back to exact integers before they are copied
+  // (the lookup kernels would do that to the rows in place; a Gaussian family's centre is the handle's, and the copy
+  // holds the same centred values)
+  if (h->emis_cat) CK(cat_uncentre(h));
+  CK(ensure(h->sub_obs, (size_t)R * D * sizeof(double)));
+  if (h->have_mask) CK(ensure(h->sub_mask, (size_t)R));
+  CK(ensure(h->sub_tab, tab.size() * sizeof(int64_t)));
+  CK(upload_staged(h, h->sub_tab.p, tab.data(), tab.size() * sizeof(int64_t)));
+  CK(launch_seq_gather(h, M, (const int64_t*)h->sub_tab.p, (int)maxlen, (double*)h->sub_obs.p, (uint8_t*)h->sub_mask.p));
+  std::vector<int64_t> compact(tab.begin(), tab.begin() + M + 1);
+  {
+    SubsetView view(h, R, compact);
+    CK(estep_sequences_fp64(h, flags, true));
+  }
+  if (out_seq_lb) CK(d2h(h, out_seq_lb, h->seq_out.p, (size_t)M * sizeof(double)));
+  if (out_q0) CK(d2h(h, out_q0, (const double*)h->seq_out.p + M, (size_t)h->K * sizeof(double)));
   if (out_packed) CK(read_packed_host(h, out_packed));
   HIPCK(hipStreamSynchronize(h->stream));
   CK(check_emission_status(h));

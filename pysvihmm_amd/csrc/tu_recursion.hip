@@ -1131,6 +1131,20 @@ int launch_seq_finish(svihmm_ctx* h, int N, const int64_t* seq_off, bool wrap, c
   HIPCK(hipGetLastError());
   return 0;
 }
+// svihmm_estep_sequence_subset: the M listed sequences of the resident rows (and mask bytes) into the compact copy
+// obs_out [R][D] / mask_out [R].  tab (device): dst_off [M + 1] | src_off [M], in rows.  maxlen: the longest of them.
+int launch_seq_gather(svihmm_ctx* h, int M, const int64_t* tab, int maxlen, double* obs_out, uint8_t* mask_out) {
+  // 8 KiB of rows per workgroup and pass, at most 1024 workgroups per occurrence
+  int64_t nseg = ((int64_t)maxlen * h->D * 8 + 8191) / 8192;
+  if (nseg > 1024) nseg = 1024;
+  if (nseg < 1) nseg = 1;
+  ProfScope ps(h, KS_MISC);
+  hipLaunchKernelGGL(k_seq_gather, dim3((unsigned)M, (unsigned)nseg), dim3(256), 0, h->stream,
+                     (const unsigned long long*)h->obs.p, h->have_mask ? (const uint8_t*)h->mask.p : nullptr, tab,
+                     tab + M + 1, h->D, (unsigned long long*)obs_out, h->have_mask ? mask_out : nullptr);
+  HIPCK(hipGetLastError());
+  return 0;
+}
 
 // ---- decoding all declared sequences in one call (kernels_decode_sequences.h) -------------------
 // svihmm_viterbi_sequences.  Sequences whose psi fits the LDS budget (len <= vit_lds_rows(KS); all of them when no

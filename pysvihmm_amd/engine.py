@@ -394,6 +394,29 @@ class HipEngine(object):
         self._rows = self.T
         return (self._wrap_packed(out) if read else None), seq_lb[:n], q0[:self.K]
 
+    def estep_sequence_subset(self, idx, flags=0, read=True):
+        """E-step of a minibatch of whole sequences in one device call (``svihmm_estep_sequence_subset``):
+        ``idx`` lists declared sequences (any integer sequence, any order; a repeated entry counts once per
+        occurrence).  Returns ``(stats, seq_lb[M], q0[K])`` as ``estep_sequences`` does, restricted to the
+        listed sequences, ``seq_lb`` in the order of ``idx``.  The cost follows the listed rows ``R``.
+        Afterwards ``var_x`` of those ``R`` rows, in the order of ``idx``, is readable
+        (``read_rows("var_x", 0, R)``, ``state_argmax``)."""
+        self._pre_mutate()
+        ix = np.ascontiguousarray(np.asarray(idx).ravel(), dtype=np.int32)
+        if len(ix) < 1:
+            raise RuntimeError("estep_sequence_subset: idx is empty (at least one sequence must be listed)")
+        if not np.array_equal(ix, np.asarray(idx).ravel()):
+            raise RuntimeError("estep_sequence_subset: idx must hold integers that fit 32 bits")
+        out = np.empty(self._packed_len()) if read else None
+        seq_lb = np.empty(len(ix))
+        q0 = np.empty(max(self.K, 1))
+        L.check(self._lib.svihmm_estep_sequence_subset(self._h, ix.ctypes.data_as(C.POINTER(C.c_int32)), len(ix),
+                                                       int(flags), L.dptr(out), L.dptr(seq_lb), L.dptr(q0)),
+                "svihmm_estep_sequence_subset")
+        off = self.seq_off
+        self._rows = int((off[ix + 1] - off[ix]).sum())
+        return (self._wrap_packed(out) if read else None), seq_lb, q0[:self.K]
+
     def _packed_len(self):
         if self.V:
             return PackedCatStats.size(self.K, self.V)

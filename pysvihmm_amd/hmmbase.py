@@ -288,6 +288,36 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         st.lb[0] = lb
         return st, lb, q0
 
+    def _sequence_subset_estep(self, idx):
+        """E-step of the sequences listed in ``idx`` only (a minibatch of whole sequences; an entry that
+        occurs twice counts twice): ``(stats, lb, q0)`` as ``_sequences_estep`` returns them, summed over the
+        listed sequences.  One ``estep_sequence_subset`` call where the engine has it, else one
+        ``estep([off], len)`` per listed sequence with the sums formed here.  No per-row attribute is set."""
+        if not (self._niw_fastpath() or self._diag_fastpath() or self._cat_fastpath()):
+            raise RuntimeError("several sequences need an emission family the device evaluates "
+                               "(NIW / diagonal Gaussian, Categorical): host lliks are not supported")
+        self._psi_expectations()
+        self._upload_obs()
+        self._push_globals()
+        flags = self._push_emission()
+        self._seq_flags = flags
+        eng = self.engine
+        self._seq_var_x = None
+        if hasattr(eng, "estep_sequence_subset"):
+            st, seq_lb, q0 = eng.estep_sequence_subset(idx, flags=flags)
+            return st, float(st.lb[0]), q0
+        so = self.seq_off
+        total, lb, q0 = None, 0., np.zeros(self.K)
+        for s in idx:
+            off, ln = int(so[s]), int(so[s + 1] - so[s])
+            st = eng.estep([off], ln, flags=flags)
+            total = st.buf.copy() if total is None else total + st.buf
+            lb += float(st.lb[0])
+            q0 += eng.read_rows("var_x", 0, 1)[0]
+        st = type(st)(total, st.K, getattr(st, "V", None) if hasattr(st, "counts") else st.D)
+        st.lb[0] = lb
+        return st, lb, q0
+
     def _read_var_x(self):
         """``var_x`` [T, K] of the last fused E-step."""
         if self._multi() and self.__dict__.get("_seq_var_x") is not None:

@@ -1,6 +1,8 @@
 """Batch natural-gradient VB -- class surface of reference ``hmmbatchsgd.py``.
 Full-data E-step on the MI355X each iteration, Robbins-Monro natural-gradient
-M-step on the host (hmmbatchsgd.py:202-259)."""
+M-step on the host (hmmbatchsgd.py:202-259).  With ``seq_minibatch=M`` on a list of sequences: stochastic
+variational inference over whole sequences -- the E-step of M sampled sequences per iteration, their
+statistics scaled by ``batchfactor = N / M`` (the factor hmmbatchsgd.py:120-123 names and never sets)."""
 from __future__ import division
 
 import sys
@@ -17,18 +19,30 @@ kappa0 = 0.7
 
 
 class VBHMM(VariationalHMMBase):
-    """Same constructor as reference hmmbatchsgd.py:64-66."""
+    """Same constructor as reference hmmbatchsgd.py:64-66.
+
+    ``seq_minibatch`` (default None: every iteration is a pass over all rows, as in the reference).  An integer
+    ``M`` needs ``obs`` to be a list of ``N >= 2`` sequences and ``1 <= M <= N`` (``RuntimeError`` otherwise).
+    Each iteration of ``infer()`` then draws ``idx = np.sort(np.random.choice(N, size=M, replace=False))`` from the
+    global ``np.random`` stream, sets ``batchfactor = N / M``, runs the E-step of the drawn sequences only (one
+    ``estep_sequence_subset`` device call) and takes the natural-gradient step on their statistics times
+    ``batchfactor``: ``var_init`` is blended like the other factors, ``elbo_vec[it]`` is the usual noisy
+    estimate (``batchfactor`` times the minibatch's local bound), ``pred_logprob_mean / _std`` stay NaN per
+    iteration.  After the last iteration one E-step over all sequences under the final parameters fills
+    ``var_x, lalpha, lbeta, lliks`` (all ``T`` rows) and ``hamming``."""
 
     @staticmethod
     def make_param_dict(prior_init, prior_tran, prior_emit, tau=tau0,
-                        kappa=kappa0, mask=None):
+                        kappa=kappa0, mask=None, seq_minibatch=None):
+        """``seq_minibatch``: optional, default None (see the class)."""
         return {'prior_init': prior_init, 'prior_tran': prior_tran,
                 'prior_emit': prior_emit, 'mask': mask, 'tau': tau,
-                'kappa': kappa}
+                'kappa': kappa, 'seq_minibatch': seq_minibatch}
 
     def __init__(self, obs, prior_init, prior_tran, prior_emit, tau=tau0,
                  kappa=kappa0, mask=None, init_init=None, init_tran=None,
-                 epsilon=1e-8, maxit=100, verbose=False, sts=None, engine=None, device=0, dtype="f64"):
+                 epsilon=1e-8, maxit=100, verbose=False, sts=None, engine=None, device=0, dtype="f64",
+                 seq_minibatch=None):
         super(VBHMM, self).__init__(obs, prior_init, prior_tran, prior_emit,
                                     mask=mask, init_init=init_init,
                                     init_tran=init_tran, verbose=verbose,
@@ -41,6 +55,14 @@ class VBHMM(VariationalHMMBase):
         self.epsilon = epsilon
         self.maxit = maxit
         self.batchfactor = 1.
+        self.seq_minibatch = None
+        if seq_minibatch is not None:
+            n = len(self.seq_off) - 1 if self._multi() else 0
+            if n < 2:
+                raise RuntimeError("seq_minibatch needs obs to be a list of at least two sequences")
+            if int(seq_minibatch) != seq_minibatch or not 1 <= int(seq_minibatch) <= n:
+                raise RuntimeError("seq_minibatch = %r must be an integer in [1, N = %d]" % (seq_minibatch, n))
+            self.seq_minibatch = int(seq_minibatch)
 
         self.var_x = np.ones((self.T, self.K))
         self.var_x /= np.sum(self.var_x, axis=1)[:, np.newaxis]
@@ -57,6 +79,7 @@ class VBHMM(VariationalHMMBase):
                 or type(self).global_update is not VBHMM.global_update:
             fused = False
         self._require_fused_sequences(fused)
+        mb = self.seq_minibatch       # (a list of sequences: the line above has refused everything but the fused path)
         route = not fused and self._batch_stats_route(VBHMM.global_update, ("niw", "diag"))
         self.obs_full = self.obs.copy()
         self.obs[self.mask, :] = np.nan       # hmmbatchsgd.py:149 (NaN rows -> lliks 0)
@@ -71,7 +94,10 @@ class VBHMM(VariationalHMMBase):
         for it in range(maxit):
             start_time = time.time()
             self.lrate = (it + self.tau) ** (-self.kappa)
-            if fused:
+            if mb is not None:
+                st = self._seq_minibatch_stats()
+                self._global_update_from_stats(st)
+            elif fused:
                 st = self._batch_estep_stats()
                 self._global_update_from_stats(st)
             elif route:
@@ -91,7 +117,7 @@ class VBHMM(VariationalHMMBase):
 
             self.elbo = lb
             self.elbo_vec[it] = lb
-            if np.any(self.mask):
+            if mb is None and np.any(self.mask):    # (a minibatch leaves posteriors of M sequences only: NaN)
                 if fused:
                     self.var_x = self._read_var_x()
                 tmp = self.pred_logprob()
@@ -105,6 +131,9 @@ class VBHMM(VariationalHMMBase):
         self.pred_logprob_std = self.pred_logprob_std[lbidx]
         self.iter_time = self.iter_time[lbidx]
 
+        if mb is not None:
+            # the per-row attributes cover all T rows: one E-step over every sequence under the final parameters
+            _, self._lZ, _ = self._sequences_estep()
         if fused:
             self._fetch_local()
         if self.sts is not None:
@@ -130,9 +159,25 @@ class VBHMM(VariationalHMMBase):
             nats_new = (1. - lrate) * nats_old + lrate * nats_t
             util.NIW_mf_moment_pars(G, *nats_new)
 
+    def _seq_minibatch_stats(self):
+        """One iteration's minibatch of whole sequences: the draw, ``batchfactor = N / M``, the E-step of the
+        drawn sequences and their statistics times ``batchfactor`` (every entry of the packed layout is a sum
+        over rows, so the whole buffer scales); ``_lZ`` the scaled local bound, ``_q0`` the unscaled sum of
+        first posterior rows (``_global_update_from_stats`` scales it)."""
+        n = len(self.seq_off) - 1
+        idx = np.sort(np.random.choice(n, size=self.seq_minibatch, replace=False))
+        self.batchfactor = bf = n / self.seq_minibatch
+        st, lb, self._q0 = self._sequence_subset_estep(idx)
+        st = type(st)(st.buf * bf, st.K, getattr(st, "V", None) if hasattr(st, "counts") else st.D)
+        self._lZ = bf * lb
+        return st
+
     def _global_update_from_stats(self, st):
         lrate = self.lrate
-        self.var_init = self.prior_init + self._q0
+        if self.seq_minibatch is None:
+            self.var_init = self.prior_init + self._q0
+        else:      # a noisy estimate like the others: blended, not replaced
+            self.var_init = (1. - lrate) * self.var_init + lrate * (self.prior_init + self.batchfactor * self._q0)
         nats_old = self.var_tran - 1.
         nats_t = (self.prior_tran + st.A_raw) - 1.
         self.var_tran = ((1. - lrate) * nats_old + lrate * nats_t) + 1.
