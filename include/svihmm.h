@@ -495,6 +495,36 @@ int svihmm_svi_read_state(svihmm_ctx* h, double* var_tran, double* var_init, dou
 int svihmm_set_emission_cat(svihmm_ctx* h, int32_t K, int32_t V, const double* logp);
 int64_t svihmm_packed_len(svihmm_ctx* h);
 
+/* Multi-column Categorical emissions: D discrete tracks per row, independent given the state,
+ *   p(x_t | z_t = k) = prod_d Cat(x_t[d] | theta_{k,d}).
+ * V[d] >= 1 is the number of symbols of column d, F = sum_d V[d], off_d the exclusive prefix sum of V;
+ * logp[k][off_d + v] = E_q log theta_{k,d}[v] = psi(alpha_{k,d}[v]) - psi(sum_v alpha_{k,d}[v]) (host, SciPy
+ * digamma, per column).  obs is [T][D], each entry a symbol index stored as a double and truncated with (int)x
+ * as for svihmm_set_emission_cat.
+ * Entry (t, d) is PRESENT when it is not NaN and 0 <= (int)x < V[d].  An entry that is not present is skipped:
+ * it adds nothing to the row's llik and nothing to the counts; the row's other columns are not affected.
+ * lliks: ll[t][k] = s, where s starts at +0.0 and receives one plain add of logp[k][off_d + x_td] per present
+ * column in ascending d (all zeros for a row masked under SVIHMM_MASK_AS_NAN): given the same table, bit-identical
+ * to that loop in NumPy, and for D = 1 what svihmm_set_emission_cat returns.
+ * Packed statistics (svihmm_packed_len): [A_raw K*K | counts K*F | lb], counts[k][off_d + v] = sum of var_x[t][k]
+ * over the rows t with mask[t] == 0 (whatever the flags) whose entry d is present with symbol v.  A_raw, lb,
+ * SVIHMM_TRANS_WRAP and the inner segment of svihmm_estep_minibatch_ex behave as for the Categorical family, and
+ * so does every entry point that dispatches on the emission family: loglik, forward_backward, estep_minibatch(_ex),
+ * suffstats, estep_sequences, estep_sequence_subset, viterbi(_sequences), ffbs, ffbs_windows, ffbs_sequences,
+ * grow_windows, state_argmax, read_intermediate / read_rows, read_packed, export / import / allreduce_packed.
+ * The symbol columns stay exact integers in the resident copy: an upload while the family is active is not
+ * centred, a copy centred earlier is brought back, a Gaussian family that follows centres again.
+ * Fails with a message before any device work (the handle stays usable): NULL V or logp; K < 1 or K > 256;
+ * D < 1 or D > SVIHMM_MCAT_MAX_D; a V[d] < 1; F > SVIHMM_MCAT_MAX_F; a non-finite table entry; and, at the first
+ * E-step-type call, resident observations whose D differs from the family's.
+ * Out of scope, each refused with a message: the resident SVI loop (svihmm_svi_begin_* replaces the family;
+ * svihmm_svi_iteration refuses), svihmm_pred_logprob (NIW only), the fp32 mode (svihmm_get_precision reports
+ * last_batch_f32 = 0), and the device paths of hmmsgd_metaobs.VBHMM (host lliks through the plugin there). */
+#define SVIHMM_MCAT_MAX_D 128
+#define SVIHMM_MCAT_MAX_F 1024
+int svihmm_set_emission_mcat(svihmm_ctx* h, int32_t K, int32_t D, const int32_t* V /*[D]*/,
+                             const double* logp /*[K][F]*/);
+
 /* ELBO bookkeeping of the SVI loop (hmmsgd_metaobs.py:273-296 global_lower_bound,
  * hmmbase.py:183-185: sum_k var_emit[k].get_vlb()): the data-dependent scalars of the NIW
  * factors' term for the given mean-field parameters (D <= SVIHMM_NIW_MAX_D; D <= 64 runs the

@@ -121,6 +121,9 @@ struct svihmm_ctx {
   bool uwd_valid = false, emd_attr_set[2] = {false, false};
   bool emb_attr_set = false;
   bool emis_cat = false; int V = 0;          // Categorical emission: table [V][K] = E log theta
+  // multi-column Categorical (svihmm_set_emission_mcat): emis_cat is set as well -- every route the host picks by asking
+  // emis_cat is the one this family takes -- with V = F = sum_d V[d]; mcat_meta = [off_d D | V_d D | d(f) F | v(f) F] int32
+  bool emis_mcat = false; Buf mcat_meta;
   bool emis_diag = false;                    // diagonal Gaussian family: 2 D + 1 features, h->niw = [mu | nus | alphas | betas]
   bool tab_diag = false;                     // feature table currently on the device is the diagonal one
   void* theta_zero_p = nullptr; size_t theta_zero_n = 0;   // what the last theta memset covered
@@ -386,6 +389,13 @@ int wait_globals(svihmm_ctx* h);
 int svi_flush_elbo(svihmm_ctx* h);
 int ensure_starts_pulled(svihmm_ctx* h);
 int cat_uncentre(svihmm_ctx* h);
+// what an E-step-type call says when the emission family's D is not the resident observations'
+extern "C++" inline std::string emission_d_message(const svihmm_ctx* h) {
+  if (h->emis_mcat)
+    return "svihmm_set_emission_mcat: the family has D = " + std::to_string(h->eD) +
+           " symbol columns, the resident observations have " + std::to_string(h->D);
+  return "emission D does not match obs D";
+}
 int launch_fb_chain(svihmm_ctx* h, int Lm, bool total);
 int launch_emission_deferred(svihmm_ctx* h);
 int launch_viterbi(svihmm_ctx* h, int B, int Lm, const double* ll, bool want_z, int32_t** dz_out, double** dscore_out);

@@ -79,7 +79,7 @@ int svihmm_destroy(svihmm_ctx* h) {
   Buf* bufs[] = {&h->obs, &h->mask, &h->mod_init, &h->ltran, &h->Aexp, &h->AexpT, &h->theta, &h->niw,
                  &h->fab, &h->starts, &h->user_q, &h->user_starts, &h->vit, &h->ll, &h->la, &h->lb, &h->q, &h->lse_part,
                  &h->local_lb, &h->logz, &h->part, &h->packed, &h->scratch, &h->kexp, &h->hx, &h->gx,
-                 &h->zfac, &h->llE, &h->m_ll, &h->m_la, &h->m_lb, &h->chain, &h->chain2, &h->cat_table, &h->partc, &h->theta_orb, &h->prior, &h->vlb_aux, &h->gen_z,
+                 &h->zfac, &h->llE, &h->m_ll, &h->m_la, &h->m_lb, &h->chain, &h->chain2, &h->cat_table, &h->mcat_meta, &h->partc, &h->theta_orb, &h->prior, &h->vlb_aux, &h->gen_z,
                  &h->svi_state, &h->svi_prior, &h->svi_work, &h->commtmp, &h->ll0, &h->a0v, &h->a0e,
                  &h->shift_d, &h->uwb, &h->uwd, &h->AexpF, &h->AexpTF, &h->svi_sync, &h->pipe_cnt,
                  &h->pipe_tabs[0].buf, &h->pipe_tabs[1].buf, &h->pipe_tabs[2].buf, &h->pipe_tabs[3].buf,
@@ -704,7 +704,60 @@ int svihmm_set_emission_cat(svihmm_ctx* h, int32_t K, int32_t V, const double* l
     for (int v = 0; v < V; ++v) hp[(size_t)v * K + k] = logp[(size_t)k * V + v];
   HIPCK(hipMemcpyAsync(h->cat_table.p, hp, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
   CK(pin_release(h, slot));
-  h->eK = K; h->eD = 1; h->V = V; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16; h->have_emission = true; h->emis_cat = true; h->emis_diag = false; h->uw_valid = false;
+  h->eK = K; h->eD = 1; h->V = V; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16; h->have_emission = true; h->emis_cat = true; h->emis_mcat = false; h->emis_diag = false; h->uw_valid = false;
+  return 0;
+}
+// D symbol columns, independent per state (kernels_mcat.h).  The family rides the Categorical branches of the host
+// code (emis_cat) with V = F features; only the lookup and the count launches differ (emis_mcat).
+int svihmm_set_emission_mcat(svihmm_ctx* h, int32_t K, int32_t D, const int32_t* V, const double* logp) {
+  if (!h) return fail("svihmm_set_emission_mcat: handle is NULL");
+  if (!V || !logp) return fail("svihmm_set_emission_mcat: V and logp must not be NULL");
+  if (K < 1 || K > 256) return fail("svihmm_set_emission_mcat: K = " + std::to_string(K) + " outside [1, 256]");
+  if (D < 1 || D > SVIHMM_MCAT_MAX_D)
+    return fail("svihmm_set_emission_mcat: D = " + std::to_string(D) + " outside [1, SVIHMM_MCAT_MAX_D = " +
+                std::to_string(SVIHMM_MCAT_MAX_D) + "]");
+  int64_t F64 = 0;
+  for (int d = 0; d < D; ++d) {
+    if (V[d] < 1)
+      return fail("svihmm_set_emission_mcat: V[" + std::to_string(d) + "] = " + std::to_string(V[d]) + " (every column needs at least one symbol)");
+    F64 += V[d];
+  }
+  if (F64 > SVIHMM_MCAT_MAX_F)
+    return fail("svihmm_set_emission_mcat: F = sum of V = " + std::to_string(F64) + " exceeds SVIHMM_MCAT_MAX_F = " +
+                std::to_string(SVIHMM_MCAT_MAX_F));
+  const int F = (int)F64;
+  const size_t n = (size_t)K * F;
+  for (size_t i = 0; i < n; ++i)
+    if (!(logp[i] > -1.7e308 && logp[i] < 1.7e308))
+      return fail("svihmm_set_emission_mcat: logp[" + std::to_string(i / F) + "][" + std::to_string(i % F) + "] is not finite");
+  CK(set_device(h));
+  h->lin_stale = true;
+  h->center_pending = false;
+  // (the resident SVI loop does not know this family: a running loop ends with this upload)
+  if (h->svi_active) CK(svi_flush_elbo(h));
+  h->svi_active = false;
+  if (h->vlb_pending) { HIPCK(hipStreamWaitEvent(h->stream, h->svi_ed, 0)); h->vlb_pending = false; }
+  CK(drop_auto_status(h));
+  CK(cat_uncentre(h));
+  const size_t nmeta = 2 * (size_t)D + 2 * (size_t)F;
+  CK(ensure(h->cat_table, n * sizeof(double)));
+  CK(ensure(h->mcat_meta, nmeta * sizeof(int)));
+  void* pin = nullptr;
+  int slot = 0;
+  CK(pinned(h, n * sizeof(double) + nmeta * sizeof(int), &pin, &slot));
+  double* hp = (double*)pin;
+  for (int k = 0; k < K; ++k)              // transpose to [F][K]: a feature's states are contiguous
+    for (int f = 0; f < F; ++f) hp[(size_t)f * K + k] = logp[(size_t)k * F + f];
+  int* mp = (int*)(hp + n);
+  for (int d = 0, o = 0; d < D; o += V[d], ++d) {
+    mp[d] = o; mp[D + d] = V[d];
+    for (int v = 0; v < V[d]; ++v) { mp[2 * D + o + v] = d; mp[2 * D + F + o + v] = v; }
+  }
+  HIPCK(hipMemcpyAsync(h->cat_table.p, hp, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCK(hipMemcpyAsync(h->mcat_meta.p, mp, nmeta * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  CK(pin_release(h, slot));
+  h->eK = K; h->eD = D; h->V = F; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16;
+  h->have_emission = true; h->emis_cat = true; h->emis_mcat = true; h->emis_diag = false; h->uw_valid = false;
   return 0;
 }
 int64_t svihmm_packed_len(svihmm_ctx* h) { return h ? (int64_t)packed_len(h) : 0; }
@@ -1130,7 +1183,7 @@ static int estep_pipelined(svihmm_ctx* h, const int64_t* starts, int B, int Lm, 
   CK(check_windows(h, starts, B, Lm, true));
   CK(upload_starts(h, starts, B));
   if (!h->have_emission) return fail("no emission parameters: call svihmm_set_emission_niw");
-  if (h->eD != h->D) return fail("emission D does not match obs D");
+  if (h->eD != h->D) return fail(emission_d_message(h));
   if (h->eK != h->K) return fail("emission K does not match globals K");
   if (!h->stream2) {
     HIPCK(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
@@ -1218,6 +1271,8 @@ int svihmm_pred_logprob(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t
                         uint32_t flags, double out2[2]) {
   if (!h || !starts || !out2) return fail("svihmm_pred_logprob: bad arguments");
   if (flags & SVIHMM_USE_HOST_LLIKS) return fail("svihmm_pred_logprob: NIW emission only");
+  if (h->have_emission && h->emis_mcat)
+    return fail("svihmm_pred_logprob: NIW emission only (the multi-column Categorical family of svihmm_set_emission_mcat is not taken)");
   CK(set_device(h));
   if (!h->have_mask) { out2[0] = NAN; out2[1] = 0.0; return 0; }
   const int var = pick_fb(h, B, Lm, false);
@@ -1357,7 +1412,7 @@ static int check_window_model(const svihmm_ctx* h, const char* fn) {
   if (h->K != h->eK)
     return bad("K of the globals (" + std::to_string(h->K) + ") differs from the emission family's K (" +
                std::to_string(h->eK) + ")");
-  if (h->eD != h->D) return bad("emission D does not match obs D");
+  if (h->eD != h->D) return bad(emission_d_message(h));
   return 0;
 }
 // every window [starts[b], starts[b] + Lm) inside [0, T)
@@ -1795,7 +1850,7 @@ static int svi_refresh_emission(svihmm_ctx* h, int elbo_it, int lb_slot, hipEven
                        (double*)h->cat_table.p, tsy);
     HIPCK(hipGetLastError());
     h->eK = K; h->eD = 1; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16;
-    h->have_emission = true; h->emis_cat = true; h->emis_diag = false; h->uw_valid = false;
+    h->have_emission = true; h->emis_cat = true; h->emis_mcat = false; h->emis_diag = false; h->uw_valid = false;
   }
   h->theta_sy = SviSync{};
   h->lin_stale = true;
@@ -2134,6 +2189,9 @@ int svihmm_svi_recoveries(svihmm_ctx* h, int32_t* out) {
 int svihmm_svi_iteration(svihmm_ctx* h, int32_t it, const int64_t* starts, int32_t B, int32_t nwin_total,
                          int32_t Lm, int32_t inner_off, int32_t inner_len, uint32_t flags, double rho,
                          double bfactA, double bfactE) {
+  if (h && !h->svi_active && h->have_emission && h->emis_mcat)
+    return fail("svihmm_svi_iteration: the resident SVI loop does not take the multi-column Categorical family "
+                "(svihmm_set_emission_mcat); step the globals on the host from svihmm_estep_minibatch's statistics");
   if (!h || !h->svi_active) return fail("svihmm_svi_iteration: call svihmm_svi_begin first");
   if (it < 0 || it >= h->svi_maxit) return fail("svihmm_svi_iteration: iteration index out of range");
   if (B < 0 || (B > 0 && !starts) || nwin_total < B) return fail("svihmm_svi_iteration: bad window batch");

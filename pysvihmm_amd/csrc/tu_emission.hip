@@ -3,6 +3,8 @@
 #include "host.h"
 #include "device_helpers.h"
 #include "kernels_emission.h"
+#define SVIHMM_MCAT_EMISSION
+#include "kernels_mcat.h"
 
 extern "C" {
 
@@ -134,7 +136,7 @@ int launch_niw_to_theta(svihmm_ctx* h, int K, int D, double* logdet_out, const S
   }
   // status comes back asynchronously; it is examined at the next synchronising call
   h->status_pending = true;
-  h->eK = K; h->eD = D; h->have_emission = true; h->emis_cat = false; h->emis_diag = false;
+  h->eK = K; h->eD = D; h->have_emission = true; h->emis_cat = false; h->emis_mcat = false; h->emis_diag = false;
   h->orb_valid = orbp != nullptr;
   h->uw_valid = uwp != nullptr && !emd;
   h->uwd_valid = emd;
@@ -165,7 +167,7 @@ int launch_diag_to_theta(svihmm_ctx* h, int K, int D) {
     HIPCK(hipGetLastError());
   }
   h->status_pending = true;
-  h->eK = K; h->eD = D; h->have_emission = true; h->emis_cat = false; h->emis_diag = true; h->uw_valid = false; h->uwd_valid = false;
+  h->eK = K; h->eD = D; h->have_emission = true; h->emis_cat = false; h->emis_mcat = false; h->emis_diag = true; h->uw_valid = false; h->uwd_valid = false;
   h->orb_valid = false;
   return 0;
 }
@@ -208,7 +210,7 @@ int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
                            double* kexp_out, hipStream_t stream,
                            size_t min_lds, double* ll0_out) {
   if (!h->have_emission) return fail("no emission parameters: call svihmm_set_emission_niw");
-  if (h->eD != h->D) return fail("emission D does not match obs D");
+  if (h->eD != h->D) return fail(emission_d_message(h));
   if (!h->have_globals || h->eK != h->K) return fail("emission K does not match globals K");
   const int64_t n = (int64_t)B * Lm;
   const int D = h->D, K = h->K, Kp = h->Kp;
@@ -247,6 +249,28 @@ int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
     if (h->shifted) {          // (a shift moved the symbol column after the table was set)
       if (stream != h->stream) return fail("internal: Categorical lookup on a side stream over a centred column");
       CK(cat_uncentre(h));
+    }
+    if (h->emis_mcat) {        // D symbol columns: one lookup and one add per present column (kernels_mcat.h)
+      const int F = h->V;
+      const size_t tb = (size_t)F * K * sizeof(double), ib = (size_t)MC_EM_ROWS * ((D + 7) & ~7) * sizeof(int);
+      const bool tlds = tb <= 64 * 1024;
+      // rows per workgroup: blocks of MC_EM_ROWS; a staged table is paid once per workgroup, so at least 256 rows,
+      // more once the launch has eight workgroups per CU
+      int64_t rpw = (n + 8 * (int64_t)h->ncu - 1) / (8 * (int64_t)h->ncu);
+      rpw = std::max<int64_t>(tlds ? 256 : MC_EM_ROWS, (rpw + MC_EM_ROWS - 1) / MC_EM_ROWS * MC_EM_ROWS);
+      if (rpw > 1 << 20) rpw = 1 << 20;
+      const size_t lds = (tlds ? tb : 0) + ib;
+      const dim3 grid((unsigned)((n + rpw - 1) / rpw));
+      if (tlds) {
+        hipFuncSetAttribute((const void*)k_emission_mcat<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(k_emission_mcat<true>, grid, dim3(256), lds, stream, (const double*)h->obs.p, mk, starts_dev,
+                           n, Lm, K, D, F, (const int*)h->mcat_meta.p, (const double*)h->cat_table.p, flags, out, (int)rpw);
+      } else {
+        hipLaunchKernelGGL(k_emission_mcat<false>, grid, dim3(256), lds, stream, (const double*)h->obs.p, mk, starts_dev,
+                           n, Lm, K, D, F, (const int*)h->mcat_meta.p, (const double*)h->cat_table.p, flags, out, (int)rpw);
+      }
+      HIPCK(hipGetLastError());
+      return 0;
     }
     hipLaunchKernelGGL(k_emission_cat, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, stream,
                        (const double*)h->obs.p, mk, starts_dev, n, Lm, K, h->V,

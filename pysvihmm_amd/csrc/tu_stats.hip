@@ -3,6 +3,8 @@
 #include "host.h"
 #include "device_helpers.h"
 #include "kernels_stats.h"
+#define SVIHMM_MCAT_STATS
+#include "kernels_mcat.h"
 
 extern "C" {
 
@@ -378,7 +380,16 @@ static int launch_stats_cat(svihmm_ctx* h, int B, int Lq, int off, int Lm, uint3
   const StatsPlan plan = stats_plan(h, n);
   if (qsrc && (int64_t)(Lq + plan.rpc) * KpT >= ((int64_t)1 << 31))
     return fail("Categorical statistics: window too long for the GEMM's 32-bit row offsets");
-  const int64_t rpcc = (n + 1023) / 1024 > 64 ? (n + 1023) / 1024 : 64;
+  // row chunks of the counts.  One column: k_stats_cat, one wave per chunk.  D columns (k_stats_onehot): whole stages
+  // of MC_RB rows, two chunks per CU for each (feature group, state group) pair -- more only adds partial sums
+  const bool mc = h->emis_mcat;
+  const int mcMT = V <= 64 ? 1 : V <= 128 ? 2 : 4;
+  const int mcGy = (V + 64 * mcMT - 1) / (64 * mcMT), mcGz = (K + 63) / 64;
+  int64_t rpcc = (n + 1023) / 1024 > 64 ? (n + 1023) / 1024 : 64;
+  if (mc) {
+    const int64_t tc = std::max<int64_t>(1, 2 * (int64_t)h->ncu / (mcGy * mcGz));
+    rpcc = std::max<int64_t>(MC_RB, ((n + tc - 1) / tc + MC_RB - 1) / MC_RB * MC_RB);
+  }
   const int nchunkc = (int)((n + rpcc - 1) / rpcc);
   CK(ensure(h->part, (size_t)plan.nchunk * KpT * KpT * sizeof(double)));
   CK(ensure(h->partc, (size_t)nchunkc * V * Kp * sizeof(double)));
@@ -395,13 +406,24 @@ static int launch_stats_cat(svihmm_ctx* h, int B, int Lq, int off, int Lm, uint3
                        (const int*)nullptr, qv, plan.rpc, flags, Lq, off,
                        (double*)h->part.p, KpT, 0, (const double*)nullptr, (const double*)nullptr,
                        (const double*)nullptr, (const double2*)nullptr, (double*)nullptr);
-    const size_t ldsc = (size_t)V * Kp * sizeof(double);
-    if (ldsc > 150 * 1024) return fail("Categorical statistics: V * K too large for the LDS table");
-    if (ldsc > 64 * 1024)
-      hipFuncSetAttribute((const void*)k_stats_cat, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsc);
-    hipLaunchKernelGGL(k_stats_cat, dim3((unsigned)nchunkc), dim3(64), ldsc, stream, (const double*)h->obs.p, mk,
-                       sv, n, Lm, K, Kp, V, qv, rpcc, Lq, off,
-                       (double*)h->partc.p);
+    if (mc) {
+      const size_t ldsm = (size_t)MC_RB * MC_QS * sizeof(double) + MC_RB * sizeof(McRow) + MC_RB * sizeof(int) +
+                          (size_t)MC_RB * (D | 1) * sizeof(short);
+      const dim3 gm((unsigned)nchunkc, mcGy, mcGz);
+#define MCL(MTV)                                                                                                   \
+  hipLaunchKernelGGL(k_stats_onehot<MTV>, gm, dim3(256), ldsm, stream, (const double*)h->obs.p, mk, sv, n, Lm, K, Kp, \
+                     D, V, (const int*)h->mcat_meta.p, qv, rpcc, Lq, off, (double*)h->partc.p)
+      if (mcMT == 1) MCL(1); else if (mcMT == 2) MCL(2); else MCL(4);
+#undef MCL
+    } else {
+      const size_t ldsc = (size_t)V * Kp * sizeof(double);
+      if (ldsc > 150 * 1024) return fail("Categorical statistics: V * K too large for the LDS table");
+      if (ldsc > 64 * 1024)
+        hipFuncSetAttribute((const void*)k_stats_cat, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsc);
+      hipLaunchKernelGGL(k_stats_cat, dim3((unsigned)nchunkc), dim3(64), ldsc, stream, (const double*)h->obs.p, mk,
+                         sv, n, Lm, K, Kp, V, qv, rpcc, Lq, off,
+                         (double*)h->partc.p);
+    }
     HIPCK(hipGetLastError());
   }
   {

@@ -30,7 +30,7 @@ import numpy as np
 import scipy.linalg as sla
 from scipy.special import digamma, gammaln
 
-__all__ = ["Gaussian", "DiagonalGaussian", "Categorical", "sample_niw", "sample_invwishart",
+__all__ = ["Gaussian", "DiagonalGaussian", "Categorical", "ProductCategorical", "sample_niw", "sample_invwishart",
            "niw_quadratic_form", "niw_vlb_batch", "niw_prior_logpart", "vlb_logz_sign"]
 
 
@@ -498,3 +498,98 @@ class Categorical(object):
         logpi_p = gammaln(a0.sum()) - gammaln(a0).sum() + ((a0 - 1) * el).sum()
         logpi_q = gammaln(a.sum()) - gammaln(a).sum() + ((a - 1) * el).sum()
         return logpi_p - logpi_q
+
+
+class ProductCategorical(object):
+    """D independent Dirichlet-Categorical factors, one per observation column:
+    ``p(x | theta) = prod_d Cat(x[d] | theta_d)`` with priors ``alphav_0[d]`` ([V_d]) and mean-field
+    factors ``alpha_mf[d]``.  An entry of a row is *present* when it is not NaN and
+    ``0 <= int(x) < V_d``; an absent entry is skipped, the row's other columns are not affected.
+    With D = 1 the class reproduces ``Categorical`` number for number."""
+
+    def __init__(self, weights=None, alphav_0=None, alpha_mf=None):
+        if alphav_0 is None:
+            raise ValueError("ProductCategorical: alphav_0 (a list of D arrays [V_d]) is required")
+        self.alphav_0 = [np.array(a, float).ravel() for a in alphav_0]
+        self.D = len(self.alphav_0)
+        if self.D < 1 or any(len(a) < 1 for a in self.alphav_0):
+            raise ValueError("ProductCategorical: at least one column, at least one symbol per column")
+        if weights is None:
+            self.weights = [np.random.dirichlet(a) for a in self.alphav_0]
+        else:
+            self.weights = [np.array(w, float).ravel() for w in weights]
+        if alpha_mf is not None:
+            self._alpha_mf = [np.array(a, float).ravel() for a in alpha_mf]
+        else:
+            self._alpha_mf = [w * a.sum() for w, a in zip(self.weights, self.alphav_0)]
+        if not (len(self.weights) == len(self._alpha_mf) == self.D) or any(
+                len(w) != len(a0) or len(a) != len(a0)
+                for w, a, a0 in zip(self.weights, self._alpha_mf, self.alphav_0)):
+            raise ValueError("ProductCategorical: weights / alpha_mf do not match alphav_0's shapes")
+
+    @property
+    def alpha_mf(self):
+        return self._alpha_mf
+
+    @property
+    def V(self):
+        """Symbols per column."""
+        return tuple(len(a) for a in self.alphav_0)
+
+    def num_parameters(self):
+        return sum(len(w) for w in self.weights)
+
+    def rvs(self, size=None):
+        cols = [np.random.choice(len(w), p=w, size=size) for w in self.weights]
+        return np.stack(cols, axis=-1)
+
+    def _present(self, x):
+        """``(xi int[n, D], ok bool[n, D])``: truncated symbols (0 where absent) and presence."""
+        x = np.asarray(x, dtype=float)
+        x = x.reshape(x.shape[0], -1) if x.ndim != 1 else x.reshape(-1, 1)
+        if x.shape[1] != self.D:
+            raise ValueError("ProductCategorical: data has %d columns, the factor has %d" % (x.shape[1], self.D))
+        nan = np.isnan(x)
+        with np.errstate(invalid="ignore"):
+            xi = np.where(nan, -1, np.trunc(np.where(nan, 0.0, x))).astype(np.int64)
+        ok = (~nan) & (xi >= 0) & (xi < np.asarray(self.V)[None, :])
+        return np.where(ok, xi, 0), ok
+
+    def expected_log_tables(self):
+        """``E_q log theta_d`` per column: ``psi(alpha_mf[d]) - psi(sum alpha_mf[d])``."""
+        return [digamma(a) - digamma(a.sum()) for a in self._alpha_mf]
+
+    def _get_weighted_statistics(self, data, weights):
+        xi, ok = self._present(data)
+        w = np.asarray(weights, float).ravel()
+        return ([np.bincount(xi[ok[:, d], d], weights=w[ok[:, d]], minlength=len(self.alphav_0[d]))
+                 for d in range(self.D)],)
+
+    def _posterior_hypparams(self, counts):
+        return [a0 + np.asarray(c, float) for a0, c in zip(self.alphav_0, counts)]
+
+    def _set_alpha(self, alpha):
+        self._alpha_mf = [np.array(a, float) for a in alpha]
+        self.weights = [a / a.sum() for a in self._alpha_mf]
+
+    def meanfieldupdate(self, data, weights):
+        self._set_alpha(self._posterior_hypparams(*self._get_weighted_statistics(data, weights)))
+
+    def expected_log_likelihood(self, x):
+        """Sum over the present columns, ascending d; NaN where no column is present (``nan_to_num``
+        then gives the 0 a missing row contributes)."""
+        xi, ok = self._present(x)
+        out = np.zeros(xi.shape[0])
+        for d, el in enumerate(self.expected_log_tables()):
+            out[ok[:, d]] += el[xi[ok[:, d], d]]
+        out[~ok.any(1)] = np.nan
+        return out
+
+    def get_vlb(self):
+        tot = 0.
+        for a, a0 in zip(self._alpha_mf, self.alphav_0):
+            el = digamma(a) - digamma(a.sum())
+            logpi_p = gammaln(a0.sum()) - gammaln(a0).sum() + ((a0 - 1) * el).sum()
+            logpi_q = gammaln(a.sum()) - gammaln(a).sum() + ((a - 1) * el).sum()
+            tot += logpi_p - logpi_q
+        return tot

@@ -65,6 +65,34 @@ class PackedCatStats(object):
         return K * K + K * V + 1
 
 
+class PackedMCatStats(object):
+    """View of the packed statistics of a multi-column Categorical E-step
+    ``[A_raw K*K | counts K*F | lb]``, ``F = sum(Vs)``: ``flat`` is the whole ``[K, F]`` block and
+    ``col_counts[d]`` the ``[K, V_d]`` view of column d (``col_counts[d][k, v]`` = sum of var_x[t, k]
+    over unmasked rows whose entry d is present with symbol v)."""
+
+    def __init__(self, buf, K, Vs):
+        Vs = tuple(int(v) for v in Vs)
+        F = sum(Vs)
+        self.buf, self.K, self.Vs, self.F = buf, K, Vs, F
+        self.A_raw = buf[:K * K].reshape(K, K)
+        self.flat = buf[K * K:K * K + K * F].reshape(K, F)
+        off = np.concatenate(([0], np.cumsum(Vs))).astype(int)
+        self.col_counts = [self.flat[:, off[d]:off[d + 1]] for d in range(len(Vs))]
+        self.lb = buf[K * K + K * F:K * K + K * F + 1]
+
+    @staticmethod
+    def size(K, Vs):
+        return K * K + K * int(sum(Vs)) + 1
+
+
+def rewrap_packed(st, buf):
+    """A view of ``st``'s type and shape over another buffer (sums / multiples of packed statistics)."""
+    if isinstance(st, PackedMCatStats):
+        return PackedMCatStats(buf, st.K, st.Vs)
+    return type(st)(buf, st.K, getattr(st, "V", None) if hasattr(st, "counts") else st.D)
+
+
 class HipEngine(object):
     """E-step engine on one MI355X.  Raises RuntimeError when the HIP library or
     a GPU is unavailable (no fallback)."""
@@ -83,6 +111,7 @@ class HipEngine(object):
         self.device = int(device)
         self.T = self.D = self.K = 0
         self.V = 0            # > 0: Categorical emission with V symbols is active
+        self.Vs = None        # multi-column Categorical emission is active: the columns' symbol counts
         self.diag = False     # diagonal-Gaussian emission is active (its own packed layout)
         self._comm = False
         self.seq_off = None   # offsets declared with set_sequences (every upload of rows removes them)
@@ -241,6 +270,7 @@ class HipEngine(object):
                 "svihmm_set_emission_niw")
         self.V = 0
         self.diag = False
+        self.Vs = None
         if check:
             L.check(self._lib.svihmm_sync(self._h), "svihmm_set_emission_niw")
 
@@ -256,6 +286,7 @@ class HipEngine(object):
                                                    L.dptr(betas)), "svihmm_set_emission_diag")
         self.V = 0
         self.diag = True
+        self.Vs = None
         if check:
             L.check(self._lib.svihmm_sync(self._h), "svihmm_set_emission_diag")
 
@@ -418,11 +449,15 @@ class HipEngine(object):
         return (self._wrap_packed(out) if read else None), seq_lb, q0[:self.K]
 
     def _packed_len(self):
+        if self.Vs:
+            return PackedMCatStats.size(self.K, self.Vs)
         if self.V:
             return PackedCatStats.size(self.K, self.V)
         return PackedDiagStats.size(self.K, self.D) if self.diag else PackedStats.size(self.K, self.D)
 
     def _wrap_packed(self, buf):
+        if self.Vs:
+            return PackedMCatStats(buf, self.K, self.Vs)
         if self.V:
             return PackedCatStats(buf, self.K, self.V)
         return PackedDiagStats(buf, self.K, self.D) if self.diag else PackedStats(buf, self.K, self.D)
@@ -435,6 +470,24 @@ class HipEngine(object):
         L.check(self._lib.svihmm_set_emission_cat(self._h, K, V, L.dptr(logp)), "svihmm_set_emission_cat")
         self.V = V
         self.diag = False
+        self.Vs = None
+
+    def set_emission_mcat(self, tables):
+        """Multi-column Categorical emissions (``svihmm_set_emission_mcat``): ``tables`` is a list of D
+        arrays, ``tables[d][k, v] = E_q log theta_{k,d}[v]``; obs is ``[T, D]`` symbol indices.
+        Statistics then come back as ``PackedMCatStats``."""
+        self._pre_mutate()
+        tabs = [L.as_f64(t) for t in tables]
+        if len(tabs) < 1 or any(t.ndim != 2 or t.shape[0] != tabs[0].shape[0] for t in tabs):
+            raise RuntimeError("set_emission_mcat: tables must be a non-empty list of [K, V_d] arrays")
+        K = tabs[0].shape[0]
+        Vs = np.ascontiguousarray([t.shape[1] for t in tabs], dtype=np.int32)
+        logp = np.ascontiguousarray(np.concatenate(tabs, axis=1))
+        L.check(self._lib.svihmm_set_emission_mcat(self._h, K, len(tabs), Vs.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                   L.dptr(logp)), "svihmm_set_emission_mcat")
+        self.V = 0
+        self.diag = False
+        self.Vs = tuple(int(v) for v in Vs)
 
     def pred_logprob(self, starts, Lm, flags=L.MASK_AS_NAN):
         """Mean predictive log-probability of the masked rows of the windows and their number
@@ -638,6 +691,7 @@ class HipEngine(object):
                 "svihmm_svi_begin")
         self.K, self.V = K, 0
         self.diag = False
+        self.Vs = None
         self._svi_shape = (K, D)
         self._svi_family = "niw"
 
@@ -655,6 +709,7 @@ class HipEngine(object):
                                                 L.dptr(fb), int(maxit)), "svihmm_svi_begin_diag")
         self.K, self.V = K, 0
         self.diag = True
+        self.Vs = None
         self._svi_shape = (K, D)
         self._svi_family = "diag"
 
@@ -671,6 +726,7 @@ class HipEngine(object):
                                                L.dptr(alpha), int(maxit)), "svihmm_svi_begin_cat")
         self.K, self.V = K, V
         self.diag = False
+        self.Vs = None
         self._svi_shape = (K, V)
         self._svi_family = "cat"
 

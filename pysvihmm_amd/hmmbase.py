@@ -29,6 +29,7 @@ from scipy.special import digamma, gammaln
 from . import util
 from . import _lib as L
 from .distributions import Gaussian
+from .engine import rewrap_packed
 
 # This is for taking logs of things so we don't get -inf (reference hmmbase.py:30)
 eps = 1e-9
@@ -260,9 +261,10 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         the statistics summed over the sequences (batch transition form), ``lb = sum_s local_lb[s]``
         and ``q0 = sum_s var_x[first row of s]``.  One ``estep_sequences`` call where the engine has
         it, else one ``estep([off], len)`` per sequence with the sums formed here."""
-        if not (self._niw_fastpath() or self._diag_fastpath() or self._cat_fastpath()):
+        if not self._device_family():
             raise RuntimeError("several sequences need an emission family the device evaluates "
-                               "(NIW / diagonal Gaussian, Categorical): host lliks are not supported")
+                               "(NIW / diagonal Gaussian, Categorical, multi-column Categorical on an engine "
+                               "with set_emission_mcat): host lliks are not supported")
         self._psi_expectations()
         self._upload_obs()
         self._push_globals()
@@ -284,7 +286,7 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
             var_x[off:off + ln] = eng.read_intermediate("var_x", 1, ln)[0]
             q0 += var_x[off]
         self._seq_var_x = var_x
-        st = type(st)(total, st.K, getattr(st, "V", None) if hasattr(st, "counts") else st.D)
+        st = rewrap_packed(st, total)
         st.lb[0] = lb
         return st, lb, q0
 
@@ -293,9 +295,10 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         occurs twice counts twice): ``(stats, lb, q0)`` as ``_sequences_estep`` returns them, summed over the
         listed sequences.  One ``estep_sequence_subset`` call where the engine has it, else one
         ``estep([off], len)`` per listed sequence with the sums formed here.  No per-row attribute is set."""
-        if not (self._niw_fastpath() or self._diag_fastpath() or self._cat_fastpath()):
+        if not self._device_family():
             raise RuntimeError("several sequences need an emission family the device evaluates "
-                               "(NIW / diagonal Gaussian, Categorical): host lliks are not supported")
+                               "(NIW / diagonal Gaussian, Categorical, multi-column Categorical on an engine "
+                               "with set_emission_mcat): host lliks are not supported")
         self._psi_expectations()
         self._upload_obs()
         self._push_globals()
@@ -314,7 +317,7 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
             total = st.buf.copy() if total is None else total + st.buf
             lb += float(st.lb[0])
             q0 += eng.read_rows("var_x", 0, 1)[0]
-        st = type(st)(total, st.K, getattr(st, "V", None) if hasattr(st, "counts") else st.D)
+        st = rewrap_packed(st, total)
         st.lb[0] = lb
         return st, lb, q0
 
@@ -361,6 +364,25 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         return (all(type(e) is Categorical for e in ve)
                 and len({e.num_parameters() for e in ve}) == 1
                 and (self.obs.ndim == 1 or self.obs.shape[1] == 1))
+
+    def _mcat_fastpath(self):
+        """Multi-column Categorical emissions (``ProductCategorical``: D symbol columns, independent
+        given the state) on an engine that has the family: the device keeps the D E log theta
+        tables and counts symbols per column.  Other engines keep the host-lliks route."""
+        from .distributions import ProductCategorical
+        ve = self.var_emit
+        if not all(type(e) is ProductCategorical for e in ve) or len(ve) < 1:
+            return False
+        V = ve[0].V
+        return (all(e.V == V for e in ve)
+                and self.obs.ndim == 2 and self.obs.shape[1] == len(V)
+                and len(V) <= L.MCAT_MAX_D and sum(V) <= L.MCAT_MAX_F
+                and hasattr(self.engine, "set_emission_mcat"))
+
+    def _device_family(self):
+        """Whether the device evaluates the emitters' family itself (no host lliks)."""
+        return (self._niw_fastpath() or self._diag_fastpath() or self._cat_fastpath()
+                or self._mcat_fastpath())
 
     def _prior_arrays(self):
         """Stacked NIW prior hyperparameters (mu_0 [K,D], sigma_0 [K,D,D], kappa_0 [K], nu_0 [K]).
@@ -424,6 +446,11 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
             # looked up on the device
             table = np.stack([digamma(e.alpha_mf) - digamma(np.sum(e.alpha_mf)) for e in self.var_emit])
             self.engine.set_emission_cat(table)
+            return L.MASK_AS_NAN if nan_mask else 0
+        if self._mcat_fastpath():
+            # D symbol columns: one E log theta table [K, V_d] per column, looked up and added on the device
+            per_state = [e.expected_log_tables() for e in self.var_emit]
+            self.engine.set_emission_mcat([np.stack([t[d] for t in per_state]) for d in range(len(per_state[0]))])
             return L.MASK_AS_NAN if nan_mask else 0
         obs = self.obs if self.obs.ndim == 2 else self.obs[:, None]
         if windows is None:
@@ -542,7 +569,7 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         self._q0 = self.engine.read_rows("var_x", 0, 1)[0]
         return st
 
-    def _batch_stats_route(self, literal_global_update, families=("niw", "diag", "cat")):
+    def _batch_stats_route(self, literal_global_update, families=("niw", "diag", "cat", "mcat")):
         """Whether the host loop of a batch class (a ``local_update`` override, or
         ``infer(fused=False)``) may take the statistics of ``self.var_x`` on the device instead of
         the literal ``global_update``: only where that method is the class's own and the engine and
@@ -551,7 +578,8 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
             return False
         if not hasattr(self.engine, "suffstats"):
             return False
-        fam = {"niw": self._niw_fastpath, "diag": self._diag_fastpath, "cat": self._cat_fastpath}
+        fam = {"niw": self._niw_fastpath, "diag": self._diag_fastpath, "cat": self._cat_fastpath,
+               "mcat": self._mcat_fastpath}
         return any(fam[f]() for f in families)
 
     def _batch_suffstats(self):

@@ -128,6 +128,12 @@ class VBHMM(VariationalHMMBase):
                 G._alpha_mf = G._posterior_hypparams(st.counts[k])
                 G.weights = G._alpha_mf / G._alpha_mf.sum()
             return
+        if hasattr(st, "col_counts"):
+            # multi-column Categorical emitters: alpha_mf[d] = alphav_0[d] + the column's counts of state k
+            for k in range(self.K):
+                G = self.var_emit[k]
+                G._set_alpha(G._posterior_hypparams([c[k] for c in st.col_counts]))
+            return
         if hasattr(st, "xsq"):
             # diagonal family: meanfieldupdate(obs[inds], q[inds, k]) from (n, sum q x, sum q x^2)
             for k in range(self.K):

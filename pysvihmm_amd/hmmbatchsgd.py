@@ -11,6 +11,8 @@ import time
 import numpy as np
 
 from .hmmbase import VariationalHMMBase, is_niw_gaussian, is_diag_gaussian
+from .distributions import ProductCategorical
+from .engine import rewrap_packed
 from . import util
 
 eps = 1e-9
@@ -145,6 +147,11 @@ class VBHMM(VariationalHMMBase):
     def _natgrad_emissions(self, lrate, stats_for_k):
         for k in range(self.K):
             G = self.var_emit[k]
+            if type(G) is ProductCategorical:
+                # Dirichlet factors: the natural parameters are alpha - 1, so the blend is the blend of alpha
+                new = stats_for_k(G, k)
+                G._set_alpha([(1. - lrate) * a + lrate * b for a, b in zip(G.alpha_mf, new)])
+                continue
             if is_diag_gaussian(G):
                 # the same blend in the diagonal family's natural parameters (the reference's
                 # NIW arithmetic, util.py:28-60, has no counterpart for it)
@@ -168,7 +175,7 @@ class VBHMM(VariationalHMMBase):
         idx = np.sort(np.random.choice(n, size=self.seq_minibatch, replace=False))
         self.batchfactor = bf = n / self.seq_minibatch
         st, lb, self._q0 = self._sequence_subset_estep(idx)
-        st = type(st)(st.buf * bf, st.K, getattr(st, "V", None) if hasattr(st, "counts") else st.D)
+        st = rewrap_packed(st, st.buf * bf)
         self._lZ = bf * lb
         return st
 
@@ -183,6 +190,8 @@ class VBHMM(VariationalHMMBase):
         self.var_tran = ((1. - lrate) * nats_old + lrate * nats_t) + 1.
 
         def from_stats(G, k):
+            if hasattr(st, "col_counts"):
+                return G._posterior_hypparams([c[k] for c in st.col_counts])
             if hasattr(st, "xsq"):
                 return G._posterior_hypparams(st.neff[k], st.xbar[k], st.xsq[k])
             if not is_niw_gaussian(G):
@@ -207,6 +216,9 @@ class VBHMM(VariationalHMMBase):
         nats_t = tran_mf - 1.
         self.var_tran = ((1. - lrate) * nats_old + lrate * nats_t) + 1.
         inds = np.logical_not(self.mask)
-        self._natgrad_emissions(
-            lrate, lambda G, k: (G._posterior_hypparams(*G._get_weighted_statistics(batch[inds, :], self.var_x[inds, k]))
-                                 if is_diag_gaussian(G) else util.NIW_meanfield(G, batch[inds, :], self.var_x[inds, k])))
+        def from_rows(G, k):
+            x, w = batch[inds, :], self.var_x[inds, k]
+            if is_diag_gaussian(G) or type(G) is ProductCategorical:
+                return G._posterior_hypparams(*G._get_weighted_statistics(x, w))
+            return util.NIW_meanfield(G, x, w)
+        self._natgrad_emissions(lrate, from_rows)

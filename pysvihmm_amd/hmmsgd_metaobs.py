@@ -91,6 +91,11 @@ class VBHMM(VariationalHMMBase):
     lbeta = _lazy_window_attr("lbeta")
     var_x = _lazy_window_attr("var_x")
 
+    def _mcat_fastpath(self):
+        # the metaobs loop does not know the multi-column Categorical family: ProductCategorical emitters keep the
+        # route of every plugin it does not know (host lliks through expected_log_likelihood)
+        return False
+
     @staticmethod
     def make_param_dict(prior_init, prior_tran, prior_emit, tau=tau0,
                         kappa=kappa0, metaobs_half=metaobs_half0, mb_sz=mb_sz0,
