@@ -2,7 +2,7 @@
 // every window of a batch from ONE forward filter.  lalpha [B][Lm][K] is resident (launch_fb / the chain scan);
 // a draw walks one window backwards,
 //     z[Lm-1] ~ softmax_k lalpha[Lm-1][k],   z[t] ~ softmax_k (lalpha[t][k] + logA[k][z[t+1]]),
-// by the inverse-CDF rule of k_ffbs_paths' per-lane branch (kernels_recursion.h):  lp_k the sum above,
+// by the inverse-CDF draw every FFBS kernel shares (kernels_ffbs_draw.h):  lp_k the sum above,
 // m = max_k lp_k, p_k = exp(lp_k - m), c_k the running sum in state order, the draw the smallest k with
 // u * c_{K-1} <= c_k (K - 1 if none).
 //
@@ -26,14 +26,13 @@
 //                                 4-byte stores per step
 // At KMAX = 64 that is 33 KB + max(16 KB, one step of the wave's windows: up to 33 KB) + 9 KB: two workgroups
 // per CU, one when a wave spans 32 windows or more.
-// Registers: lp[KMAX] doubles per lane as in k_ffbs_paths (128 VGPRs at KMAX = 64; 256 VGPRs + 46 AGPRs in all,
-// one wave per SIMD, no scratch; 191 at KMAX = 32, 119 at KMAX = 16).
+// Registers: lp[KMAX] doubles per lane as in k_ffbs_paths (128 VGPRs at KMAX = 64; 256 VGPRs + 44 AGPRs in all,
+// one wave per SIMD, no scratch; 190 at KMAX = 32, 118 at KMAX = 16).
 // A step costs KMAX exps per lane: 8.7 us at KMAX = 64 on an MI355X ("FFBS for windows"),
 // 15.6 us where a wave spans 64 windows and stages 64 rows for every step; the uniform of the next step is
 // fetched (or computed: Philox) before the draw of the current one.
 //
-// 64 < K <= 256 (k_ffbs_win_wide): the three passes of k_ffbs_paths_wide's uncoupled branch (maximum, total,
-// inverse CDF) per lane; the lalpha row (same address in the lanes of one window) and the transition column
+// 64 < K <= 256 (k_ffbs_win_wide): the three passes of ffbs_draw_wide (maximum, total, inverse CDF) per lane; the lalpha row (same address in the lanes of one window) and the transition column
 // come from L2, only the z tile uses LDS.
 #pragma once
 
@@ -74,10 +73,7 @@ __global__ __launch_bounds__(64) void k_ffbs_win(
   long long* gb = (long long*)(rows + (size_t)RT * nwmax * (KMAX + 1));   // [64] output offset of the lane's path
   int* zt = (int*)(gb + 64);                                     // [64][FFW_ZT + 1]
   const int lane = threadIdx.x;
-  for (int e = lane; e < K * K; e += 64) {
-    const int k = e / K, sidx = e - k * K;
-    lAT[sidx * (KMAX + 1) + k] = logA[e];
-  }
+  ffbs_stage_logAT<KMAX>(lAT, logA, K, lane);
   const int64_t npairs = (int64_t)B * S;
   const int64_t p0 = (int64_t)blockIdx.x * 64;
   const bool valid = p0 + lane < npairs;
@@ -124,28 +120,7 @@ __global__ __launch_bounds__(64) void k_ffbs_win(
         const bool first = t == Lm - 1;                          // no transition term
         const double* rw = rows + ((size_t)(t - rlo) * nwmax + w) * (KMAX + 1);
         const double* tr = lAT + cur * (KMAX + 1);
-        // the draw of k_ffbs_paths' per-lane branch, operation for operation
-        double lp[KMAX], m = -INFINITY;
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k) {
-          lp[k] = rw[k] + ((first || k >= K) ? 0.0 : tr[k]);
-          m = fmax(m, lp[k]);
-        }
-        double tot = 0.0;
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k) { lp[k] = k < K ? exp(lp[k] - m) : 0.0; tot += lp[k]; }
-        const double thr = r * tot;
-        double c = 0.0;
-        int zz = K - 1;
-        bool found = false;
-#pragma unroll
-        for (int k = 0; k < KMAX; ++k) {
-          c += lp[k];
-          const bool hit = !found && k < K && thr <= c;
-          zz = hit ? k : zz;
-          found = found || hit;
-        }
-        cur = zz;
+        FFBS_DRAW(cur, KMAX, rw[k], tr, first, K, r);
         zt[lane * (FFW_ZT + 1) + (t - tlo)] = cur;
       }
     }
@@ -182,19 +157,7 @@ __global__ __launch_bounds__(64) void k_ffbs_win_wide(
       if (t > 0) unext = ffw_uniform(unif, seed, g0 + t - 1);
       const bool first = t == Lm - 1;
       const double* __restrict__ rw = la + ((int64_t)b * Lm + t) * K;
-      const double* __restrict__ col = logA + cur;               // logA[k][cur] = col[k * K]
-      double m = -INFINITY;
-      for (int k = 0; k < K; ++k) m = fmax(m, rw[k] + (first ? 0.0 : col[(size_t)k * K]));
-      double tot = 0.0;
-      for (int k = 0; k < K; ++k) tot += exp(rw[k] + (first ? 0.0 : col[(size_t)k * K]) - m);
-      const double thr = r * tot;
-      double c = 0.0;
-      int zz = K - 1;
-      for (int k = 0; k < K; ++k) {
-        c += exp(rw[k] + (first ? 0.0 : col[(size_t)k * K]) - m);
-        if (thr <= c) { zz = k; break; }
-      }
-      cur = zz;
+      cur = ffbs_draw_wide(rw, logA + cur, first, K, r);
       zt[lane * (FFW_ZT + 1) + (t - tlo)] = cur;
     }
     __syncthreads();

@@ -2351,10 +2351,7 @@ __global__ __launch_bounds__(64) void k_ffbs_paths(
   double* lAT = fsm;                       // [K][KMAX + 1]: lAT[s][k] = logA[k][s]
   double* row = lAT + K * (KMAX + 1);      // [2][KMAX] the lalpha row of the step
   const int lane = threadIdx.x;
-  for (int e = lane; e < K * K; e += 64) {
-    const int k = e / K, sidx = e - k * K;
-    lAT[sidx * (KMAX + 1) + k] = logA[e];
-  }
+  ffbs_stage_logAT<KMAX>(lAT, logA, K, lane);
   const int64_t lo = (int64_t)blockIdx.x * Ls;
   const int64_t hi = lo + Ls < T ? lo + Ls : T;
   int cur = lane < K ? lane : 0;           // lane s: the state at row t+1 on the path entered at s
@@ -2367,27 +2364,7 @@ __global__ __launch_bounds__(64) void k_ffbs_paths(
     if (lane < KMAX) rw[lane] = lane < K ? la[t * K + lane] : -INFINITY;
     if (!coupled) {
       const double* tr = lAT + cur * (KMAX + 1);
-      double lp[KMAX], m = -INFINITY;
-#pragma unroll
-      for (int k = 0; k < KMAX; ++k) {
-        lp[k] = rw[k] + ((first || k >= K) ? 0.0 : tr[k]);
-        m = fmax(m, lp[k]);
-      }
-      double tot = 0.0;
-#pragma unroll
-      for (int k = 0; k < KMAX; ++k) { lp[k] = k < K ? exp(lp[k] - m) : 0.0; tot += lp[k]; }
-      const double thr = r * tot;
-      double c = 0.0;
-      int zz = K - 1;
-      bool found = false;
-#pragma unroll
-      for (int k = 0; k < KMAX; ++k) {
-        c += lp[k];
-        const bool hit = !found && k < K && thr <= c;
-        zz = hit ? k : zz;
-        found = found || hit;
-      }
-      cur = zz;
+      FFBS_DRAW(cur, KMAX, rw[k], tr, first, K, r);
       const int c0 = __builtin_amdgcn_readfirstlane(cur);
       coupled = __ballot(lane < K && cur != c0) == 0ull;
     } else {
@@ -2436,19 +2413,7 @@ __global__ __launch_bounds__(256) void k_ffbs_paths_wide(
     if (tid == 0) { flag[0] = 0; }
     __syncthreads();
     if (!coupled) {
-      const double* __restrict__ col = logA + cur;    // logA[k][cur] = col[k * K]
-      double m = -INFINITY;
-      for (int k = 0; k < K; ++k) m = fmax(m, rw[k] + (first ? 0.0 : col[(size_t)k * K]));
-      double tot = 0.0;
-      for (int k = 0; k < K; ++k) tot += exp(rw[k] + (first ? 0.0 : col[(size_t)k * K]) - m);
-      const double thr = r * tot;
-      double c = 0.0;
-      int zz = K - 1;
-      for (int k = 0; k < K; ++k) {
-        c += exp(rw[k] + (first ? 0.0 : col[(size_t)k * K]) - m);
-        if (thr <= c) { zz = k; break; }
-      }
-      cur = zz;
+      cur = ffbs_draw_wide(rw, logA + cur, first, K, r);
       if (tid == 0) flag[1] = cur;
       __syncthreads();
       if (vs && cur != flag[1]) flag[0] = 1;          // benign race: any writer writes 1

@@ -17,34 +17,83 @@
 //   vit_lds_rows(64) = 1008, vit_lds_rows(256) = 240.
 // Windows up to that length keep psi in LDS and backtrack inside the forward launch; longer windows write
 // psi to HBM and are backtracked in chunks of the same length (k_vit_paths stages one chunk of psi in LDS).
+//
+// ONE body serves svihmm_viterbi (windows of equal length) and svihmm_viterbi_sequences (declared sequences of
+// unequal length): the kernels take a `Units` policy by value that says where unit u of the launch finds its rows
+// (VitWindows / VitSequences below).  The policy is a template parameter: nothing about the caller is decided at
+// run time, and the step, the tie rule and the chase exist once per width.
 #pragma once
 
 #define VIT_LDS_BUDGET 65536
 __host__ __device__ constexpr int vit_lds_rows(int KS) { return (VIT_LDS_BUDGET - 2 * KS * 8) / KS; }
 
+// What a unit of work (one workgroup of a forward launch) decodes: `len` rows of ll from row0 on, z back to the same
+// rows; psi at padded rows prow + t when it goes to HBM; the score into score[si].  zlast is indexed by the unit.
+struct VitUnit { size_t row0; int len; size_t prow; int si; };
+
+// B windows of Lm rows each, window u at rows u * Lm; padded to Lpad = Cw * Ls rows each for the chunked backtrack
+struct VitWindows {
+  int Lm;
+  int64_t Lpad;
+  template <bool LDSBT>
+  __device__ __forceinline__ VitUnit unit(int u) const {
+    return {(size_t)u * Lm, Lm, (size_t)u * Lpad, u};
+  }
+  // chunk c of the padded run = chunk cw of window u
+  __device__ __forceinline__ void chunk(int c, int Ls, int& u, int& cw) const {
+    const int Cw = (Lm + Ls - 1) / Ls;
+    u = c / Cw;
+    cw = c - u * Cw;
+  }
+};
+
+// The resident rows as N chains laid end to end (seq_off[N + 1]).  Unit u is sequence order[u] (longest first), so a
+// sequence's result never depends on what else is declared or where it lies.  Long sequences share ONE padded run of
+// chunks: pad_off[u] = prefix sum of Cw * Ls over the launch's units (read only when psi goes to HBM), and the chunk
+// table ctab[c] = (u, cw) finds a chunk's sequence.  score[s] and zlast[u] are written by the unit that owns s.
+struct VitSequences {
+  const int64_t* __restrict__ seq_off;
+  const int32_t* __restrict__ order;
+  const int64_t* __restrict__ pad_off;
+  const int32_t* __restrict__ ctab;
+  template <bool LDSBT>
+  __device__ __forceinline__ VitUnit unit(int u) const {
+    const int s = order[u];
+    const int64_t r0 = seq_off[s];
+    return {(size_t)r0, (int)(seq_off[s + 1] - r0), LDSBT ? 0 : (size_t)pad_off[u], s};
+  }
+  __device__ __forceinline__ void chunk(int c, int, int& u, int& cw) const {
+    u = ctab[2 * c];
+    cw = ctab[2 * c + 1];
+  }
+};
+
 // ------------------------------------------------------------------------------------
-//  V1: forward max-plus sweep, K <= 64: one wave per window, lane = destination state j, column j of
+//  V1: forward max-plus sweep, K <= 64: one wave per unit, lane = destination state j, column j of
 //  ltran in registers, the delta row exchanged through a double-buffered LDS row (one wave: LDS
 //  operations retire in order, a wave barrier keeps the compiler from reordering them).  The ll rows
 //  are not on the dependent chain: they are loaded U steps ahead.
 //  LDSBT: psi stays in LDS, the backtrack runs at the end of the launch and only z is written.
-//  Otherwise psi goes to HBM (rows of 64 bytes at padded row b * Lpad + t) with the final argmax in zlast.
+//  Otherwise psi goes to HBM (rows of 64 bytes at padded row prow + t) with the final argmax in zlast.
+//  The launch's dynamic LDS is sized by the longest unit it serves.
 // ------------------------------------------------------------------------------------
-template <int KMAX, bool LDSBT>
+template <int KMAX, bool LDSBT, class Units>
 __global__ __launch_bounds__(64) void k_vit_wave(
     const double* __restrict__ ll, const double* __restrict__ ltran, const double* __restrict__ mod_init,
-    int Lm, int K, int64_t Lpad, unsigned char* __restrict__ psi_g, int32_t* __restrict__ z,
+    Units units, int K, unsigned char* __restrict__ psi_g, int32_t* __restrict__ z,
     int32_t* __restrict__ zlast, double* __restrict__ score) {
   extern __shared__ __align__(16) unsigned char vit_sm[];
   double* drow = (double*)vit_sm;                    // [2][64]
   unsigned char* psiL = vit_sm + 2 * 64 * 8;         // [Lm][64] (LDSBT with z wanted)
   const int lane = threadIdx.x, b = blockIdx.x;
+  const VitUnit w = units.template unit<LDSBT>(b);
+  const int Lm = w.len;
   const bool vj = lane < K;
   const int jc = vj ? lane : 0;
   double lt[KMAX];
 #pragma unroll
   for (int i = 0; i < KMAX; ++i) lt[i] = (i < K && vj) ? ltran[(size_t)i * K + jc] : -INFINITY;
-  const double* __restrict__ lw = ll + (size_t)b * Lm * K + jc;
+  const double* __restrict__ lw = ll + w.row0 * K + jc;
   double d = vj ? mod_init[jc] + lw[0] : -INFINITY;
   drow[lane] = d;
   drow[64 + lane] = -INFINITY;
@@ -73,7 +122,7 @@ __global__ __launch_bounds__(64) void k_vit_wave(
         d = vj ? best + cur[u] : -INFINITY;
         drow[(t & 1) * 64 + lane] = d;
         if (LDSBT) { if (z) psiL[(size_t)t * 64 + lane] = (unsigned char)arg; }
-        else psi_g[((size_t)b * Lpad + t) * 64 + lane] = (unsigned char)arg;
+        else psi_g[(w.prow + t) * 64 + lane] = (unsigned char)arg;
         __builtin_amdgcn_wave_barrier();
       }
     }
@@ -83,7 +132,7 @@ __global__ __launch_bounds__(64) void k_vit_wave(
   const double m = wave_max(d);                      // (lanes >= K hold -inf)
   const unsigned long long bal = __ballot(vj && d == m);
   const int zl = bal ? __ffsll((long long)bal) - 1 : 0;
-  if (lane == 0 && score) score[b] = m;
+  if (lane == 0 && score) score[w.si] = m;
   if (!LDSBT) {
     if (lane == 0) zlast[b] = zl;
     return;
@@ -99,27 +148,29 @@ __global__ __launch_bounds__(64) void k_vit_wave(
     psiL[0] = (unsigned char)zc;
   }
   __builtin_amdgcn_wave_barrier();
-  for (int t = lane; t < Lm; t += 64) z[(size_t)b * Lm + t] = psiL[(size_t)t * 64];
+  for (int t = lane; t < Lm; t += 64) z[w.row0 + t] = psiL[(size_t)t * 64];
 }
 
 // ------------------------------------------------------------------------------------
-//  V2: forward max-plus sweep, 64 < K <= 256: one workgroup of 256 threads per window, thread =
+//  V2: forward max-plus sweep, 64 < K <= 256: one workgroup of 256 threads per unit, thread =
 //  destination state, delta row double-buffered in LDS (one barrier per step), the transition column
 //  streamed from L2 (coalesced over the threads, as k_ffbs_paths_wide reads it).  psi rows of 256 bytes.
 // ------------------------------------------------------------------------------------
-template <bool LDSBT>
+template <bool LDSBT, class Units>
 __global__ __launch_bounds__(256) void k_vit_wide(
     const double* __restrict__ ll, const double* __restrict__ ltran, const double* __restrict__ mod_init,
-    int Lm, int K, int64_t Lpad, unsigned char* __restrict__ psi_g, int32_t* __restrict__ z,
+    Units units, int K, unsigned char* __restrict__ psi_g, int32_t* __restrict__ z,
     int32_t* __restrict__ zlast, double* __restrict__ score) {
   extern __shared__ __align__(16) unsigned char vit_sm[];
   double* drow = (double*)vit_sm;                    // [2][256]
   unsigned char* psiL = vit_sm + 2 * 256 * 8;        // [Lm][256] (LDSBT with z wanted)
   const int tid = threadIdx.x, b = blockIdx.x;
+  const VitUnit w = units.template unit<LDSBT>(b);
+  const int Lm = w.len;
   const bool vj = tid < K;
   const int jc = vj ? tid : 0;
   const double* __restrict__ col = ltran + jc;       // ltran[i][j] = col[i * K]
-  const double* __restrict__ lw = ll + (size_t)b * Lm * K + jc;
+  const double* __restrict__ lw = ll + w.row0 * K + jc;
   double d = vj ? mod_init[jc] + lw[0] : -INFINITY;
   drow[tid] = d;
   double lnext = lw[(size_t)(1 < Lm ? 1 : Lm - 1) * K];
@@ -140,7 +191,7 @@ __global__ __launch_bounds__(256) void k_vit_wide(
     d = vj ? best + lcur : -INFINITY;
     drow[(t & 1) * 256 + tid] = d;
     if (LDSBT) { if (z) psiL[(size_t)t * 256 + tid] = (unsigned char)arg; }
-    else psi_g[((size_t)b * Lpad + t) * 256 + tid] = (unsigned char)arg;
+    else psi_g[(w.prow + t) * 256 + tid] = (unsigned char)arg;
     __syncthreads();
   }
   if (tid == 0) {                                    // first maximum of the final row, then the chase
@@ -148,7 +199,7 @@ __global__ __launch_bounds__(256) void k_vit_wide(
     double m = dl[0];
     int zc = 0;
     for (int j = 1; j < K; ++j) if (dl[j] > m) { m = dl[j]; zc = j; }
-    if (score) score[b] = m;
+    if (score) score[w.si] = m;
     if (!LDSBT) zlast[b] = zc;
     else if (z) {
       for (int t = Lm - 1; t >= 1; --t) {
@@ -161,32 +212,37 @@ __global__ __launch_bounds__(256) void k_vit_wide(
   }
   if (!LDSBT || !z) return;
   __syncthreads();
-  for (int t = tid; t < Lm; t += 256) z[(size_t)b * Lm + t] = psiL[(size_t)t * 256];
+  for (int t = tid; t < Lm; t += 256) z[w.row0 + t] = psiL[(size_t)t * 256];
 }
 
 // ------------------------------------------------------------------------------------
 //  V3: backtrack of long windows without a sequential pass (the FFBS scheme, K6b in kernels_recursion.h):
-//  z[t-1] = psi[t][z[t]] is a composition of maps.  Every window is cut into Cw chunks of Ls rows (the
-//  last one ragged) and stored at padded rows b * Lpad + t, Lpad = Cw * Ls, so that the chunks of all
-//  windows form one uniform sequence.
+//  z[t-1] = psi[t][z[t]] is a composition of maps.  Every unit is cut into Cw chunks of Ls rows (the
+//  last one ragged) and stored at padded rows prow + t, Cw * Ls of them, so that the chunks of all
+//  units form one uniform sequence (Units::chunk maps a chunk of that run to its unit).
 //    k_vit_paths: one workgroup of KS threads per chunk, thread = the chunk's entry state s (the state at
 //      the first row of the next chunk); path[t][s] = the state at row t.  The chunk's psi rows are staged
 //      in LDS once (coalesced), then every thread chases its own path there.  The last chunk of a window
 //      starts from the argmax of the final delta for every entry: its map is constant, so
-//    k_ffbs_compose, run unchanged over the B * Cw chunks, never carries anything across a window boundary;
-//    k_vit_gather: z[b][t] = path[t][entry of t's chunk], int32, back in the unpadded order.
+//    k_ffbs_compose, run unchanged over all the chunks, never carries anything across a unit's boundary;
+//    k_vit_gather: z[b][t] = path[t][entry of t's chunk], int32, back in the unpadded order (a thread per row of
+//      the windows; the ragged form, a workgroup per chunk, is k_vitseq_gather in kernels_decode_sequences.h).
 // ------------------------------------------------------------------------------------
+template <class Units>
 __global__ __launch_bounds__(256) void k_vit_paths(
-    const unsigned char* __restrict__ psi, const int32_t* __restrict__ zlast, int Lm, int Ls, int Cw,
-    int64_t Lpad, int KS, int K, unsigned char* __restrict__ path) {
+    const unsigned char* __restrict__ psi, const int32_t* __restrict__ zlast, Units units, int Ls, int KS, int K,
+    unsigned char* __restrict__ path) {
   extern __shared__ __align__(16) unsigned char vit_ps[];     // [Ls][KS]: row r = psi row lo + 1 + r
   const int tid = threadIdx.x;
-  const int c = blockIdx.x, b = c / Cw, cw = c - b * Cw;
+  int b, cw;
+  units.chunk(blockIdx.x, Ls, b, cw);
+  const VitUnit w = units.template unit<false>(b);
+  const int Lm = w.len, Cw = (Lm + Ls - 1) / Ls;
   const int lo = cw * Ls;
   const bool last = cw == Cw - 1;
   const int hi = last ? Lm : lo + Ls;                          // the chunk's rows: lo .. hi - 1
   const int nst = (last ? Lm - 1 : hi) - lo;                   // psi rows lo + 1 .. lo + nst
-  const size_t row0 = (size_t)b * Lpad + lo;
+  const size_t row0 = w.prow + lo;
   const unsigned char* __restrict__ src = psi + (row0 + 1) * KS;
   const int nvec = nst * (KS / 16);
   for (int e = tid; e < nvec; e += KS) ((uint4*)vit_ps)[e] = ((const uint4*)src)[e];

@@ -129,11 +129,29 @@ int svihmm_set_precision(svihmm_ctx* h, int32_t mode) {
   h->prec = mode;
   return 0;
 }
+// whether the last E-step batch ran in fp32: a value held over calls that are no E-step batch, else the live flags
+static int f32_report(const svihmm_ctx* h) {
+  return h->f32_report_hold >= 0 ? h->f32_report_hold : (h->cur_f32 || h->eh_float) ? 1 : 0;
+}
+// Holds that report over a pass that is not an E-step batch of the caller's, on every path out of the scope.
+// internal: the pass addresses declared sequences' rows as windows of its own (seq_internal lifts the boundary
+// check); fp64: the precision mode is set aside for the pass.
+struct ReportHold {
+  svihmm_ctx* h; int report, prec; bool internal;
+  ReportHold(svihmm_ctx* h_, bool internal_, bool fp64) : h(h_), report(f32_report(h_)), prec(h_->prec), internal(internal_) {
+    if (internal) h->seq_internal = true;
+    if (fp64) h->prec = 0;
+  }
+  ~ReportHold() {
+    if (internal) h->seq_internal = false;
+    h->prec = prec;
+    h->f32_report_hold = report;
+  }
+};
 int svihmm_get_precision(svihmm_ctx* h, int32_t* mode_out, int32_t* last_batch_f32_out) {
   if (!h) return fail("svihmm_get_precision: NULL handle");
   if (mode_out) *mode_out = h->prec;
-  if (last_batch_f32_out)
-    *last_batch_f32_out = h->f32_report_hold >= 0 ? h->f32_report_hold : (h->cur_f32 || h->eh_float) ? 1 : 0;
+  if (last_batch_f32_out) *last_batch_f32_out = f32_report(h);
   return 0;
 }
 int svihmm_sync(svihmm_ctx* h) {
@@ -1546,19 +1564,44 @@ static int estep_sequences_core(svihmm_ctx* h, uint32_t flags, bool subset = fal
 // estep_sequences_core always in fp64, the precision mode's report about the last E-step batch held (as
 // svihmm_grow_windows), then the packed result's host-visible mirror
 static int estep_sequences_fp64(svihmm_ctx* h, uint32_t flags, bool subset) {
-  const int report = h->f32_report_hold >= 0 ? h->f32_report_hold : (h->cur_f32 || h->eh_float) ? 1 : 0;
-  const int prec = h->prec;
-  h->prec = 0;
-  h->seq_internal = true;
-  const int rc = estep_sequences_core(h, flags, subset);
-  h->seq_internal = false;
-  h->prec = prec;
+  int rc;
+  {
+    ReportHold hold(h, true, true);
+    rc = estep_sequences_core(h, flags, subset);
+  }
   h->cur_f32 = false; h->eh_float = false;
-  h->f32_report_hold = report;
   if (rc) return rc;
   h->have_packed = true;
   h->mirror_valid = false;
   return launch_mirror(h);
+}
+
+// What svihmm_estep_sequences and svihmm_estep_sequence_subset share, found before any device work:
+// what can be wrong with the model ...
+static int check_estep_sequences(const svihmm_ctx* h, const char* fn, uint32_t flags) {
+  const auto bad = [fn](const std::string& what) { return fail(std::string(fn) + ": " + what); };
+  if (flags & SVIHMM_USE_HOST_LLIKS) return bad("SVIHMM_USE_HOST_LLIKS is not supported (host lliks carry no sequence offsets)");
+  if (!h->have_globals) return bad("no globals: call svihmm_set_globals first");
+  CK(check_window_model(h, fn));
+  if (h->K > 256) return bad("K = " + std::to_string(h->K) + " > 256 not supported");
+  return 0;
+}
+// ... the statistics pass addressing the call's R rows as one window (launch_stats_posteriors' limit; `rows`: their
+// name in the message) ...
+static int check_stats_rows(const svihmm_ctx* h, const char* fn, int64_t R, const std::string& rows) {
+  const int64_t rpc = h->emis_cat ? 0 : stats_plan(h, R, h->variant[SVIHMM_VAR_STATS_CHUNKS]).rpc;
+  if (R > 0x7fffffff || (R + rpc) * (int64_t)(h->emis_cat ? 1 : h->Kp) >= ((int64_t)1 << 31))
+    return fail(std::string(fn) + ": " + rows + " are too many for the statistics GEMM's 32-bit row offsets");
+  return 0;
+}
+// ... and the results of the M sequences the E-step ran over
+static int read_estep_sequences(svihmm_ctx* h, int M, double* out_packed, double* out_seq_lb, double* out_q0) {
+  if (out_seq_lb) CK(d2h(h, out_seq_lb, h->seq_out.p, (size_t)M * sizeof(double)));
+  if (out_q0) CK(d2h(h, out_q0, (const double*)h->seq_out.p + M, (size_t)h->K * sizeof(double)));
+  if (out_packed) CK(read_packed_host(h, out_packed));
+  HIPCK(hipStreamSynchronize(h->stream));
+  CK(check_emission_status(h));
+  return 0;
 }
 
 int svihmm_estep_sequences(svihmm_ctx* h, uint32_t flags, double* out_packed, double* out_seq_lb, double* out_q0) {
@@ -1566,26 +1609,12 @@ int svihmm_estep_sequences(svihmm_ctx* h, uint32_t flags, double* out_packed, do
   const auto bad = [fn](const std::string& what) { return fail(std::string(fn) + ": " + what); };
   if (!h) return bad("NULL handle");
   if (h->seq_off.empty()) return bad("no sequences declared: call svihmm_set_sequences first");
-  if (flags & SVIHMM_USE_HOST_LLIKS) return bad("SVIHMM_USE_HOST_LLIKS is not supported (host lliks carry no sequence offsets)");
-  if (!h->have_globals) return bad("no globals: call svihmm_set_globals first");
-  CK(check_window_model(h, fn));
-  if (h->K > 256) return bad("K = " + std::to_string(h->K) + " > 256 not supported");
-  {
-    // (the statistics pass addresses the T rows as one window: launch_stats_posteriors' limit, before any device work)
-    const int64_t rpc = h->emis_cat ? 0 : stats_plan(h, h->T, h->variant[SVIHMM_VAR_STATS_CHUNKS]).rpc;
-    if (h->T > 0x7fffffff || (h->T + rpc) * (int64_t)(h->emis_cat ? 1 : h->Kp) >= ((int64_t)1 << 31))
-      return bad("T = " + std::to_string(h->T) + " rows are too many for the statistics GEMM's 32-bit row offsets");
-  }
+  CK(check_estep_sequences(h, fn, flags));
+  CK(check_stats_rows(h, fn, h->T, "T = " + std::to_string(h->T) + " rows"));
   CK(set_device(h));
   CK(wait_side_streams(h));
   CK(estep_sequences_fp64(h, flags, false));
-  const int N = (int)h->seq_off.size() - 1;
-  if (out_seq_lb) CK(d2h(h, out_seq_lb, h->seq_out.p, (size_t)N * sizeof(double)));
-  if (out_q0) CK(d2h(h, out_q0, (const double*)h->seq_out.p + N, (size_t)h->K * sizeof(double)));
-  if (out_packed) CK(read_packed_host(h, out_packed));
-  HIPCK(hipStreamSynchronize(h->stream));
-  CK(check_emission_status(h));
-  return 0;
+  return read_estep_sequences(h, (int)h->seq_off.size() - 1, out_packed, out_seq_lb, out_q0);
 }
 
 // ---- a minibatch of whole sequences (svihmm_estep_sequence_subset) ------------------------------
@@ -1631,16 +1660,8 @@ int svihmm_estep_sequence_subset(svihmm_ctx* h, const int32_t* idx, int32_t M, u
     maxlen = std::max(maxlen, so[s + 1] - so[s]);
   }
   tab[M] = R;
-  if (flags & SVIHMM_USE_HOST_LLIKS) return bad("SVIHMM_USE_HOST_LLIKS is not supported (host lliks carry no sequence offsets)");
-  if (!h->have_globals) return bad("no globals: call svihmm_set_globals first");
-  CK(check_window_model(h, fn));
-  if (h->K > 256) return bad("K = " + std::to_string(h->K) + " > 256 not supported");
-  {
-    // (the statistics pass addresses the R listed rows as one window: svihmm_estep_sequences' check on T)
-    const int64_t rpc = h->emis_cat ? 0 : stats_plan(h, R, h->variant[SVIHMM_VAR_STATS_CHUNKS]).rpc;
-    if (R > 0x7fffffff || (R + rpc) * (int64_t)(h->emis_cat ? 1 : h->Kp) >= ((int64_t)1 << 31))
-      return bad("R = " + std::to_string(R) + " listed rows are too many for the statistics GEMM's 32-bit row offsets");
-  }
+  CK(check_estep_sequences(h, fn, flags));
+  CK(check_stats_rows(h, fn, R, "R = " + std::to_string(R) + " listed rows"));
   CK(set_device(h));
   CK(wait_side_streams(h));
   // the resident copy's lazily applied state first: symbol indices go back to exact integers before they are copied
@@ -1657,12 +1678,7 @@ int svihmm_estep_sequence_subset(svihmm_ctx* h, const int32_t* idx, int32_t M, u
     SubsetView view(h, R, compact);
     CK(estep_sequences_fp64(h, flags, true));
   }
-  if (out_seq_lb) CK(d2h(h, out_seq_lb, h->seq_out.p, (size_t)M * sizeof(double)));
-  if (out_q0) CK(d2h(h, out_q0, (const double*)h->seq_out.p + M, (size_t)h->K * sizeof(double)));
-  if (out_packed) CK(read_packed_host(h, out_packed));
-  HIPCK(hipStreamSynchronize(h->stream));
-  CK(check_emission_status(h));
-  return 0;
+  return read_estep_sequences(h, M, out_packed, out_seq_lb, out_q0);
 }
 
 // ---- device-resident SVI loop (hmmsgd_metaobs.py:347-445) ------------------------------------
@@ -2571,6 +2587,20 @@ int svihmm_viterbi(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t Lm, 
 // ---- FFBS for window batches x draws (kernels_ffbs_windows.h) ---------------------------------
 // Everything that can be wrong with the call is found here, before any device work; the filter and the draws
 // are launch_ffbs_windows' (tu_recursion.hip).
+// logA[k][z_next]: -inf is probability zero; every column needs one finite entry to draw from
+static int check_logA(const char* fn, const double* logA, int K) {
+  const auto bad = [fn](const std::string& what) { return fail(std::string(fn) + ": " + what); };
+  for (int j = 0; j < K; ++j) {
+    bool any = false;
+    for (int k = 0; k < K; ++k) {
+      const double v = logA[(size_t)k * K + j];
+      if (v != v || v == INFINITY) return bad("logA[" + std::to_string(k) + "][" + std::to_string(j) + "] is NaN or +inf");
+      any = any || v > -INFINITY;
+    }
+    if (!any) return bad("column " + std::to_string(j) + " of logA has no finite entry");
+  }
+  return 0;
+}
 int svihmm_ffbs_windows(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t Lm, uint32_t flags,
                         const double* logA, int32_t S, const double* uniforms, uint64_t seed,
                         int32_t* out_z, double* out_lalpha) {
@@ -2582,27 +2612,16 @@ int svihmm_ffbs_windows(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t
   const int K = h->K;
   if (K > 256) return fail("svihmm_ffbs_windows: K = " + std::to_string(K) + " > 256 not supported");
   CK(check_window_call(h, "svihmm_ffbs_windows", starts, B, Lm, flags));
-  // logA[k][z_next]: -inf is probability zero; every column needs one finite entry to draw from
-  for (int j = 0; j < K; ++j) {
-    bool any = false;
-    for (int k = 0; k < K; ++k) {
-      const double v = logA[(size_t)k * K + j];
-      if (v != v || v == INFINITY)
-        return fail("svihmm_ffbs_windows: logA[" + std::to_string(k) + "][" + std::to_string(j) + "] is NaN or +inf");
-      any = any || v > -INFINITY;
-    }
-    if (!any) return fail("svihmm_ffbs_windows: column " + std::to_string(j) + " of logA has no finite entry");
-  }
+  CK(check_logA("svihmm_ffbs_windows", logA, K));
   CK(set_device(h));
   CK(wait_side_streams(h));
   int32_t* dz = nullptr;
   const double* dla = nullptr;
-  // (not an E-step batch: what svihmm_get_precision reports about the last one stays)
-  const int report = h->f32_report_hold >= 0 ? h->f32_report_hold : (h->cur_f32 || h->eh_float) ? 1 : 0;
-  const int rc = launch_ffbs_windows(h, starts, B, Lm, flags & (SVIHMM_MASK_AS_NAN | SVIHMM_USE_HOST_LLIKS), logA, S,
-                                     uniforms, seed, out_lalpha != nullptr, &dz, &dla);
-  h->f32_report_hold = report;
-  if (rc) return rc;
+  {
+    ReportHold hold(h, false, false);
+    CK(launch_ffbs_windows(h, starts, B, Lm, flags & (SVIHMM_MASK_AS_NAN | SVIHMM_USE_HOST_LLIKS), logA, S, uniforms,
+                           seed, out_lalpha != nullptr, &dz, &dla));
+  }
   CK(d2h(h, out_z, dz, (size_t)S * B * Lm * sizeof(int32_t)));
   if (out_lalpha) CK(d2h(h, out_lalpha, dla, (size_t)B * Lm * K * sizeof(double)));
   HIPCK(hipStreamSynchronize(h->stream));
@@ -2641,13 +2660,10 @@ int svihmm_viterbi_sequences(svihmm_ctx* h, uint32_t flags, int32_t* out_z, doub
   CK(wait_side_streams(h));
   const int N = (int)h->seq_off.size() - 1;
   const int64_t T = h->T, st0 = 0;
-  // (not an E-step batch: what svihmm_get_precision reports about the last one stays)
-  const int report = h->f32_report_hold >= 0 ? h->f32_report_hold : (h->cur_f32 || h->eh_float) ? 1 : 0;
-  h->seq_internal = true;
-  int rc = prepare_ll(h, &st0, 1, (int)T, flags & (SVIHMM_MASK_AS_NAN | SVIHMM_USE_HOST_LLIKS), false);
-  h->seq_internal = false;
-  h->f32_report_hold = report;
-  if (rc) return rc;
+  {
+    ReportHold hold(h, true, false);
+    CK(prepare_ll(h, &st0, 1, (int)T, flags & (SVIHMM_MASK_AS_NAN | SVIHMM_USE_HOST_LLIKS), false));
+  }
   h->lastB = 1; h->lastLm = (int)T;
   h->dec_result = 1;
   int32_t* dz = nullptr;
@@ -2669,29 +2685,17 @@ int svihmm_ffbs_sequences(svihmm_ctx* h, uint32_t flags, const double* logA, int
   CK(check_decode_sequences(h, fn, flags));
   const int K = h->K, N = (int)h->seq_off.size() - 1;
   if ((int64_t)S * N >= ((int64_t)1 << 31)) return fail("svihmm_ffbs_sequences: S * N too large");
-  // logA[k][z_next]: -inf is probability zero; every column needs one finite entry to draw from
-  for (int j = 0; j < K; ++j) {
-    bool any = false;
-    for (int k = 0; k < K; ++k) {
-      const double v = logA[(size_t)k * K + j];
-      if (v != v || v == INFINITY)
-        return fail("svihmm_ffbs_sequences: logA[" + std::to_string(k) + "][" + std::to_string(j) + "] is NaN or +inf");
-      any = any || v > -INFINITY;
-    }
-    if (!any) return fail("svihmm_ffbs_sequences: column " + std::to_string(j) + " of logA has no finite entry");
-  }
+  CK(check_logA("svihmm_ffbs_sequences", logA, K));
   CK(set_device(h));
   CK(wait_side_streams(h));
   const int64_t T = h->T;
   int32_t* dz = nullptr;
   const double* dla = nullptr;
-  const int report = h->f32_report_hold >= 0 ? h->f32_report_hold : (h->cur_f32 || h->eh_float) ? 1 : 0;
-  h->seq_internal = true;
-  const int rc = launch_ffbs_sequences(h, flags & (SVIHMM_MASK_AS_NAN | SVIHMM_USE_HOST_LLIKS), logA, S, uniforms, seed,
-                                       out_lalpha != nullptr, &dz, &dla);
-  h->seq_internal = false;
-  h->f32_report_hold = report;
-  if (rc) return rc;
+  {
+    ReportHold hold(h, true, false);
+    CK(launch_ffbs_sequences(h, flags & (SVIHMM_MASK_AS_NAN | SVIHMM_USE_HOST_LLIKS), logA, S, uniforms, seed,
+                             out_lalpha != nullptr, &dz, &dla));
+  }
   h->dec_result = 2;
   CK(d2h(h, out_z, dz, (size_t)S * T * sizeof(int32_t)));
   if (out_lalpha) CK(d2h(h, out_lalpha, dla, (size_t)T * K * sizeof(double)));
@@ -2819,20 +2823,15 @@ int svihmm_grow_windows(svihmm_ctx* h, const int64_t* centers, int32_t n, int32_
   const bool products = method == SVIHMM_GROW_PRODUCTS || (method == SVIHMM_GROW_AUTO && products_ok);
   CK(set_device(h));
   CK(wait_side_streams(h));
-  // always fp64, and not an E-step batch: the precision mode is set aside for the call and what
-  // svihmm_get_precision reports about the last E-step batch stays
-  const int report = h->f32_report_hold >= 0 ? h->f32_report_hold : (h->cur_f32 || h->eh_float) ? 1 : 0;
-  const int prec = h->prec;
-  h->prec = 0;
   const uint32_t fl = flags & SVIHMM_MASK_AS_NAN;
   const int cap = out_trace ? trace_cap : 0;
-  const int rc = products ? grow_products(h, centers, n, half0, probe_off, increment, cutoff, epsilon, rule, fl, cap,
-                                          out_half, out_steps, out_trace)
-                          : grow_literal(h, centers, n, half0, probe_off, increment, cutoff, epsilon, rule, fl, cap,
-                                         out_half, out_steps, out_trace);
-  h->prec = prec;
-  h->f32_report_hold = report;
-  if (rc) return rc;
+  {
+    ReportHold hold(h, false, true);   // always fp64
+    CK(products ? grow_products(h, centers, n, half0, probe_off, increment, cutoff, epsilon, rule, fl, cap, out_half,
+                                out_steps, out_trace)
+                : grow_literal(h, centers, n, half0, probe_off, increment, cutoff, epsilon, rule, fl, cap, out_half,
+                               out_steps, out_trace));
+  }
   CK(check_emission_status(h));
   return 0;
 }

@@ -3,12 +3,32 @@
 #include <algorithm>
 #include "host.h"
 #include "device_helpers.h"
+#include "kernels_ffbs_draw.h"
 #include "kernels_recursion.h"
 #include "kernels_viterbi.h"
 #include "kernels_ffbs_windows.h"
 #include "kernels_grow.h"
 #include "kernels_sequences.h"
 #include "kernels_decode_sequences.h"
+
+// The Viterbi forward sweep of n units addressed by `units` (kernels_viterbi.h: VitWindows / VitSequences): the one
+// dispatch on the model's width.  LDSBT: psi in LDS, the launch writes z itself (z null: score only); otherwise psi
+// goes to HBM and unit u's final argmax to zlast[u].  lds: the launch's dynamic LDS, sized by its longest unit.
+template <bool LDSBT, class Units>
+static void vit_sweep(svihmm_ctx* h, unsigned n, size_t lds, const double* ll, const Units& units, unsigned char* psi,
+                      int32_t* z, int32_t* zlast, double* score) {
+  const int K = h->K;
+  const double* lt = (const double*)h->ltran.p;
+  const double* mi = (const double*)h->mod_init.p;
+#define VITW(KM)                                                                                                   \
+  hipLaunchKernelGGL((k_vit_wave<KM, LDSBT, Units>), dim3(n), dim3(64), lds, h->stream, ll, lt, mi, units, K, psi, \
+                     z, zlast, score)
+  if (K <= 16) VITW(16); else if (K <= 32) VITW(32); else if (K <= 64) VITW(64);
+  else
+    hipLaunchKernelGGL((k_vit_wide<LDSBT, Units>), dim3(n), dim3(256), lds, h->stream, ll, lt, mi, units, K, psi, z,
+                       zlast, score);
+#undef VITW
+}
 
 extern "C" {
 
@@ -789,12 +809,57 @@ int svihmm_ffbs(svihmm_ctx* h, const double* logA, const double* uniforms, uint3
   return 0;
 }
 
+// The device inputs and output of the window / sequence samplers in h->vit: logA | z int32 [n] | the caller's
+// uniforms [n] (null: Philox), n = draws x rows; logA and the uniforms are uploaded here.
+struct FfbsIo { double* logA; int32_t* z; double* unif; };
+static int ffbs_io(svihmm_ctx* h, const double* logA, const double* uniforms, size_t n, FfbsIo* io) {
+  const int K = h->K;
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t o_z = up((size_t)K * K * sizeof(double)), o_u = o_z + up(n * sizeof(int32_t));
+  CK(ensure(h->vit, o_u + (uniforms ? n * sizeof(double) : 0) + 256));
+  char* base = (char*)h->vit.p;
+  io->logA = (double*)base;
+  io->z = (int32_t*)(base + o_z);
+  io->unif = uniforms ? (double*)(base + o_u) : nullptr;
+  HIPCK(hipMemcpyAsync(io->logA, logA, (size_t)K * K * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (uniforms) HIPCK(hipMemcpyAsync(io->unif, uniforms, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  return 0;
+}
+// Long windows / sequences: the blocked composition of ffbs_launch once per (unit, draw).  The per-draw scratch in
+// h->scratch = (Philox: uniforms [maxlen]) | z int64 [maxlen] | path, chunk maps is reused by every draw.
+// ffbs_blocked_draw: the path of `len` rows from the unit's lalpha rows `la` into io.z[g0 ..]; its uniforms are
+// entries g0 .. of the caller's, or of the Philox stream.
+struct FfbsBlockedScratch { double* unif; int64_t* z; unsigned char* path; };
+static int ffbs_blocked_scratch(svihmm_ctx* h, const FfbsIo& io, int64_t maxlen, size_t extra, FfbsBlockedScratch* sc) {
+  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t o_zl = io.unif ? 0 : up((size_t)maxlen * sizeof(double));
+  const size_t o_path = o_zl + up((size_t)maxlen * sizeof(int64_t));
+  CK(ensure(h->scratch, o_path + extra));
+  char* sb = (char*)h->scratch.p;
+  sc->unif = (double*)sb;
+  sc->z = (int64_t*)(sb + o_zl);
+  sc->path = (unsigned char*)(sb + o_path);
+  return 0;
+}
+static int ffbs_blocked_draw(svihmm_ctx* h, const FfbsIo& io, const FfbsBlockedScratch& sc, uint64_t seed,
+                             const double* la, int64_t len, int64_t g0) {
+  const unsigned nb256 = (unsigned)((len + 255) / 256);
+  if (!io.unif) {
+    ProfScope ps(h, KS_FFBS);
+    hipLaunchKernelGGL(k_ffw_fill_uniforms, dim3(nb256), dim3(256), 0, h->stream, (unsigned long long)seed, g0, len,
+                       sc.unif);
+  }
+  CK(ffbs_launch(h, ffbs_plan(h, len, h->K), la, len, h->K, io.logA, io.unif ? io.unif + g0 : sc.unif, sc.z, sc.path));
+  ProfScope ps(h, KS_FFBS);
+  hipLaunchKernelGGL(k_ffw_store_path, dim3(nb256), dim3(256), 0, h->stream, (const int64_t*)sc.z, len, io.z + g0);
+  return 0;
+}
+
 // svihmm_ffbs_windows: one forward filter over the windows (ffbs_filter), then S backward draws of every window
 // from the resident lalpha.  Windows below FFW_SWITCH rows: one launch, a lane per (window, draw) pair
-// (kernels_ffbs_windows.h).  Longer ones -- the whole chain included -- run the blocked composition of ffbs_launch
-// once per (window, draw) on la + b Lm K; the path / chunk-map scratch is reused by every draw.
-// h->vit: logA | z int32 [S][B][Lm] | the caller's uniforms [S][B][Lm]; nothing scales with S T K.
-// *dz_out / *dla_out (lalpha [B][Lm][K]) stay valid until the next call.
+// (kernels_ffbs_windows.h).  Longer ones -- the whole chain included -- run the blocked composition once per
+// (window, draw) on la + b Lm K (ffbs_blocked_draw).  Nothing scales with S T K.
+// *dz_out (int32 [S][B][Lm]) / *dla_out (lalpha [B][Lm][K]) stay valid until the next call.
 int launch_ffbs_windows(svihmm_ctx* h, const int64_t* starts, int B, int Lm, uint32_t flags, const double* logA,
                         int S, const double* uniforms, uint64_t seed, bool want_lalpha, int32_t** dz_out,
                         const double** dla_out) {
@@ -805,17 +870,9 @@ int launch_ffbs_windows(svihmm_ctx* h, const int64_t* starts, int B, int Lm, uin
   CK(ffbs_filter(h, starts, B, Lm, flags, want_lalpha, &la));
   h->have_lb = false;
   h->lastB = B; h->lastLm = Lm;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t n = (size_t)S * B * Lm;
-  const size_t o_z = up((size_t)K * K * sizeof(double)), o_u = o_z + up(n * sizeof(int32_t));
-  CK(ensure(h->vit, o_u + (uniforms ? n * sizeof(double) : 0) + 256));
-  char* base = (char*)h->vit.p;
-  double* dlogA = (double*)base;
-  int32_t* dz = (int32_t*)(base + o_z);
-  double* dun = uniforms ? (double*)(base + o_u) : nullptr;
-  HIPCK(hipMemcpyAsync(dlogA, logA, (size_t)K * K * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (uniforms) HIPCK(hipMemcpyAsync(dun, uniforms, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  *dz_out = dz;
+  FfbsIo io;
+  CK(ffbs_io(h, logA, uniforms, (size_t)S * B * Lm, &io));
+  *dz_out = io.z;
   *dla_out = la;
   if (Lm < FFW_SWITCH) {
     const unsigned nblk = (unsigned)(((int64_t)B * S + 63) / 64);
@@ -828,40 +885,23 @@ int launch_ffbs_windows(svihmm_ctx* h, const int64_t* starts, int B, int Lm, uin
   do {                                                                                                              \
     if (lds > 64 * 1024)                                                                                            \
       hipFuncSetAttribute((const void*)k_ffbs_win<KMAX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);     \
-    hipLaunchKernelGGL(k_ffbs_win<KMAX>, dim3(nblk), dim3(64), lds, h->stream, la, (const double*)dlogA,            \
-                       (const double*)dun, (unsigned long long)seed, B, S, Lm, K, nwmax, RT, dz);                   \
+    hipLaunchKernelGGL(k_ffbs_win<KMAX>, dim3(nblk), dim3(64), lds, h->stream, la, (const double*)io.logA,          \
+                       (const double*)io.unif, (unsigned long long)seed, B, S, Lm, K, nwmax, RT, io.z);             \
   } while (0)
       if (KM == 16) FWIN(16); else if (KM == 32) FWIN(32); else FWIN(64);
 #undef FWIN
     } else {
-      hipLaunchKernelGGL(k_ffbs_win_wide, dim3(nblk), dim3(64), 0, h->stream, la, (const double*)dlogA,
-                         (const double*)dun, (unsigned long long)seed, B, S, Lm, K, dz);
+      hipLaunchKernelGGL(k_ffbs_win_wide, dim3(nblk), dim3(64), 0, h->stream, la, (const double*)io.logA,
+                         (const double*)io.unif, (unsigned long long)seed, B, S, Lm, K, io.z);
     }
     HIPCK(hipGetLastError());
     return 0;
   }
-  // long windows: per-draw scratch in h->scratch = (Philox: uniforms [Lm]) | z int64 [Lm] | path, chunk maps
-  const FfbsPlan pl = ffbs_plan(h, Lm, K);
-  const size_t o_zl = uniforms ? 0 : up((size_t)Lm * sizeof(double));
-  const size_t o_path = o_zl + up((size_t)Lm * sizeof(int64_t));
-  CK(ensure(h->scratch, o_path + pl.extra));
-  char* sb = (char*)h->scratch.p;
-  int64_t* dzl = (int64_t*)(sb + o_zl);
-  const unsigned nb256 = (unsigned)((Lm + 255) / 256);
+  FfbsBlockedScratch sc;
+  CK(ffbs_blocked_scratch(h, io, Lm, ffbs_plan(h, Lm, K).extra, &sc));
   for (int s = 0; s < S; ++s)
-    for (int b = 0; b < B; ++b) {
-      const int64_t g0 = ((int64_t)s * B + b) * Lm;
-      const double* du = dun ? dun + g0 : (const double*)sb;
-      if (!dun) {
-        ProfScope ps(h, KS_FFBS);
-        hipLaunchKernelGGL(k_ffw_fill_uniforms, dim3(nb256), dim3(256), 0, h->stream, (unsigned long long)seed, g0,
-                           (int64_t)Lm, (double*)sb);
-      }
-      CK(ffbs_launch(h, pl, la + (size_t)b * Lm * K, Lm, K, dlogA, du, dzl, (unsigned char*)(sb + o_path)));
-      ProfScope ps(h, KS_FFBS);
-      hipLaunchKernelGGL(k_ffw_store_path, dim3(nb256), dim3(256), 0, h->stream, (const int64_t*)dzl, (int64_t)Lm,
-                         dz + g0);
-    }
+    for (int b = 0; b < B; ++b)
+      CK(ffbs_blocked_draw(h, io, sc, seed, la + (size_t)b * Lm * K, Lm, ((int64_t)s * B + b) * Lm));
   HIPCK(hipGetLastError());
   return 0;
 }
@@ -884,6 +924,30 @@ int svihmm_ffbs_sample(svihmm_ctx* h, int64_t T, int32_t K, const double* lalpha
   return 0;
 }
 
+// h->vit of the Viterbi launchers: score [nscore] | z int32 [nz] | final argmax [nlast] | psi | path (P padded rows of
+// KS bytes each) | chunk maps mA, mB [C][KS] | entry [C].  P = C = 0 when every unit backtracks inside its launch.
+struct VitScratch { double* score; int32_t *z, *zlast; unsigned char *psi, *path, *mA, *mB, *entry; };
+static int vit_scratch(svihmm_ctx* h, size_t nscore, size_t nz, size_t nlast, int64_t P, int64_t C, int KS,
+                       VitScratch* v) {
+  size_t o = 0;
+  auto take = [&o](size_t bytes) { const size_t at = o; o += (bytes + 255) & ~(size_t)255; return at; };
+  const size_t o_score = take(nscore * sizeof(double)), o_z = take(nz * sizeof(int32_t));
+  const size_t o_zlast = take(nlast * sizeof(int32_t));
+  const size_t o_psi = take((size_t)P * KS), o_path = take((size_t)P * KS);
+  const size_t o_mA = take((size_t)C * KS), o_mB = take((size_t)C * KS), o_entry = take((size_t)C);
+  CK(ensure(h->vit, o + 256));
+  char* base = (char*)h->vit.p;
+  v->score = (double*)(base + o_score);
+  v->z = (int32_t*)(base + o_z);
+  v->zlast = (int32_t*)(base + o_zlast);
+  v->psi = (unsigned char*)(base + o_psi);
+  v->path = (unsigned char*)(base + o_path);
+  v->mA = (unsigned char*)(base + o_mA);
+  v->mB = (unsigned char*)(base + o_mB);
+  v->entry = (unsigned char*)(base + o_entry);
+  return 0;
+}
+
 // svihmm_viterbi: max-plus forward sweep + backtrack over the lliks ll [B*Lm, K] with the globals currently set.
 // Windows whose psi fits the LDS budget (kernels_viterbi.h: Lm <= vit_lds_rows(KS)) are decoded in one launch;
 // longer ones write psi to HBM and backtrack by composing chunk maps (k_vit_paths, k_ffbs_compose, k_vit_gather).
@@ -899,55 +963,24 @@ int launch_viterbi(svihmm_ctx* h, int B, int Lm, const double* ll, bool want_z, 
   const int64_t Lpad = (int64_t)Cw * Ls;
   const int64_t C = (int64_t)B * Cw;
   if (!in_lds && C * KS >= ((int64_t)1 << 31)) return fail("svihmm_viterbi: too many row chunks for the map composition");
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
   const size_t n = (size_t)B * Lm;
-  const size_t o_score = 0, o_z = up((size_t)B * sizeof(double)), o_zlast = o_z + up(n * sizeof(int32_t));
-  const size_t o_psi = o_zlast + up((size_t)B * sizeof(int32_t));
-  const size_t nps = in_lds ? 0 : up((size_t)B * Lpad * KS);
-  const size_t o_path = o_psi + nps, o_mA = o_path + nps;
-  const size_t nmap = in_lds ? 0 : up((size_t)C * KS);
-  const size_t o_mB = o_mA + nmap, o_entry = o_mB + nmap;
-  CK(ensure(h->vit, o_entry + (in_lds ? 0 : up((size_t)C)) + 256));
-  char* base = (char*)h->vit.p;
-  double* dscore = (double*)(base + o_score);
-  int32_t* dz = (int32_t*)(base + o_z);
-  int32_t* zlast = (int32_t*)(base + o_zlast);
-  unsigned char* psi = (unsigned char*)(base + o_psi);
-  unsigned char* path = (unsigned char*)(base + o_path);
-  unsigned char* mA = (unsigned char*)(base + o_mA);
-  unsigned char* mB = (unsigned char*)(base + o_mB);
-  unsigned char* entry = (unsigned char*)(base + o_entry);
-  *dz_out = want_z ? dz : nullptr;
-  *dscore_out = dscore;
-  const double* lt = (const double*)h->ltran.p;
-  const double* mi = (const double*)h->mod_init.p;
+  VitScratch v;
+  CK(vit_scratch(h, B, n, B, in_lds ? 0 : B * Lpad, in_lds ? 0 : C, KS, &v));
+  *dz_out = want_z ? v.z : nullptr;
+  *dscore_out = v.score;
+  const VitWindows units{Lm, Lpad};
   ProfScope ps(h, KS_MISC);
   const size_t lds = (size_t)2 * KS * 8 + (in_lds && want_z ? (size_t)Lm * KS : 0);
-#define VITW(KM)                                                                                                  \
-  do {                                                                                                            \
-    if (in_lds)                                                                                                   \
-      hipLaunchKernelGGL((k_vit_wave<KM, true>), dim3(B), dim3(64), lds, h->stream, ll, lt, mi, Lm, K, Lpad,      \
-                         (unsigned char*)nullptr, want_z ? dz : (int32_t*)nullptr, (int32_t*)nullptr, dscore);    \
-    else                                                                                                          \
-      hipLaunchKernelGGL((k_vit_wave<KM, false>), dim3(B), dim3(64), lds, h->stream, ll, lt, mi, Lm, K, Lpad,     \
-                         psi, (int32_t*)nullptr, zlast, dscore);                                                  \
-  } while (0)
-  if (K <= 16) VITW(16); else if (K <= 32) VITW(32); else if (K <= 64) VITW(64);
-  else if (in_lds)
-    hipLaunchKernelGGL(k_vit_wide<true>, dim3(B), dim3(256), lds, h->stream, ll, lt, mi, Lm, K, Lpad,
-                       (unsigned char*)nullptr, want_z ? dz : (int32_t*)nullptr, (int32_t*)nullptr, dscore);
-  else
-    hipLaunchKernelGGL(k_vit_wide<false>, dim3(B), dim3(256), lds, h->stream, ll, lt, mi, Lm, K, Lpad, psi,
-                       (int32_t*)nullptr, zlast, dscore);
-#undef VITW
+  if (in_lds) vit_sweep<true>(h, B, lds, ll, units, nullptr, want_z ? v.z : nullptr, nullptr, v.score);
+  else vit_sweep<false>(h, B, lds, ll, units, v.psi, nullptr, v.zlast, v.score);
   HIPCK(hipGetLastError());
   if (!in_lds && want_z) {
-    hipLaunchKernelGGL(k_vit_paths, dim3((unsigned)C), dim3(KS), (size_t)Ls * KS, h->stream, (const unsigned char*)psi,
-                       (const int32_t*)zlast, Lm, Ls, Cw, Lpad, KS, K, path);
-    hipLaunchKernelGGL(k_ffbs_compose, dim3(1), dim3(1024), 0, h->stream, (const unsigned char*)path, (int64_t)B * Lpad,
-                       KS, Ls, (int)C, mA, mB, entry);
+    hipLaunchKernelGGL(k_vit_paths<VitWindows>, dim3((unsigned)C), dim3(KS), (size_t)Ls * KS, h->stream,
+                       (const unsigned char*)v.psi, (const int32_t*)v.zlast, units, Ls, KS, K, v.path);
+    hipLaunchKernelGGL(k_ffbs_compose, dim3(1), dim3(1024), 0, h->stream, (const unsigned char*)v.path, (int64_t)B * Lpad,
+                       KS, Ls, (int)C, v.mA, v.mB, v.entry);
     hipLaunchKernelGGL(k_vit_gather, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
-                       (const unsigned char*)path, (const unsigned char*)entry, Lm, Ls, Cw, Lpad, KS, (int64_t)n, dz);
+                       (const unsigned char*)v.path, (const unsigned char*)v.entry, Lm, Ls, Cw, Lpad, KS, (int64_t)n, v.z);
     HIPCK(hipGetLastError());
   }
   return 0;
@@ -1057,9 +1090,45 @@ int grow_state_results(svihmm_ctx* h, int n, int trace_cap, const int32_t** ist_
 }
 
 // ---- svihmm_estep_sequences (kernels_sequences.h) ----------------------------------------------
-// The ragged sweeps over the nseq sequences listed in `order` (device, longest first): lliks `ll` whose row 0 is
-// global row row_base, span rows -> posterior rows at their global index in q [T][K] and seq_lb[s].  lalpha / lbeta /
-// the per-row LSE live in h->seq_work, which no other route touches.  maxlen: the longest of the sequences.
+// The ragged sweeps over the nseq sequences listed in `order` (device, longest first), ndir directions of them: 2 =
+// forward and backward (la, lb), 1 = the forward filter alone (lb null; the kernels take the direction from
+// blockIdx.y).  ll's row 0 is global row row_base.
+static int launch_seq_sweeps(svihmm_ctx* h, int nseq, int ndir, const int32_t* order, const int64_t* seq_off,
+                             int64_t row_base, const double* ll, double* la, double* lb) {
+  const int K = h->K;
+  const double* A = (const double*)h->Aexp.p;
+  const double* mi = (const double*)h->mod_init.p;
+  dim3 grid((unsigned)nseq, (unsigned)ndir);
+  ProfScope ps(h, KS_FB);
+  if (h->exact_log) {
+    const int threads = (K + 63) / 64 * 64;
+    const int in_lds = ((size_t)K * (K + 1) + 2 * K) * 8 <= 150 * 1024;
+    const size_t lds = (2 * (size_t)K + (in_lds ? (size_t)K * (K + 1) : 0)) * 8;
+    if (lds > 64 * 1024)
+      hipFuncSetAttribute((const void*)k_seq_exact, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(k_seq_exact, grid, dim3(threads), lds, h->stream, ll, row_base, seq_off, order,
+                       (const double*)h->ltran.p, mi, K, in_lds, la, lb);
+  } else if (K <= 16)
+    hipLaunchKernelGGL(k_seq_wave<16>, grid, dim3(64), 0, h->stream, ll, row_base, seq_off, order, A, mi, K, la, lb);
+  else if (K <= 32)
+    hipLaunchKernelGGL(k_seq_wave<32>, grid, dim3(64), 0, h->stream, ll, row_base, seq_off, order, A, mi, K, la, lb);
+  else if (K <= 64)
+    hipLaunchKernelGGL(k_seq_wave<64>, grid, dim3(64), 0, h->stream, ll, row_base, seq_off, order, A, mi, K, la, lb);
+  else {
+    const int threads = (K + 63) / 64 * 64;
+    const int in_lds = ((size_t)K * K * 8 + 2 * K * 8 + 128) <= 150 * 1024;
+    const size_t lds = (2 * (size_t)K + 16) * 8 + (in_lds ? (size_t)K * K * 8 : 0);
+    if (lds > 64 * 1024)
+      hipFuncSetAttribute((const void*)k_seq_block, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(k_seq_block, grid, dim3(threads), lds, h->stream, ll, row_base, seq_off, order, A,
+                       (const double*)h->AexpT.p, mi, K, in_lds, la, lb);
+  }
+  HIPCK(hipGetLastError());
+  return 0;
+}
+// Sweeps + posterior over the span rows of those sequences -> posterior rows at their global index in q [T][K] and
+// seq_lb[s].  lalpha / lbeta / the per-row LSE live in h->seq_work, which no other route touches.  maxlen: the longest
+// of the sequences.
 int launch_fb_sequences(svihmm_ctx* h, int nseq, const int32_t* order, const int64_t* seq_off, int64_t row_base,
                         int64_t span, int maxlen, const double* ll, double* q, double* seq_lb) {
   if (!h->have_globals) return fail("no globals: call svihmm_set_globals");
@@ -1070,36 +1139,7 @@ int launch_fb_sequences(svihmm_ctx* h, int nseq, const int32_t* order, const int
   double* la = (double*)h->seq_work.p;
   double* lb = la + ne;
   double* row_lse = lb + ne;
-  const double* A = (const double*)h->Aexp.p;
-  const double* mi = (const double*)h->mod_init.p;
-  dim3 grid((unsigned)nseq, 2);
-  {
-    ProfScope ps(h, KS_FB);
-    if (h->exact_log) {
-      const int threads = (K + 63) / 64 * 64;
-      const int in_lds = ((size_t)K * (K + 1) + 2 * K) * 8 <= 150 * 1024;
-      const size_t lds = (2 * (size_t)K + (in_lds ? (size_t)K * (K + 1) : 0)) * 8;
-      if (lds > 64 * 1024)
-        hipFuncSetAttribute((const void*)k_seq_exact, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(k_seq_exact, grid, dim3(threads), lds, h->stream, ll, row_base, seq_off, order,
-                         (const double*)h->ltran.p, mi, K, in_lds, la, lb);
-    } else if (K <= 16)
-      hipLaunchKernelGGL(k_seq_wave<16>, grid, dim3(64), 0, h->stream, ll, row_base, seq_off, order, A, mi, K, la, lb);
-    else if (K <= 32)
-      hipLaunchKernelGGL(k_seq_wave<32>, grid, dim3(64), 0, h->stream, ll, row_base, seq_off, order, A, mi, K, la, lb);
-    else if (K <= 64)
-      hipLaunchKernelGGL(k_seq_wave<64>, grid, dim3(64), 0, h->stream, ll, row_base, seq_off, order, A, mi, K, la, lb);
-    else {
-      const int threads = (K + 63) / 64 * 64;
-      const int in_lds = ((size_t)K * K * 8 + 2 * K * 8 + 128) <= 150 * 1024;
-      const size_t lds = (2 * (size_t)K + 16) * 8 + (in_lds ? (size_t)K * K * 8 : 0);
-      if (lds > 64 * 1024)
-        hipFuncSetAttribute((const void*)k_seq_block, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(k_seq_block, grid, dim3(threads), lds, h->stream, ll, row_base, seq_off, order, A,
-                         (const double*)h->AexpT.p, mi, K, in_lds, la, lb);
-    }
-    HIPCK(hipGetLastError());
-  }
+  CK(launch_seq_sweeps(h, nseq, 2, order, seq_off, row_base, ll, la, lb));
   {
     ProfScope ps(h, KS_POSTERIOR);
     // 64 rows per posterior workgroup of the longest sequence, at most 1024 workgroups per sequence
@@ -1149,14 +1189,10 @@ int launch_seq_gather(svihmm_ctx* h, int M, const int64_t* tab, int maxlen, doub
 // ---- decoding all declared sequences in one call (kernels_decode_sequences.h) -------------------
 // svihmm_viterbi_sequences.  Sequences whose psi fits the LDS budget (len <= vit_lds_rows(KS); all of them when no
 // path is wanted) are decoded inside the forward launch; all longer ones go in ONE forward launch that writes psi
-// to a common run of padded chunks, backtracked by k_vitseq_paths / k_ffbs_compose / k_vitseq_gather.
-// A launch's dynamic LDS is one number: the short sequences go in ONE launch sized by the longest of them.  Cutting
-// them (longest first) into up to three launches by LDS request -- 64 / 40 / 20 KiB, i.e. 2 / 4 / 8 workgroups per CU --
-// measured slower ("Decoding several sequences": the launches run one after the other and each
-// ends in its own tail); SVIHMM_DECODE_LDS_BINS=1 (measurement only) selects that form.
-// h->vit: score [N] | z int32 [T] | final argmax [long] | psi | path | chunk maps.
-// h->dec_tab: pad_off int64 [long] | order (short) | order (long) | chunk table.
-static const int VITSEQ_BINS[3] = {65536, 40960, 20480};
+// to a common run of padded chunks, backtracked by k_vit_paths / k_ffbs_compose / k_vitseq_gather.
+// A launch's dynamic LDS is one number: the short sequences go in ONE launch sized by the longest of them (cutting
+// them into several launches by LDS request measured slower: DESIGN.md section 4, "Decoding several sequences").
+// h->vit: vit_scratch.  h->dec_tab: pad_off int64 [long] | order (short) | order (long) | chunk table.
 int64_t viterbi_sequences_chunks(const svihmm_ctx* h) {
   const int Ls = vit_lds_rows(h->K <= 64 ? 64 : 256);
   int64_t C = 0;
@@ -1203,72 +1239,28 @@ int launch_viterbi_sequences(svihmm_ctx* h, const double* ll, bool want_z, int32
   const int32_t* dos = (const int32_t*)(tb + t_os);
   const int32_t* dol = (const int32_t*)(tb + t_ol);
   const int32_t* dct = (const int32_t*)(tb + t_ct);
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_z = up((size_t)N * sizeof(double)), o_zlast = o_z + up((size_t)T * sizeof(int32_t));
-  const size_t o_psi = o_zlast + up(nl * sizeof(int32_t));
-  const size_t nps = up((size_t)P * KS);
-  const size_t o_path = o_psi + nps, o_mA = o_path + nps;
-  const size_t nmap = up((size_t)C * KS);
-  const size_t o_mB = o_mA + nmap, o_entry = o_mB + nmap;
-  CK(ensure(h->vit, o_entry + up((size_t)C) + 256));
-  char* base = (char*)h->vit.p;
-  double* dscore = (double*)base;
-  int32_t* dz = (int32_t*)(base + o_z);
-  int32_t* zlast = (int32_t*)(base + o_zlast);
-  unsigned char* psi = (unsigned char*)(base + o_psi);
-  unsigned char* path = (unsigned char*)(base + o_path);
-  unsigned char* mA = (unsigned char*)(base + o_mA);
-  unsigned char* mB = (unsigned char*)(base + o_mB);
-  unsigned char* entry = (unsigned char*)(base + o_entry);
-  *dz_out = want_z ? dz : nullptr;
-  *dscore_out = dscore;
-  const double* lt = (const double*)h->ltran.p;
-  const double* mi = (const double*)h->mod_init.p;
+  VitScratch v;
+  CK(vit_scratch(h, N, (size_t)T, nl, P, C, KS, &v));
+  *dz_out = want_z ? v.z : nullptr;
+  *dscore_out = v.score;
   const int64_t* sod = (const int64_t*)h->seq_off_d.p;
-  int32_t* zw = want_z ? dz : (int32_t*)nullptr;
   ProfScope ps(h, KS_MISC);
-  static const bool binned = [] { const char* e = std::getenv("SVIHMM_DECODE_LDS_BINS"); return e && std::atoi(e) != 0; }();
-  // the short sequences: ranges [a, b) of the order array that share an LDS bin
-  for (size_t a = 0; a < ns;) {
-    size_t b = ns;
-    const int64_t la = so[shorts[a] + 1] - so[shorts[a]];
+  if (ns) {
+    const int64_t la = so[shorts[0] + 1] - so[shorts[0]];
     const size_t lds = (size_t)2 * KS * 8 + (want_z ? (size_t)la * KS : 0);
-    if (want_z && binned) {
-      int bin = 0;
-      while (bin + 1 < 3 && lds <= (size_t)VITSEQ_BINS[bin + 1]) ++bin;
-      if (bin + 1 < 3) {     // the range ends where the next smaller bin begins
-        const size_t rows_next = ((size_t)VITSEQ_BINS[bin + 1] - (size_t)2 * KS * 8) / KS;
-        for (b = a; b < ns && (size_t)(so[shorts[b] + 1] - so[shorts[b]]) > rows_next; ++b) {}
-      }
-    }
-    const unsigned n = (unsigned)(b - a);
-#define VSW(KM)                                                                                                    \
-  hipLaunchKernelGGL((k_vitseq_wave<KM, true>), dim3(n), dim3(64), lds, h->stream, ll, lt, mi, sod, dos + a,       \
-                     (const int64_t*)nullptr, K, (unsigned char*)nullptr, zw, (int32_t*)nullptr, dscore)
-    if (K <= 16) VSW(16); else if (K <= 32) VSW(32); else if (K <= 64) VSW(64);
-    else
-      hipLaunchKernelGGL(k_vitseq_wide<true>, dim3(n), dim3(256), lds, h->stream, ll, lt, mi, sod, dos + a,
-                         (const int64_t*)nullptr, K, (unsigned char*)nullptr, zw, (int32_t*)nullptr, dscore);
-#undef VSW
-    a = b;
+    vit_sweep<true>(h, (unsigned)ns, lds, ll, VitSequences{sod, dos, nullptr, nullptr}, nullptr,
+                    want_z ? v.z : nullptr, nullptr, v.score);
   }
   HIPCK(hipGetLastError());
   if (nl) {
-    const size_t lds = (size_t)2 * KS * 8;
-#define VSW(KM)                                                                                                    \
-  hipLaunchKernelGGL((k_vitseq_wave<KM, false>), dim3((unsigned)nl), dim3(64), lds, h->stream, ll, lt, mi, sod,    \
-                     dol, dpad, K, psi, (int32_t*)nullptr, zlast, dscore)
-    if (K <= 16) VSW(16); else if (K <= 32) VSW(32); else if (K <= 64) VSW(64);
-    else
-      hipLaunchKernelGGL(k_vitseq_wide<false>, dim3((unsigned)nl), dim3(256), lds, h->stream, ll, lt, mi, sod, dol,
-                         dpad, K, psi, (int32_t*)nullptr, zlast, dscore);
-#undef VSW
-    hipLaunchKernelGGL(k_vitseq_paths, dim3((unsigned)C), dim3(KS), (size_t)Ls * KS, h->stream,
-                       (const unsigned char*)psi, (const int32_t*)zlast, sod, dol, dpad, dct, Ls, KS, K, path);
-    hipLaunchKernelGGL(k_ffbs_compose, dim3(1), dim3(1024), 0, h->stream, (const unsigned char*)path, P, KS, Ls,
-                       (int)C, mA, mB, entry);
-    hipLaunchKernelGGL(k_vitseq_gather, dim3((unsigned)C), dim3(256), 0, h->stream, (const unsigned char*)path,
-                       (const unsigned char*)entry, sod, dol, dpad, dct, Ls, KS, dz);
+    const VitSequences units{sod, dol, dpad, dct};
+    vit_sweep<false>(h, (unsigned)nl, (size_t)2 * KS * 8, ll, units, v.psi, nullptr, v.zlast, v.score);
+    hipLaunchKernelGGL(k_vit_paths<VitSequences>, dim3((unsigned)C), dim3(KS), (size_t)Ls * KS, h->stream,
+                       (const unsigned char*)v.psi, (const int32_t*)v.zlast, units, Ls, KS, K, v.path);
+    hipLaunchKernelGGL(k_ffbs_compose, dim3(1), dim3(1024), 0, h->stream, (const unsigned char*)v.path, P, KS, Ls,
+                       (int)C, v.mA, v.mB, v.entry);
+    hipLaunchKernelGGL(k_vitseq_gather, dim3((unsigned)C), dim3(256), 0, h->stream, (const unsigned char*)v.path,
+                       (const unsigned char*)v.entry, units, Ls, KS, v.z);
     HIPCK(hipGetLastError());
   }
   return 0;
@@ -1280,8 +1272,8 @@ int launch_viterbi_sequences(svihmm_ctx* h, const double* ll, bool want_z, int32
 // host lliks -- in one launch of the ragged sweeps' forward direction (grid (n, 1): the kernels take the direction
 // from blockIdx.y).  The emission pass over all T rows comes last, so the lliks of all rows stay readable.
 // Draws: sequences below FFW_SWITCH rows in one launch, a lane per (sequence, draw) pair; longer ones through the
-// blocked composition once per (sequence, draw), as launch_ffbs_windows does.
-// h->vit: logA | z int32 [S][T] | the caller's uniforms [S][T]; h->dec_tab: order (filter) | order (sampler).
+// blocked composition once per (sequence, draw), as launch_ffbs_windows does (ffbs_blocked_draw).
+// *dz_out: int32 [S][T]; h->dec_tab: order (filter) | order (sampler).
 int launch_ffbs_sequences(svihmm_ctx* h, uint32_t flags, const double* logA, int S, const double* uniforms, uint64_t seed,
                           bool want_lalpha, int32_t** dz_out, const double** dla_out) {
   const int K = h->K, N = (int)h->seq_off.size() - 1;
@@ -1321,48 +1313,10 @@ int launch_ffbs_sequences(svihmm_ctx* h, uint32_t flags, const double* logA, int
   const int32_t* dlanes = dor + nr;
   const int64_t* sod = (const int64_t*)h->seq_off_d.p;
   const double* ll = (const double*)h->ll.p;
-  if (nr) {
-    const double* A = (const double*)h->Aexp.p;
-    const double* mi = (const double*)h->mod_init.p;
-    double* nolb = nullptr;
-    dim3 grid((unsigned)nr, 1);
-    ProfScope ps(h, KS_FB);
-    if (h->exact_log) {
-      const int threads = (K + 63) / 64 * 64;
-      const int in_lds = ((size_t)K * (K + 1) + 2 * K) * 8 <= 150 * 1024;
-      const size_t lds = (2 * (size_t)K + (in_lds ? (size_t)K * (K + 1) : 0)) * 8;
-      if (lds > 64 * 1024)
-        hipFuncSetAttribute((const void*)k_seq_exact, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(k_seq_exact, grid, dim3(threads), lds, h->stream, ll, (int64_t)0, sod, dor,
-                         (const double*)h->ltran.p, mi, K, in_lds, la_all, nolb);
-    } else if (K <= 16)
-      hipLaunchKernelGGL(k_seq_wave<16>, grid, dim3(64), 0, h->stream, ll, (int64_t)0, sod, dor, A, mi, K, la_all, nolb);
-    else if (K <= 32)
-      hipLaunchKernelGGL(k_seq_wave<32>, grid, dim3(64), 0, h->stream, ll, (int64_t)0, sod, dor, A, mi, K, la_all, nolb);
-    else if (K <= 64)
-      hipLaunchKernelGGL(k_seq_wave<64>, grid, dim3(64), 0, h->stream, ll, (int64_t)0, sod, dor, A, mi, K, la_all, nolb);
-    else {
-      const int threads = (K + 63) / 64 * 64;
-      const int in_lds = ((size_t)K * K * 8 + 2 * K * 8 + 128) <= 150 * 1024;
-      const size_t lds = (2 * (size_t)K + 16) * 8 + (in_lds ? (size_t)K * K * 8 : 0);
-      if (lds > 64 * 1024)
-        hipFuncSetAttribute((const void*)k_seq_block, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      hipLaunchKernelGGL(k_seq_block, grid, dim3(threads), lds, h->stream, ll, (int64_t)0, sod, dor, A,
-                         (const double*)h->AexpT.p, mi, K, in_lds, la_all, nolb);
-    }
-    HIPCK(hipGetLastError());
-  }
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t n = (size_t)S * T;
-  const size_t o_z = up((size_t)K * K * sizeof(double)), o_u = o_z + up(n * sizeof(int32_t));
-  CK(ensure(h->vit, o_u + (uniforms ? n * sizeof(double) : 0) + 256));
-  char* base = (char*)h->vit.p;
-  double* dlogA = (double*)base;
-  int32_t* dz = (int32_t*)(base + o_z);
-  double* dun = uniforms ? (double*)(base + o_u) : nullptr;
-  HIPCK(hipMemcpyAsync(dlogA, logA, (size_t)K * K * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (uniforms) HIPCK(hipMemcpyAsync(dun, uniforms, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  *dz_out = dz;
+  if (nr) CK(launch_seq_sweeps(h, (int)nr, 1, dor, sod, 0, ll, la_all, nullptr));
+  FfbsIo io;
+  CK(ffbs_io(h, logA, uniforms, (size_t)S * T, &io));
+  *dz_out = io.z;
   *dla_out = la_all;
   if (nlane) {
     const unsigned nblk = (unsigned)(((int64_t)nlane * S + 63) / 64);
@@ -1372,46 +1326,29 @@ int launch_ffbs_sequences(svihmm_ctx* h, uint32_t flags, const double* logA, int
       const size_t lds = ffs_lds_bytes(K, KM);
 #define FSEQ(KMAX)                                                                                                 \
   hipLaunchKernelGGL(k_ffbs_seq<KMAX>, dim3(nblk), dim3(64), lds, h->stream, (const double*)la_all,                \
-                     (const double*)dlogA, (const double*)dun, (unsigned long long)seed, sod, dlanes, (int)nlane,  \
-                     S, T, K, dz)
+                     (const double*)io.logA, (const double*)io.unif, (unsigned long long)seed, sod, dlanes,     \
+                     (int)nlane, S, T, K, io.z)
       if (KM == 16) FSEQ(16); else if (KM == 32) FSEQ(32); else FSEQ(64);
 #undef FSEQ
     } else {
       hipLaunchKernelGGL(k_ffbs_seq_wide, dim3(nblk), dim3(64), 0, h->stream, (const double*)la_all,
-                         (const double*)dlogA, (const double*)dun, (unsigned long long)seed, sod, dlanes, (int)nlane,
-                         S, T, K, dz);
+                         (const double*)io.logA, (const double*)io.unif, (unsigned long long)seed, sod, dlanes,
+                         (int)nlane, S, T, K, io.z);
     }
     HIPCK(hipGetLastError());
   }
   if (blocked.empty()) return 0;
-  // long sequences: per-draw scratch in h->scratch = (Philox: uniforms [len]) | z int64 [len] | path, chunk maps
   int64_t maxlen = 0;
   size_t extra = 0;
   for (int32_t s : blocked) {
     maxlen = std::max(maxlen, so[s + 1] - so[s]);
     extra = std::max(extra, ffbs_plan(h, so[s + 1] - so[s], K).extra);
   }
-  const size_t o_zl = uniforms ? 0 : up((size_t)maxlen * sizeof(double));
-  const size_t o_path = o_zl + up((size_t)maxlen * sizeof(int64_t));
-  CK(ensure(h->scratch, o_path + extra));
-  char* sb = (char*)h->scratch.p;
-  int64_t* dzl = (int64_t*)(sb + o_zl);
+  FfbsBlockedScratch sc;
+  CK(ffbs_blocked_scratch(h, io, maxlen, extra, &sc));
   for (int d = 0; d < S; ++d)
-    for (int32_t s : blocked) {
-      const int64_t len = so[s + 1] - so[s];
-      const FfbsPlan pl = ffbs_plan(h, len, K);
-      const unsigned nb256 = (unsigned)((len + 255) / 256);
-      const int64_t g0 = (int64_t)d * T + so[s];
-      const double* du = dun ? dun + g0 : (const double*)sb;
-      if (!dun) {
-        ProfScope ps(h, KS_FFBS);
-        hipLaunchKernelGGL(k_ffw_fill_uniforms, dim3(nb256), dim3(256), 0, h->stream, (unsigned long long)seed, g0,
-                           len, (double*)sb);
-      }
-      CK(ffbs_launch(h, pl, la_all + (size_t)so[s] * K, len, K, dlogA, du, dzl, (unsigned char*)(sb + o_path)));
-      ProfScope ps(h, KS_FFBS);
-      hipLaunchKernelGGL(k_ffw_store_path, dim3(nb256), dim3(256), 0, h->stream, (const int64_t*)dzl, len, dz + g0);
-    }
+    for (int32_t s : blocked)
+      CK(ffbs_blocked_draw(h, io, sc, seed, la_all + (size_t)so[s] * K, so[s + 1] - so[s], (int64_t)d * T + so[s]));
   HIPCK(hipGetLastError());
   return 0;
 }

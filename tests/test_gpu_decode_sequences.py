@@ -81,7 +81,7 @@ def _decode_host(e, ll, mod_init, ltran, lengths, declare=True):
 
 # ---- Viterbi, exact, host-lliks route ------------------------------------------------------------------
 @pytest.mark.parametrize("kind", ["random", "flat", "cycle"])
-@pytest.mark.parametrize("K", [5, 16, 64, 65, 130, 256])
+@pytest.mark.parametrize("K", [5, 16, 17, 64, 65, 130, 256])
 def test_viterbi_exact_host_lliks(eng, K, kind):
     lengths = _lengths(K)
     off = offsets(lengths)
@@ -299,7 +299,7 @@ def _ffbs_checked(e, K, S, sparse=False):
 
 
 @pytest.mark.parametrize("S", [1, 3, 70])
-@pytest.mark.parametrize("K", [5, 64, 80])
+@pytest.mark.parametrize("K", [5, 17, 64, 80])
 def test_ffbs_paths_and_lalpha(eng, K, S):
     _ffbs_checked(eng, K, S)
 

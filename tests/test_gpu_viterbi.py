@@ -84,7 +84,7 @@ def _host_exact(eng, ll, mod_init, ltran):
 
 
 # ---- exact, host-lliks route ---------------------------------------------------------------------
-@pytest.mark.parametrize("K", [2, 5, 16, 64])
+@pytest.mark.parametrize("K", [2, 5, 16, 17, 64])
 @pytest.mark.parametrize("B", [1, 3])
 @pytest.mark.parametrize("Lm", [1, 2, 7, 33])
 def test_wave_kernel_lds_backtrack(eng, K, B, Lm):
@@ -113,7 +113,7 @@ def test_score_only_and_path_only(eng):
 
 # K <= 64: psi in LDS up to 1008 rows, chunks of 1008 rows beyond
 @pytest.mark.parametrize("kind", ["sticky", "flat", "cycle"])
-@pytest.mark.parametrize("K", [5, 64])
+@pytest.mark.parametrize("K", [5, 17, 64])
 @pytest.mark.parametrize("B,Lm", [(1, 1008), (1, 1009), (1, 2016), (1, 2017), (1, 2047), (1, 2048), (1, 5000), (3, 3000)])
 def test_long_windows(eng, K, kind, B, Lm):
     """sticky: the paths coalesce within a few rows; flat: near-uniform transitions, weak emissions;

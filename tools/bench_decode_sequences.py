@@ -13,8 +13,6 @@ drawn uniformly from [32, 512], about 1.1e6 rows):
           in HBM and is backtracked through the common chunk run
 Routes:
   new    one call for all sequences (results read back, the call ends in a stream synchronisation)
-  newb   `vit` / `wide` only: the same call with SVIHMM_DECODE_LDS_BINS=1 -- the short sequences cut into up to
-         three launches binned by LDS request instead of ONE launch sized by the longest (measurement of that choice)
   loop   one viterbi([off], len) / ffbs_windows([off], len, ..) call per sequence -- the only route before the two
          calls existed.  With --parent-lib it runs on that library (a build of the parent commit, loaded through
          SVIHMM_HIP_LIB) as well as on the current one.
@@ -125,7 +123,7 @@ def run_child(case, route):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--case", choices=CASES)
-    ap.add_argument("--route", choices=["new", "newb", "loop"])
+    ap.add_argument("--route", choices=["new", "loop"])
     ap.add_argument("--out", default=None)
     ap.add_argument("--parent-lib", default=None, help="library built from the parent commit (path relative to the repository)")
     ap.add_argument("--limit", type=int, default=600)
@@ -144,18 +142,13 @@ def main():
             if args.parent_lib:
                 plan.append((rnd, case, "loop", args.parent_lib))
             plan.append((rnd, case, "new", None))
-            if case in ("vit", "wide"):
-                plan.append((rnd, case, "newb", None))
             plan.append((rnd, case, "loop", None))
     results, rc = [], 0
     for rnd, case, route, lib in plan:
         env = dict(os.environ)
         env.pop("SVIHMM_HIP_LIB", None)
-        env.pop("SVIHMM_DECODE_LDS_BINS", None)
         if lib:
             env["SVIHMM_HIP_LIB"] = os.path.join(REPO, lib)
-        if route == "newb":
-            env["SVIHMM_DECODE_LDS_BINS"] = "1"
         tag = {"round": rnd, "case": case, "route": route, "lib": lib or "current"}
         try:
             p = subprocess.run([sys.executable, os.path.abspath(__file__), "--case", case, "--route", route], cwd=REPO,
@@ -181,8 +174,6 @@ def main():
                 best[key] = min(best.get(key, float("inf")), r["call_ms"])
         if ("new", "current") in best:
             s = {"new_ms": best[("new", "current")]}
-            if ("newb", "current") in best:
-                s["new_lds_bins_ms"] = best[("newb", "current")]
             for which in ("parent", "current"):
                 if ("loop", which) in best:
                     s["loop_%s_ms" % which] = best[("loop", which)]
