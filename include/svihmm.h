@@ -525,6 +525,44 @@ int64_t svihmm_packed_len(svihmm_ctx* h);
 int svihmm_set_emission_mcat(svihmm_ctx* h, int32_t K, int32_t D, const int32_t* V /*[D]*/,
                              const double* logp /*[K][F]*/);
 
+/* Poisson count emissions: D count tracks per row, independent given the state,
+ *   p(x_t | z_t = k) = prod_d Poisson(x_t[d] | lambda_{k,d}),  mean-field factors q(lambda_{k,d}) = Gamma(a_{k,d},
+ * b_{k,d}) (shape, rate).  The host forms the expectations (SciPy): elog[k][d] = psi(a) - log(b), erate[k][d] = a / b,
+ * and the table logfact[c] = lgamma(c + 1) for c = 0..C (scipy.special.gammaln): a table keeps lgamma off the device
+ * and makes the lliks reproducible to the bit.  obs is [T][D], each entry a count stored as a double.
+ * Entry (t, d) is PRESENT when it is not NaN and x >= 0.0 && x < (double)(C + 1), compared as doubles (+inf, -0.5, -1
+ * and C + 1 are absent); its count is c = (int)x (3.7 counts as 3).  An absent entry adds nothing to the row's llik
+ * and nothing to the statistics; the row's other columns are not affected.
+ * lliks, for row t and state k: s = +0.0, g = +0.0; for the present d in ascending order p = (double)c_d * elog[k][d]
+ * (one rounded multiply, never fused with the add), s = s + p, s = s - erate[k][d], g = g + logfact[c_d]; then
+ * ll[t][k] = s - g.  Given the same tables this is bit-identical to that loop in NumPy.  A row masked under
+ * SVIHMM_MASK_AS_NAN, or one with no present entry, gives +0.0 for every k.
+ * Packed statistics (svihmm_packed_len): [A_raw K*K | stat K*2D | lb], stat[k] = [sx[k][0..D) | n[k][0..D)],
+ * sx[k][d] = sum var_x[t][k] c_td and n[k][d] = sum var_x[t][k], both over the rows t with mask[t] == 0 (whatever
+ * the flags) whose entry d is present: the conjugate update is a = a0 + sx, b = b0 + n.  A_raw, lb,
+ * SVIHMM_TRANS_WRAP and the inner segment of svihmm_estep_minibatch_ex behave as for the Categorical families.  The
+ * statistics carry no coordinates: export, import and all-reduce pass them through unchanged.
+ * Every entry point that dispatches on the emission family takes this one: loglik, forward_backward,
+ * estep_minibatch(_ex), suffstats, estep_sequences, estep_sequence_subset, viterbi(_sequences), ffbs, ffbs_windows,
+ * ffbs_sequences, grow_windows (both methods), state_argmax, read_intermediate / read_rows, read_packed, export /
+ * import / allreduce_packed.  Always fp64, K <= 256.
+ * The counts stay exact in the resident copy, as for svihmm_set_emission_mcat: an upload while the family is active
+ * is not centred, a copy centred earlier is brought back before the first lookup (an entry within 2^-20, relative,
+ * of an integer becomes that integer; a fractional entry keeps its value to rounding, so 3.7 still counts as 3 and
+ * -0.5 stays absent), a Gaussian family that follows centres again.
+ * Fails with a message before any device work, with the handle and the family set before still in force: NULL elog,
+ * erate or logfact; K < 1 or K > 256; D < 1 or D > SVIHMM_POISSON_MAX_D; C < 0 or C > SVIHMM_POISSON_MAX_COUNT; a
+ * non-finite elog[k][d], erate[k][d] or logfact[c] (the message names the entry); and, at the first E-step-type call,
+ * resident observations whose D differs from the family's.
+ * Out of scope, each refused with a message: the resident SVI loop (svihmm_svi_begin_* replaces the family;
+ * svihmm_svi_iteration refuses), svihmm_pred_logprob (NIW only), the fp32 mode (svihmm_get_precision reports
+ * last_batch_f32 = 0), and the device paths of hmmsgd_metaobs.VBHMM (host lliks through the plugin there). */
+#define SVIHMM_POISSON_MAX_D     128
+#define SVIHMM_POISSON_MAX_COUNT ((1 << 20) - 1)
+int svihmm_set_emission_poisson(svihmm_ctx* h, int32_t K, int32_t D,
+                                const double* elog /*[K][D]*/, const double* erate /*[K][D]*/,
+                                const double* logfact /*[C + 1]*/, int32_t C);
+
 /* ELBO bookkeeping of the SVI loop (hmmsgd_metaobs.py:273-296 global_lower_bound,
  * hmmbase.py:183-185: sum_k var_emit[k].get_vlb()): the data-dependent scalars of the NIW
  * factors' term for the given mean-field parameters (D <= SVIHMM_NIW_MAX_D; D <= 64 runs the

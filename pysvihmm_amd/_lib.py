@@ -25,6 +25,8 @@ NIW_MAX_D = 96                    # wider observations: host-evaluated lliks (ge
 DIAG_MAX_D = 128                  # diagonal family on the device up to this width
 MCAT_MAX_D = 128                  # multi-column Categorical family: columns ...
 MCAT_MAX_F = 1024                 # ... and features (sum of the columns' symbol counts)
+POISSON_MAX_D = 128               # Poisson count family: columns ...
+POISSON_MAX_COUNT = (1 << 20) - 1 # ... and the largest count the logfact table may reach
 LTRAN_F32_MIN = -60.0
 F64, F32 = 0, 1
 GROW_METHOD = {"auto": 0, "literal": 1, "products": 2}     # SVIHMM_GROW_* of include/svihmm.h
@@ -93,6 +95,8 @@ SIGNATURES = {
     "svihmm_read_globals": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p]),
     "svihmm_set_emission_cat": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _c_double_p]),
     "svihmm_set_emission_mcat": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _c_double_p]),
+    "svihmm_set_emission_poisson": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _c_double_p, _c_double_p, _c_double_p,
+                                              C.c_int32]),
     "svihmm_packed_len": (C.c_int64, [C.c_void_p]),
     "svihmm_pred_logprob": (C.c_int, [C.c_void_p, _c_int64_p, C.c_int32, C.c_int32, C.c_uint32, _c_double_p]),
     "svihmm_alloc_obs": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),

@@ -124,6 +124,9 @@ struct svihmm_ctx {
   // multi-column Categorical (svihmm_set_emission_mcat): emis_cat is set as well -- every route the host picks by asking
   // emis_cat is the one this family takes -- with V = F = sum_d V[d]; mcat_meta = [off_d D | V_d D | d(f) F | v(f) F] int32
   bool emis_mcat = false; Buf mcat_meta;
+  // Poisson counts (svihmm_set_emission_poisson): emis_cat is set as well, with V = F = 2 D statistics rows [sx | n];
+  // cat_table = [D + 1][K] pairs (elog, erate) with row D all zeros, pois_logfact = lgamma(c + 1) for c = 0..pois_C (pois_lf_host: what it holds)
+  bool emis_pois = false; int pois_C = 0; Buf pois_logfact; std::vector<double> pois_lf_host;
   bool emis_diag = false;                    // diagonal Gaussian family: 2 D + 1 features, h->niw = [mu | nus | alphas | betas]
   bool tab_diag = false;                     // feature table currently on the device is the diagonal one
   void* theta_zero_p = nullptr; size_t theta_zero_n = 0;   // what the last theta memset covered
@@ -388,12 +391,15 @@ bool use_chain(const svihmm_ctx* h, int B, int Lm);
 int wait_globals(svihmm_ctx* h);
 int svi_flush_elbo(svihmm_ctx* h);
 int ensure_starts_pulled(svihmm_ctx* h);
-int cat_uncentre(svihmm_ctx* h);
+int cat_uncentre(svihmm_ctx* h, int counts = -1);
 // what an E-step-type call says when the emission family's D is not the resident observations'
 extern "C++" inline std::string emission_d_message(const svihmm_ctx* h) {
   if (h->emis_mcat)
     return "svihmm_set_emission_mcat: the family has D = " + std::to_string(h->eD) +
            " symbol columns, the resident observations have " + std::to_string(h->D);
+  if (h->emis_pois)
+    return "svihmm_set_emission_poisson: the family has D = " + std::to_string(h->eD) +
+           " count columns, the resident observations have " + std::to_string(h->D);
   return "emission D does not match obs D";
 }
 int launch_fb_chain(svihmm_ctx* h, int Lm, bool total);

@@ -262,13 +262,18 @@ __global__ void k_mirror(const double* __restrict__ src, double* __restrict__ ds
 // obs[t][d] -= shift[d], in place, for n consecutive entries of whole rows (the handle keeps the
 // resident copy centred; svihmm_shift_obs).  ROUND: the result is an integer-valued symbol column
 // again (a Categorical table follows data that had been centred for a NIW family).
-template <bool ROUND>
+// ROUND = 2 (count columns, svihmm_set_emission_poisson): an entry within 2^-20 (relative) of an integer becomes that
+// integer -- the counts are exact again --, any other keeps its value, so that a 3.7 still truncates to 3 and a -0.5
+// stays negative (NaN and +-Inf pass through either way).
+template <int ROUND>
 __global__ __launch_bounds__(256) void k_shift_obs(double* __restrict__ obs, int64_t n, int D,
                                                    const double* __restrict__ shift) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) {
     const double v = obs[i] - shift[i % D];
-    obs[i] = ROUND ? rint(v) : v;
+    const double r = rint(v);
+    if (ROUND == 2) obs[i] = fabs(v - r) <= 0x1p-20 * fmax(1.0, fabs(r)) ? r : v;
+    else obs[i] = ROUND ? r : v;
   }
 }
 // rows of [K][D] means -= shift (the NIW factors / prior resident on the device follow a change of

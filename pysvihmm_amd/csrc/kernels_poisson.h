@@ -1,0 +1,239 @@
+// kernels_poisson.h -- Poisson count emissions (svihmm_set_emission_poisson)
+//
+//   p(x_t | z_t = k) = prod_d Poisson(x_t[d] | lambda_{k,d}),   q(lambda_{k,d}) = Gamma(a_{k,d}, b_{k,d}),
+//   obs [T][D] counts stored as doubles; the host supplies elog = psi(a) - log b, erate = a / b and
+//   logfact[c] = lgamma(c + 1) for c = 0..C.
+//
+// Entry (t, d) is PRESENT when x >= 0.0 && x < (double)(C + 1), compared as doubles (a NaN fails both); its count is
+// c = (int)x.  An absent entry adds nothing to the row's llik and nothing to the statistics, the row's other columns
+// are not affected.
+//
+//   k_emission_poisson   ll[row][k] = s - g, with s = g = +0.0 and, for the present d in ascending order,
+//                          p = (double)c_d * elog[k][d] (one rounded multiply), s = s + p, s = s - erate[k][d],
+//                          g = g + logfact[c_d]:
+//                        contraction is off in the kernel, so the result is bit-identical to that loop on the host.
+//                        g is formed once per row.  A row masked under SVIHMM_MASK_AS_NAN, or without a present
+//                        entry, is all +0.0.  Output in the layout / scaling convention of k_emission_cat.
+//   k_stats_poisson      [sx | n] as a GEMM on v_mfma_f64_16x16x4_f64 with F = 2 D feature rows:
+//                          out[f][k]     = sum_t c_tf q[t][k]                     (f < D)
+//                          out[D + d][k] = sum_t 1[entry (t, d) present] q[t][k]
+//                        over the unmasked rows.  A operand formed on the fly from 32-bit staged counts (-1: absent or
+//                        masked row).  Per-chunk partials [chunk][F][Kp] (the layout k_stats_cat writes), reduced in
+//                        chunk order by k_finalize_cat with V = 2 D: no atomics, a run is bit-reproducible.
+//
+// Shapes: every D <= SVIHMM_POISSON_MAX_D, C <= SVIHMM_POISSON_MAX_COUNT, K <= 256 runs on these two kernels.  The
+// GEMM's operand layout, chunking and posterior staging are k_stats_onehot's (kernels_mcat.h: MC_RB, MC_QS, McRow).
+//
+// Out of scope for this family, as for the multi-column Categorical one: the resident SVI loop, svihmm_pred_logprob,
+// the fp32 mode and the device paths of hmmsgd_metaobs.VBHMM.
+#pragma once
+
+#define PO_EM_ROWS 32          // rows whose counts k_emission_poisson stages at a time
+
+#ifdef SVIHMM_POISSON_EMISSION
+// lane = state (strided for K > 64); a wave owns every fourth row of the staged block.
+// tab: [D + 1][K] pairs (elog, erate), so one 16-byte read serves a column's multiply-add-subtract; row D is all +0.0.
+// An absent column is walked as count 0 against row D: p = 0.0 * 0.0 = +0.0 and the subtrahend is +0.0, which leave
+// every value s can hold unchanged (see the note at the g pass) -- the bits of the loop that skips, without a select
+// on the vector side (the count is one value for the wave, so the row and the count are chosen on the scalar side).
+// TLDS: the pairs sit in LDS (the host picks it when 2 D K doubles fit 64 KB), otherwise they are read through L2.
+// LDS: [ pairs (D+1)*K double2 (TLDS) | g PO_EM_ROWS doubles | counts PO_EM_ROWS * CS ints ],  CS = ((D + 3) & ~3) + 4
+template <bool TLDS>
+__global__ __launch_bounds__(256) void k_emission_poisson(
+    const double* __restrict__ obs, const uint8_t* __restrict__ mask, const int64_t* __restrict__ starts,
+    int64_t nrows, int Lm, int K, int D, int C, const double2* __restrict__ table,
+    const double* __restrict__ logfact, uint32_t flags, double* __restrict__ ll, int rows_per_wg) {
+#pragma clang fp contract(off)
+  extern __shared__ __attribute__((aligned(16))) char po_smem[];
+  double2* tab = (double2*)po_smem;
+  double* gs = (double*)(po_smem + (TLDS ? (size_t)(D + 1) * K * sizeof(double2) : 0));
+  int* cnt = (int*)(gs + PO_EM_ROWS);
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  if (TLDS)
+    for (int e = tid; e < (D + 1) * K; e += 256) tab[e] = table[e];
+  const double2* __restrict__ T = TLDS ? (const double2*)tab : table;
+  const bool use_mask = (flags & SVIHMM_MASK_AS_NAN) && mask;
+  const int DP = (D + 3) & ~3;       // a row's counts padded with "absent" to whole groups of four
+  const int CS = DP + 4;             // (rows stay 16-byte aligned: four counts come in one read)
+  const double lim = (double)(C + 1);
+  const int64_t r0 = (int64_t)blockIdx.x * rows_per_wg;
+  const int64_t r1 = imin64(nrows, r0 + rows_per_wg);
+  for (int64_t base = r0; base < r1; base += PO_EM_ROWS) {
+    __syncthreads();       // (the previous block's counts are consumed; first trip: the table is staged)
+    const int nr = (int)imin64(PO_EM_ROWS, r1 - base);
+    for (int e = tid; e < nr * DP; e += 256) {
+      const int r = e / DP, d = e - r * DP;
+      int c = -1;
+      if (d < D) {
+        const int64_t g = base + r;
+        const int64_t b = g / Lm;
+        const int64_t orow = starts[b] + (g - b * Lm);
+        const double x = obs[orow * D + d];
+        if (x >= 0.0 && x < lim && !(use_mask && mask[orow])) c = (int)x;
+      }
+      cnt[r * CS + d] = c;
+    }
+    __syncthreads();
+    // g of each row, once: the logfact reads of four columns overlap, the adds stay in ascending d.  An absent column
+    // adds +0.0, which leaves every value g (and s below) can hold unchanged: both start at +0.0, and in
+    // round-to-nearest a sum or difference is -0.0 only when the running value already is.
+    if (tid < nr) {
+      const int* __restrict__ cr = cnt + tid * CS;
+      double g = 0.0;
+      for (int d0 = 0; d0 < DP; d0 += 4) {
+        double t[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int c = cr[d0 + j];
+          const double v = logfact[c < 0 ? 0 : c];
+          t[j] = c < 0 ? 0.0 : v;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) g = g + t[j];
+      }
+      gs[tid] = g;
+    }
+    __syncthreads();
+    for (int r = w; r < nr; r += 4) {
+      const int* __restrict__ cr = cnt + r * CS;
+      const double g = gs[r];
+      for (int k = lane; k < K; k += 64) {
+        double s = 0.0;
+        for (int d0 = 0; d0 < DP; d0 += 4) {
+          double p[4], e[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const int c = __builtin_amdgcn_readfirstlane(cr[d0 + j]);     // the row's entry: one value for the wave
+            const double2 v = T[(size_t)(c < 0 ? D : d0 + j) * K + k];
+            p[j] = (double)(c < 0 ? 0 : c) * v.x;
+            e[j] = v.y;
+          }
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            s = s + p[j];
+            s = s - e[j];
+          }
+        }
+        ll[(base + r) * K + k] = s - g;
+      }
+    }
+  }
+}
+#endif  // SVIHMM_POISSON_EMISSION
+
+#ifdef SVIHMM_POISSON_STATS
+// Workgroup (blockIdx.x = row chunk, .y = group of 64 MT features, .z = group of 64 states), 4 waves; wave w owns
+// the feature tiles 4 m + w (m < MT) of its group against the four state tiles: the scheme, the operand layout and
+// the posterior staging of k_stats_onehot (kernels_mcat.h, included before this file).
+// A operand of feature f for row r: (double)c_rf for f < D, 1.0 for D <= f < 2 D, either 0.0 when the entry is absent,
+// the row masked or beyond the chunk.  A row that is masked, or whose every entry is absent, is staged with zero
+// posteriors (k_stats_onehot's rule): a NaN or Inf a svihmm_suffstats caller left there stays out.
+// LDS: [ q MC_RB * MC_QS doubles | row records MC_RB * 2 int64 | row-has-a-present-entry MC_RB ints | counts MC_RB * (D | 1) ints ]
+template <int MT>
+__global__ __launch_bounds__(256) void k_stats_poisson(
+    const double* __restrict__ obs, const uint8_t* __restrict__ mask, const int64_t* __restrict__ starts,
+    int64_t nrows, int Lm, int K, int Kp, int D, int C, const double* __restrict__ q, int64_t rows_per_chunk,
+    int Lq, int off, double* __restrict__ partc) {
+  extern __shared__ __attribute__((aligned(16))) char po_smem[];
+  double* qs = (double*)po_smem;
+  McRow* rows = (McRow*)(po_smem + (size_t)MC_RB * MC_QS * sizeof(double));
+  int* present = (int*)(po_smem + (size_t)MC_RB * MC_QS * sizeof(double) + MC_RB * sizeof(McRow));
+  int* cnt = present + MC_RB;
+  const int DS = D | 1;            // (odd row stride of the counts)
+  const int F = 2 * D;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int li = lane & 15, lg = lane >> 4;
+  const int kbase = 64 * blockIdx.z;
+  const int fbase = 64 * MT * blockIdx.y;
+  const double lim = (double)(C + 1);
+  // this lane's feature of each tile: its column, and what a present entry contributes (the count, or one)
+  int myd[MT];
+  bool issx[MT];
+  double one[MT];
+#pragma unroll
+  for (int m = 0; m < MT; ++m) {
+    const int f = fbase + 16 * (4 * m + w) + li;
+    myd[m] = f < D ? f : f < F ? f - D : 0;
+    issx[m] = f < D;
+    one[m] = (f >= D && f < F) ? 1.0 : 0.0;
+  }
+  typedef MF<double>::v4 v4;
+  v4 acc[MT][4];
+#pragma unroll
+  for (int m = 0; m < MT; ++m)
+#pragma unroll
+    for (int n = 0; n < 4; ++n) acc[m][n] = v4{0.0, 0.0, 0.0, 0.0};
+  const int64_t c0 = (int64_t)blockIdx.x * rows_per_chunk;
+  const int64_t c1 = imin64(nrows, c0 + rows_per_chunk);
+  for (int64_t s0 = c0; s0 < c1; s0 += MC_RB) {
+    __syncthreads();                 // (the previous stage is consumed)
+    if (tid < MC_RB) {
+      const int64_t g = s0 + tid;
+      McRow rr = {-1, -1};
+      if (g < c1) {
+        const int64_t bw = g / Lm;
+        const int64_t t = g - bw * Lm;
+        const int64_t orow = starts[bw] + off + t;
+        rr.qrow = bw * Lq + off + t;
+        rr.orow = (mask && mask[orow]) ? -1 : orow;
+      }
+      rows[tid] = rr;
+      present[tid] = 0;
+    }
+    __syncthreads();
+    // posteriors: MC_RB rows x the group's 64 states, loaded now and committed once the counts have said which
+    // rows count (zeros beyond K, beyond the chunk, for masked rows and for rows without a present entry)
+    const int qc = tid & 63;
+    double qreg[MC_RB / 4];
+#pragma unroll
+    for (int i = 0; i < MC_RB / 4; ++i) {
+      const McRow rr = rows[(tid >> 6) + 4 * i];
+      qreg[i] = (rr.orow >= 0 && kbase + qc < K) ? q[rr.qrow * K + kbase + qc] : 0.0;
+    }
+    // counts: -1 for an absent entry and for every entry of a masked / missing row
+    for (int e = tid; e < MC_RB * D; e += 256) {
+      const int r = e / D, d = e - r * D;
+      const int64_t orow = rows[r].orow;
+      int c = -1;
+      if (orow >= 0) {
+        const double x = obs[orow * D + d];
+        if (x >= 0.0 && x < lim) c = (int)x;
+      }
+      cnt[r * DS + d] = c;
+      if (c >= 0) present[r] = 1;        // (every writer stores the same value)
+    }
+    __syncthreads();
+#pragma unroll
+    for (int i = 0; i < MC_RB / 4; ++i) {
+      const int r = (tid >> 6) + 4 * i;
+      qs[r * MC_QS + qc] = present[r] ? qreg[i] : 0.0;
+    }
+    __syncthreads();
+#pragma unroll 2
+    for (int ks = 0; ks < MC_RB / 4; ++ks) {
+      const int r = 4 * ks + lg;
+      double Bv[4];
+#pragma unroll
+      for (int n = 0; n < 4; ++n) Bv[n] = qs[r * MC_QS + 16 * n + li];
+#pragma unroll
+      for (int m = 0; m < MT; ++m) {
+        const int c = cnt[r * DS + myd[m]];
+        const double A = c < 0 ? 0.0 : issx[m] ? (double)c : one[m];
+#pragma unroll
+        for (int n = 0; n < 4; ++n) acc[m][n] = MF<double>::mma(A, Bv[n], acc[m][n]);
+      }
+    }
+  }
+  double* __restrict__ out = partc + (size_t)blockIdx.x * F * Kp;
+#pragma unroll
+  for (int m = 0; m < MT; ++m)
+#pragma unroll
+    for (int n = 0; n < 4; ++n)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int f = fbase + 16 * (4 * m + w) + MF<double>::crow(lg, r);
+        const int k = kbase + 16 * n + li;
+        if (f < F && k < Kp) out[(size_t)f * Kp + k] = acc[m][n][r];
+      }
+}
+#endif  // SVIHMM_POISSON_STATS

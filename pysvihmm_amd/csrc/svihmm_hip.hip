@@ -79,7 +79,7 @@ int svihmm_destroy(svihmm_ctx* h) {
   Buf* bufs[] = {&h->obs, &h->mask, &h->mod_init, &h->ltran, &h->Aexp, &h->AexpT, &h->theta, &h->niw,
                  &h->fab, &h->starts, &h->user_q, &h->user_starts, &h->vit, &h->ll, &h->la, &h->lb, &h->q, &h->lse_part,
                  &h->local_lb, &h->logz, &h->part, &h->packed, &h->scratch, &h->kexp, &h->hx, &h->gx,
-                 &h->zfac, &h->llE, &h->m_ll, &h->m_la, &h->m_lb, &h->chain, &h->chain2, &h->cat_table, &h->mcat_meta, &h->partc, &h->theta_orb, &h->prior, &h->vlb_aux, &h->gen_z,
+                 &h->zfac, &h->llE, &h->m_ll, &h->m_la, &h->m_lb, &h->chain, &h->chain2, &h->cat_table, &h->mcat_meta, &h->pois_logfact, &h->partc, &h->theta_orb, &h->prior, &h->vlb_aux, &h->gen_z,
                  &h->svi_state, &h->svi_prior, &h->svi_work, &h->commtmp, &h->ll0, &h->a0v, &h->a0e,
                  &h->shift_d, &h->uwb, &h->uwd, &h->AexpF, &h->AexpTF, &h->svi_sync, &h->pipe_cnt,
                  &h->pipe_tabs[0].buf, &h->pipe_tabs[1].buf, &h->pipe_tabs[2].buf, &h->pipe_tabs[3].buf,
@@ -119,7 +119,7 @@ static double* svi_ptr(svihmm_ctx* h, int which);
 static int wait_side_streams(svihmm_ctx* h);
 static void sample_center(const svihmm_ctx* h, const double* obs, int64_t T, int D, std::vector<double>& c);
 static int reset_shift(svihmm_ctx* h, const std::vector<double>& c, int64_t row0, int64_t nrows);
-static int shift_rows(svihmm_ctx* h, const double* delta, int64_t row0, int64_t nrows, bool round_symbols);
+static int shift_rows(svihmm_ctx* h, const double* delta, int64_t row0, int64_t nrows, int round_symbols);
 static int store_shift(svihmm_ctx* h, const std::vector<double>& c);
 static int params_follow_centre(svihmm_ctx* h, const double* delta);
 static int drop_auto_status(svihmm_ctx* h);
@@ -218,7 +218,7 @@ static void sample_center(const svihmm_ctx* h, const double* obs, int64_t T, int
   }
 }
 // rows [row0, row0 + nrows) of the resident copy -= delta[D] (host vector)
-static int shift_rows(svihmm_ctx* h, const double* delta, int64_t row0, int64_t nrows, bool round_symbols) {
+static int shift_rows(svihmm_ctx* h, const double* delta, int64_t row0, int64_t nrows, int round_symbols) {
   const int D = h->D;
   bool any = false;
   for (int d = 0; d < D; ++d) any = any || delta[d] != 0.0;
@@ -231,11 +231,16 @@ static int shift_rows(svihmm_ctx* h, const double* delta, int64_t row0, int64_t 
   HIPCK(hipHostGetDevicePointer(&dpin, pin, 0));
   const int64_t n = nrows * (int64_t)D;
   double* base = (double*)h->obs.p + (size_t)row0 * D;
-  if (round_symbols)
-    hipLaunchKernelGGL(k_shift_obs<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, base, n, D,
+  // round_symbols: 0 plain shift, 1 symbols (every entry to the nearest integer), 2 counts (k_shift_obs: entries at an
+  // integer snap to it, fractional ones keep their value)
+  if (round_symbols == 2)
+    hipLaunchKernelGGL(k_shift_obs<2>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, base, n, D,
+                       (const double*)dpin);
+  else if (round_symbols)
+    hipLaunchKernelGGL(k_shift_obs<1>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, base, n, D,
                        (const double*)dpin);
   else
-    hipLaunchKernelGGL(k_shift_obs<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, base, n, D,
+    hipLaunchKernelGGL(k_shift_obs<0>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, base, n, D,
                        (const double*)dpin);
   HIPCK(hipGetLastError());
   CK(pin_release(h, slot));
@@ -310,7 +315,7 @@ static int reset_shift(svihmm_ctx* h, const std::vector<double>& c, int64_t row0
   if ((int)h->shift.size() == h->D)
     for (int d = 0; d < h->D; ++d) delta[d] -= h->shift[d];
   CK(store_shift(h, c));
-  CK(shift_rows(h, c.data(), row0, nrows, false));
+  CK(shift_rows(h, c.data(), row0, nrows, 0));
   return params_follow_centre(h, delta.data());
 }
 
@@ -323,7 +328,7 @@ int svihmm_shift_obs(svihmm_ctx* h, const double* shift) {
   for (int d = 0; d < D; ++d)
     if (!(shift[d] > -1.7e308 && shift[d] < 1.7e308)) return fail("svihmm_shift_obs: shift must be finite");
   CK(wait_side_streams(h));
-  CK(shift_rows(h, shift, 0, h->T, false));
+  CK(shift_rows(h, shift, 0, h->T, 0));
   std::vector<double> c = h->shift;
   c.resize((size_t)D, 0.0);
   for (int d = 0; d < D; ++d) c[d] += shift[d];
@@ -378,7 +383,7 @@ int svihmm_set_obs_rows(svihmm_ctx* h, int64_t row0, int64_t nrows, const double
     sample_center(h, obs, nrows, h->D, c);
     CK(reset_shift(h, c, 0, 0));         // (rows written before this call would be undefined anyway)
   }
-  CK(shift_rows(h, h->shift.data(), row0, nrows, false));
+  CK(shift_rows(h, h->shift.data(), row0, nrows, 0));
   HIPCK(hipStreamSynchronize(h->stream));
   return 0;
 }
@@ -692,12 +697,15 @@ int svihmm_niw_vlb_terms(svihmm_ctx* h, int32_t K, int32_t D, const double* mu, 
 // The resident column holds symbol indices: a centred copy (an upload cannot know the family that
 // will read it; svihmm_shift_obs may have moved it) goes back to exact integers and stays uncentred.
 // Called when the table is set and again in front of every lookup / count launch.
-int cat_uncentre(svihmm_ctx* h) {
+// counts: the family that reads the copy next is the Poisson one (-1: the family in force), whose fractional entries
+// keep their value (k_shift_obs<2>).
+int cat_uncentre(svihmm_ctx* h, int counts) {
   if (h->T > 0) h->center_deferred = true;     // a Gaussian family that follows centres the copy again
   if (!h->shifted || h->T <= 0) return 0;
   std::vector<double> back(h->shift.size());
   for (size_t d = 0; d < back.size(); ++d) back[d] = -h->shift[d];
-  CK(shift_rows(h, back.data(), 0, h->T, true));
+  if (counts < 0) counts = h->emis_pois ? 1 : 0;
+  CK(shift_rows(h, back.data(), 0, h->T, counts ? 2 : 1));
   return store_shift(h, std::vector<double>((size_t)h->D, 0.0));
 }
 // feature table is also needed by the statistics kernels when only host lliks are used
@@ -722,7 +730,7 @@ int svihmm_set_emission_cat(svihmm_ctx* h, int32_t K, int32_t V, const double* l
     for (int v = 0; v < V; ++v) hp[(size_t)v * K + k] = logp[(size_t)k * V + v];
   HIPCK(hipMemcpyAsync(h->cat_table.p, hp, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
   CK(pin_release(h, slot));
-  h->eK = K; h->eD = 1; h->V = V; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16; h->have_emission = true; h->emis_cat = true; h->emis_mcat = false; h->emis_diag = false; h->uw_valid = false;
+  h->eK = K; h->eD = 1; h->V = V; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16; h->have_emission = true; h->emis_cat = true; h->emis_mcat = false; h->emis_pois = false; h->emis_diag = false; h->uw_valid = false;
   return 0;
 }
 // D symbol columns, independent per state (kernels_mcat.h).  The family rides the Categorical branches of the host
@@ -775,7 +783,69 @@ int svihmm_set_emission_mcat(svihmm_ctx* h, int32_t K, int32_t D, const int32_t*
   HIPCK(hipMemcpyAsync(h->mcat_meta.p, mp, nmeta * sizeof(int), hipMemcpyHostToDevice, h->stream));
   CK(pin_release(h, slot));
   h->eK = K; h->eD = D; h->V = F; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16;
-  h->have_emission = true; h->emis_cat = true; h->emis_mcat = true; h->emis_diag = false; h->uw_valid = false;
+  h->have_emission = true; h->emis_cat = true; h->emis_mcat = true; h->emis_pois = false; h->emis_diag = false; h->uw_valid = false;
+  return 0;
+}
+// D count columns, independent Poisson rates per state (kernels_poisson.h).  The family rides the Categorical branches
+// of the host code (emis_cat) with V = 2 D statistics rows [sx | n]; only the lookup and the statistics launches
+// differ (emis_pois).
+int svihmm_set_emission_poisson(svihmm_ctx* h, int32_t K, int32_t D, const double* elog, const double* erate,
+                                const double* logfact, int32_t C) {
+  if (!h) return fail("svihmm_set_emission_poisson: handle is NULL");
+  if (!elog || !erate || !logfact) return fail("svihmm_set_emission_poisson: elog, erate and logfact must not be NULL");
+  if (K < 1 || K > 256) return fail("svihmm_set_emission_poisson: K = " + std::to_string(K) + " outside [1, 256]");
+  if (D < 1 || D > SVIHMM_POISSON_MAX_D)
+    return fail("svihmm_set_emission_poisson: D = " + std::to_string(D) + " outside [1, SVIHMM_POISSON_MAX_D = " +
+                std::to_string(SVIHMM_POISSON_MAX_D) + "]");
+  if (C < 0 || C > SVIHMM_POISSON_MAX_COUNT)
+    return fail("svihmm_set_emission_poisson: C = " + std::to_string(C) + " outside [0, SVIHMM_POISSON_MAX_COUNT = " +
+                std::to_string(SVIHMM_POISSON_MAX_COUNT) + "]");
+  auto finite = [](double v) { return v > -1.7e308 && v < 1.7e308; };
+  const size_t n = (size_t)K * D;
+  for (size_t i = 0; i < n; ++i) {
+    if (!finite(elog[i]))
+      return fail("svihmm_set_emission_poisson: elog[" + std::to_string(i / D) + "][" + std::to_string(i % D) + "] is not finite");
+    if (!finite(erate[i]))
+      return fail("svihmm_set_emission_poisson: erate[" + std::to_string(i / D) + "][" + std::to_string(i % D) + "] is not finite");
+  }
+  const size_t nlf = (size_t)C + 1;
+  for (size_t c = 0; c < nlf; ++c)
+    if (!finite(logfact[c])) return fail("svihmm_set_emission_poisson: logfact[" + std::to_string(c) + "] is not finite");
+  CK(set_device(h));
+  h->lin_stale = true;
+  h->center_pending = false;
+  // (the resident SVI loop does not know this family: a running loop ends with this upload)
+  if (h->svi_active) CK(svi_flush_elbo(h));
+  h->svi_active = false;
+  if (h->vlb_pending) { HIPCK(hipStreamWaitEvent(h->stream, h->svi_ed, 0)); h->vlb_pending = false; }
+  CK(drop_auto_status(h));
+  CK(cat_uncentre(h, 1));
+  // the logfact table changes only with C: the device copy stays while the caller's holds the same bits
+  const bool lf_new = h->pois_lf_host.size() != nlf || std::memcmp(h->pois_lf_host.data(), logfact, nlf * sizeof(double)) != 0;
+  const size_t nt = 2 * (n + (size_t)K);     // [D + 1][K] pairs (elog, erate); row D, all +0.0, is what an absent column reads
+  CK(ensure(h->cat_table, nt * sizeof(double)));
+  if (lf_new) CK(ensure(h->pois_logfact, nlf * sizeof(double)));
+  void* pin = nullptr;
+  int slot = 0;
+  CK(pinned(h, (nt + (lf_new ? nlf : 0)) * sizeof(double), &pin, &slot));
+  double* hp = (double*)pin;
+  for (int k = 0; k < K; ++k) {            // transposed: a column's states are contiguous
+    for (int d = 0; d < D; ++d) {
+      hp[2 * ((size_t)d * K + k)] = elog[(size_t)k * D + d];
+      hp[2 * ((size_t)d * K + k) + 1] = erate[(size_t)k * D + d];
+    }
+    hp[2 * ((size_t)D * K + k)] = hp[2 * ((size_t)D * K + k) + 1] = 0.0;
+  }
+  HIPCK(hipMemcpyAsync(h->cat_table.p, hp, nt * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  if (lf_new) {
+    std::memcpy(hp + nt, logfact, nlf * sizeof(double));
+    h->pois_lf_host.clear();             // (stays empty if the copy below fails)
+    HIPCK(hipMemcpyAsync(h->pois_logfact.p, hp + nt, nlf * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    h->pois_lf_host.assign(logfact, logfact + nlf);
+  }
+  CK(pin_release(h, slot));
+  h->eK = K; h->eD = D; h->V = 2 * D; h->pois_C = C; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16;
+  h->have_emission = true; h->emis_cat = true; h->emis_mcat = false; h->emis_pois = true; h->emis_diag = false; h->uw_valid = false;
   return 0;
 }
 int64_t svihmm_packed_len(svihmm_ctx* h) { return h ? (int64_t)packed_len(h) : 0; }
@@ -1291,6 +1361,8 @@ int svihmm_pred_logprob(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t
   if (flags & SVIHMM_USE_HOST_LLIKS) return fail("svihmm_pred_logprob: NIW emission only");
   if (h->have_emission && h->emis_mcat)
     return fail("svihmm_pred_logprob: NIW emission only (the multi-column Categorical family of svihmm_set_emission_mcat is not taken)");
+  if (h->have_emission && h->emis_pois)
+    return fail("svihmm_pred_logprob: NIW emission only (the Poisson family of svihmm_set_emission_poisson is not taken)");
   CK(set_device(h));
   if (!h->have_mask) { out2[0] = NAN; out2[1] = 0.0; return 0; }
   const int var = pick_fb(h, B, Lm, false);
@@ -1866,7 +1938,7 @@ static int svi_refresh_emission(svihmm_ctx* h, int elbo_it, int lb_slot, hipEven
                        (double*)h->cat_table.p, tsy);
     HIPCK(hipGetLastError());
     h->eK = K; h->eD = 1; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16;
-    h->have_emission = true; h->emis_cat = true; h->emis_mcat = false; h->emis_diag = false; h->uw_valid = false;
+    h->have_emission = true; h->emis_cat = true; h->emis_mcat = false; h->emis_pois = false; h->emis_diag = false; h->uw_valid = false;
   }
   h->theta_sy = SviSync{};
   h->lin_stale = true;
@@ -2208,6 +2280,9 @@ int svihmm_svi_iteration(svihmm_ctx* h, int32_t it, const int64_t* starts, int32
   if (h && !h->svi_active && h->have_emission && h->emis_mcat)
     return fail("svihmm_svi_iteration: the resident SVI loop does not take the multi-column Categorical family "
                 "(svihmm_set_emission_mcat); step the globals on the host from svihmm_estep_minibatch's statistics");
+  if (h && !h->svi_active && h->have_emission && h->emis_pois)
+    return fail("svihmm_svi_iteration: the resident SVI loop does not take the Poisson family "
+                "(svihmm_set_emission_poisson); step the globals on the host from svihmm_estep_minibatch's statistics");
   if (!h || !h->svi_active) return fail("svihmm_svi_iteration: call svihmm_svi_begin first");
   if (it < 0 || it >= h->svi_maxit) return fail("svihmm_svi_iteration: iteration index out of range");
   if (B < 0 || (B > 0 && !starts) || nwin_total < B) return fail("svihmm_svi_iteration: bad window batch");

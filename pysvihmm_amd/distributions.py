@@ -30,7 +30,7 @@ import numpy as np
 import scipy.linalg as sla
 from scipy.special import digamma, gammaln
 
-__all__ = ["Gaussian", "DiagonalGaussian", "Categorical", "ProductCategorical", "sample_niw", "sample_invwishart",
+__all__ = ["Gaussian", "DiagonalGaussian", "Categorical", "ProductCategorical", "ProductPoisson", "sample_niw", "sample_invwishart",
            "niw_quadratic_form", "niw_vlb_batch", "niw_prior_logpart", "vlb_logz_sign"]
 
 
@@ -593,3 +593,113 @@ class ProductCategorical(object):
             logpi_q = gammaln(a.sum()) - gammaln(a).sum() + ((a - 1) * el).sum()
             tot += logpi_p - logpi_q
         return tot
+
+
+_LOGFACT = {}
+
+
+def _logfact_table(max_count):
+    """``gammaln(c + 1)`` for c = 0..max_count, built once per ``max_count`` (the last few are kept)."""
+    tab = _LOGFACT.get(max_count)
+    if tab is None:
+        if len(_LOGFACT) >= 4:
+            _LOGFACT.clear()
+        tab = _LOGFACT[max_count] = gammaln(np.arange(max_count + 1, dtype=np.float64) + 1.0)
+    return tab
+
+
+class ProductPoisson(object):
+    """D independent Gamma-Poisson factors, one per observation column:
+    ``p(x | lambda) = prod_d Poisson(x[d] | lambda_d)`` with priors ``Gamma(alpha_0[d], beta_0[d])``
+    (shape, rate) and mean-field factors ``Gamma(alpha_mf[d], beta_mf[d])``.  An entry of a row is
+    *present* when it is not NaN and ``0 <= x < max_count + 1``, and counts as ``int(x)``; an absent
+    entry is skipped, the row's other columns are not affected."""
+
+    def __init__(self, alpha_0, beta_0, alpha_mf=None, beta_mf=None, max_count=4095):
+        self.alpha_0 = np.array(alpha_0, float).ravel()
+        self.beta_0 = np.array(beta_0, float).ravel()
+        self.D = len(self.alpha_0)
+        self.max_count = int(max_count)
+        if self.D < 1 or len(self.beta_0) != self.D:
+            raise ValueError("ProductPoisson: alpha_0 and beta_0 need one entry per column, at least one column")
+        if self.max_count < 0:
+            raise ValueError("ProductPoisson: max_count must not be negative")
+        if (alpha_mf is None) != (beta_mf is None):
+            raise ValueError("ProductPoisson: give alpha_mf and beta_mf together")
+        if alpha_mf is None:
+            # a draw of the rates from the prior, held with the prior's strength
+            lam = np.random.gamma(self.alpha_0, 1. / self.beta_0)
+            alpha_mf, beta_mf = np.maximum(lam, 1e-8) * self.beta_0, self.beta_0
+        self._set_mf(alpha_mf, beta_mf)
+        if len(self._alpha_mf) != self.D or len(self._beta_mf) != self.D:
+            raise ValueError("ProductPoisson: alpha_mf / beta_mf do not match alpha_0's shape")
+
+    @property
+    def alpha_mf(self):
+        return self._alpha_mf
+
+    @property
+    def beta_mf(self):
+        return self._beta_mf
+
+    def num_parameters(self):
+        return self.D
+
+    def rvs(self, size=None):
+        shape = (self.D,) if size is None else tuple(np.atleast_1d(size)) + (self.D,)
+        return np.random.poisson(self.rates, size=shape).astype(float)
+
+    def _present(self, x):
+        """``(c int[n, D], ok bool[n, D])``: truncated counts (0 where absent) and presence."""
+        x = np.asarray(x, dtype=float)
+        x = x.reshape(x.shape[0], -1) if x.ndim != 1 else x.reshape(-1, 1)
+        if x.shape[1] != self.D:
+            raise ValueError("ProductPoisson: data has %d columns, the factor has %d" % (x.shape[1], self.D))
+        with np.errstate(invalid="ignore"):
+            ok = (x >= 0.0) & (x < float(self.max_count + 1))
+        return np.where(ok, x, 0.0).astype(np.int64), ok
+
+    def expected_tables(self):
+        """``(elog[D], erate[D])``: ``E_q log lambda_d = psi(a) - log(b)`` and ``E_q lambda_d = a / b``."""
+        return digamma(self._alpha_mf) - np.log(self._beta_mf), self._alpha_mf / self._beta_mf
+
+    def _get_weighted_statistics(self, data, weights):
+        c, ok = self._present(data)
+        w = np.asarray(weights, float).ravel()[:, None] * ok
+        return (w * c).sum(0), w.sum(0)
+
+    def _posterior_hypparams(self, sx, n):
+        return self.alpha_0 + np.asarray(sx, float), self.beta_0 + np.asarray(n, float)
+
+    def _set_mf(self, alpha, beta):
+        self._alpha_mf = np.array(alpha, float).ravel()
+        self._beta_mf = np.array(beta, float).ravel()
+        self.rates = self._alpha_mf / self._beta_mf
+
+    def meanfieldupdate(self, data, weights):
+        self._set_mf(*self._posterior_hypparams(*self._get_weighted_statistics(data, weights)))
+
+    def expected_log_likelihood(self, x):
+        """``s - g`` of the present columns in ascending d, ``s`` taking ``c * elog[d]`` (one rounded
+        multiply) and then ``- erate[d]``, ``g`` taking ``gammaln(c + 1)``; NaN where no column is
+        present (``nan_to_num`` then gives the 0 a missing row contributes)."""
+        c, ok = self._present(x)
+        elog, erate = self.expected_tables()
+        logfact = _logfact_table(self.max_count)
+        s = np.zeros(c.shape[0])
+        g = np.zeros(c.shape[0])
+        for d in range(self.D):
+            p = c[:, d].astype(np.float64) * elog[d]
+            s = np.where(ok[:, d], s + p, s)
+            s = np.where(ok[:, d], s - erate[d], s)
+            g = np.where(ok[:, d], g + logfact[c[:, d]], g)
+        out = s - g
+        out[~ok.any(1)] = np.nan
+        return out
+
+    def get_vlb(self):
+        """``- sum_d KL(Gamma(a_d, b_d) || Gamma(a0_d, b0_d))``."""
+        a, b, a0, b0 = self._alpha_mf, self._beta_mf, self.alpha_0, self.beta_0
+        kl = ((a - a0) * digamma(a) - gammaln(a) + gammaln(a0) + a0 * (np.log(b) - np.log(b0))
+              + a * (b0 - b) / b)
+        return -kl.sum()

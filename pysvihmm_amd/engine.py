@@ -86,8 +86,28 @@ class PackedMCatStats(object):
         return K * K + K * int(sum(Vs)) + 1
 
 
+class PackedPoissonStats(object):
+    """View of the packed statistics of a Poisson E-step ``[A_raw K*K | stat K*2D | lb]``,
+    ``stat[k] = [sx[k] D | n[k] D]``: ``sx[k, d]`` = sum of var_x[t, k] * count and ``n[k, d]`` = sum of
+    var_x[t, k], both over the unmasked rows whose entry d is present; ``flat`` is the whole ``[K, 2D]`` block."""
+
+    def __init__(self, buf, K, D):
+        self.buf, self.K, self.D = buf, K, D
+        self.A_raw = buf[:K * K].reshape(K, K)
+        self.flat = buf[K * K:K * K + 2 * K * D].reshape(K, 2 * D)
+        self.sx = self.flat[:, :D]
+        self.n = self.flat[:, D:]
+        self.lb = buf[K * K + 2 * K * D:K * K + 2 * K * D + 1]
+
+    @staticmethod
+    def size(K, D):
+        return K * K + 2 * K * D + 1
+
+
 def rewrap_packed(st, buf):
     """A view of ``st``'s type and shape over another buffer (sums / multiples of packed statistics)."""
+    if isinstance(st, PackedPoissonStats):
+        return PackedPoissonStats(buf, st.K, st.D)
     if isinstance(st, PackedMCatStats):
         return PackedMCatStats(buf, st.K, st.Vs)
     return type(st)(buf, st.K, getattr(st, "V", None) if hasattr(st, "counts") else st.D)
@@ -112,6 +132,7 @@ class HipEngine(object):
         self.T = self.D = self.K = 0
         self.V = 0            # > 0: Categorical emission with V symbols is active
         self.Vs = None        # multi-column Categorical emission is active: the columns' symbol counts
+        self.pois = 0         # Poisson count emission is active: its D
         self.diag = False     # diagonal-Gaussian emission is active (its own packed layout)
         self._comm = False
         self.seq_off = None   # offsets declared with set_sequences (every upload of rows removes them)
@@ -271,6 +292,7 @@ class HipEngine(object):
         self.V = 0
         self.diag = False
         self.Vs = None
+        self.pois = 0
         if check:
             L.check(self._lib.svihmm_sync(self._h), "svihmm_set_emission_niw")
 
@@ -287,6 +309,7 @@ class HipEngine(object):
         self.V = 0
         self.diag = True
         self.Vs = None
+        self.pois = 0
         if check:
             L.check(self._lib.svihmm_sync(self._h), "svihmm_set_emission_diag")
 
@@ -449,6 +472,8 @@ class HipEngine(object):
         return (self._wrap_packed(out) if read else None), seq_lb, q0[:self.K]
 
     def _packed_len(self):
+        if self.pois:
+            return PackedPoissonStats.size(self.K, self.pois)
         if self.Vs:
             return PackedMCatStats.size(self.K, self.Vs)
         if self.V:
@@ -456,6 +481,8 @@ class HipEngine(object):
         return PackedDiagStats.size(self.K, self.D) if self.diag else PackedStats.size(self.K, self.D)
 
     def _wrap_packed(self, buf):
+        if self.pois:
+            return PackedPoissonStats(buf, self.K, self.pois)
         if self.Vs:
             return PackedMCatStats(buf, self.K, self.Vs)
         if self.V:
@@ -471,6 +498,7 @@ class HipEngine(object):
         self.V = V
         self.diag = False
         self.Vs = None
+        self.pois = 0
 
     def set_emission_mcat(self, tables):
         """Multi-column Categorical emissions (``svihmm_set_emission_mcat``): ``tables`` is a list of D
@@ -488,6 +516,31 @@ class HipEngine(object):
         self.V = 0
         self.diag = False
         self.Vs = tuple(int(v) for v in Vs)
+        self.pois = 0
+
+    def set_emission_poisson(self, elog, erate, max_count):
+        """Poisson count emissions (``svihmm_set_emission_poisson``): ``elog[k, d] = psi(a) - log(b)`` and
+        ``erate[k, d] = a / b`` of the Gamma factors; obs is ``[T, D]`` counts, an entry present when
+        ``0 <= x < max_count + 1``.  The ``gammaln(c + 1)`` table is built once per ``max_count``.
+        Statistics then come back as ``PackedPoissonStats``."""
+        self._pre_mutate()
+        elog, erate = L.as_f64(elog), L.as_f64(erate)
+        if elog.ndim != 2 or erate.shape != elog.shape:
+            raise RuntimeError("set_emission_poisson: elog and erate must be [K, D] arrays of one shape")
+        C_ = int(max_count)
+        if not 0 <= C_ <= L.POISSON_MAX_COUNT:
+            raise RuntimeError("set_emission_poisson: max_count = %d outside [0, %d]" % (C_, L.POISSON_MAX_COUNT))
+        if getattr(self, "_logfact_C", None) != C_:
+            from scipy.special import gammaln
+            self._logfact = np.ascontiguousarray(gammaln(np.arange(C_ + 1, dtype=np.float64) + 1.0))
+            self._logfact_C = C_
+        K, D = elog.shape
+        L.check(self._lib.svihmm_set_emission_poisson(self._h, K, D, L.dptr(elog), L.dptr(erate),
+                                                      L.dptr(self._logfact), C_), "svihmm_set_emission_poisson")
+        self.V = 0
+        self.diag = False
+        self.Vs = None
+        self.pois = D
 
     def pred_logprob(self, starts, Lm, flags=L.MASK_AS_NAN):
         """Mean predictive log-probability of the masked rows of the windows and their number
@@ -692,6 +745,7 @@ class HipEngine(object):
         self.K, self.V = K, 0
         self.diag = False
         self.Vs = None
+        self.pois = 0
         self._svi_shape = (K, D)
         self._svi_family = "niw"
 
@@ -710,6 +764,7 @@ class HipEngine(object):
         self.K, self.V = K, 0
         self.diag = True
         self.Vs = None
+        self.pois = 0
         self._svi_shape = (K, D)
         self._svi_family = "diag"
 
@@ -727,6 +782,7 @@ class HipEngine(object):
         self.K, self.V = K, V
         self.diag = False
         self.Vs = None
+        self.pois = 0
         self._svi_shape = (K, V)
         self._svi_family = "cat"
 

@@ -263,8 +263,8 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         it, else one ``estep([off], len)`` per sequence with the sums formed here."""
         if not self._device_family():
             raise RuntimeError("several sequences need an emission family the device evaluates "
-                               "(NIW / diagonal Gaussian, Categorical, multi-column Categorical on an engine "
-                               "with set_emission_mcat): host lliks are not supported")
+                               "(NIW / diagonal Gaussian, Categorical, multi-column Categorical or Poisson on an "
+                               "engine with set_emission_mcat / _poisson): host lliks are not supported")
         self._psi_expectations()
         self._upload_obs()
         self._push_globals()
@@ -297,8 +297,8 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         ``estep([off], len)`` per listed sequence with the sums formed here.  No per-row attribute is set."""
         if not self._device_family():
             raise RuntimeError("several sequences need an emission family the device evaluates "
-                               "(NIW / diagonal Gaussian, Categorical, multi-column Categorical on an engine "
-                               "with set_emission_mcat): host lliks are not supported")
+                               "(NIW / diagonal Gaussian, Categorical, multi-column Categorical or Poisson on an "
+                               "engine with set_emission_mcat / _poisson): host lliks are not supported")
         self._psi_expectations()
         self._upload_obs()
         self._push_globals()
@@ -379,10 +379,24 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
                 and len(V) <= L.MCAT_MAX_D and sum(V) <= L.MCAT_MAX_F
                 and hasattr(self.engine, "set_emission_mcat"))
 
+    def _poisson_fastpath(self):
+        """Poisson count emissions (``ProductPoisson``: D count columns, independent given the state) on
+        an engine that has the family: the device keeps the (E log lambda, E lambda) tables and sums
+        counts per column.  Other engines keep the host-lliks route."""
+        from .distributions import ProductPoisson
+        ve = self.var_emit
+        if not all(type(e) is ProductPoisson for e in ve) or len(ve) < 1:
+            return False
+        D, C = ve[0].D, ve[0].max_count
+        return (all(e.D == D and e.max_count == C for e in ve)
+                and self.obs.ndim == 2 and self.obs.shape[1] == D
+                and D <= L.POISSON_MAX_D and C <= L.POISSON_MAX_COUNT
+                and hasattr(self.engine, "set_emission_poisson"))
+
     def _device_family(self):
         """Whether the device evaluates the emitters' family itself (no host lliks)."""
         return (self._niw_fastpath() or self._diag_fastpath() or self._cat_fastpath()
-                or self._mcat_fastpath())
+                or self._mcat_fastpath() or self._poisson_fastpath())
 
     def _prior_arrays(self):
         """Stacked NIW prior hyperparameters (mu_0 [K,D], sigma_0 [K,D,D], kappa_0 [K], nu_0 [K]).
@@ -451,6 +465,12 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
             # D symbol columns: one E log theta table [K, V_d] per column, looked up and added on the device
             per_state = [e.expected_log_tables() for e in self.var_emit]
             self.engine.set_emission_mcat([np.stack([t[d] for t in per_state]) for d in range(len(per_state[0]))])
+            return L.MASK_AS_NAN if nan_mask else 0
+        if self._poisson_fastpath():
+            # D count columns: (E log lambda, E lambda) per state and column, multiplied and added on the device
+            tabs = [e.expected_tables() for e in self.var_emit]
+            self.engine.set_emission_poisson(np.stack([t[0] for t in tabs]), np.stack([t[1] for t in tabs]),
+                                             self.var_emit[0].max_count)
             return L.MASK_AS_NAN if nan_mask else 0
         obs = self.obs if self.obs.ndim == 2 else self.obs[:, None]
         if windows is None:
@@ -569,7 +589,7 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         self._q0 = self.engine.read_rows("var_x", 0, 1)[0]
         return st
 
-    def _batch_stats_route(self, literal_global_update, families=("niw", "diag", "cat", "mcat")):
+    def _batch_stats_route(self, literal_global_update, families=("niw", "diag", "cat", "mcat", "poisson")):
         """Whether the host loop of a batch class (a ``local_update`` override, or
         ``infer(fused=False)``) may take the statistics of ``self.var_x`` on the device instead of
         the literal ``global_update``: only where that method is the class's own and the engine and
@@ -579,7 +599,7 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         if not hasattr(self.engine, "suffstats"):
             return False
         fam = {"niw": self._niw_fastpath, "diag": self._diag_fastpath, "cat": self._cat_fastpath,
-               "mcat": self._mcat_fastpath}
+               "mcat": self._mcat_fastpath, "poisson": self._poisson_fastpath}
         return any(fam[f]() for f in families)
 
     def _batch_suffstats(self):

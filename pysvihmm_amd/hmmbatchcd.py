@@ -134,6 +134,12 @@ class VBHMM(VariationalHMMBase):
                 G = self.var_emit[k]
                 G._set_alpha(G._posterior_hypparams([c[k] for c in st.col_counts]))
             return
+        if hasattr(st, "sx"):
+            # Poisson emitters: Gamma(alpha_0 + sx[k], beta_0 + n[k]) per column
+            for k in range(self.K):
+                G = self.var_emit[k]
+                G._set_mf(*G._posterior_hypparams(st.sx[k], st.n[k]))
+            return
         if hasattr(st, "xsq"):
             # diagonal family: meanfieldupdate(obs[inds], q[inds, k]) from (n, sum q x, sum q x^2)
             for k in range(self.K):

@@ -11,7 +11,7 @@ import time
 import numpy as np
 
 from .hmmbase import VariationalHMMBase, is_niw_gaussian, is_diag_gaussian
-from .distributions import ProductCategorical
+from .distributions import ProductCategorical, ProductPoisson
 from .engine import rewrap_packed
 from . import util
 
@@ -152,6 +152,11 @@ class VBHMM(VariationalHMMBase):
                 new = stats_for_k(G, k)
                 G._set_alpha([(1. - lrate) * a + lrate * b for a, b in zip(G.alpha_mf, new)])
                 continue
+            if type(G) is ProductPoisson:
+                # Gamma factors: the natural parameters are (a - 1, -b), so the blend is linear in (a, b)
+                a, b = stats_for_k(G, k)
+                G._set_mf((1. - lrate) * G.alpha_mf + lrate * a, (1. - lrate) * G.beta_mf + lrate * b)
+                continue
             if is_diag_gaussian(G):
                 # the same blend in the diagonal family's natural parameters (the reference's
                 # NIW arithmetic, util.py:28-60, has no counterpart for it)
@@ -192,6 +197,8 @@ class VBHMM(VariationalHMMBase):
         def from_stats(G, k):
             if hasattr(st, "col_counts"):
                 return G._posterior_hypparams([c[k] for c in st.col_counts])
+            if hasattr(st, "sx"):
+                return G._posterior_hypparams(st.sx[k], st.n[k])
             if hasattr(st, "xsq"):
                 return G._posterior_hypparams(st.neff[k], st.xbar[k], st.xsq[k])
             if not is_niw_gaussian(G):
@@ -218,7 +225,7 @@ class VBHMM(VariationalHMMBase):
         inds = np.logical_not(self.mask)
         def from_rows(G, k):
             x, w = batch[inds, :], self.var_x[inds, k]
-            if is_diag_gaussian(G) or type(G) is ProductCategorical:
+            if is_diag_gaussian(G) or type(G) in (ProductCategorical, ProductPoisson):
                 return G._posterior_hypparams(*G._get_weighted_statistics(x, w))
             return util.NIW_meanfield(G, x, w)
         self._natgrad_emissions(lrate, from_rows)

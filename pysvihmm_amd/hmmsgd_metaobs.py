@@ -96,6 +96,10 @@ class VBHMM(VariationalHMMBase):
         # route of every plugin it does not know (host lliks through expected_log_likelihood)
         return False
 
+    def _poisson_fastpath(self):
+        # nor the Poisson family: ProductPoisson emitters keep host lliks as well
+        return False
+
     @staticmethod
     def make_param_dict(prior_init, prior_tran, prior_emit, tau=tau0,
                         kappa=kappa0, metaobs_half=metaobs_half0, mb_sz=mb_sz0,
