@@ -35,7 +35,8 @@
 extern "C" {
 #endif
 
-/* 3 (addition, nothing else changed meaning): svihmm_estep_sequence_subset.
+/* 3 (addition, nothing else changed meaning): svihmm_svi_begin_mcat, svihmm_svi_begin_poisson.
+ * 3 (addition, nothing else changed meaning): svihmm_estep_sequence_subset.
  * 3 (addition, nothing else changed meaning): svihmm_viterbi_sequences, svihmm_ffbs_sequences.
  * 3 (addition, nothing else changed meaning): svihmm_set_sequences, svihmm_estep_sequences.
  * 3 (addition, nothing else changed meaning): svihmm_grow_windows.
@@ -463,7 +464,7 @@ int svihmm_svi_iteration(svihmm_ctx* h, int32_t it, const int64_t* starts, int32
  * svihmm_svi_begin_cat: Categorical emitters over ONE integer-valued observation column (D = 1),
  *   Dirichlet factors alpha[K][V] and prior alpha0[K][V]: global step hmmsgd_metaobs.py:1071-1084 with
  *   every window's alpha_0 + counts - 1 (:907-926), the E log theta table rebuilt on the device.
- * svihmm_svi_iteration / svihmm_svi_read_elbo / svihmm_svi_set_adagrad work for all three;
+ * svihmm_svi_iteration / svihmm_svi_read_elbo / svihmm_svi_set_adagrad work for every family;
  * svihmm_svi_read_factors hands back the state in the family's block layout (NIW: [mu | sigma |
  * kappa | nu]; any of the three pointers may be NULL). */
 int svihmm_svi_begin_diag(svihmm_ctx* h, int32_t K, int32_t D, const double* prior_tran, const double* var_tran,
@@ -471,6 +472,36 @@ int svihmm_svi_begin_diag(svihmm_ctx* h, int32_t K, int32_t D, const double* pri
 int svihmm_svi_begin_cat(svihmm_ctx* h, int32_t K, int32_t V, const double* prior_tran, const double* var_tran,
                          const double* alpha0, const double* alpha, int32_t maxit);
 int svihmm_svi_read_factors(svihmm_ctx* h, double* var_tran, double* var_init, double* factors_out);
+/* The same loop for the two table-driven families (declared here, described with svihmm_set_emission_mcat /
+ * svihmm_set_emission_poisson below, whose K, D, V, F and C limits, feature offsets and presence rules they share):
+ * svihmm_svi_begin_mcat: distributions.ProductCategorical, D Dirichlet factors per state; alpha0 / alpha [K][F],
+ *   feature off_d + v.  Per element the Categorical rule of svihmm_svi_begin_cat,
+ *     alpha' = ((1 - rho)(alpha - 1) + (rho bE)(nwin (alpha0 - 1) + counts)) + 1
+ *   (every window contributes alpha0 + counts - 1 per column, hmmsgd_metaobs.py:907-926, 1071-1084): a D = 1 model
+ *   steps like svihmm_svi_begin_cat bit for bit.  ELBO term: the sum over the columns of the Dirichlet term.
+ * svihmm_svi_begin_poisson: distributions.ProductPoisson, Gamma factors; prior_blk = [a0 | b0], factor_blk = [a | b],
+ *   each [K][D]; logfact[c] = lgamma(c + 1), c = 0..C, as for svihmm_set_emission_poisson.  The Gaussian branch's
+ *   blend (hmmsgd_metaobs.py:1050-1069, the prior once) in the Gamma natural parameters (a - 1, -b):
+ *     a' = (1 - rho) a + rho (a0 + bE sx[k][d]),   b' = (1 - rho) b + rho (b0 + bE n[k][d]),
+ *   positive for every rho in [0, 1].  ELBO term: -sum_d KL(Gamma(a, b) || Gamma(a0, b0)).
+ * Both fail with a message before any state is touched -- the handle and a loop begun earlier stay as they were --
+ * on: a NULL pointer; K < 1 or K > 256; D outside the family's range or different from the resident observations';
+ * a V[d] < 1; F > SVIHMM_MCAT_MAX_F; C outside [0, SVIHMM_POISSON_MAX_COUNT]; a non-finite logfact[c]; a Dirichlet or
+ * Gamma parameter that is not > 0.  What svihmm_svi_begin checks of prior_tran / var_tran holds as well.
+ * The E log theta table (k_mcat_table), respectively the (E log lambda, E lambda) pairs (k_pois_table), are rebuilt on
+ * the device every iteration.  svihmm_svi_iteration, _read_elbo, _set_adagrad, _read_adagrad, svihmm_read_globals,
+ * SVIHMM_SVI_KEEP_WINDOW, the inner segment and a communicator's all-reduce work as for the other families;
+ * svihmm_svi_read_factors hands back alpha [K][F], respectively [a | b]; svihmm_svi_read_state refuses (NIW layout).
+ * A svihmm_set_emission_mcat / _poisson upload of the same family and shape (K and V[], respectively K and D) keeps
+ * the loop alive, as svihmm_set_emission_cat does for its family; any other emission upload ends it. */
+int svihmm_svi_begin_mcat(svihmm_ctx* h, int32_t K, int32_t D, const int32_t* V /*[D]*/,
+                          const double* prior_tran, const double* var_tran,
+                          const double* alpha0 /*[K][F]*/, const double* alpha /*[K][F]*/, int32_t maxit);
+int svihmm_svi_begin_poisson(svihmm_ctx* h, int32_t K, int32_t D,
+                             const double* prior_tran, const double* var_tran,
+                             const double* prior_blk /*[a0 | b0], each [K][D]*/,
+                             const double* factor_blk /*[a | b]*/,
+                             const double* logfact /*[C + 1]*/, int32_t C, int32_t maxit);
 /* AdaGrad-scaled transition step (hmmsgd_metaobs.py:179-183 ada_G = ones, :1036-1040
  * ada_G += nats_old^2; adaMatrix = ada_G^.25; nats_new = (1 - 1/adaMatrix) nats_old + A_up/adaMatrix):
  * after svihmm_svi_begin, svihmm_svi_set_adagrad uploads the K x K accumulator (NULL: the plain rho
@@ -517,9 +548,10 @@ int64_t svihmm_packed_len(svihmm_ctx* h);
  * Fails with a message before any device work (the handle stays usable): NULL V or logp; K < 1 or K > 256;
  * D < 1 or D > SVIHMM_MCAT_MAX_D; a V[d] < 1; F > SVIHMM_MCAT_MAX_F; a non-finite table entry; and, at the first
  * E-step-type call, resident observations whose D differs from the family's.
- * Out of scope, each refused with a message: the resident SVI loop (svihmm_svi_begin_* replaces the family;
- * svihmm_svi_iteration refuses), svihmm_pred_logprob (NIW only), the fp32 mode (svihmm_get_precision reports
- * last_batch_f32 = 0), and the device paths of hmmsgd_metaobs.VBHMM (host lliks through the plugin there). */
+ * The resident SVI loop takes the family through svihmm_svi_begin_mcat (above); after this call alone
+ * svihmm_svi_iteration refuses with a message that says so.
+ * Out of scope, each refused with a message: svihmm_pred_logprob (NIW only) and the fp32 mode
+ * (svihmm_get_precision reports last_batch_f32 = 0). */
 #define SVIHMM_MCAT_MAX_D 128
 #define SVIHMM_MCAT_MAX_F 1024
 int svihmm_set_emission_mcat(svihmm_ctx* h, int32_t K, int32_t D, const int32_t* V /*[D]*/,
@@ -554,9 +586,10 @@ int svihmm_set_emission_mcat(svihmm_ctx* h, int32_t K, int32_t D, const int32_t*
  * erate or logfact; K < 1 or K > 256; D < 1 or D > SVIHMM_POISSON_MAX_D; C < 0 or C > SVIHMM_POISSON_MAX_COUNT; a
  * non-finite elog[k][d], erate[k][d] or logfact[c] (the message names the entry); and, at the first E-step-type call,
  * resident observations whose D differs from the family's.
- * Out of scope, each refused with a message: the resident SVI loop (svihmm_svi_begin_* replaces the family;
- * svihmm_svi_iteration refuses), svihmm_pred_logprob (NIW only), the fp32 mode (svihmm_get_precision reports
- * last_batch_f32 = 0), and the device paths of hmmsgd_metaobs.VBHMM (host lliks through the plugin there). */
+ * The resident SVI loop takes the family through svihmm_svi_begin_poisson (above); after this call alone
+ * svihmm_svi_iteration refuses with a message that says so.
+ * Out of scope, each refused with a message: svihmm_pred_logprob (NIW only) and the fp32 mode
+ * (svihmm_get_precision reports last_batch_f32 = 0). */
 #define SVIHMM_POISSON_MAX_D     128
 #define SVIHMM_POISSON_MAX_COUNT ((1 << 20) - 1)
 int svihmm_set_emission_poisson(svihmm_ctx* h, int32_t K, int32_t D,

@@ -88,6 +88,10 @@ SIGNATURES = {
     "svihmm_svi_read_elbo": (C.c_int, [C.c_void_p, C.c_int32, _c_double_p, _c_double_p]),
     "svihmm_svi_begin_diag": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [_c_double_p] * 4 + [C.c_int32]),
     "svihmm_svi_begin_cat": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [_c_double_p] * 4 + [C.c_int32]),
+    "svihmm_svi_begin_mcat": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32)] + [_c_double_p] * 4
+                              + [C.c_int32]),
+    "svihmm_svi_begin_poisson": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [_c_double_p] * 5
+                                 + [C.c_int32, C.c_int32]),
     "svihmm_svi_read_factors": (C.c_int, [C.c_void_p] + [_c_double_p] * 3),
     "svihmm_svi_set_adagrad": (C.c_int, [C.c_void_p, _c_double_p]),
     "svihmm_svi_read_adagrad": (C.c_int, [C.c_void_p, _c_double_p]),

@@ -22,10 +22,11 @@
 // kernel).  A workgroup of the GEMM always carries four state tiles (64 states): models with K < 64 run the
 // remaining tiles on zero columns.
 //
-// Out of scope for this family: the resident SVI loop (svihmm_svi_begin_* replaces the family, svihmm_svi_iteration
-// refuses with a message), svihmm_pred_logprob (NIW only: refuses with a message), the fp32 mode (the family rides the
-// Categorical branches, which never enter it: last_batch_f32 stays 0), and the device paths of
-// hmmsgd_metaobs.VBHMM (that class keeps host lliks through the plugin's expected_log_likelihood).
+// The resident SVI loop takes the family as its family 3 (svihmm_svi_begin_mcat; kernels_svi.h: k_mcat_table rebuilds
+// the table these kernels read, the step and the ELBO term are the Categorical family's, column by column), and
+// hmmsgd_metaobs.VBHMM runs on it.
+// Out of scope for this family: svihmm_pred_logprob (NIW only: refuses with a message) and the fp32 mode (the family
+// rides the Categorical branches, which never enter it: last_batch_f32 stays 0).
 #pragma once
 
 // meta (int32, device): [ off_d  D | V_d  D | d(f)  F | v(f)  F ]

@@ -24,8 +24,9 @@
 // Shapes: every D <= SVIHMM_POISSON_MAX_D, C <= SVIHMM_POISSON_MAX_COUNT, K <= 256 runs on these two kernels.  The
 // GEMM's operand layout, chunking and posterior staging are k_stats_onehot's (kernels_mcat.h: MC_RB, MC_QS, McRow).
 //
-// Out of scope for this family, as for the multi-column Categorical one: the resident SVI loop, svihmm_pred_logprob,
-// the fp32 mode and the device paths of hmmsgd_metaobs.VBHMM.
+// The resident SVI loop takes the family as its family 4 (svihmm_svi_begin_poisson; kernels_svi.h: k_pois_table
+// rebuilds the pairs these kernels read, svi_pois_step blends the Gamma factors), and hmmsgd_metaobs.VBHMM runs on it.
+// Out of scope for this family, as for the multi-column Categorical one: svihmm_pred_logprob and the fp32 mode.
 #pragma once
 
 #define PO_EM_ROWS 32          // rows whose counts k_emission_poisson stages at a time

@@ -468,8 +468,32 @@ __global__ __launch_bounds__(64) void k_svi_elbo(int K, const double* __restrict
 //      packed = [A_raw | counts K*V | lb]; every window contributes alpha_0 + counts - 1, so
 //      alpha <- (1-rho)(alpha - 1) + rho bE (nwin (alpha_0 - 1) + counts) + 1; ELBO term as
 //      distributions.Categorical.get_vlb.
+//    fam 3, multi-column Categorical (distributions.ProductCategorical): D Dirichlet factors per state side by side,
+//      alpha[K][W = F], F = sum_d V[d]; packed = [A_raw | counts K*F | lb].  Element by element the rule and the
+//      expression of fam 2 (every window contributes alpha_0 + counts - 1 per column), so a D = 1 model steps like
+//      fam 2 bit for bit; ELBO term: the sum over the columns of fam 2's Dirichlet term
+//      (ProductCategorical.get_vlb; svi_mcat_vlb, the columns from mcat_meta = [off_d D | V_d D | d(f) F | ..]).
+//    fam 4, Poisson (distributions.ProductPoisson): Gamma factors, blocks [a | b], each [K][W = D]; packed =
+//      [A_raw | stat K*2D | lb], stat[k] = [sx[k] | n[k]].  The Gaussian branch's blend (prior once) in the Gamma
+//      natural parameters (a - 1, -b), whose affine offsets cancel: a <- (1-rho) a + rho (a_0 + bE sx),
+//      b <- (1-rho) b + rho (b_0 + bE n) -- positive for every rho in [0, 1], which fam 2's rule (the prior once per
+//      window, minus one) is not for factors below 1.  ELBO term: -sum_d KL(Gamma(a, b) || Gamma(a_0, b_0))
+//      (ProductPoisson.get_vlb).
 //  grid: nem = ceil(K W / 256) element blocks + ceil(K^2 / 256) transition blocks.
 // ------------------------------------------------------------------------------------
+// fam 4, element e = (k, d): every product and sum rounded on its own (as svi_niw_* in device_helpers.h), which is
+// what the host loop's NumPy does
+__device__ __forceinline__ void svi_pois_step(size_t e, int K, int D, const double* __restrict__ packed,
+                                              double* __restrict__ blk, const double* __restrict__ prior,
+                                              double rho, double bE) {
+#pragma clang fp contract(off)
+  const size_t n = (size_t)K * D;
+  const int k = (int)(e / D), d = (int)(e - (size_t)k * D);
+  const double* __restrict__ st = packed + (size_t)K * K + (size_t)k * 2 * D;
+  const double sx = st[d], ne = st[D + d];
+  blk[e] = (1.0 - rho) * blk[e] + rho * (prior[e] + bE * sx);
+  blk[n + e] = (1.0 - rho) * blk[n + e] + rho * (prior[n + e] + bE * ne);
+}
 __device__ __forceinline__ void k_svi_global_step_simple_body(
     int fam, const double* __restrict__ packed, const double* __restrict__ prior_tran,
     double* __restrict__ var_tran, double* __restrict__ blk, const double* __restrict__ prior, int K, int W,
@@ -479,13 +503,14 @@ __device__ __forceinline__ void k_svi_global_step_simple_body(
   const size_t n = (size_t)K * W;
   if ((int)blockIdx.x >= nem) {
     const int e = ((int)blockIdx.x - nem) * 256 + tid;
-    if (e == 0) *lb_keep = packed[(size_t)K * K + (fam == 1 ? 2 * n + K : n)];
+    if (e == 0) *lb_keep = packed[(size_t)K * K + (fam == 1 ? 2 * n + K : fam == 4 ? 2 * n : n)];
     svi_tran_step(e, K, packed, prior_tran, var_tran, rho, bA, nwin, ada_G);
     return;
   }
   const size_t e = (size_t)blockIdx.x * 256 + tid;
   if (e >= n) return;
-  if (fam == 2) {
+  if (fam == 4) { svi_pois_step(e, K, W, packed, blk, prior, rho, bE); return; }
+  if (fam == 2 || fam == 3) {
     const double counts = packed[(size_t)K * K + e];
     const double inter = nwin * (prior[e] - 1.0) + counts;
     blk[e] = ((1.0 - rho) * (blk[e] - 1.0) + (rho * bE) * inter) + 1.0;
@@ -512,11 +537,60 @@ __global__ __launch_bounds__(256) void k_svi_global_step_simple(
   svi_arrive(sy);
 }
 
+// energy + entropy of one Dirichlet factor a[V] under the prior a0[V] (distributions.Categorical.get_vlb), one wave;
+// every lane returns the value
+__device__ __forceinline__ double svi_dirichlet_vlb(const double* __restrict__ a_, const double* __restrict__ a0_, int V,
+                                                    int lane) {
+  double sa = 0.0, s0 = 0.0;
+  for (int v = lane; v < V; v += 64) { sa += a_[v]; s0 += a0_[v]; }
+  sa = wave_sum(sa); s0 = wave_sum(s0);
+  const double dgs = digamma_d(sa);
+  double acc = 0.0;
+  for (int v = lane; v < V; v += 64) {
+    const double a = a_[v], a0 = a0_[v];
+    const double el = digamma_d(a) - dgs;
+    acc += (a0 - a) * el - lgamma(a0) + lgamma(a);      // ((a0-1) - (a-1)) el - gammaln(a0) + gammaln(a)
+  }
+  acc = wave_sum(acc);
+  return acc + lgamma(s0) - lgamma(sa);
+}
+// The same for the D Dirichlet factors of one state side by side (a[F], meta = [off_d D | V_d D | d(f) F | ..]):
+// sum_d svi_dirichlet_vlb(column d), with the transcendental functions evaluated for 64 columns, then 64 features at a
+// time instead of column by column on the V_d lanes a column fills (32 two-symbol columns: 136 us that way).  Column
+// sums in k_mcat_table's order; the terms are then added lane-strided over the columns and the features and reduced
+// once.  One wave; every lane returns the value.
+__device__ __forceinline__ double svi_mcat_vlb(const double* __restrict__ a_, const double* __restrict__ a0_, int F, int D,
+                                               const int* __restrict__ meta, int lane) {
+  __shared__ double sa_s[SVIHMM_MCAT_MAX_D], s0_s[SVIHMM_MCAT_MAX_D];
+  for (int d = 0; d < D; ++d) {
+    const int off = meta[d], V = meta[D + d];
+    double sa = 0.0, s0 = 0.0;
+    for (int v = lane; v < V; v += 64) { sa += a_[off + v]; s0 += a0_[off + v]; }
+    sa = wave_sum(sa); s0 = wave_sum(s0);
+    if (lane == 0) { sa_s[d] = sa; s0_s[d] = s0; }
+  }
+  __syncthreads();
+  double acc = 0.0;
+  for (int d = lane; d < D; d += 64) {               // (a lane rewrites its own columns only)
+    const double sa = sa_s[d];
+    acc += lgamma(s0_s[d]) - lgamma(sa);
+    sa_s[d] = digamma_d(sa);
+  }
+  __syncthreads();
+  const int* __restrict__ col = meta + 2 * D;
+  for (int f = lane; f < F; f += 64) {
+    const double a = a_[f], a0 = a0_[f];
+    const double el = digamma_d(a) - sa_s[col[f]];
+    acc += (a0 - a) * el - lgamma(a0) + lgamma(a);
+  }
+  return wave_sum(acc);
+}
 // grid 2 K waves: [0, K) the factors' ELBO terms vlb[k], [K, 2K) the transition rows' terms
+// (meta, D: fam 3 only -- the columns' offsets and widths inside a state's W = F features)
 __device__ __forceinline__ void k_svi_vlb_simple_body(
     int fam, const double* __restrict__ blk, const double* __restrict__ prior, int K, int W,
     double* __restrict__ vlb, const double* __restrict__ prior_tran, const double* __restrict__ var_tran,
-    double* __restrict__ rowterm) {
+    double* __restrict__ rowterm, const int* __restrict__ meta, int D) {
   const int lane = threadIdx.x;
   if ((int)blockIdx.x >= K) {
     svi_rowterm((int)blockIdx.x - K, K, lane, prior_tran, var_tran, rowterm);
@@ -525,18 +599,23 @@ __device__ __forceinline__ void k_svi_vlb_simple_body(
   const int k = blockIdx.x;
   const size_t n = (size_t)K * W, o = (size_t)k * W;
   if (fam == 2) {
-    double sa = 0.0, s0 = 0.0;
-    for (int v = lane; v < W; v += 64) { sa += blk[o + v]; s0 += prior[o + v]; }
-    sa = wave_sum(sa); s0 = wave_sum(s0);
-    const double dgs = digamma_d(sa);
+    const double t = svi_dirichlet_vlb(blk + o, prior + o, W, lane);
+    if (lane == 0) vlb[k] = t;
+    return;
+  }
+  if (fam == 3) {
+    const double t = svi_mcat_vlb(blk + o, prior + o, W, D, meta, lane);
+    if (lane == 0) vlb[k] = t;
+    return;
+  }
+  if (fam == 4) {
     double acc = 0.0;
-    for (int v = lane; v < W; v += 64) {
-      const double a = blk[o + v], a0 = prior[o + v];
-      const double el = digamma_d(a) - dgs;
-      acc += (a0 - a) * el - lgamma(a0) + lgamma(a);      // ((a0-1) - (a-1)) el - gammaln(a0) + gammaln(a)
+    for (int d = lane; d < W; d += 64) {
+      const double a = blk[o + d], b = blk[n + o + d], a0 = prior[o + d], b0 = prior[n + o + d];
+      acc += (a - a0) * digamma_d(a) - lgamma(a) + lgamma(a0) + a0 * (log(b) - log(b0)) + a * (b0 - b) / b;   // KL
     }
     acc = wave_sum(acc);
-    if (lane == 0) vlb[k] = acc + lgamma(s0) - lgamma(sa);
+    if (lane == 0) vlb[k] = -acc;
     return;
   }
   const double LN2PI = 1.8378770664093454836;
@@ -558,9 +637,9 @@ __device__ __forceinline__ void k_svi_vlb_simple_body(
 __global__ __launch_bounds__(64) void k_svi_vlb_simple(
     int fam, const double* __restrict__ blk, const double* __restrict__ prior, int K, int W,
     double* __restrict__ vlb, const double* __restrict__ prior_tran, const double* __restrict__ var_tran,
-    double* __restrict__ rowterm, SviSync sy, SviElboTail et) {
+    double* __restrict__ rowterm, const int* __restrict__ meta, int D, SviSync sy, SviElboTail et) {
   const bool go = svi_gate(sy);
-  if (go) k_svi_vlb_simple_body(fam, blk, prior, K, W, vlb, prior_tran, var_tran, rowterm);
+  if (go) k_svi_vlb_simple_body(fam, blk, prior, K, W, vlb, prior_tran, var_tran, rowterm, meta, D);
   svi_arrive_elbo(sy, go, et, K, vlb, rowterm);
 }
 
@@ -578,6 +657,47 @@ __device__ __forceinline__ void k_cat_table_body(const double* __restrict__ alph
 __global__ __launch_bounds__(64) void k_cat_table(const double* __restrict__ alpha, int K, int V,
                                                   double* __restrict__ table, SviSync sy) {
   if (svi_gate(sy)) k_cat_table_body(alpha, K, V, table);
+  svi_arrive(sy);
+}
+
+// The same table for D Dirichlet factors per state (fam 3): E log theta[f][k] = psi(alpha[k][f]) - psi(sum of
+// alpha[k][.] over the column of f), layout [F][K] as k_emission_mcat reads it.  One workgroup of four waves per state
+// (K arrivals, as k_cat_table); wave w takes the columns w, w + 4, .. with k_cat_table_body's summation order
+// (lane-strided partials, then wave_sum), so a D = 1 table has fam 2's bits.  meta = [off_d D | V_d D | ..].
+__device__ __forceinline__ void k_mcat_table_body(const double* __restrict__ alpha, int K, int D, int F,
+                                                   const int* __restrict__ meta, double* __restrict__ table) {
+  const int k = blockIdx.x, lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const double* __restrict__ a = alpha + (size_t)k * F;
+  for (int d = w; d < D; d += 4) {
+    const int off = meta[d], V = meta[D + d];
+    double s = 0.0;
+    for (int v = lane; v < V; v += 64) s += a[off + v];
+    s = wave_sum(s);
+    const double dgs = digamma_d(s);
+    for (int v = lane; v < V; v += 64) table[(size_t)(off + v) * K + k] = digamma_d(a[off + v]) - dgs;
+  }
+}
+__global__ __launch_bounds__(256) void k_mcat_table(const double* __restrict__ alpha, int K, int D, int F,
+                                                    const int* __restrict__ meta, double* __restrict__ table, SviSync sy) {
+  if (svi_gate(sy)) k_mcat_table_body(alpha, K, D, F, meta, table);
+  svi_arrive(sy);
+}
+// The Poisson pairs (fam 4): (E log lambda, E lambda) = (psi(a) - log b, a / b) of the Gamma factors blk = [a | b]
+// (each [K][D]) in the [D + 1][K] pair layout k_emission_poisson reads; row D, what an absent entry reads, is +0.0.
+// One workgroup per state (K arrivals).
+__device__ __forceinline__ void k_pois_table_body(const double* __restrict__ blk, int K, int D,
+                                                   double2* __restrict__ table) {
+  const int k = blockIdx.x;
+  const size_t n = (size_t)K * D;
+  for (int d = threadIdx.x; d < D; d += 64) {
+    const double a = blk[(size_t)k * D + d], b = blk[n + (size_t)k * D + d];
+    table[(size_t)d * K + k] = make_double2(digamma_d(a) - log(b), a / b);
+  }
+  if (threadIdx.x == 0) table[(size_t)D * K + k] = make_double2(0.0, 0.0);
+}
+__global__ __launch_bounds__(64) void k_pois_table(const double* __restrict__ blk, int K, int D,
+                                                   double2* __restrict__ table, SviSync sy) {
+  if (svi_gate(sy)) k_pois_table_body(blk, K, D, table);
   svi_arrive(sy);
 }
 

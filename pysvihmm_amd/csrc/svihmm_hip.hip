@@ -270,7 +270,7 @@ static int params_follow_centre(svihmm_ctx* h, const double* delta) {
   bool any = false;
   for (int d = 0; d < D; ++d) any = any || delta[d] != 0.0;
   const bool live = h->have_emission && !h->emis_cat && h->eD == D && h->niw.p;   // (NIW or diagonal: means lead the block)
-  const bool svi = h->svi_active && h->svi_D == D && h->svi_family != 2;   // (Categorical: no means)
+  const bool svi = h->svi_active && h->svi_D == D && h->svi_family < 2;    // (symbol and count families: no means)
   if (!any || (!live && !svi)) return 0;
   CK(wait_side_streams(h));
   if (live) CK(drop_auto_status(h));      // this rebuild supersedes what an earlier automatic one reported
@@ -733,6 +733,13 @@ int svihmm_set_emission_cat(svihmm_ctx* h, int32_t K, int32_t V, const double* l
   h->eK = K; h->eD = 1; h->V = V; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16; h->have_emission = true; h->emis_cat = true; h->emis_mcat = false; h->emis_pois = false; h->emis_diag = false; h->uw_valid = false;
   return 0;
 }
+// mcat_meta = [off_d D | V_d D | d(f) F | v(f) F]
+static void mcat_fill_meta(int* mp, int D, int F, const int32_t* V) {
+  for (int d = 0, o = 0; d < D; o += V[d], ++d) {
+    mp[d] = o; mp[D + d] = V[d];
+    for (int v = 0; v < V[d]; ++v) { mp[2 * D + o + v] = d; mp[2 * D + F + o + v] = v; }
+  }
+}
 // D symbol columns, independent per state (kernels_mcat.h).  The family rides the Categorical branches of the host
 // code (emis_cat) with V = F features; only the lookup and the count launches differ (emis_mcat).
 int svihmm_set_emission_mcat(svihmm_ctx* h, int32_t K, int32_t D, const int32_t* V, const double* logp) {
@@ -759,9 +766,9 @@ int svihmm_set_emission_mcat(svihmm_ctx* h, int32_t K, int32_t D, const int32_t*
   CK(set_device(h));
   h->lin_stale = true;
   h->center_pending = false;
-  // (the resident SVI loop does not know this family: a running loop ends with this upload)
+  // (a device loop of another family or shape ends with this upload, as in svihmm_set_emission_cat)
+  if (h->svi_active && !(h->svi_family == 3 && h->svi_K == K && h->svi_mcat_V == std::vector<int>(V, V + D))) h->svi_active = false;
   if (h->svi_active) CK(svi_flush_elbo(h));
-  h->svi_active = false;
   if (h->vlb_pending) { HIPCK(hipStreamWaitEvent(h->stream, h->svi_ed, 0)); h->vlb_pending = false; }
   CK(drop_auto_status(h));
   CK(cat_uncentre(h));
@@ -775,10 +782,7 @@ int svihmm_set_emission_mcat(svihmm_ctx* h, int32_t K, int32_t D, const int32_t*
   for (int k = 0; k < K; ++k)              // transpose to [F][K]: a feature's states are contiguous
     for (int f = 0; f < F; ++f) hp[(size_t)f * K + k] = logp[(size_t)k * F + f];
   int* mp = (int*)(hp + n);
-  for (int d = 0, o = 0; d < D; o += V[d], ++d) {
-    mp[d] = o; mp[D + d] = V[d];
-    for (int v = 0; v < V[d]; ++v) { mp[2 * D + o + v] = d; mp[2 * D + F + o + v] = v; }
-  }
+  mcat_fill_meta(mp, D, F, V);
   HIPCK(hipMemcpyAsync(h->cat_table.p, hp, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCK(hipMemcpyAsync(h->mcat_meta.p, mp, nmeta * sizeof(int), hipMemcpyHostToDevice, h->stream));
   CK(pin_release(h, slot));
@@ -814,9 +818,9 @@ int svihmm_set_emission_poisson(svihmm_ctx* h, int32_t K, int32_t D, const doubl
   CK(set_device(h));
   h->lin_stale = true;
   h->center_pending = false;
-  // (the resident SVI loop does not know this family: a running loop ends with this upload)
+  // (a device loop of another family or shape ends with this upload, as in svihmm_set_emission_cat)
+  if (h->svi_active && !(h->svi_family == 4 && h->svi_K == K && h->svi_D == D)) h->svi_active = false;
   if (h->svi_active) CK(svi_flush_elbo(h));
-  h->svi_active = false;
   if (h->vlb_pending) { HIPCK(hipStreamWaitEvent(h->stream, h->svi_ed, 0)); h->vlb_pending = false; }
   CK(drop_auto_status(h));
   CK(cat_uncentre(h, 1));
@@ -1932,13 +1936,21 @@ static int svi_refresh_emission(svihmm_ctx* h, int elbo_it, int lb_slot, hipEven
   if (fam == 0) CK(launch_niw_to_theta(h, K, D, svi_ptr(h, 4), step));
   else if (fam == 1) CK(launch_diag_to_theta(h, K, D));
   else {
-    // E log theta[v][k] = psi(alpha_kv) - psi(sum_v alpha_kv) (what hmmbase._push_emission uploads)
+    // E log theta[v][k] = psi(alpha_kv) - psi(sum_v alpha_kv) (what hmmbase._push_emission uploads); per column for
+    // fam 3; the pairs (psi(a) - log b, a / b) for fam 4
     ProfScope ps(h, KS_MISC);
-    hipLaunchKernelGGL(k_cat_table, dim3(K), dim3(64), 0, h->stream, (const double*)h->niw.p, K, h->V,
-                       (double*)h->cat_table.p, tsy);
+    if (fam == 2)
+      hipLaunchKernelGGL(k_cat_table, dim3(K), dim3(64), 0, h->stream, (const double*)h->niw.p, K, h->V,
+                         (double*)h->cat_table.p, tsy);
+    else if (fam == 3)
+      hipLaunchKernelGGL(k_mcat_table, dim3(K), dim3(256), 0, h->stream, (const double*)h->niw.p, K, D, h->V,
+                         (const int*)h->mcat_meta.p, (double*)h->cat_table.p, tsy);
+    else
+      hipLaunchKernelGGL(k_pois_table, dim3(K), dim3(64), 0, h->stream, (const double*)h->niw.p, K, D,
+                         (double2*)h->cat_table.p, tsy);
     HIPCK(hipGetLastError());
-    h->eK = K; h->eD = 1; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16;
-    h->have_emission = true; h->emis_cat = true; h->emis_mcat = false; h->emis_pois = false; h->emis_diag = false; h->uw_valid = false;
+    h->eK = K; h->eD = D; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16;
+    h->have_emission = true; h->emis_cat = true; h->emis_mcat = fam == 3; h->emis_pois = fam == 4; h->emis_diag = false; h->uw_valid = false;
   }
   h->theta_sy = SviSync{};
   h->lin_stale = true;
@@ -1986,8 +1998,9 @@ static int svi_launch_elbo(svihmm_ctx* h, int elbo_it, int lb_slot, bool behind_
                          (const double*)svi_ptr(h, 1), (const double*)svi_ptr(h, 0), svi_ptr(h, 6), vsy, et);
     else
       hipLaunchKernelGGL(k_svi_vlb_simple, dim3(2 * K), dim3(64), 0, s2, fam, (const double*)h->niw.p,
-                         (const double*)h->svi_prior.p, K, fam == 1 ? D : h->V, svi_ptr(h, 3),
-                         (const double*)svi_ptr(h, 1), (const double*)svi_ptr(h, 0), svi_ptr(h, 6), vsy, et);
+                         (const double*)h->svi_prior.p, K, fam == 1 || fam == 4 ? D : h->V, svi_ptr(h, 3),
+                         (const double*)svi_ptr(h, 1), (const double*)svi_ptr(h, 0), svi_ptr(h, 6),
+                         (const int*)(fam == 3 ? h->mcat_meta.p : nullptr), D, vsy, et);
     if (elbo_it >= 0 && !tail) {      // (stream-event choreography: no arrival counter to tell the last workgroup by)
       hipLaunchKernelGGL(k_svi_elbo, dim3(1), dim3(64), 0, s2, K, (const double*)svi_ptr(h, 3),
                          (const double*)svi_ptr(h, 6), h->svi_prior_const, (const double*)svi_ptr(h, 8) + lb_slot,
@@ -2006,7 +2019,7 @@ int svi_flush_elbo(svihmm_ctx* h) {
   return svi_launch_elbo(h, h->elbo_pend_it, h->elbo_pend_slot, false, nullptr);
 }
 
-// What the three families' begin calls share: range check of the transition factor, the resident
+// What the families' begin calls share: range check of the transition factor, the resident
 // state (var_tran | prior_tran | ...), the ELBO / event rings.  The caller uploads its prior / factor
 // blocks between svi_begin_common and svi_begin_finish.
 static int svi_begin_common(svihmm_ctx* h, int K, int D, const double* prior_tran, const double* var_tran,
@@ -2020,7 +2033,7 @@ static int svi_begin_common(svihmm_ctx* h, int K, int D, const double* prior_tra
   CK(set_device(h));
   CK(wait_side_streams(h));
   CK(drop_auto_status(h));
-  if (family != 2) CK(centre_deferred(h));
+  if (family < 2) CK(centre_deferred(h));       // (symbol and count families: the copy stays uncentred)
   const size_t kk = (size_t)K * K;
   {
     // The global step is var_tran <- (1 - rho) var_tran + rho (1 + bA (A_raw + nwin (prior_tran - 1)))
@@ -2214,9 +2227,108 @@ int svihmm_svi_begin_cat(svihmm_ctx* h, int32_t K, int32_t V, const double* prio
   return svi_begin_finish(h);
 }
 
+// Multi-column Categorical family (distributions.ProductCategorical): D Dirichlet factors per state over the D symbol
+// columns, alpha0 / alpha [K][F] with the feature offsets of svihmm_set_emission_mcat.  Column by column the step and
+// the ELBO term of svihmm_svi_begin_cat; the [F][K] table is rebuilt by k_mcat_table every iteration.
+int svihmm_svi_begin_mcat(svihmm_ctx* h, int32_t K, int32_t D, const int32_t* V, const double* prior_tran,
+                          const double* var_tran, const double* alpha0, const double* alpha, int32_t maxit) {
+  if (!h || !V || !prior_tran || !var_tran || !alpha0 || !alpha || maxit <= 0)
+    return fail("svihmm_svi_begin_mcat: bad arguments");
+  if (K < 1 || K > 256) return fail("svihmm_svi_begin_mcat: K = " + std::to_string(K) + " outside [1, 256]");
+  if (D < 1 || D > SVIHMM_MCAT_MAX_D)
+    return fail("svihmm_svi_begin_mcat: D = " + std::to_string(D) + " outside [1, SVIHMM_MCAT_MAX_D = " +
+                std::to_string(SVIHMM_MCAT_MAX_D) + "]");
+  int64_t F64 = 0;
+  for (int d = 0; d < D; ++d) {
+    if (V[d] < 1)
+      return fail("svihmm_svi_begin_mcat: V[" + std::to_string(d) + "] = " + std::to_string(V[d]) + " (every column needs at least one symbol)");
+    F64 += V[d];
+  }
+  if (F64 > SVIHMM_MCAT_MAX_F)
+    return fail("svihmm_svi_begin_mcat: F = sum of V = " + std::to_string(F64) + " exceeds SVIHMM_MCAT_MAX_F = " +
+                std::to_string(SVIHMM_MCAT_MAX_F));
+  if (h->D != D)
+    return fail("svihmm_svi_begin_mcat: the family has D = " + std::to_string(D) + " symbol columns, the resident observations have " +
+                std::to_string(h->D));
+  const int F = (int)F64;
+  const size_t n = (size_t)K * F;
+  for (size_t i = 0; i < n; ++i)       // (validated before any state is touched)
+    if (!(alpha0[i] > 0.0) || !(alpha[i] > 0.0)) return fail("svihmm_svi_begin_mcat: Dirichlet parameters must be positive");
+  CK(svi_begin_common(h, K, D, prior_tran, var_tran, maxit, 3));
+  h->V = F;
+  h->svi_mcat_V.assign(V, V + D);
+  CK(cat_uncentre(h, 0));
+  const size_t nmeta = 2 * (size_t)D + 2 * (size_t)F;
+  CK(ensure(h->svi_prior, (n + 8) * sizeof(double)));
+  CK(ensure(h->niw, n * sizeof(double) + 64));
+  CK(ensure(h->cat_table, n * sizeof(double)));
+  CK(ensure(h->mcat_meta, nmeta * sizeof(int)));
+  void* pin = nullptr;
+  int slot = 0;
+  CK(pinned(h, nmeta * sizeof(int), &pin, &slot));
+  mcat_fill_meta((int*)pin, D, F, V);
+  HIPCK(hipMemcpyAsync(h->mcat_meta.p, pin, nmeta * sizeof(int), hipMemcpyHostToDevice, h->stream));
+  CK(pin_release(h, slot));
+  CK(svi_upload(h, h->svi_prior.p, alpha0, n, nullptr, 0, 0, 0));
+  CK(svi_upload(h, h->niw.p, alpha, n, nullptr, 0, 0, 0));
+  return svi_begin_finish(h);
+}
+
+// Poisson family (distributions.ProductPoisson): Gamma factors (shape a, rate b) per state and count column, blocks
+// [a | b], each [K][D].  The (E log lambda, E lambda) pairs are rebuilt by k_pois_table every iteration; the logfact
+// table is uploaded here, once.
+int svihmm_svi_begin_poisson(svihmm_ctx* h, int32_t K, int32_t D, const double* prior_tran, const double* var_tran,
+                             const double* prior_blk, const double* factor_blk, const double* logfact, int32_t C,
+                             int32_t maxit) {
+  if (!h || !prior_tran || !var_tran || !prior_blk || !factor_blk || !logfact || maxit <= 0)
+    return fail("svihmm_svi_begin_poisson: bad arguments");
+  if (K < 1 || K > 256) return fail("svihmm_svi_begin_poisson: K = " + std::to_string(K) + " outside [1, 256]");
+  if (D < 1 || D > SVIHMM_POISSON_MAX_D)
+    return fail("svihmm_svi_begin_poisson: D = " + std::to_string(D) + " outside [1, SVIHMM_POISSON_MAX_D = " +
+                std::to_string(SVIHMM_POISSON_MAX_D) + "]");
+  if (C < 0 || C > SVIHMM_POISSON_MAX_COUNT)
+    return fail("svihmm_svi_begin_poisson: C = " + std::to_string(C) + " outside [0, SVIHMM_POISSON_MAX_COUNT = " +
+                std::to_string(SVIHMM_POISSON_MAX_COUNT) + "]");
+  const size_t nlf = (size_t)C + 1;
+  for (size_t c = 0; c < nlf; ++c)
+    if (!(logfact[c] > -1.7e308 && logfact[c] < 1.7e308))
+      return fail("svihmm_svi_begin_poisson: logfact[" + std::to_string(c) + "] is not finite");
+  if (h->D != D)
+    return fail("svihmm_svi_begin_poisson: the family has D = " + std::to_string(D) + " count columns, the resident observations have " +
+                std::to_string(h->D));
+  const size_t n2 = 2 * (size_t)K * D;
+  for (size_t i = 0; i < n2; ++i)      // (validated before any state is touched)
+    if (!(prior_blk[i] > 0.0) || !(factor_blk[i] > 0.0)) return fail("svihmm_svi_begin_poisson: Gamma parameters must be positive");
+  CK(svi_begin_common(h, K, D, prior_tran, var_tran, maxit, 4));
+  h->V = 2 * D;
+  h->pois_C = C;
+  CK(cat_uncentre(h, 1));
+  CK(ensure(h->svi_prior, (n2 + 8) * sizeof(double)));
+  CK(ensure(h->niw, n2 * sizeof(double) + 64));
+  CK(ensure(h->cat_table, (n2 + 2 * (size_t)K) * sizeof(double)));
+  // (the device copy of the logfact table stays while the caller's holds the same bits: svihmm_set_emission_poisson)
+  if (h->pois_lf_host.size() != nlf || std::memcmp(h->pois_lf_host.data(), logfact, nlf * sizeof(double)) != 0) {
+    CK(ensure(h->pois_logfact, nlf * sizeof(double)));
+    void* pin = nullptr;
+    int slot = 0;
+    CK(pinned(h, nlf * sizeof(double), &pin, &slot));
+    std::memcpy(pin, logfact, nlf * sizeof(double));
+    h->pois_lf_host.clear();             // (stays empty if the copy below fails)
+    HIPCK(hipMemcpyAsync(h->pois_logfact.p, pin, nlf * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    h->pois_lf_host.assign(logfact, logfact + nlf);
+    CK(pin_release(h, slot));
+  }
+  CK(svi_upload(h, h->svi_prior.p, prior_blk, n2, nullptr, 0, 0, 0));
+  CK(svi_upload(h, h->niw.p, factor_blk, n2, nullptr, 0, 0, 0));
+  return svi_begin_finish(h);
+}
+
 static int svi_iteration_impl(svihmm_ctx* h, int32_t it, const int64_t* starts, int32_t B, int32_t nwin_total,
                               int32_t Lm, int32_t inner_off, int32_t inner_len, uint32_t flags, double rho,
                               double bfactA, double bfactE);
+// elements per state of the element-wise global step: D (diagonal, Poisson: one thread per (k, d)), V (Categorical),
+// F (multi-column Categorical: h->V holds it)
+static int svi_step_width(const svihmm_ctx* h) { return h->svi_family == 1 || h->svi_family == 4 ? h->svi_D : h->V; }
 // Leave the counters in the middle of a loop and carry on with the stream-event choreography (round 6).  Two
 // callers: a gate of the loop gave up (the status word is set: a tool that serialises kernels attached after
 // svihmm_svi_begin's probe, another process time-slicing the device, a partition too small for the loop's
@@ -2279,10 +2391,10 @@ int svihmm_svi_iteration(svihmm_ctx* h, int32_t it, const int64_t* starts, int32
                          double bfactA, double bfactE) {
   if (h && !h->svi_active && h->have_emission && h->emis_mcat)
     return fail("svihmm_svi_iteration: the resident SVI loop does not take the multi-column Categorical family "
-                "(svihmm_set_emission_mcat); step the globals on the host from svihmm_estep_minibatch's statistics");
+                "from svihmm_set_emission_mcat alone: the family enters the loop through svihmm_svi_begin_mcat");
   if (h && !h->svi_active && h->have_emission && h->emis_pois)
     return fail("svihmm_svi_iteration: the resident SVI loop does not take the Poisson family "
-                "(svihmm_set_emission_poisson); step the globals on the host from svihmm_estep_minibatch's statistics");
+                "from svihmm_set_emission_poisson alone: the family enters the loop through svihmm_svi_begin_poisson");
   if (!h || !h->svi_active) return fail("svihmm_svi_iteration: call svihmm_svi_begin first");
   if (it < 0 || it >= h->svi_maxit) return fail("svihmm_svi_iteration: iteration index out of range");
   if (B < 0 || (B > 0 && !starts) || nwin_total < B) return fail("svihmm_svi_iteration: bad window batch");
@@ -2378,7 +2490,7 @@ static int svi_iteration_impl(svihmm_ctx* h, int32_t it, const int64_t* starts, 
   const bool merged = h->svi_family == 0 && step_theta_ok(h, K, D);
   const unsigned ntran = merged ? (unsigned)((K * K + 63) / 64) : (unsigned)((K * K + 255) / 256);
   const unsigned step_grid = h->svi_family == 0 ? (unsigned)K + ntran
-                                                : (unsigned)(((size_t)K * (h->svi_family == 1 ? D : h->V) + 255) / 256) + ntran;
+                                                : (unsigned)(((size_t)K * svi_step_width(h) + 255) / 256) + ntran;
   SviSync ssy = svi_sy(h);
   if (h->svi_flags) {
     ssy.gate = svi_cnt(h, 3); ssy.gate_tgt = (unsigned)h->tgt_side; ssy.arrive = svi_cnt(h, 0);
@@ -2407,7 +2519,7 @@ static int svi_iteration_impl(svihmm_ctx* h, int32_t it, const int64_t* starts, 
                          (double*)h->niw.p, (const double*)h->svi_prior.p, K, D, rho, bfactA, bfactE,
                          (double)nwin_total, svi_ptr(h, 8) + (it & 1), adag, ssy);
     else {
-      const int W = h->svi_family == 1 ? D : h->V;
+      const int W = svi_step_width(h);
       const unsigned nem = (unsigned)(((size_t)K * W + 255) / 256);
       hipLaunchKernelGGL(k_svi_global_step_simple, dim3(nem + ntran), dim3(256), 0, h->stream, h->svi_family,
                          (const double*)h->packed.p, (const double*)svi_ptr(h, 1), svi_ptr(h, 0),
@@ -2528,7 +2640,8 @@ int svihmm_svi_read_state(svihmm_ctx* h, double* var_tran, double* var_init, dou
 }
 
 // The loop's state in the family's own block layout: NIW [mu | sigma | kappa | nu], diagonal
-// [mu | nus | alphas | betas] (each [K][D]), Categorical alpha[K][V]; means in the caller's coordinates.
+// [mu | nus | alphas | betas] (each [K][D]), Categorical alpha[K][V], multi-column Categorical alpha[K][F], Poisson
+// [a | b] (each [K][D]); means in the caller's coordinates.
 int svihmm_svi_read_factors(svihmm_ctx* h, double* var_tran, double* var_init, double* factors_out) {
   if (!h || !h->svi_active) return fail("svihmm_svi_read_factors: no SVI state on the device");
   CK(set_device(h));
@@ -2542,7 +2655,7 @@ int svihmm_svi_read_factors(svihmm_ctx* h, double* var_tran, double* var_init, d
   HIPCK(hipStreamSynchronize(h->stream));
   if (h->stream3) HIPCK(hipStreamSynchronize(h->stream3));   // ELBO kernels still reading the factors
   h->vlb_pending = false;
-  if (factors_out && h->svi_family != 2) from_centred(h, factors_out, (int)K, (int)D);
+  if (factors_out && h->svi_family < 2) from_centred(h, factors_out, (int)K, (int)D);
   CK(check_emission_status(h));
   return 0;
 }

@@ -786,17 +786,84 @@ class HipEngine(object):
         self._svi_shape = (K, V)
         self._svi_family = "cat"
 
+    def svi_begin_mcat(self, prior_tran, var_tran, alpha0_cols, alpha_cols, maxit):
+        """The same loop for ``ProductCategorical`` emitters over D symbol columns: Dirichlet priors and
+        factors as lists of D arrays ``[K, V_d]`` (``svihmm_svi_begin_mcat``)."""
+        self._pre_mutate()
+        var_tran = L.as_f64(var_tran)
+        K = var_tran.shape[0]
+        prior_tran = L.as_f64(prior_tran, (K, K))
+        a0 = [L.as_f64(a) for a in alpha0_cols]
+        if len(a0) < 1 or any(a.ndim != 2 or a.shape[0] != K for a in a0):
+            raise RuntimeError("svi_begin_mcat: alpha0_cols must be a non-empty list of [K, V_d] arrays")
+        if len(alpha_cols) != len(a0):
+            raise RuntimeError("svi_begin_mcat: alpha_cols must have one array per column of alpha0_cols")
+        al = [L.as_f64(a, p.shape) for a, p in zip(alpha_cols, a0)]
+        Vs = np.ascontiguousarray([a.shape[1] for a in a0], dtype=np.int32)
+        p0 = np.ascontiguousarray(np.concatenate(a0, axis=1))
+        p1 = np.ascontiguousarray(np.concatenate(al, axis=1))
+        L.check(self._lib.svihmm_svi_begin_mcat(self._h, K, len(a0), Vs.ctypes.data_as(C.POINTER(C.c_int32)),
+                                                L.dptr(prior_tran), L.dptr(var_tran), L.dptr(p0), L.dptr(p1),
+                                                int(maxit)), "svihmm_svi_begin_mcat")
+        self.K, self.V = K, 0
+        self.diag = False
+        self.Vs = tuple(int(v) for v in Vs)
+        self.pois = 0
+        self._svi_shape = (K, self.Vs)
+        self._svi_family = "mcat"
+
+    def svi_begin_poisson(self, prior_tran, var_tran, prior, factors, max_count, maxit):
+        """The same loop for ``ProductPoisson`` emitters over D count columns: Gamma ``prior = (a0, b0)`` and
+        ``factors = (a, b)`` (shape, rate), each ``[K, D]``; an entry is present when
+        ``0 <= x < max_count + 1`` (``svihmm_svi_begin_poisson``)."""
+        from .distributions import _logfact_table
+        self._pre_mutate()
+        var_tran = L.as_f64(var_tran)
+        K = var_tran.shape[0]
+        prior_tran = L.as_f64(prior_tran, (K, K))
+        a0 = L.as_f64(prior[0])
+        if a0.ndim != 2 or a0.shape[0] != K:
+            raise RuntimeError("svi_begin_poisson: the Gamma parameters must be [K, D] arrays")
+        D = a0.shape[1]
+        C_ = int(max_count)
+        if not 0 <= C_ <= L.POISSON_MAX_COUNT:
+            raise RuntimeError("svi_begin_poisson: max_count = %d outside [0, %d]" % (C_, L.POISSON_MAX_COUNT))
+        pb = np.ascontiguousarray(np.stack([a0, L.as_f64(prior[1], (K, D))]))
+        fb = np.ascontiguousarray(np.stack([L.as_f64(a, (K, D)) for a in factors]))
+        logfact = np.ascontiguousarray(_logfact_table(C_), dtype=np.float64)
+        L.check(self._lib.svihmm_svi_begin_poisson(self._h, K, D, L.dptr(prior_tran), L.dptr(var_tran), L.dptr(pb),
+                                                   L.dptr(fb), L.dptr(logfact), C_, int(maxit)),
+                "svihmm_svi_begin_poisson")
+        self.K, self.V = K, 0
+        self.diag = False
+        self.Vs = None
+        self.pois = D
+        self._svi_shape = (K, D)
+        self._svi_family = "poisson"
+
     def svi_read_factors(self):
         """(var_tran, var_init, factors) with ``factors`` in the loop's family layout: NIW
-        (mu, sigma, kappa, nu), diagonal (mu, nus, alphas, betas), Categorical alpha [K, V]."""
+        (mu, sigma, kappa, nu), diagonal (mu, nus, alphas, betas), Categorical alpha [K, V],
+        multi-column Categorical the list of D arrays alpha_d [K, V_d], Poisson (a, b), each [K, D]."""
         K, W = self._svi_shape
         fam = getattr(self, "_svi_family", "niw")
-        n = {"niw": K * W + K * W * W + 2 * K, "diag": 4 * K * W, "cat": K * W}[fam]
+        if fam == "mcat":
+            n = K * sum(W)
+        elif fam == "poisson":
+            n = 2 * K * W
+        else:
+            n = {"niw": K * W + K * W * W + 2 * K, "diag": 4 * K * W, "cat": K * W}[fam]
         vt, vi, blk = np.empty((K, K)), np.empty(K), np.empty(n)
         L.check(self._lib.svihmm_svi_read_factors(self._h, L.dptr(vt), L.dptr(vi), L.dptr(blk)),
                 "svihmm_svi_read_factors")
         if fam == "diag":
             fac = tuple(blk.reshape(4, K, W))
+        elif fam == "mcat":
+            off = np.concatenate(([0], np.cumsum(W))).astype(int)
+            flat = blk.reshape(K, sum(W))
+            fac = [np.ascontiguousarray(flat[:, off[d]:off[d + 1]]) for d in range(len(W))]
+        elif fam == "poisson":
+            fac = tuple(blk.reshape(2, K, W))
         elif fam == "cat":
             fac = blk.reshape(K, W)
         else:
@@ -843,6 +910,8 @@ class HipEngine(object):
     def svi_read_state(self):
         """Current (var_tran, var_init, mu, sigma, kappa, nu); waits for the device."""
         K, D = self._svi_shape
+        if isinstance(D, tuple):                # (multi-column Categorical: the library refuses, NIW layout)
+            D = len(D)
         out = [np.empty((K, K)), np.empty(K), np.empty((K, D)), np.empty((K, D, D)), np.empty(K), np.empty(K)]
         L.check(self._lib.svihmm_svi_read_state(self._h, *[L.dptr(a) for a in out]), "svihmm_svi_read_state")
         return tuple(out)

@@ -28,7 +28,7 @@ from numpy import newaxis as npa
 from scipy.special import digamma
 
 from .hmmbase import VariationalHMMBase, is_niw_gaussian, is_diag_gaussian, dirichlet_elbo
-from .distributions import Gaussian, Categorical, DiagonalGaussian
+from .distributions import Gaussian, Categorical, DiagonalGaussian, ProductCategorical, ProductPoisson
 from . import util
 from . import _lib as L
 
@@ -90,15 +90,6 @@ class VBHMM(VariationalHMMBase):
     lalpha = _lazy_window_attr("lalpha")
     lbeta = _lazy_window_attr("lbeta")
     var_x = _lazy_window_attr("var_x")
-
-    def _mcat_fastpath(self):
-        # the metaobs loop does not know the multi-column Categorical family: ProductCategorical emitters keep the
-        # route of every plugin it does not know (host lliks through expected_log_likelihood)
-        return False
-
-    def _poisson_fastpath(self):
-        # nor the Poisson family: ProductPoisson emitters keep host lliks as well
-        return False
 
     @staticmethod
     def make_param_dict(prior_init, prior_tran, prior_emit, tau=tau0,
@@ -262,7 +253,7 @@ class VBHMM(VariationalHMMBase):
         if (any(getattr(type(self), n) is not getattr(VBHMM, n) for n in
                 ("local_update", "intermediate_pars", "intermediate_pars_buffer", "forward_msgs",
                  "backward_msgs", "local_lower_bound"))
-                or not (self._niw_fastpath() or self._cat_fastpath() or self._diag_fastpath())):
+                or not self._device_family()):
             # subclass overrides, or an emission family the device statistics kernels
             # do not know (the reference dispatches on the type too, :887,907):
             # follow the reference loop literally, E-step recursions still on the device
@@ -336,10 +327,13 @@ class VBHMM(VariationalHMMBase):
                 route = self._suffstats_route()
                 segs = []
                 A_inter = np.zeros_like(self.var_tran)
-                if type(self.var_emit[0]) is Categorical:
+                if type(self.var_emit[0]) in (Categorical, ProductCategorical):
                     # the reference calls util.NIW_zero_nat_pars here for every family
                     # (:399), which raises for a Categorical; zeros of the right shape instead
+                    # (ProductCategorical: the D columns side by side, F = sum of the V_d entries)
                     emit_inter = [np.zeros(self.var_emit[0].num_parameters()) for k in range(K)]
+                elif type(self.var_emit[0]) is ProductPoisson:
+                    emit_inter = [np.zeros((2, self.var_emit[0].D)) for k in range(K)]      # [sx | n]
                 elif is_diag_gaussian(self.var_emit[0]):
                     emit_inter = [np.zeros((4, self.D)) for k in range(K)]
                 else:
@@ -408,16 +402,23 @@ class VBHMM(VariationalHMMBase):
             return "diag"
         if self._cat_fastpath():
             return "cat"
+        if self._mcat_fastpath():
+            return "mcat"
+        if self._poisson_fastpath():
+            return "poisson"
         return None
 
     def _svi_device_ok(self):
         eng = self.engine
         fam = self._svi_family()
-        if fam is None or not hasattr(eng, {"niw": "svi_begin", "diag": "svi_begin_diag", "cat": "svi_begin_cat"}[fam]):
+        begin = {"niw": "svi_begin", "diag": "svi_begin_diag", "cat": "svi_begin_cat", "mcat": "svi_begin_mcat",
+                 "poisson": "svi_begin_poisson"}
+        if fam is None or not hasattr(eng, begin[fam]):
             return False
         if self.adagrad and not hasattr(eng, "svi_set_adagrad"):
             return False
-        cls = {"niw": Gaussian, "diag": DiagonalGaussian, "cat": Categorical}[fam]
+        cls = {"niw": Gaussian, "diag": DiagonalGaussian, "cat": Categorical, "mcat": ProductCategorical,
+               "poisson": ProductPoisson}[fam]
         if any(type(e).get_vlb is not cls.get_vlb for e in self.var_emit):
             return False
         for name in self._LOOP_HOOKS:
@@ -442,8 +443,10 @@ class VBHMM(VariationalHMMBase):
             vt, vi, fac = self.engine.svi_read_factors()
             self.var_tran, self.var_init = vt, vi
             for k, G in enumerate(self.var_emit):
-                if fam == "diag":
+                if fam in ("diag", "poisson"):
                     G._set_mf(*[a[k].copy() for a in fac])
+                elif fam == "mcat":
+                    G._set_alpha([c[k] for c in fac])
                 else:
                     G._alpha_mf = fac[k].copy()
                     G.weights = G._alpha_mf / G._alpha_mf.sum()
@@ -484,6 +487,16 @@ class VBHMM(VariationalHMMBase):
             prior = tuple(np.array([getattr(g, n) for g in ve], dtype=np.float64)
                           for n in ("mu_0", "nus_0", "alphas_0", "betas_0"))
             eng.svi_begin_diag(self.prior_tran, self.var_tran, prior, self._diag_arrays(), maxit)
+        elif fam == "mcat":
+            ve = self.var_emit
+            stack = lambda name: [np.array([getattr(g, name)[d] for g in ve], dtype=np.float64)
+                                  for d in range(ve[0].D)]
+            eng.svi_begin_mcat(self.prior_tran, self.var_tran, stack("alphav_0"), stack("alpha_mf"), maxit)
+        elif fam == "poisson":
+            ve = self.var_emit
+            stack = lambda *names: tuple(np.array([getattr(g, n) for g in ve], dtype=np.float64) for n in names)
+            eng.svi_begin_poisson(self.prior_tran, self.var_tran, stack("alpha_0", "beta_0"),
+                                  stack("alpha_mf", "beta_mf"), ve[0].max_count, maxit)
         else:
             ve = self.var_emit
             eng.svi_begin_cat(self.prior_tran, self.var_tran, np.array([g.alphav_0 for g in ve], dtype=np.float64),
@@ -624,7 +637,7 @@ class VBHMM(VariationalHMMBase):
                 return False
         if self.comm is not None or not hasattr(self.engine, "suffstats"):
             return False
-        return self._niw_fastpath() or self._diag_fastpath() or self._cat_fastpath()
+        return self._device_family()
 
     def _segments_inter(self, segs, A_inter, emit_inter):
         """``(A_inter, emit_inter)`` of the windows ``segs = [(loff, uoff, var_x), ...]``: what the
@@ -658,6 +671,13 @@ class VBHMM(VariationalHMMBase):
         if hasattr(st, "counts"):
             # Categorical (reference :907-926): every window contributes alpha_0 + counts - 1
             emit_inter = [nwin * (G.alphav_0 - 1.) + st.counts[k] for k, G in enumerate(self.var_emit)]
+        elif hasattr(st, "col_counts"):
+            # ProductCategorical: the same per column, the columns side by side
+            emit_inter = [np.concatenate([nwin * (a0 - 1.) + c[k] for a0, c in zip(G.alphav_0, st.col_counts)])
+                          for k, G in enumerate(self.var_emit)]
+        elif hasattr(st, "sx"):
+            # ProductPoisson: expected sufficient statistics [sum q c, sum q] per state and column
+            emit_inter = [np.stack([st.sx[k], st.n[k]]) for k in range(K)]
         elif hasattr(st, "xsq"):
             # diagonal family: expected sufficient statistics [sum q x, n, sum q x^2, n] per state
             emit_inter = [np.stack([st.xbar[k], np.full(D, st.neff[k]), st.xsq[k], np.full(D, st.neff[k])])
@@ -765,7 +785,7 @@ class VBHMM(VariationalHMMBase):
         would call."""
         if not self.device_growth or not hasattr(self.engine, "grow_windows"):
             return False
-        if not (self._niw_fastpath() or self._diag_fastpath() or self._cat_fastpath()):
+        if not self._device_family():
             return False
         cls = type(self)
         return all(getattr(cls, nm) is getattr(VBHMM, nm)
@@ -954,6 +974,23 @@ class VBHMM(VariationalHMMBase):
                 wz = w[:, None] * z
                 alpha_mf = G._posterior_hypparams(*G._get_weighted_statistics(data, wz))
                 emit_inter.append(alpha_mf - 1.)
+        elif type(self.var_emit[0]) is ProductCategorical:
+            # the Categorical branch per column, over the rows whose entry is present: alpha_0 + counts - 1
+            xi, ok = self.var_emit[0]._present(obs[loff:(uoff + 1)][inds])
+            for k in range(self.K):
+                G = self.var_emit[k]
+                w = var_x[inds, k]
+                cols = []
+                for d, a0 in enumerate(G.alphav_0):
+                    z = np.zeros((xi.shape[0], len(a0)))
+                    z[np.where(ok[:, d])[0], xi[ok[:, d], d]] = 1
+                    cols.append(a0 + (w[:, None] * z).sum(0) - 1.)
+                emit_inter.append(np.concatenate(cols))
+        elif type(self.var_emit[0]) is ProductPoisson:
+            x = obs[loff:(uoff + 1)][inds]
+            for k in range(self.K):
+                sx, n = self.var_emit[k]._get_weighted_statistics(x, var_x[inds, k])
+                emit_inter.append(np.stack([sx, n]))
         return A_inter, emit_inter
 
     # -- global natural-gradient step (reference :1010-1084) -------------------------------------
@@ -1002,6 +1039,21 @@ class VBHMM(VariationalHMMBase):
                 nats_new = (1. - lrate) * nats_old + lrate * bfact * emit_inter[k]
                 G._alpha_mf = nats_new + 1.
                 G.weights = G._alpha_mf / G._alpha_mf.sum()
+        elif type(self.var_emit[0]) is ProductCategorical:
+            # the Categorical rule element by element (emit_inter[k]: the D columns side by side)
+            for k in range(self.K):
+                G = self.var_emit[k]
+                nats_old = np.concatenate(G.alpha_mf) - 1.
+                nats_new = (1. - lrate) * nats_old + lrate * bfact * emit_inter[k]
+                G._set_alpha(np.split(nats_new + 1., np.cumsum(G.V)[:-1]))
+        elif type(self.var_emit[0]) is ProductPoisson:
+            # the Gaussian branch's blend (reference :1050-1069, the prior once) in the Gamma natural parameters
+            # (a - 1, -b): their offsets cancel, and the factors stay positive for every lrate in [0, 1]
+            for k in range(self.K):
+                G = self.var_emit[k]
+                sx, n = emit_inter[k]
+                G._set_mf((1. - lrate) * G.alpha_mf + lrate * (G.alpha_0 + bfact * sx),
+                          (1. - lrate) * G.beta_mf + lrate * (G.beta_0 + bfact * n))
 
     def _global_update_niw_stacked(self, lrate, bfact, E):
         """The K-loop of reference :1050-1069 + util.py:28-60 on stacked arrays: the same
