@@ -309,9 +309,12 @@ int svihmm_suffstats(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t Lm
  *   fail with "... svihmm_estep_sequences keeps var_x only".
  * The E-step of a chosen subset of the declared sequences: svihmm_estep_sequence_subset below.
  * Decoding all declared sequences in one call: svihmm_viterbi_sequences / svihmm_ffbs_sequences below.
+ * The resident SVI loop on minibatches of whole sequences: svihmm_svi_sequences / svihmm_svi_iteration_sequences
+ *   (with the svihmm_svi_* family below).
  * Not covered: hmmsgd_metaobs.VBHMM on a list (its batch factors, quirk Q3, have no agreed multi-sequence
  *   form; the boundary check above lets a caller sample windows safely), the fp32 mode, host lliks in
- *   svihmm_estep_sequences, K > 256. */
+ *   svihmm_estep_sequences, K > 256; in the resident loop on sequences additionally AdaGrad and a communicator
+ *   (multi-GPU minibatches of sequences). */
 int svihmm_set_sequences(svihmm_ctx* h, const int64_t* seq_off, int32_t N);
 int svihmm_estep_sequences(svihmm_ctx* h, uint32_t flags, double* out_packed, double* out_seq_lb,
                            double* out_q0);
@@ -446,7 +449,8 @@ int svihmm_ffbs_sequences(svihmm_ctx* h, uint32_t flags, const double* logA, int
  *   to back -- to the last workgroup of its theta builder; either may be NULL).  The loop orders its
  *   streams with device-side counters; a dependency that is not met within a minute (a kernel of
  *   the loop never ran) makes this call fail and ends the loop.  svihmm_svi_read_state: current var_tran [K,K], var_init [K] (the stationary vector
- *   of the last iteration, quirk Q5), NIW factors; any pointer may be NULL. */
+ *   of the last iteration, quirk Q5; after svihmm_svi_sequences the LEARNED initial-state factor), NIW factors; any
+ *   pointer may be NULL. */
 int svihmm_svi_begin(svihmm_ctx* h, int32_t K, int32_t D, const double* prior_tran,
                      const double* var_tran, const double* mu0, const double* sigma0,
                      const double* kappa0, const double* nu0, const double* prior_logpart,
@@ -516,6 +520,44 @@ int svihmm_svi_read_elbo(svihmm_ctx* h, int32_t n, double* out_elbo, double* out
 int svihmm_read_globals(svihmm_ctx* h, double* mod_init_out, double* ltran_out);
 int svihmm_svi_read_state(svihmm_ctx* h, double* var_tran, double* var_init, double* mu,
                           double* sigma, double* kappa, double* nu);
+
+/* The resident loop on minibatches of WHOLE declared sequences (hmmbatchsgd.VBHMM(seq_minibatch = M)): after any
+ * svihmm_svi_begin* the loop steps on M of the N sequences of svihmm_set_sequences per iteration instead of windows of
+ * one chain.  The initial-state factor is a LEARNED Dirichlet (no stationary vector, no quirk Q2 / Q3).
+ *
+ * svihmm_svi_sequences(prior_init[K], var_init[K]): puts both into the resident state and switches the loop to the
+ *   sequence form.  Needs a running loop and a declaration.  Fails with a message before any state is touched on: no
+ *   loop; no declaration; a NULL pointer; an entry of prior_init or var_init that is not finite or lies below
+ *   SVIHMM_SVI_MIN_PSEUDOCOUNT (every later var_init is a convex combination of var_init and prior_init + bf q0, so
+ *   none falls below the smaller of the two -- svihmm_svi_begin's argument for var_tran); an AdaGrad accumulator is
+ *   set; a communicator is attached (multi-GPU minibatches of sequences are out of scope).
+ *   Afterwards svihmm_svi_iteration fails and names svihmm_svi_iteration_sequences, and svihmm_svi_set_adagrad with an
+ *   accumulator fails; without this call svihmm_svi_iteration_sequences fails and names it.  The next
+ *   svihmm_svi_begin* starts a window loop again.  From this call on the loop is ordered by its streams and events
+ *   (no device-side counters; svihmm_svi_recoveries is not raised).
+ * svihmm_svi_iteration_sequences(it, idx[M], flags, rho, bfact): one iteration, asynchronous.  With bf = bfact (N / M):
+ *   1. globals: ltran as in the window loop; mod_init[k] = psi(var_init[k] + eps) - psi(sum var_init + eps) from the
+ *      resident learned var_init.  svihmm_read_globals afterwards returns these -- the globals the iteration's E-step
+ *      ran under (formed from the state BEFORE its step).
+ *   2. E-step: exactly what svihmm_estep_sequence_subset(idx, M, flags) defines (routing, presence rules,
+ *      SVIHMM_MASK_AS_NAN, SVIHMM_TRANS_WRAP, duplicates once per occurrence), always fp64; nothing is read back.
+ *   3. step, every product and sum rounded on its own:
+ *        var_init' = (1 - rho) var_init + rho (prior_init + bf q0)
+ *        var_tran' = ((1 - rho)(var_tran - 1) + rho ((prior_tran - 1) + bf A_raw)) + 1      (the prior once)
+ *        emission factors: the family's blend with bE = bf (NIW, diagonal, Poisson: the window loop's expressions);
+ *        Categorical / multi-column Categorical: alpha' = ((1 - rho)(alpha - 1) + rho ((alpha0 - 1) + bf counts)) + 1
+ *   4. elbo[it] = bf lb + dirichlet(prior_init, var_init') + sum_i dirichlet_row_i(prior_tran, var_tran')
+ *      + sum_k vlb_k(factors'): hmmbase.lower_bound() with _lZ = bf lb on the state after the step.
+ *   svihmm_svi_read_elbo, _read_factors, _read_state and svihmm_read_globals work as before; var_init is the learned
+ *   factor.  After an iteration var_x of the R listed rows is readable (what = 3) and svihmm_read_packed gives the
+ *   statistics the step consumed, as after svihmm_estep_sequence_subset; the declaration, the resident rows, the mask,
+ *   T and the centre are untouched.
+ *   Fails before any device work on: it outside [0, maxit); idx NULL; M < 1; an entry outside [0, N) (position and
+ *   value in the message); SVIHMM_USE_HOST_LLIKS; SVIHMM_SVI_KEEP_WINDOW; rho or bfact not finite; R beyond the
+ *   statistics GEMM's row offsets; and what svihmm_estep_sequence_subset refuses about the model (K > 256). */
+int svihmm_svi_sequences(svihmm_ctx* h, const double* prior_init /*[K]*/, const double* var_init /*[K]*/);
+int svihmm_svi_iteration_sequences(svihmm_ctx* h, int32_t it, const int32_t* idx, int32_t M,
+                                   uint32_t flags, double rho, double bfact);
 
 /* Categorical emissions (hmmsgd_metaobs.py:907-926, 1071-1084; pybasicbayes Categorical):
  * obs must be [T][1] holding the symbol index 0..V-1 as a double; logp[k][v] =

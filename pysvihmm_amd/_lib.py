@@ -85,6 +85,9 @@ SIGNATURES = {
     "svihmm_svi_begin": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [_c_double_p] * 11 + [C.c_int32, C.c_double]),
     "svihmm_svi_iteration": (C.c_int, [C.c_void_p, C.c_int32, _c_int64_p, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_int32, C.c_int32, C.c_uint32, C.c_double, C.c_double, C.c_double]),
+    "svihmm_svi_sequences": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p]),
+    "svihmm_svi_iteration_sequences": (C.c_int, [C.c_void_p, C.c_int32, C.POINTER(C.c_int32), C.c_int32, C.c_uint32,
+                                                 C.c_double, C.c_double]),
     "svihmm_svi_read_elbo": (C.c_int, [C.c_void_p, C.c_int32, _c_double_p, _c_double_p]),
     "svihmm_svi_begin_diag": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [_c_double_p] * 4 + [C.c_int32]),
     "svihmm_svi_begin_cat": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32] + [_c_double_p] * 4 + [C.c_int32]),

@@ -277,9 +277,17 @@ __device__ __forceinline__ void svi_arrive(const SviSync& sy) {
 // entry e of the transition factor (shared by the families' global-step kernels)
 __device__ __forceinline__ void svi_tran_step(int e, int K, const double* __restrict__ packed,
                                               const double* __restrict__ prior_tran, double* __restrict__ var_tran,
-                                              double rho, double bA, double nwin, double* __restrict__ ada_G) {
+                                              double rho, double bA, double nwin, double* __restrict__ ada_G,
+                                              const SviSeqStep& sq = SviSeqStep{nullptr, nullptr, nullptr, nullptr}) {
 #pragma clang fp contract(off)     // (see svi_niw_* below: the same roundings in whichever kernel this is inlined into)
   if (e >= K * K) return;
+  if (sq.q0) {
+    // minibatch of whole sequences (hmmbatchsgd._global_update_from_stats): the prior enters once, not once per
+    // window; bA = N / M.  The first K threads also step the learned initial-state factor.
+    if (e < K) sq.var_init[e] = (1.0 - rho) * sq.var_init[e] + rho * (sq.prior_init[e] + bA * sq.q0[e]);
+    var_tran[e] = ((1.0 - rho) * (var_tran[e] - 1.0) + rho * ((prior_tran[e] - 1.0) + bA * packed[e])) + 1.0;
+    return;
+  }
   const double a_inter = packed[e] + nwin * (prior_tran[e] - 1.0);
   const double nat_old = var_tran[e] - 1.0;
   if (ada_G) {
@@ -292,6 +300,16 @@ __device__ __forceinline__ void svi_tran_step(int e, int K, const double* __rest
   } else {
     var_tran[e] = ((1.0 - rho) * nat_old + rho * (bA * a_inter)) + 1.0;
   }
+}
+
+// the minibatch's local bound as the ELBO kernel adds it: the windows' sum as it is, a minibatch of whole sequences
+// times bE = N / M (hmmbase.lower_bound with _lZ = bf lb)
+__device__ __forceinline__ double svi_lb_keep(double lb, double bE, const SviSeqStep& sq) { return sq.q0 ? bE * lb : lb; }
+// One Dirichlet pseudo-count of the Categorical families (fam 2 / 3) in the sequence form of the step: the prior once,
+// the counts times bE = N / M; every product and sum rounded on its own
+__device__ __forceinline__ double svi_dirichlet_seq_step(double rho, double bE, double alpha, double alpha0, double counts) {
+#pragma clang fp contract(off)
+  return ((1.0 - rho) * (alpha - 1.0) + rho * ((alpha0 - 1.0) + bE * counts)) + 1.0;
 }
 
 // The NIW factor's natural-parameter blend (hmmsgd_metaobs.py:1048-1069, util.py:28-60), one scalar at a time, for the

@@ -219,6 +219,10 @@ struct svihmm_ctx {
   int svi_family = 0;       // 0 NIW, 1 diagonal Gaussian, 2 Categorical, 3 multi-column Categorical, 4 Poisson
   std::vector<int> svi_mcat_V;   // family 3: the columns' symbol counts the loop was begun with
   double svi_zsign = 1.0, svi_prior_const = 0.0;
+  // svihmm_svi_sequences: the loop steps on minibatches of whole declared sequences (stream order and events only);
+  // the prior-only constant of the learned initial-state factor's ELBO term (0 in the window loop)
+  bool svi_seq = false;
+  double svi_prior_const_init = 0.0;
   double* svi_elbo = nullptr; int svi_elbo_cap = 0;      // pinned + mapped: elbo_vec
   std::vector<hipEvent_t> svi_ev;                        // iteration boundaries (iter_time)
   std::vector<int> svi_ev_begin;                         // event that marks the start of iteration it
@@ -345,6 +349,7 @@ struct SviStepArgs {
   const double* packed; const double* prior_tran; double* var_tran; const double* prior;
   double rho, bA, bE, nwin; double* lb_keep; double* ada_G;
   SviSync sy;          // the step's gate / poison / arrival
+  SviSeqStep sq;       // the sequence form of the step (all nullptr: the window loop)
 };
 // up to this many windows the wave-per-window scaled sweep beats the MFMA one (which is
 // latency-bound at ~0.9 us per step however few windows it gets): 2 x 1024 waves are resident

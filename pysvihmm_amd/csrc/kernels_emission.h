@@ -1648,15 +1648,15 @@ __global__ __launch_bounds__(64) void k_svi_step_theta32s(
     double* __restrict__ niw, const double* __restrict__ prior, int K, int D, double rho, double bA, double bE,
     double nwin, double* __restrict__ lb_keep, double* __restrict__ ada_G, SviSync ssy,
     int Kp, double* __restrict__ theta, int* __restrict__ status, double* __restrict__ orb,
-    double* __restrict__ logdet_out, uint4* __restrict__ uw, SviSync tsy) {
+    double* __restrict__ logdet_out, uint4* __restrict__ uw, SviSync tsy, SviSeqStep sq) {
   const size_t nmu = (size_t)K * D, nsg = (size_t)K * D * D;
   const int a = threadIdx.x;
   const bool go = svi_step_gate(ssy);
   if ((int)blockIdx.x >= K) {
     if (go) {
       const int e = ((int)blockIdx.x - K) * 64 + a;
-      if (e == 0) *lb_keep = packed[(size_t)K * K + nmu + K + nsg];
-      svi_tran_step(e, K, packed, prior_tran, var_tran, rho, bA, nwin, ada_G);
+      if (e == 0) *lb_keep = svi_lb_keep(packed[(size_t)K * K + nmu + K + nsg], bE, sq);
+      svi_tran_step(e, K, packed, prior_tran, var_tran, rho, bA, nwin, ada_G, sq);     // (sq: the sequence form, as in k_svi_global_step)
     }
     svi_arrive(ssy);
     return;

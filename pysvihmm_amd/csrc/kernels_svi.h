@@ -75,6 +75,55 @@ struct GthBack<0> {
   static __device__ __forceinline__ void run(const double (&)[64], int, int, double&) {}
 };
 
+// (a) for transition row i, by one workgroup of NWV waves (rs: NWV doubles of LDS)
+template <int NWV>
+__device__ __forceinline__ void svi_globals_row(int i, const double* __restrict__ var_tran, int K,
+                                                double* __restrict__ ltran, double* __restrict__ Aexp,
+                                                double* __restrict__ AexpT, double* __restrict__ rs) {
+  constexpr int NT = 64 * NWV;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  double s = 0.0;
+  for (int j = tid; j < K; j += NT) s += var_tran[(size_t)i * K + j];
+  s = wave_sum(s);
+  if (lane == 0) rs[w] = s;
+  __syncthreads();
+  double rsum = 0.0;
+  for (int u = 0; u < NWV; ++u) rsum += rs[u];
+  const double dgs = digamma_d(rsum + SVI_EPS);
+  for (int j = tid; j < K; j += NT) {
+    const size_t e = (size_t)i * K + j;
+    const double l = digamma_d(var_tran[e] + SVI_EPS) - dgs;
+    const double x = exp(l);
+    ltran[e] = l;
+    Aexp[e] = x;
+    AexpT[(size_t)j * K + i] = x;
+  }
+}
+// G1 for the loop on minibatches of whole sequences (svihmm_svi_iteration_sequences): (a) as above by workgroups
+// 0 .. K-1; the last workgroup forms mod_init[k] = psi(var_init[k] + eps) - psi(sum var_init + eps) from the resident
+// LEARNED initial-state factor -- no stationary vector, no elimination.  Stream order only: no gate, no arrival.
+template <int NWV>
+__global__ __launch_bounds__(64 * NWV) void k_svi_globals_seq(
+    const double* __restrict__ var_tran, const double* __restrict__ var_init, int K, double* __restrict__ ltran,
+    double* __restrict__ Aexp, double* __restrict__ AexpT, double* __restrict__ mod_init) {
+  __shared__ double rs[NWV];
+  constexpr int NT = 64 * NWV;
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  if ((int)blockIdx.x < K) {
+    svi_globals_row<NWV>(blockIdx.x, var_tran, K, ltran, Aexp, AexpT, rs);
+    return;
+  }
+  double s = 0.0;
+  for (int k = tid; k < K; k += NT) s += var_init[k];
+  s = wave_sum(s);
+  if (lane == 0) rs[w] = s;
+  __syncthreads();
+  double tot = 0.0;
+  for (int u = 0; u < NWV; ++u) tot += rs[u];
+  const double dsum = digamma_d(tot + SVI_EPS);
+  for (int k = tid; k < K; k += NT) mod_init[k] = digamma_d(var_init[k] + SVI_EPS) - dsum;
+}
+
 template <bool LDSW, int NWV>
 __device__ __forceinline__ void k_svi_globals_body(
     const double* __restrict__ var_tran, int K, double* __restrict__ work_g,
@@ -91,23 +140,7 @@ __device__ __forceinline__ void k_svi_globals_body(
     // ---- (a) psi-expectations of transition row i = blockIdx.x: 4096 digamma / exp evaluations
     // are ~40k cycles of fp64 work on one CU, so they are spread over K workgroups that run
     // beside the elimination (the last workgroup)
-    const int i = blockIdx.x;
-    double s = 0.0;
-    for (int j = tid; j < K; j += NT) s += var_tran[(size_t)i * K + j];
-    s = wave_sum(s);
-    if (lane == 0) rs[w] = s;
-    __syncthreads();
-    double rsum = 0.0;
-    for (int u = 0; u < NWV; ++u) rsum += rs[u];
-    const double dgs = digamma_d(rsum + SVI_EPS);
-    for (int j = tid; j < K; j += NT) {
-      const size_t e = (size_t)i * K + j;
-      const double l = digamma_d(var_tran[e] + SVI_EPS) - dgs;
-      const double x = exp(l);
-      ltran[e] = l;
-      Aexp[e] = x;
-      AexpT[(size_t)j * K + i] = x;
-    }
+    svi_globals_row<NWV>(blockIdx.x, var_tran, K, ltran, Aexp, AexpT, rs);
     return;
   }
   // ---- (b) stationary vector by GTH elimination, (c) mod_init: the last workgroup
@@ -255,6 +288,11 @@ __global__ __launch_bounds__(64 * NWV) void k_svi_globals(
 //                 G += (var_tran - 1)^2, step 1 / G^(1/4) per entry instead of rho
 //    emissions  : eta = [kappa mu, kappa, sigma + kappa mu mu', nu + 2 + D];
 //                 eta <- (1-rho) eta + rho (eta_0 + bE * [xbar, neff, S, neff]);  back to moments.
+//  Minibatches of whole sequences (sq.q0 != nullptr, svihmm_svi_iteration_sequences; bA = bE = N / M):
+//    transitions: var_tran <- (1-rho)(var_tran - 1) + rho ((prior_tran - 1) + bA A_raw) + 1   (the prior once; no AdaGrad)
+//    initial    : var_init <- (1-rho) var_init + rho (prior_init + bA q0)                      (svi_tran_step, entries < K)
+//    emissions  : the blends above and below with bE = N / M; fam 2 / 3 with the prior once (svi_dirichlet_seq_step);
+//    lb_keep = bE lb.
 //  grid: K workgroups (one NIW factor each) + ceil(K^2 / 256) for the transition factor.
 //  niw = [mu K*D | sigma K*D*D | kappa K | nu K] (the E-step's parameter block, updated in place);
 //  prior = [mu0 K*D | sigma0 K*D*D | kappa0 K | nu0 K].
@@ -262,15 +300,15 @@ __global__ __launch_bounds__(64 * NWV) void k_svi_globals(
 __device__ __forceinline__ void k_svi_global_step_body(
     const double* __restrict__ packed, const double* __restrict__ prior_tran, double* __restrict__ var_tran,
     double* __restrict__ niw, const double* __restrict__ prior, int K, int D, double rho, double bA,
-    double bE, double nwin, double* __restrict__ lb_keep, double* __restrict__ ada_G) {
+    double bE, double nwin, double* __restrict__ lb_keep, double* __restrict__ ada_G, const SviSeqStep& sq) {
   const size_t nmu = (size_t)K * D, nsg = (size_t)K * D * D;
   const int tid = threadIdx.x;
   if ((int)blockIdx.x >= K) {
     const int e = ((int)blockIdx.x - K) * 256 + tid;
     // the minibatch's local bound, kept for the ELBO kernel (which runs on a side stream while
-    // the next E-step already rewrites `packed`)
-    if (e == 0) *lb_keep = packed[(size_t)K * K + nmu + K + nsg];
-    svi_tran_step(e, K, packed, prior_tran, var_tran, rho, bA, nwin, ada_G);
+    // the next E-step already rewrites `packed`); sequence minibatches: times N / M
+    if (e == 0) *lb_keep = svi_lb_keep(packed[(size_t)K * K + nmu + K + nsg], bE, sq);
+    svi_tran_step(e, K, packed, prior_tran, var_tran, rho, bA, nwin, ada_G, sq);
     return;
   }
   const int k = blockIdx.x;
@@ -308,8 +346,8 @@ __device__ __forceinline__ void k_svi_global_step_body(
 __global__ __launch_bounds__(256) void k_svi_global_step(
     const double* __restrict__ packed, const double* __restrict__ prior_tran, double* __restrict__ var_tran,
     double* __restrict__ niw, const double* __restrict__ prior, int K, int D, double rho, double bA,
-    double bE, double nwin, double* __restrict__ lb_keep, double* __restrict__ ada_G, SviSync sy) {
-  if (svi_step_gate(sy)) k_svi_global_step_body(packed, prior_tran, var_tran, niw, prior, K, D, rho, bA, bE, nwin, lb_keep, ada_G);
+    double bE, double nwin, double* __restrict__ lb_keep, double* __restrict__ ada_G, SviSync sy, SviSeqStep sq) {
+  if (svi_step_gate(sy)) k_svi_global_step_body(packed, prior_tran, var_tran, niw, prior, K, D, rho, bA, bE, nwin, lb_keep, ada_G, sq);
   svi_arrive(sy);
 }
 
@@ -342,13 +380,15 @@ __device__ __forceinline__ void k_svi_vlb_body(
     const double* __restrict__ niw, const double* __restrict__ logdet, const double* __restrict__ prior,
     const double* __restrict__ prior_logpart, double zsign, int K, double* __restrict__ vlb,
     const double* __restrict__ prior_tran, const double* __restrict__ var_tran,
-    double* __restrict__ rowterm) {
+    double* __restrict__ rowterm, const SviSeqStep& sq) {
   const int lane = threadIdx.x;
   if ((int)blockIdx.x >= K) {
     // Dirichlet energy + entropy of transition row i for the UPDATED var_tran (hmmbase.
     // dirichlet_elbo, reference hmmsgd_metaobs.py:277-292) minus the prior-only constants
     // (lgamma of the prior row: added once by the host-supplied prior_const in k_svi_elbo)
-    svi_rowterm((int)blockIdx.x - K, K, lane, prior_tran, var_tran, rowterm);
+    // (workgroup 2 K, sequence minibatches only: the learned initial-state factor as one more such row)
+    if ((int)blockIdx.x - K == K) svi_rowterm(0, K, lane, sq.prior_init, sq.var_init, sq.term);
+    else svi_rowterm((int)blockIdx.x - K, K, lane, prior_tran, var_tran, rowterm);
     return;
   }
   const int k = blockIdx.x;
@@ -426,9 +466,9 @@ __global__ __launch_bounds__(64) void k_svi_vlb(
     const double* __restrict__ niw, const double* __restrict__ logdet, const double* __restrict__ prior,
     const double* __restrict__ prior_logpart, double zsign, int K, double* __restrict__ vlb,
     const double* __restrict__ prior_tran, const double* __restrict__ var_tran,
-    double* __restrict__ rowterm, SviSync sy, SviElboTail et) {
+    double* __restrict__ rowterm, SviSync sy, SviElboTail et, SviSeqStep sq) {
   const bool go = svi_gate(sy);
-  if (go) k_svi_vlb_body(theta, fab, F, D, Kp, niw, logdet, prior, prior_logpart, zsign, K, vlb, prior_tran, var_tran, rowterm);
+  if (go) k_svi_vlb_body(theta, fab, F, D, Kp, niw, logdet, prior, prior_logpart, zsign, K, vlb, prior_tran, var_tran, rowterm, sq);
   svi_arrive_elbo(sy, go, et, K, vlb, rowterm);
 }
 
@@ -440,18 +480,21 @@ __global__ __launch_bounds__(64) void k_svi_vlb(
 // ------------------------------------------------------------------------------------
 __device__ __forceinline__ void k_svi_elbo_body(int K, const double* __restrict__ vlb,
                                                  const double* __restrict__ rowterm, double prior_const,
-                                                 const double* __restrict__ lb, double* __restrict__ elbo_out) {
+                                                 const double* __restrict__ lb, double* __restrict__ elbo_out,
+                                                 const double* __restrict__ init_term) {
   if (threadIdx.x == 0) {
     double v = 0.0, d = 0.0;
     for (int k = 0; k < K; ++k) v += vlb[k];
     for (int i = 0; i < K; ++i) d += rowterm[i];
+    if (init_term) d += init_term[0];          // (sequence minibatches: the initial factor's row; its prior constant is in prior_const)
     *elbo_out = lb[0] + (d + prior_const) + v;
   }
 }
 __global__ __launch_bounds__(64) void k_svi_elbo(int K, const double* __restrict__ vlb,
                                                  const double* __restrict__ rowterm, double prior_const,
-                                                 const double* __restrict__ lb, double* __restrict__ elbo_out, SviSync sy) {
-  if (svi_gate(sy)) k_svi_elbo_body(K, vlb, rowterm, prior_const, lb, elbo_out);
+                                                 const double* __restrict__ lb, double* __restrict__ elbo_out, SviSync sy,
+                                                 const double* __restrict__ init_term) {
+  if (svi_gate(sy)) k_svi_elbo_body(K, vlb, rowterm, prior_const, lb, elbo_out, init_term);
   svi_arrive(sy);
 }
 
@@ -498,13 +541,13 @@ __device__ __forceinline__ void k_svi_global_step_simple_body(
     int fam, const double* __restrict__ packed, const double* __restrict__ prior_tran,
     double* __restrict__ var_tran, double* __restrict__ blk, const double* __restrict__ prior, int K, int W,
     double rho, double bA, double bE, double nwin, double* __restrict__ lb_keep, double* __restrict__ ada_G,
-    int nem) {
+    int nem, const SviSeqStep& sq) {
   const int tid = threadIdx.x;
   const size_t n = (size_t)K * W;
   if ((int)blockIdx.x >= nem) {
     const int e = ((int)blockIdx.x - nem) * 256 + tid;
-    if (e == 0) *lb_keep = packed[(size_t)K * K + (fam == 1 ? 2 * n + K : fam == 4 ? 2 * n : n)];
-    svi_tran_step(e, K, packed, prior_tran, var_tran, rho, bA, nwin, ada_G);
+    if (e == 0) *lb_keep = svi_lb_keep(packed[(size_t)K * K + (fam == 1 ? 2 * n + K : fam == 4 ? 2 * n : n)], bE, sq);
+    svi_tran_step(e, K, packed, prior_tran, var_tran, rho, bA, nwin, ada_G, sq);
     return;
   }
   const size_t e = (size_t)blockIdx.x * 256 + tid;
@@ -512,6 +555,7 @@ __device__ __forceinline__ void k_svi_global_step_simple_body(
   if (fam == 4) { svi_pois_step(e, K, W, packed, blk, prior, rho, bE); return; }
   if (fam == 2 || fam == 3) {
     const double counts = packed[(size_t)K * K + e];
+    if (sq.q0) { blk[e] = svi_dirichlet_seq_step(rho, bE, blk[e], prior[e], counts); return; }   // (the prior once)
     const double inter = nwin * (prior[e] - 1.0) + counts;
     blk[e] = ((1.0 - rho) * (blk[e] - 1.0) + (rho * bE) * inter) + 1.0;
     return;
@@ -532,8 +576,8 @@ __global__ __launch_bounds__(256) void k_svi_global_step_simple(
     int fam, const double* __restrict__ packed, const double* __restrict__ prior_tran,
     double* __restrict__ var_tran, double* __restrict__ blk, const double* __restrict__ prior, int K, int W,
     double rho, double bA, double bE, double nwin, double* __restrict__ lb_keep, double* __restrict__ ada_G,
-    int nem, SviSync sy) {
-  if (svi_step_gate(sy)) k_svi_global_step_simple_body(fam, packed, prior_tran, var_tran, blk, prior, K, W, rho, bA, bE, nwin, lb_keep, ada_G, nem);
+    int nem, SviSync sy, SviSeqStep sq) {
+  if (svi_step_gate(sy)) k_svi_global_step_simple_body(fam, packed, prior_tran, var_tran, blk, prior, K, W, rho, bA, bE, nwin, lb_keep, ada_G, nem, sq);
   svi_arrive(sy);
 }
 
@@ -590,10 +634,11 @@ __device__ __forceinline__ double svi_mcat_vlb(const double* __restrict__ a_, co
 __device__ __forceinline__ void k_svi_vlb_simple_body(
     int fam, const double* __restrict__ blk, const double* __restrict__ prior, int K, int W,
     double* __restrict__ vlb, const double* __restrict__ prior_tran, const double* __restrict__ var_tran,
-    double* __restrict__ rowterm, const int* __restrict__ meta, int D) {
+    double* __restrict__ rowterm, const int* __restrict__ meta, int D, const SviSeqStep& sq) {
   const int lane = threadIdx.x;
   if ((int)blockIdx.x >= K) {
-    svi_rowterm((int)blockIdx.x - K, K, lane, prior_tran, var_tran, rowterm);
+    if ((int)blockIdx.x - K == K) svi_rowterm(0, K, lane, sq.prior_init, sq.var_init, sq.term);   // (as in k_svi_vlb_body)
+    else svi_rowterm((int)blockIdx.x - K, K, lane, prior_tran, var_tran, rowterm);
     return;
   }
   const int k = blockIdx.x;
@@ -637,9 +682,9 @@ __device__ __forceinline__ void k_svi_vlb_simple_body(
 __global__ __launch_bounds__(64) void k_svi_vlb_simple(
     int fam, const double* __restrict__ blk, const double* __restrict__ prior, int K, int W,
     double* __restrict__ vlb, const double* __restrict__ prior_tran, const double* __restrict__ var_tran,
-    double* __restrict__ rowterm, const int* __restrict__ meta, int D, SviSync sy, SviElboTail et) {
+    double* __restrict__ rowterm, const int* __restrict__ meta, int D, SviSync sy, SviElboTail et, SviSeqStep sq) {
   const bool go = svi_gate(sy);
-  if (go) k_svi_vlb_simple_body(fam, blk, prior, K, W, vlb, prior_tran, var_tran, rowterm, meta, D);
+  if (go) k_svi_vlb_simple_body(fam, blk, prior, K, W, vlb, prior_tran, var_tran, rowterm, meta, D, sq);
   svi_arrive_elbo(sy, go, et, K, vlb, rowterm);
 }
 

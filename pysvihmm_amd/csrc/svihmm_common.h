@@ -37,3 +37,16 @@ struct SviSync {
   unsigned poison_val;
 };
 #define SVI_POISON_BASE 0x7fffffffu
+
+// The loop on minibatches of whole sequences (svihmm_svi_iteration_sequences); passed by value, all nullptr in the
+// window loop.  The global-step kernels: q0 != nullptr selects the sequence form of the step (the prior once, the
+// statistics times N / M) and the step of the learned initial-state factor
+//   var_init <- (1 - rho) var_init + rho (prior_init + bf q0),
+// taken by the threads that step the first K transition entries.  The ELBO kernels: term != nullptr adds one
+// workgroup that forms the initial factor's Dirichlet term from prior_init / var_init.
+struct SviSeqStep {
+  const double* q0;            // [K] sum of the listed sequences' first posterior rows (behind the M local bounds)
+  const double* prior_init;    // [K]
+  double* var_init;            // [K] resident, learned
+  double* term;                // the initial factor's ELBO term (one double)
+};

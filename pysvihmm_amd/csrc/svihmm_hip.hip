@@ -1639,7 +1639,7 @@ static int estep_sequences_core(svihmm_ctx* h, uint32_t flags, bool subset = fal
 
 // estep_sequences_core always in fp64, the precision mode's report about the last E-step batch held (as
 // svihmm_grow_windows), then the packed result's host-visible mirror
-static int estep_sequences_fp64(svihmm_ctx* h, uint32_t flags, bool subset) {
+static int estep_sequences_fp64(svihmm_ctx* h, uint32_t flags, bool subset, bool mirror = true) {
   int rc;
   {
     ReportHold hold(h, true, true);
@@ -1649,7 +1649,8 @@ static int estep_sequences_fp64(svihmm_ctx* h, uint32_t flags, bool subset) {
   if (rc) return rc;
   h->have_packed = true;
   h->mirror_valid = false;
-  return launch_mirror(h);
+  // (the resident SVI loop reads nothing back: svihmm_read_packed fills the mirror when somebody asks)
+  return mirror ? launch_mirror(h) : 0;
 }
 
 // What svihmm_estep_sequences and svihmm_estep_sequence_subset share, found before any device work:
@@ -1713,53 +1714,74 @@ struct SubsetView {
   }
 };
 
-int svihmm_estep_sequence_subset(svihmm_ctx* h, const int32_t* idx, int32_t M, uint32_t flags, double* out_packed,
-                                 double* out_seq_lb, double* out_q0) {
-  const char* fn = "svihmm_estep_sequence_subset";
+// The host half of a subset call, before any device work: the listed sequences checked, dst_off [M + 1] | src_off [M]
+// (the compact copy's offsets -- its declaration -- and where each occurrence comes from), the model and the
+// statistics pass's limits.  `fn`: the entry point's name in the messages.
+struct SubsetPlan { std::vector<int64_t> tab; int64_t R = 0, maxlen = 0; };
+static int subset_plan(const svihmm_ctx* h, const char* fn, const int32_t* idx, int32_t M, uint32_t flags, SubsetPlan& p) {
   const auto bad = [fn](const std::string& what) { return fail(std::string(fn) + ": " + what); };
-  if (!h) return bad("NULL handle");
   if (h->seq_off.empty()) return bad("no sequences declared: call svihmm_set_sequences first");
   if (!idx) return bad("idx is NULL");
   if (M < 1) return bad("M = " + std::to_string(M) + ": at least one sequence must be listed");
-  const int N = (int)h->seq_off.size() - 1, D = h->D;
+  const int N = (int)h->seq_off.size() - 1;
   const std::vector<int64_t>& so = h->seq_off;
-  // dst_off [M + 1] | src_off [M]: the compact copy's offsets (its declaration) and where each occurrence comes from
-  std::vector<int64_t> tab((size_t)2 * M + 1);
+  p.tab.assign((size_t)2 * M + 1, 0);
   int64_t R = 0, maxlen = 0;
   for (int m = 0; m < M; ++m) {
     const int32_t s = idx[m];
     if (s < 0 || s >= N)
       return bad("idx[" + std::to_string(m) + "] = " + std::to_string(s) + " is outside [0, N = " + std::to_string(N) + ")");
-    tab[m] = R;
-    tab[(size_t)M + 1 + m] = so[s];
+    p.tab[m] = R;
+    p.tab[(size_t)M + 1 + m] = so[s];
     R += so[s + 1] - so[s];
     maxlen = std::max(maxlen, so[s + 1] - so[s]);
   }
-  tab[M] = R;
+  p.tab[M] = R;
+  p.R = R; p.maxlen = maxlen;
   CK(check_estep_sequences(h, fn, flags));
   CK(check_stats_rows(h, fn, R, "R = " + std::to_string(R) + " listed rows"));
+  return 0;
+}
+// The device half, enqueue only: gather, then the E-step of the compact copy into h->packed, h->seq_out
+// (local_lb[M] | q0[K]) and the posteriors of the R rows.  `in_loop`: svihmm_svi_iteration_sequences -- stream order
+// carries the loop's dependencies (no wait for its side stream here), and the statistics' host-visible mirror is
+// left to whoever reads them.
+static int subset_enqueue(svihmm_ctx* h, const SubsetPlan& p, int M, uint32_t flags, bool in_loop) {
+  const int D = h->D;
+  const int64_t R = p.R;
   CK(set_device(h));
-  CK(wait_side_streams(h));
+  if (!in_loop) CK(wait_side_streams(h));
   // the resident copy's lazily applied state first: symbol indices go back to exact integers before they are copied
   // (the lookup kernels would do that to the rows in place; a Gaussian family's centre is the handle's, and the copy
   // holds the same centred values)
   if (h->emis_cat) CK(cat_uncentre(h));
   CK(ensure(h->sub_obs, (size_t)R * D * sizeof(double)));
   if (h->have_mask) CK(ensure(h->sub_mask, (size_t)R));
-  CK(ensure(h->sub_tab, tab.size() * sizeof(int64_t)));
-  CK(upload_staged(h, h->sub_tab.p, tab.data(), tab.size() * sizeof(int64_t)));
-  CK(launch_seq_gather(h, M, (const int64_t*)h->sub_tab.p, (int)maxlen, (double*)h->sub_obs.p, (uint8_t*)h->sub_mask.p));
-  std::vector<int64_t> compact(tab.begin(), tab.begin() + M + 1);
+  CK(ensure(h->sub_tab, p.tab.size() * sizeof(int64_t)));
+  CK(upload_staged(h, h->sub_tab.p, p.tab.data(), p.tab.size() * sizeof(int64_t)));
+  CK(launch_seq_gather(h, M, (const int64_t*)h->sub_tab.p, (int)p.maxlen, (double*)h->sub_obs.p, (uint8_t*)h->sub_mask.p));
+  std::vector<int64_t> compact(p.tab.begin(), p.tab.begin() + M + 1);
   {
     SubsetView view(h, R, compact);
-    CK(estep_sequences_fp64(h, flags, true));
+    CK(estep_sequences_fp64(h, flags, true, !in_loop));
   }
+  return 0;
+}
+
+int svihmm_estep_sequence_subset(svihmm_ctx* h, const int32_t* idx, int32_t M, uint32_t flags, double* out_packed,
+                                 double* out_seq_lb, double* out_q0) {
+  const char* fn = "svihmm_estep_sequence_subset";
+  if (!h) return fail(std::string(fn) + ": NULL handle");
+  SubsetPlan p;
+  CK(subset_plan(h, fn, idx, M, flags, p));
+  CK(subset_enqueue(h, p, M, flags, false));
   return read_estep_sequences(h, M, out_packed, out_seq_lb, out_q0);
 }
 
 // ---- device-resident SVI loop (hmmsgd_metaobs.py:347-445) ------------------------------------
 // layout of h->svi_state: var_tran K*K | prior_tran K*K | var_init K | vlb K | logdet K | prior_logpart K | rowterm K |
-// var_init' K (the stationary vector is double-buffered: the next iteration's is computed ahead)
+// var_init' K (the stationary vector is double-buffered: the next iteration's is computed ahead) | lb block 16 |
+// ada_G K*K | prior_init K.  Sequence minibatches (svihmm_svi_sequences): var_init is the learned factor, first slot only
 static double* svi_ptr(svihmm_ctx* h, int which) {
   const size_t K = h->svi_K, kk = K * K;
   double* b = (double*)h->svi_state.p;
@@ -1773,6 +1795,8 @@ static double* svi_ptr(svihmm_ctx* h, int which) {
     case 6: return b + 2 * kk + 4 * K;   // rowterm (Dirichlet terms of the transition rows)
     case 7: return b + 2 * kk + 5 * K;   // second var_init slot
     case 8: return b + 2 * kk + 6 * K;   // lb of the last two iterations (read by the side-stream ELBO kernel)
+    case 10: return b + 3 * kk + 6 * K + 16;   // prior_init K (svihmm_svi_sequences)
+    case 11: return b + 2 * kk + 6 * K + 2;    // the initial factor's ELBO term (svihmm_svi_sequences; in the lb block)
     default: return b + 2 * kk + 6 * K + 16;   // ada_G K*K (AdaGrad: accumulated squared natural parameters)
   }
 }
@@ -1847,9 +1871,10 @@ static int svi_probe_concurrency(svihmm_ctx* h) {
   h->svi_concurrent = ok;
   return 0;
 }
-static int svi_globals(svihmm_ctx* h, int slot, int for_it) {
+// mod_init / ltran / exp(ltran) and its transpose for the loop's K, the padding rows behind the two matrices zeroed on
+// stream `st` when the buffers are new
+static int svi_globals_buffers(svihmm_ctx* h, hipStream_t st, bool zero_now) {
   const int K = h->svi_K;
-  double* vi_out = svi_ptr(h, slot ? 7 : 2);
   const size_t kk = (size_t)K * K * sizeof(double);
   CK(ensure(h->mod_init, K * sizeof(double)));
   CK(ensure(h->ltran, kk));
@@ -1857,6 +1882,17 @@ static int svi_globals(svihmm_ctx* h, int slot, int for_it) {
   const size_t slack = (size_t)(reach - K + 16) * K * sizeof(double);
   CK(ensure(h->Aexp, kk + slack));
   CK(ensure(h->AexpT, kk + slack));
+  if (zero_now && (h->slack_a != h->Aexp.p || h->slack_t != h->AexpT.p || h->slack_k != K)) {
+    HIPCK(hipMemsetAsync((char*)h->Aexp.p + kk, 0, slack, st));
+    HIPCK(hipMemsetAsync((char*)h->AexpT.p + kk, 0, slack, st));
+    h->slack_a = h->Aexp.p; h->slack_t = h->AexpT.p; h->slack_k = K;
+  }
+  return 0;
+}
+static int svi_globals(svihmm_ctx* h, int slot, int for_it) {
+  const int K = h->svi_K;
+  double* vi_out = svi_ptr(h, slot ? 7 : 2);
+  CK(svi_globals_buffers(h, nullptr, false));
   // The globals kernel depends on var_tran only, i.e. on the previous global step: it is launched
   // on a side stream right after that step and runs beside the rest of the iteration (theta, ELBO
   // kernels) and the next iteration's uploads and emission GEMM; the sweeps wait for it
@@ -1880,11 +1916,7 @@ static int svi_globals(svihmm_ctx* h, int slot, int for_it) {
     HIPCK(hipEventRecord(h->svi_ea, h->stream));
     HIPCK(hipStreamWaitEvent(s2, h->svi_ea, 0));
   }
-  if (h->slack_a != h->Aexp.p || h->slack_t != h->AexpT.p || h->slack_k != K) {
-    HIPCK(hipMemsetAsync((char*)h->Aexp.p + kk, 0, slack, s2));
-    HIPCK(hipMemsetAsync((char*)h->AexpT.p + kk, 0, slack, s2));
-    h->slack_a = h->Aexp.p; h->slack_t = h->AexpT.p; h->slack_k = K;
-  }
+  CK(svi_globals_buffers(h, s2, true));       // (the padding rows, behind the wait above)
   const size_t work = 2 * (size_t)K * (K | 1) * sizeof(double);
   const int use_lds = work + 9 * 1024 <= 150 * 1024;
   if (!use_lds) CK(ensure(h->svi_work, work));
@@ -1916,6 +1948,13 @@ static int svi_globals(svihmm_ctx* h, int slot, int for_it) {
 // their ELBO term vlb[] and, with elbo_it >= 0, elbo_vec[elbo_it] on the side stream -- only the
 // ELBO trace needs them, so they stay off the critical path of the iteration chain.
 static int svi_launch_elbo(svihmm_ctx* h, int elbo_it, int lb_slot, bool behind_sweeps, hipEvent_t after_theta);
+// what the step and ELBO kernels take for the loop on sequence minibatches (all nullptr: the window loop); M: the
+// minibatch's size -- q0 lies behind the M local bounds in h->seq_out
+static SviSeqStep svi_seq_args(svihmm_ctx* h, int M) {
+  if (!h->svi_seq) return SviSeqStep{nullptr, nullptr, nullptr, nullptr};
+  return SviSeqStep{M > 0 ? (const double*)h->seq_out.p + M : (const double*)nullptr, (const double*)svi_ptr(h, 10),
+                    svi_ptr(h, 2), svi_ptr(h, 11)};
+}
 static int svi_refresh_emission(svihmm_ctx* h, int elbo_it, int lb_slot, hipEvent_t after_theta = nullptr,
                                 bool defer_elbo = false, const SviStepArgs* step = nullptr) {
   const int K = h->svi_K, D = h->svi_D, fam = h->svi_family;
@@ -1990,21 +2029,26 @@ static int svi_launch_elbo(svihmm_ctx* h, int elbo_it, int lb_slot, bool behind_
     const bool tail = h->svi_flags && elbo_it >= 0;
     const SviElboTail et = {tail ? delbo + elbo_it : (double*)nullptr, (const double*)svi_ptr(h, 8) + lb_slot,
                             h->svi_prior_const, (unsigned)h->tgt_side};
+    // sequence minibatches (stream events only, no tail): one more workgroup for the learned initial-state factor's
+    // term, its prior constant beside the rows'
+    const SviSeqStep sq = svi_seq_args(h, 0);
+    const unsigned nvlb = (unsigned)(2 * K) + (h->svi_seq ? 1u : 0u);
+    const double prior_const = h->svi_seq ? h->svi_prior_const + h->svi_prior_const_init : h->svi_prior_const;
     if (fam == 0)
-      hipLaunchKernelGGL(k_svi_vlb, dim3(2 * K), dim3(64), 0, s2, (const double*)h->theta.p,
+      hipLaunchKernelGGL(k_svi_vlb, dim3(nvlb), dim3(64), 0, s2, (const double*)h->theta.p,
                          (const int*)h->fab.p, h->F, D, h->Kp, (const double*)h->niw.p,
                          (const double*)svi_ptr(h, 4), (const double*)h->svi_prior.p,
                          (const double*)svi_ptr(h, 5), h->svi_zsign, K, svi_ptr(h, 3),
-                         (const double*)svi_ptr(h, 1), (const double*)svi_ptr(h, 0), svi_ptr(h, 6), vsy, et);
+                         (const double*)svi_ptr(h, 1), (const double*)svi_ptr(h, 0), svi_ptr(h, 6), vsy, et, sq);
     else
-      hipLaunchKernelGGL(k_svi_vlb_simple, dim3(2 * K), dim3(64), 0, s2, fam, (const double*)h->niw.p,
+      hipLaunchKernelGGL(k_svi_vlb_simple, dim3(nvlb), dim3(64), 0, s2, fam, (const double*)h->niw.p,
                          (const double*)h->svi_prior.p, K, fam == 1 || fam == 4 ? D : h->V, svi_ptr(h, 3),
                          (const double*)svi_ptr(h, 1), (const double*)svi_ptr(h, 0), svi_ptr(h, 6),
-                         (const int*)(fam == 3 ? h->mcat_meta.p : nullptr), D, vsy, et);
+                         (const int*)(fam == 3 ? h->mcat_meta.p : nullptr), D, vsy, et, sq);
     if (elbo_it >= 0 && !tail) {      // (stream-event choreography: no arrival counter to tell the last workgroup by)
       hipLaunchKernelGGL(k_svi_elbo, dim3(1), dim3(64), 0, s2, K, (const double*)svi_ptr(h, 3),
-                         (const double*)svi_ptr(h, 6), h->svi_prior_const, (const double*)svi_ptr(h, 8) + lb_slot,
-                         delbo + elbo_it, vsy);
+                         (const double*)svi_ptr(h, 6), prior_const, (const double*)svi_ptr(h, 8) + lb_slot,
+                         delbo + elbo_it, vsy, (const double*)sq.term);
     }
     HIPCK(hipGetLastError());
   }
@@ -2030,6 +2074,7 @@ static int svi_begin_common(svihmm_ctx* h, int K, int D, const double* prior_tra
   // leave it marked as live (svi_begin_finish sets the flag again once everything is in place)
   h->svi_active = false;
   h->svi_adagrad = false;
+  h->svi_seq = false; h->svi_prior_const_init = 0.0;
   CK(set_device(h));
   CK(wait_side_streams(h));
   CK(drop_auto_status(h));
@@ -2062,7 +2107,7 @@ static int svi_begin_common(svihmm_ctx* h, int K, int D, const double* prior_tra
     }
     h->svi_prior_const = pc;
   }
-  CK(ensure(h->svi_state, (3 * kk + 6 * (size_t)K + 16) * sizeof(double)));
+  CK(ensure(h->svi_state, (3 * kk + 7 * (size_t)K + 16) * sizeof(double)));
   h->svi_adagrad = false;
   void* pin = nullptr;
   int slot = 0;
@@ -2339,6 +2384,21 @@ static int svi_step_width(const svihmm_ctx* h) { return h->svi_family == 1 || h-
 // most eight iterations ahead: the window-start ring), the last applied iteration's ELBO entry is formed again
 // if its kernels were caught by the shutdown.  The event loop computes bit for bit what the counter loop does
 // (tests/test_gpu_classes.py::test_svi_loop_on_counters_equals_the_stream_event_loop).
+// every stream idle: counters, targets and the status word cleared, the iteration events there -- from here on the loop
+// runs on stream order and events
+static int svi_leave_counters(svihmm_ctx* h) {
+  HIPCK(hipMemset(h->svi_sync.p, 0, 8 * 64));
+  h->pin_status[1] = 0;
+  h->tgt_step = h->tgt_glob = h->tgt_theta = h->tgt_side = h->tgt_early = 0;
+  h->elbo_pending = false; h->vlb_pending = false; h->globals_ev = nullptr;
+  h->svi_flags = false;
+  while ((int)h->svi_ev.size() < 2 * h->svi_maxit) {
+    hipEvent_t e;
+    HIPCK(hipEventCreate(&e));
+    h->svi_ev.push_back(e);
+  }
+  return 0;
+}
 static int svi_recover(svihmm_ctx* h, bool clean) {
   if (!h->svi_flags) return 0;
   if (clean) CK(svi_flush_elbo(h));
@@ -2349,17 +2409,8 @@ static int svi_recover(svihmm_ctx* h, bool clean) {
   HIPCK(hipMemcpy(&poison, svi_cnt(h, 5), sizeof(unsigned), hipMemcpyDeviceToHost));
   const int submitted = h->svi_last_it;                     // last iteration handed to the device
   const int p = poison ? (int)(SVI_POISON_BASE - poison) : submitted + 1;   // first iteration that did not reach the state
-  HIPCK(hipMemset(h->svi_sync.p, 0, 8 * 64));
-  h->pin_status[1] = 0;
-  h->tgt_step = h->tgt_glob = h->tgt_theta = h->tgt_side = h->tgt_early = 0;
-  h->elbo_pending = false; h->vlb_pending = false; h->globals_ev = nullptr;
-  h->svi_flags = false;
+  CK(svi_leave_counters(h));
   ++h->svi_recoveries;
-  while ((int)h->svi_ev.size() < 2 * h->svi_maxit) {
-    hipEvent_t e;
-    HIPCK(hipEventCreate(&e));
-    h->svi_ev.push_back(e);
-  }
   if (p > submitted + 1 || p < 0) return fail("SVI loop: inconsistent poison word after a gate gave up");
   // the ELBO entry of the last iteration that did reach the state: its kernels may have found the loop dead
   if (p >= 1 && std::isnan(h->svi_elbo[p - 1])) CK(svi_launch_elbo(h, p - 1, (p - 1) & 1, false, nullptr));
@@ -2396,6 +2447,9 @@ int svihmm_svi_iteration(svihmm_ctx* h, int32_t it, const int64_t* starts, int32
     return fail("svihmm_svi_iteration: the resident SVI loop does not take the Poisson family "
                 "from svihmm_set_emission_poisson alone: the family enters the loop through svihmm_svi_begin_poisson");
   if (!h || !h->svi_active) return fail("svihmm_svi_iteration: call svihmm_svi_begin first");
+  if (h->svi_seq)
+    return fail("svihmm_svi_iteration: the loop steps on minibatches of whole sequences since svihmm_svi_sequences: "
+                "call svihmm_svi_iteration_sequences");
   if (it < 0 || it >= h->svi_maxit) return fail("svihmm_svi_iteration: iteration index out of range");
   if (B < 0 || (B > 0 && !starts) || nwin_total < B) return fail("svihmm_svi_iteration: bad window batch");
   if (flags & SVIHMM_USE_HOST_LLIKS) return fail("svihmm_svi_iteration: device-side emission families only");
@@ -2508,7 +2562,8 @@ static int svi_iteration_impl(svihmm_ctx* h, int32_t it, const int64_t* starts, 
   } else if (h->vlb_pending) { HIPCK(hipStreamWaitEvent(h->stream, h->svi_ed, 0)); h->vlb_pending = false; }
   double* adag = h->svi_adagrad ? svi_ptr(h, 9) : (double*)nullptr;
   SviStepArgs sargs = {(const double*)h->packed.p, (const double*)svi_ptr(h, 1), svi_ptr(h, 0), (const double*)h->svi_prior.p,
-                       rho, bfactA, bfactE, (double)nwin_total, svi_ptr(h, 8) + (it & 1), adag, ssy};
+                       rho, bfactA, bfactE, (double)nwin_total, svi_ptr(h, 8) + (it & 1), adag, ssy,
+                       SviSeqStep{nullptr, nullptr, nullptr, nullptr}};
   if (merged) {
     if (h->svi_flags) h->tgt_step += ntran;          // (the merged kernel's transition workgroups: see k_svi_step_theta32s)
   } else {
@@ -2517,14 +2572,14 @@ static int svi_iteration_impl(svihmm_ctx* h, int32_t it, const int64_t* starts, 
       hipLaunchKernelGGL(k_svi_global_step, dim3((unsigned)K + ntran), dim3(256), (size_t)3 * D * sizeof(double), h->stream,
                          (const double*)h->packed.p, (const double*)svi_ptr(h, 1), svi_ptr(h, 0),
                          (double*)h->niw.p, (const double*)h->svi_prior.p, K, D, rho, bfactA, bfactE,
-                         (double)nwin_total, svi_ptr(h, 8) + (it & 1), adag, ssy);
+                         (double)nwin_total, svi_ptr(h, 8) + (it & 1), adag, ssy, sargs.sq);
     else {
       const int W = svi_step_width(h);
       const unsigned nem = (unsigned)(((size_t)K * W + 255) / 256);
       hipLaunchKernelGGL(k_svi_global_step_simple, dim3(nem + ntran), dim3(256), 0, h->stream, h->svi_family,
                          (const double*)h->packed.p, (const double*)svi_ptr(h, 1), svi_ptr(h, 0),
                          (double*)h->niw.p, (const double*)h->svi_prior.p, K, W, rho, bfactA, bfactE,
-                         (double)nwin_total, svi_ptr(h, 8) + (it & 1), adag, (int)nem, ssy);
+                         (double)nwin_total, svi_ptr(h, 8) + (it & 1), adag, (int)nem, ssy, sargs.sq);
     }
     HIPCK(hipGetLastError());
     if (h->svi_flags) h->tgt_step += step_grid;
@@ -2559,6 +2614,7 @@ int svihmm_svi_set_adagrad(svihmm_ctx* h, const double* ada_G) {
   if (!h || !h->svi_active) return fail("svihmm_svi_set_adagrad: call svihmm_svi_begin first");
   CK(set_device(h));
   if (!ada_G) { h->svi_adagrad = false; return 0; }
+  if (h->svi_seq) return fail("svihmm_svi_set_adagrad: AdaGrad is not supported on minibatches of whole sequences (svihmm_svi_sequences)");
   const size_t kk = (size_t)h->svi_K * h->svi_K;
   // ada_G >= 1: the reference starts it at ones and only adds squares (hmmsgd_metaobs.py:179-183,
   // :1036-1040), and the step's weights 1 / ada_G^.25 must stay <= 1 -- a larger weight would let
@@ -2595,6 +2651,131 @@ static int svi_settle(svihmm_ctx* h) {
   }
   return 0;
 }
+// ---- the loop on minibatches of whole declared sequences (include/svihmm.h) ----------------------
+// svihmm_svi_sequences: prior_init / var_init join the resident state, the loop leaves the counters for stream order
+// and events (what svi_recover(clean) does mid-loop, without counting as a recovery) and from here on steps through
+// svihmm_svi_iteration_sequences.
+int svihmm_svi_sequences(svihmm_ctx* h, const double* prior_init, const double* var_init) {
+  const char* fn = "svihmm_svi_sequences";
+  const auto bad = [fn](const std::string& what) { return fail(std::string(fn) + ": " + what); };
+  if (!h) return bad("NULL handle");
+  if (!h->svi_active) return bad("no loop: call one of svihmm_svi_begin, _begin_diag, _begin_cat, _begin_mcat, _begin_poisson first");
+  if (h->seq_off.empty()) return bad("no sequences declared: call svihmm_set_sequences first");
+  if (!prior_init) return bad("prior_init is NULL");
+  if (!var_init) return bad("var_init is NULL");
+  const int K = h->svi_K;
+  // every later var_init is a convex combination of var_init and prior_init + bf q0 (q0 >= 0): none falls below the
+  // smaller of the two -- svi_begin_common's argument for var_tran
+  for (int k = 0; k < K; ++k) {
+    if (!(prior_init[k] >= SVIHMM_SVI_MIN_PSEUDOCOUNT && prior_init[k] < 1.7e308))
+      return bad("prior_init[" + std::to_string(k) + "] = " + std::to_string(prior_init[k]) +
+                 " is not finite or lies below SVIHMM_SVI_MIN_PSEUDOCOUNT");
+    if (!(var_init[k] >= SVIHMM_SVI_MIN_PSEUDOCOUNT && var_init[k] < 1.7e308))
+      return bad("var_init[" + std::to_string(k) + "] = " + std::to_string(var_init[k]) +
+                 " is not finite or lies below SVIHMM_SVI_MIN_PSEUDOCOUNT");
+  }
+  if (h->svi_adagrad) return bad("an AdaGrad accumulator is set (svihmm_svi_set_adagrad): not supported on minibatches of whole sequences");
+  if (h->comm) return bad("a communicator is attached: multi-GPU minibatches of whole sequences are not supported");
+  CK(set_device(h));
+  // everything in flight first: begin's globals kernel writes the stationary vector into the slot var_init takes
+  CK(svi_settle(h));
+  if (h->svi_flags) CK(svi_leave_counters(h));
+  CK(svi_upload(h, svi_ptr(h, 2), var_init, (size_t)K, nullptr, 0, 0, 0));
+  CK(svi_upload(h, svi_ptr(h, 10), prior_init, (size_t)K, nullptr, 0, 0, 0));
+  {   // lgamma(sum_k p_k + eps) - sum_k lgamma(p_k + eps): the prior-only part of the initial factor's energy
+    double sum = 0.0, lg = 0.0;
+    for (int k = 0; k < K; ++k) { sum += prior_init[k]; lg += std::lgamma(prior_init[k] + 1e-9); }
+    h->svi_prior_const_init = std::lgamma(sum + 1e-9) - lg;
+  }
+  h->svi_seq = true;
+  h->svi_vi_cur = 0;
+  h->svi_globals_ready = false; h->globals_ev = nullptr;     // (each iteration forms its own globals, in stream order)
+  return 0;
+}
+
+// G1 of a sequence iteration, main stream: short without the elimination, and the E-step behind it needs no event
+static int svi_globals_sequences(svihmm_ctx* h) {
+  const int K = h->svi_K;
+  CK(svi_globals_buffers(h, h->stream, true));
+  {
+    ProfScope ps(h, KS_MISC);
+    hipLaunchKernelGGL((k_svi_globals_seq<SVI_GW>), dim3(K + 1), dim3(64 * SVI_GW), 0, h->stream,
+                       (const double*)svi_ptr(h, 0), (const double*)svi_ptr(h, 2), K, (double*)h->ltran.p,
+                       (double*)h->Aexp.p, (double*)h->AexpT.p, (double*)h->mod_init.p);
+    HIPCK(hipGetLastError());
+  }
+  h->globals_ev = nullptr;
+  h->K = K; h->have_globals = true; h->lin_stale = true;
+  h->exact_log = false; h->f32_ok = h->svi_f32_ok;
+  return 0;
+}
+
+int svihmm_svi_iteration_sequences(svihmm_ctx* h, int32_t it, const int32_t* idx, int32_t M, uint32_t flags, double rho,
+                                   double bfact) {
+  const char* fn = "svihmm_svi_iteration_sequences";
+  const auto bad = [fn](const std::string& what) { return fail(std::string(fn) + ": " + what); };
+  if (!h) return bad("NULL handle");
+  if (!h->svi_active) return bad("no loop: call one of svihmm_svi_begin* and svihmm_svi_sequences first");
+  if (!h->svi_seq) return bad("the loop steps on windows: call svihmm_svi_sequences first");
+  if (it < 0 || it >= h->svi_maxit)
+    return bad("it = " + std::to_string(it) + " is outside [0, maxit = " + std::to_string(h->svi_maxit) + ")");
+  if (flags & SVIHMM_SVI_KEEP_WINDOW) return bad("SVIHMM_SVI_KEEP_WINDOW is not supported (the iteration has no windows)");
+  if (!(std::fabs(rho) < 1.7e308)) return bad("rho is not finite");
+  if (!(std::fabs(bfact) < 1.7e308)) return bad("bfact is not finite");
+  // (the globals are the loop's own: formed below from the resident factors)
+  h->K = h->svi_K; h->have_globals = true;
+  SubsetPlan p;
+  CK(subset_plan(h, fn, idx, M, flags, p));
+  CK(set_device(h));
+  const int K = h->svi_K, D = h->svi_D;
+  h->svi_cur_it = it;
+  if ((int)h->svi_it_events.size() < h->svi_maxit) h->svi_it_events.resize(h->svi_maxit, (char)0);
+  h->svi_it_events[it] = (char)1;
+  // start of the iteration: the previous iteration's end marker while that iteration still runs (svi_iteration_impl)
+  if ((int)h->svi_ev_begin.size() < h->svi_maxit) h->svi_ev_begin.resize(h->svi_maxit, 0);
+  h->svi_ev_begin[it] = 2 * it;
+  if (it > 0 && h->svi_last_it == it - 1 && hipEventQuery(h->svi_ev[2 * it - 1]) == hipErrorNotReady)
+    h->svi_ev_begin[it] = 2 * it - 1;
+  else
+    HIPCK(hipEventRecord(h->svi_ev[2 * it], h->stream));
+  (void)hipGetLastError();            // (hipErrorNotReady is not an error here)
+  h->svi_last_it = it;
+  CK(svi_globals_sequences(h));
+  CK(subset_enqueue(h, p, M, flags, true));
+  // the previous iteration's ELBO kernels (their own stream) read var_tran / var_init / theta / logdet, which the step
+  // and the theta builder rewrite: the stream waits for their event
+  if (h->vlb_pending) { HIPCK(hipStreamWaitEvent(h->stream, h->svi_ed, 0)); h->vlb_pending = false; }
+  const bool merged = h->svi_family == 0 && step_theta_ok(h, K, D);
+  const unsigned ntran = (unsigned)((K * K + 255) / 256);
+  const SviSeqStep sq = svi_seq_args(h, M);
+  double* lb_keep = svi_ptr(h, 8) + (it & 1);
+  SviStepArgs sargs = {(const double*)h->packed.p, (const double*)svi_ptr(h, 1), svi_ptr(h, 0), (const double*)h->svi_prior.p,
+                       rho, bfact, bfact, 1.0, lb_keep, (double*)nullptr, SviSync{}, sq};
+  if (!merged) {
+    ProfScope ps(h, KS_MISC);
+    if (h->svi_family == 0)
+      hipLaunchKernelGGL(k_svi_global_step, dim3((unsigned)K + ntran), dim3(256), (size_t)3 * D * sizeof(double), h->stream,
+                         sargs.packed, sargs.prior_tran, sargs.var_tran, (double*)h->niw.p, sargs.prior, K, D, rho, bfact,
+                         bfact, 1.0, lb_keep, (double*)nullptr, SviSync{}, sq);
+    else {
+      const int W = svi_step_width(h);
+      const unsigned nem = (unsigned)(((size_t)K * W + 255) / 256);
+      hipLaunchKernelGGL(k_svi_global_step_simple, dim3(nem + ntran), dim3(256), 0, h->stream, h->svi_family,
+                         sargs.packed, sargs.prior_tran, sargs.var_tran, (double*)h->niw.p, sargs.prior, K, W, rho, bfact,
+                         bfact, 1.0, lb_keep, (double*)nullptr, (int)nem, SviSync{}, sq);
+    }
+    HIPCK(hipGetLastError());
+  }
+  // lower bound of var_tran after the step: (1 - rho) v + rho (prior_tran + bf A_raw) >= (1 - rho) bound + rho
+  if (rho >= 0.0 && rho <= 1.0) {
+    h->svi_vmin = (1.0 - rho) * h->svi_vmin + rho;
+    h->svi_f32_ok = h->svi_vmin > 0.05;
+  }
+  // theta / table of the new factors (with the step in the same launch where the window loop merges them), then the
+  // ELBO kernels on their own stream behind the iteration's end marker
+  return svi_refresh_emission(h, it, it & 1, h->svi_ev[2 * it + 1], false, merged ? &sargs : nullptr);
+}
+
 int svihmm_svi_read_elbo(svihmm_ctx* h, int32_t n, double* out_elbo, double* out_ms) {
   if (!h || !h->svi_active || n < 0 || n > h->svi_maxit) return fail("svihmm_svi_read_elbo: bad arguments");
   CK(set_device(h));

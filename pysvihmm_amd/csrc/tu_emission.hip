@@ -112,7 +112,7 @@ int launch_niw_to_theta(svihmm_ctx* h, int K, int D, double* logdet_out, const S
       hipLaunchKernelGGL(k_svi_step_theta32s, dim3((unsigned)K + ntr), dim3(64), 0, h->stream, step->packed, step->prior_tran,
                          step->var_tran, (double*)dmu, step->prior, K, D, step->rho, step->bA, step->bE, step->nwin,
                          step->lb_keep, step->ada_G, step->sy, Kp, (double*)h->theta.p, dstatus, orbp, logdet_out, uwp,
-                         h->theta_sy);
+                         h->theta_sy, step->sq);
     }
     else if (step) return fail("internal: step_theta_ok and launch_niw_to_theta disagree");
     else if (emd) NIWW(64);

@@ -881,6 +881,29 @@ class HipEngine(object):
                                                int(Lm), off, ln, int(flags), float(rho), float(bfactA),
                                                float(bfactE)), "svihmm_svi_iteration")
 
+    def svi_sequences(self, prior_init, var_init):
+        """After any ``svi_begin*``: the loop steps on minibatches of whole declared sequences
+        (``svihmm_svi_sequences``); ``prior_init`` / ``var_init`` [K], the learned initial-state factor, join the
+        resident state."""
+        self._pre_mutate()
+        shape = getattr(self, "_svi_shape", None)      # (no loop begun through this object: the library says so)
+        K = shape[0] if shape else np.asarray(var_init).shape[0]
+        p, v = L.as_f64(prior_init, (K,)), L.as_f64(var_init, (K,))
+        L.check(self._lib.svihmm_svi_sequences(self._h, L.dptr(p), L.dptr(v)), "svihmm_svi_sequences")
+
+    def svi_iteration_sequences(self, it, idx, flags, rho, bfact):
+        """Enqueue iteration ``it`` on the declared sequences listed in ``idx`` (asynchronous; ``bfact = N / M``)."""
+        self._pre_mutate()
+        ix = np.ascontiguousarray(np.asarray(idx).ravel(), dtype=np.int32)
+        if not np.array_equal(ix, np.asarray(idx).ravel()):
+            raise RuntimeError("svi_iteration_sequences: idx must hold integers that fit 32 bits")
+        L.check(self._lib.svihmm_svi_iteration_sequences(
+            self._h, int(it), ix.ctypes.data_as(C.POINTER(C.c_int32)) if len(ix) else None, len(ix), int(flags),
+            float(rho), float(bfact)), "svihmm_svi_iteration_sequences")
+        off = getattr(self, "seq_off", None)
+        if off is not None and len(ix):
+            self._rows = int((off[ix + 1] - off[ix]).sum())
+
     def svi_set_adagrad(self, ada_G):
         """AdaGrad accumulator of the transition factor joins the resident state (reference
         hmmsgd_metaobs.py:1036-1040); ``None`` switches back to the plain rho step."""

@@ -398,6 +398,87 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         return (self._niw_fastpath() or self._diag_fastpath() or self._cat_fastpath()
                 or self._mcat_fastpath() or self._poisson_fastpath())
 
+    # -- the device-resident SVI loop: what its class surfaces share -------------------------
+    # (hmmsgd_metaobs.VBHMM on windows of one chain, hmmbatchsgd.VBHMM(seq_minibatch=M) on whole sequences)
+    _SVI_BEGIN = {"niw": "svi_begin", "diag": "svi_begin_diag", "cat": "svi_begin_cat", "mcat": "svi_begin_mcat",
+                  "poisson": "svi_begin_poisson"}
+
+    def _svi_family(self):
+        """Emission family the device-resident loop runs for this model (None: host loop)."""
+        if self._niw_fastpath():
+            return "niw"
+        if self._diag_fastpath():
+            return "diag"
+        if self._cat_fastpath():
+            return "cat"
+        if self._mcat_fastpath():
+            return "mcat"
+        if self._poisson_fastpath():
+            return "poisson"
+        return None
+
+    def _svi_plain_vlb(self, fam):
+        """The emitters' ``get_vlb`` is the family's own (the loop's ELBO kernels restate it)."""
+        from .distributions import Categorical, DiagonalGaussian, ProductCategorical, ProductPoisson
+        cls = {"niw": Gaussian, "diag": DiagonalGaussian, "cat": Categorical, "mcat": ProductCategorical,
+               "poisson": ProductPoisson}[fam]
+        return all(type(e).get_vlb is cls.get_vlb for e in self.var_emit)
+
+    def _svi_begin(self, fam, maxit):
+        """Upload the transition factor and the family's prior / factors: the engine's ``svi_begin*``."""
+        from .distributions import niw_prior_logpart, vlb_logz_sign
+        eng = self.engine
+        if fam == "niw":
+            prior = self._prior_arrays()
+            fac = self._emission_arrays()
+            eng.svi_begin(self.prior_tran, self.var_tran, prior, fac,
+                          niw_prior_logpart(prior[1], prior[3]), maxit, vlb_logz_sign())
+        elif fam == "diag":
+            ve = self.var_emit
+            prior = tuple(np.array([getattr(g, n) for g in ve], dtype=np.float64)
+                          for n in ("mu_0", "nus_0", "alphas_0", "betas_0"))
+            eng.svi_begin_diag(self.prior_tran, self.var_tran, prior, self._diag_arrays(), maxit)
+        elif fam == "mcat":
+            ve = self.var_emit
+            stack = lambda name: [np.array([getattr(g, name)[d] for g in ve], dtype=np.float64)
+                                  for d in range(ve[0].D)]
+            eng.svi_begin_mcat(self.prior_tran, self.var_tran, stack("alphav_0"), stack("alpha_mf"), maxit)
+        elif fam == "poisson":
+            ve = self.var_emit
+            stack = lambda *names: tuple(np.array([getattr(g, n) for g in ve], dtype=np.float64) for n in names)
+            eng.svi_begin_poisson(self.prior_tran, self.var_tran, stack("alpha_0", "beta_0"),
+                                  stack("alpha_mf", "beta_mf"), ve[0].max_count, maxit)
+        else:
+            ve = self.var_emit
+            eng.svi_begin_cat(self.prior_tran, self.var_tran, np.array([g.alphav_0 for g in ve], dtype=np.float64),
+                              np.array([g.alpha_mf for g in ve], dtype=np.float64), maxit)
+
+    def _svi_pull_state(self):
+        """Device state -> the object's attributes (reference attribute names)."""
+        fam = self._svi_family()
+        if getattr(self, "adagrad", False):
+            self.ada_G = self.engine.svi_read_adagrad()
+        if fam != "niw":
+            vt, vi, fac = self.engine.svi_read_factors()
+            self.var_tran, self.var_init = vt, vi
+            for k, G in enumerate(self.var_emit):
+                if fam in ("diag", "poisson"):
+                    G._set_mf(*[a[k].copy() for a in fac])
+                elif fam == "mcat":
+                    G._set_alpha([c[k] for c in fac])
+                else:
+                    G._alpha_mf = fac[k].copy()
+                    G.weights = G._alpha_mf / G._alpha_mf.sum()
+            return
+        vt, vi, mu, sg, ka, nu = self.engine.svi_read_state()
+        self.var_tran, self.var_init = vt, vi
+        D = self.D
+        for k, G in enumerate(self.var_emit):
+            G.mu_mf = mu[k]; G.sigma_mf = sg[k]
+            G.kappa_mf = ka[k]; G.nu_mf = nu[k]
+            G.mu = G.mu_mf
+            G.sigma = G.sigma_mf / (G.nu_mf - D - 1)
+
     def _prior_arrays(self):
         """Stacked NIW prior hyperparameters (mu_0 [K,D], sigma_0 [K,D,D], kappa_0 [K], nu_0 [K]).
         The priors of a model do not change after construction (the reference never writes

@@ -14,6 +14,7 @@ from .hmmbase import VariationalHMMBase, is_niw_gaussian, is_diag_gaussian
 from .distributions import ProductCategorical, ProductPoisson
 from .engine import rewrap_packed
 from . import util
+from . import _lib as L
 
 eps = 1e-9
 tau0 = 1.
@@ -31,7 +32,15 @@ class VBHMM(VariationalHMMBase):
     ``batchfactor``: ``var_init`` is blended like the other factors, ``elbo_vec[it]`` is the usual noisy
     estimate (``batchfactor`` times the minibatch's local bound), ``pred_logprob_mean / _std`` stay NaN per
     iteration.  After the last iteration one E-step over all sequences under the final parameters fills
-    ``var_x, lalpha, lbeta, lliks`` (all ``T`` rows) and ``hamming``."""
+    ``var_x, lalpha, lbeta, lliks`` (all ``T`` rows) and ``hamming``.
+
+    ``infer(device_loop=None)``: with ``seq_minibatch`` set, the iterations run in the engine's resident SVI loop
+    (``svi_begin*``, ``svi_sequences``, one ``svi_iteration_sequences`` call per iteration: the variational state
+    stays in HBM, the same draws come from the global stream, ``elbo_vec`` and ``iter_time`` -- device seconds --
+    from ``svi_read_elbo``) where ``_svi_sequences_refusal()`` finds nothing against it (an engine with the loop, one
+    of its emission families with the family's own ``get_vlb``, no piece of the host route overridden or wrapped,
+    ``prior_tran >= 1``, pseudo-counts in the loop's range); otherwise the host route above.  ``device_loop=False`` keeps the host route, ``device_loop=True`` raises ``RuntimeError`` with the
+    reason where the loop cannot be taken."""
 
     @staticmethod
     def make_param_dict(prior_init, prior_tran, prior_emit, tau=tau0,
@@ -75,11 +84,71 @@ class VBHMM(VariationalHMMBase):
         self.mod_init = np.zeros(self.K)
         self.mod_tran = np.zeros((self.K, self.K))
 
-    def infer(self, fused=True):
-        """reference hmmbatchsgd.py:143-200 (no early stop, ``if False:`` :180)."""
+    # pieces of the host route a subclass (or a wrapper set on the instance) may replace, and the engine calls it makes:
+    # where one is replaced the host route, which goes through them, is used (hmmsgd_metaobs.VBHMM._LOOP_HOOKS)
+    _SEQ_LOOP_HOOKS = ("local_update", "global_update", "lower_bound", "_seq_minibatch_stats", "_sequence_subset_estep",
+                       "_global_update_from_stats", "_natgrad_emissions", "_psi_expectations", "_emit_vlb",
+                       "_push_globals", "_push_emission")
+    _SEQ_ENGINE_CALLS = ("estep_sequence_subset", "set_globals", "set_emission_niw", "set_emission_diag",
+                         "set_emission_cat", "set_emission_mcat", "set_emission_poisson")
+
+    def _svi_sequences_refusal(self):
+        """Why ``infer`` cannot run in the engine's resident loop on sequence minibatches (None: it can)."""
+        if self.seq_minibatch is None:
+            return "seq_minibatch is not set"
+        eng = self.engine
+        if not (hasattr(eng, "svi_sequences") and hasattr(eng, "svi_iteration_sequences")):
+            return "the engine has no svi_sequences / svi_iteration_sequences"
+        fam = self._svi_family()
+        if fam is None or not hasattr(eng, self._SVI_BEGIN[fam]):
+            return "the emitters are none of the resident loop's families on this engine"
+        if not self._svi_plain_vlb(fam):
+            return "an emitter overrides get_vlb"
+        for name in self._SEQ_LOOP_HOOKS:
+            if name in self.__dict__ or getattr(type(self), name) is not getattr(VBHMM, name):
+                return "%s is overridden" % name
+        for name in self._SEQ_ENGINE_CALLS:
+            if name in getattr(eng, "__dict__", {}):
+                return "the engine's %s is replaced on the instance" % name
+        if np.min(self.prior_tran) < 1.0:
+            return "prior_tran has entries below 1"
+        for name in ("var_tran", "var_init", "prior_init"):
+            if not np.min(getattr(self, name)) >= L.SVI_MIN_PSEUDOCOUNT:
+                return "%s has entries below SVI_MIN_PSEUDOCOUNT = %g" % (name, L.SVI_MIN_PSEUDOCOUNT)
+        return None
+
+    def _infer_device_sequences(self):
+        """The iterations of ``infer`` in the engine's resident loop: upload once, one call per iteration with the
+        host route's draw, then ``elbo_vec`` / ``iter_time`` and the state back on the object."""
+        eng = self.engine
+        maxit, n, m = self.maxit, len(self.seq_off) - 1, self.seq_minibatch
+        self._upload_obs()
+        self._svi_begin(self._svi_family(), maxit)
+        eng.svi_sequences(self.prior_init, self.var_init)
+        self.batchfactor = bf = n / m
+        self._seq_var_x = None
+        for it in range(maxit):
+            self.lrate = (it + self.tau) ** (-self.kappa)
+            idx = np.sort(np.random.choice(n, size=m, replace=False))
+            eng.svi_iteration_sequences(it, idx, 0, self.lrate, bf)
+        elbo, ms = eng.svi_read_elbo(maxit)
+        self._svi_pull_state()
+        self.elbo_vec = elbo
+        self.iter_time = ms * 1e-3
+        self.elbo = elbo[-1]
+        if self.verbose:
+            for it in range(maxit):
+                print("iter: %d, ELBO: %.2f" % (it, elbo[it]))
+            sys.stdout.flush()
+
+    def infer(self, fused=True, device_loop=None):
+        """reference hmmbatchsgd.py:143-200 (no early stop, ``if False:`` :180).  ``device_loop``: see the class."""
         if type(self).local_update is not VariationalHMMBase.local_update \
                 or type(self).global_update is not VBHMM.global_update:
             fused = False
+        why = self._svi_sequences_refusal() if device_loop is not False else "device_loop=False"
+        if device_loop is True and why is not None:
+            raise RuntimeError("infer(device_loop=True): %s" % why)
         self._require_fused_sequences(fused)
         mb = self.seq_minibatch       # (a list of sequences: the line above has refused everything but the fused path)
         route = not fused and self._batch_stats_route(VBHMM.global_update, ("niw", "diag"))
@@ -93,7 +162,9 @@ class VBHMM(VariationalHMMBase):
         self.pred_logprob_std = np.nan * np.ones(maxit)
         self.iter_time = np.nan * np.ones(maxit)
 
-        for it in range(maxit):
+        if why is None:
+            self._infer_device_sequences()
+        for it in range(maxit if why is not None else 0):
             start_time = time.time()
             self.lrate = (it + self.tau) ** (-self.kappa)
             if mb is not None:

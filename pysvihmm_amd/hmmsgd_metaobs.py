@@ -394,32 +394,14 @@ class VBHMM(VariationalHMMBase):
                    "global_lower_bound", "local_lower_bound", "_minibatch_estep", "_stationary_init",
                    "_psi_expectations", "_emit_vlb", "_global_update_niw_stacked")
 
-    def _svi_family(self):
-        """Emission family the device-resident loop runs for this model (None: host loop)."""
-        if self._niw_fastpath():
-            return "niw"
-        if self._diag_fastpath():
-            return "diag"
-        if self._cat_fastpath():
-            return "cat"
-        if self._mcat_fastpath():
-            return "mcat"
-        if self._poisson_fastpath():
-            return "poisson"
-        return None
-
     def _svi_device_ok(self):
         eng = self.engine
         fam = self._svi_family()
-        begin = {"niw": "svi_begin", "diag": "svi_begin_diag", "cat": "svi_begin_cat", "mcat": "svi_begin_mcat",
-                 "poisson": "svi_begin_poisson"}
-        if fam is None or not hasattr(eng, begin[fam]):
+        if fam is None or not hasattr(eng, self._SVI_BEGIN[fam]):
             return False
         if self.adagrad and not hasattr(eng, "svi_set_adagrad"):
             return False
-        cls = {"niw": Gaussian, "diag": DiagonalGaussian, "cat": Categorical, "mcat": ProductCategorical,
-               "poisson": ProductPoisson}[fam]
-        if any(type(e).get_vlb is not cls.get_vlb for e in self.var_emit):
+        if not self._svi_plain_vlb(fam):
             return False
         for name in self._LOOP_HOOKS:
             if name in self.__dict__ or getattr(type(self), name) is not getattr(VBHMM, name):
@@ -434,37 +416,10 @@ class VBHMM(VariationalHMMBase):
             return False
         return True
 
-    def _svi_pull_state(self):
-        """Device state -> the object's attributes (reference attribute names)."""
-        fam = self._svi_family()
-        if self.adagrad:
-            self.ada_G = self.engine.svi_read_adagrad()
-        if fam != "niw":
-            vt, vi, fac = self.engine.svi_read_factors()
-            self.var_tran, self.var_init = vt, vi
-            for k, G in enumerate(self.var_emit):
-                if fam in ("diag", "poisson"):
-                    G._set_mf(*[a[k].copy() for a in fac])
-                elif fam == "mcat":
-                    G._set_alpha([c[k] for c in fac])
-                else:
-                    G._alpha_mf = fac[k].copy()
-                    G.weights = G._alpha_mf / G._alpha_mf.sum()
-            return
-        vt, vi, mu, sg, ka, nu = self.engine.svi_read_state()
-        self.var_tran, self.var_init = vt, vi
-        D = self.D
-        for k, G in enumerate(self.var_emit):
-            G.mu_mf = mu[k]; G.sigma_mf = sg[k]
-            G.kappa_mf = ka[k]; G.nu_mf = nu[k]
-            G.mu = G.mu_mf
-            G.sigma = G.sigma_mf / (G.nu_mf - D - 1)
-
     def _infer_device(self, adaptive, perIter, epsilon, minHalfL, avgResidual, Lincrement, Lcutoff):
         """The loop of reference :347-445 with one engine call per iteration; same random stream
         (minibatch sampling, select_L / select_buffer draws, the re-initialisation draws of
         :360-365) and same arithmetic as the host loop."""
-        from .distributions import niw_prior_logpart, vlb_logz_sign
         eng = self.engine
         comm = self.comm
         if comm is not None:
@@ -477,30 +432,7 @@ class VBHMM(VariationalHMMBase):
         fam = self._svi_family()
         wall = self.__dict__.setdefault("infer_wall_ms", {})
         t_mark = time.perf_counter()
-        if fam == "niw":
-            prior = self._prior_arrays()
-            fac = self._emission_arrays()
-            eng.svi_begin(self.prior_tran, self.var_tran, prior, fac,
-                          niw_prior_logpart(prior[1], prior[3]), maxit, vlb_logz_sign())
-        elif fam == "diag":
-            ve = self.var_emit
-            prior = tuple(np.array([getattr(g, n) for g in ve], dtype=np.float64)
-                          for n in ("mu_0", "nus_0", "alphas_0", "betas_0"))
-            eng.svi_begin_diag(self.prior_tran, self.var_tran, prior, self._diag_arrays(), maxit)
-        elif fam == "mcat":
-            ve = self.var_emit
-            stack = lambda name: [np.array([getattr(g, name)[d] for g in ve], dtype=np.float64)
-                                  for d in range(ve[0].D)]
-            eng.svi_begin_mcat(self.prior_tran, self.var_tran, stack("alphav_0"), stack("alpha_mf"), maxit)
-        elif fam == "poisson":
-            ve = self.var_emit
-            stack = lambda *names: tuple(np.array([getattr(g, n) for g in ve], dtype=np.float64) for n in names)
-            eng.svi_begin_poisson(self.prior_tran, self.var_tran, stack("alpha_0", "beta_0"),
-                                  stack("alpha_mf", "beta_mf"), ve[0].max_count, maxit)
-        else:
-            ve = self.var_emit
-            eng.svi_begin_cat(self.prior_tran, self.var_tran, np.array([g.alphav_0 for g in ve], dtype=np.float64),
-                              np.array([g.alpha_mf for g in ve], dtype=np.float64), maxit)
+        self._svi_begin(fam, maxit)
         if self.adagrad:        # the accumulator of reference :1036-1040 joins the resident state
             eng.svi_set_adagrad(self.ada_G)
         self.__dict__.pop("_pending_rows", None)
