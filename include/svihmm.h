@@ -584,7 +584,8 @@ int64_t svihmm_packed_len(svihmm_ctx* h);
  * SVIHMM_TRANS_WRAP and the inner segment of svihmm_estep_minibatch_ex behave as for the Categorical family, and
  * so does every entry point that dispatches on the emission family: loglik, forward_backward, estep_minibatch(_ex),
  * suffstats, estep_sequences, estep_sequence_subset, viterbi(_sequences), ffbs, ffbs_windows, ffbs_sequences,
- * grow_windows, state_argmax, read_intermediate / read_rows, read_packed, export / import / allreduce_packed.
+ * grow_windows, state_argmax, read_intermediate / read_rows, read_packed, export / import / allreduce_packed,
+ * heldout_rows and heldout_entries.
  * The symbol columns stay exact integers in the resident copy: an upload while the family is active is not
  * centred, a copy centred earlier is brought back, a Gaussian family that follows centres again.
  * Fails with a message before any device work (the handle stays usable): NULL V or logp; K < 1 or K > 256;
@@ -619,7 +620,7 @@ int svihmm_set_emission_mcat(svihmm_ctx* h, int32_t K, int32_t D, const int32_t*
  * Every entry point that dispatches on the emission family takes this one: loglik, forward_backward,
  * estep_minibatch(_ex), suffstats, estep_sequences, estep_sequence_subset, viterbi(_sequences), ffbs, ffbs_windows,
  * ffbs_sequences, grow_windows (both methods), state_argmax, read_intermediate / read_rows, read_packed, export /
- * import / allreduce_packed.  Always fp64, K <= 256.
+ * import / allreduce_packed, heldout_rows and heldout_entries.  Always fp64, K <= 256.
  * The counts stay exact in the resident copy, as for svihmm_set_emission_mcat: an upload while the family is active
  * is not centred, a copy centred earlier is brought back before the first lookup (an entry within 2^-20, relative,
  * of an integer becomes that integer; a fractional entry keeps its value to rounding, so 3.7 still counts as 3 and
@@ -662,6 +663,44 @@ int svihmm_niw_vlb_terms(svihmm_ctx* h, int32_t K, int32_t D, const double* mu,
  * "true observation" term). */
 int svihmm_pred_logprob(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t Lm,
                         uint32_t flags, double out2[2]);
+
+/* Held-out log-probability against the POSTERIOR BATCH CURRENTLY HELD: the var_x rows svihmm_read_rows(what = 3)
+ * would hand out, nrows of them, left by svihmm_forward_backward, svihmm_estep_minibatch(_ex), svihmm_estep_sequences
+ * or svihmm_estep_sequence_subset (svihmm_suffstats computes on the caller's posteriors and leaves the batch held as
+ * it is).  Neither function runs an E-step of its own, so one E-step can be scored several ways; both are always fp64,
+ * take K <= 256 and touch neither the packed statistics, the precision report nor var_x.  Towards a running resident
+ * SVI loop they behave as svihmm_suffstats does.  Both results are bit-reproducible run to run (fixed assignment of
+ * rows / entries to workgroups, partials added in workgroup order, no atomics).
+ *
+ * svihmm_heldout_rows (hmmbase.py:322-340), every family: for each batch row g whose resident row has mask != 0,
+ *   lp_g = LSE_k( log(var_x[g][k] + 1e-9) + ll_true[g][k] ),
+ * ll_true the family's llik of the row's resident values with the masking flag off.  After a window batch the rows
+ * are starts[b] + t (a row in two windows counts once per occurrence), after svihmm_estep_sequences all T rows,
+ * after svihmm_estep_sequence_subset the R gathered rows with the gathered copy's own values and mask bytes.
+ * out2 = {mean, count}, {NaN, 0} when no scored row is masked or the handle has no mask (then nothing is launched);
+ * out_lp (host, [nrows], optional): lp_g for the masked rows, NaN elsewhere.  The E-step is expected to have run
+ * with SVIHMM_MASK_AS_NAN; the call does not check that.
+ *
+ * svihmm_heldout_entries, the multi-column Categorical and the Poisson family: entry e is (g = row[e], d = col[e],
+ * x = val[e]), g a row of the batch held;
+ *   lp_e = LSE_k( log(var_x[g][k] + 1e-9) + term_k ),
+ *   multi-column Categorical: term_k = logp[k][off_d + (int)x]
+ *   Poisson: t = (double)c * elog[k][d] (one rounded multiply, never fused), t = t - erate[k][d], t = t - logfact[c],
+ *            c = (int)x.
+ * An entry whose x is not PRESENT under the family's own rule (above, NaN included) is skipped: out_lp[e] = NaN, not
+ * counted.  Duplicates count once each.  out2 = {mean over the counted entries, count}, {NaN, 0} when n = 0 (no
+ * launch) or nothing is counted.  The resident value at (g, d) is not looked at: blanking it before the E-step is the
+ * caller's job.
+ *
+ * Both fail with a message before any device work, the handle staying usable: NULL handle or out2; n < 0; NULL
+ * arrays with n > 0; a row[e] outside [0, nrows) or a col[e] outside [0, D) (the message gives e and the value); no
+ * posterior batch held -- no E-step-type call yet, or svihmm_loglik, svihmm_pred_logprob, a decoder or
+ * svihmm_grow_windows ran since, or new rows were uploaded (the message names the calls that leave one); K > 256 or
+ * a K of the globals that is not the batch's; _entries: another family than the two above; _rows: no
+ * emission family, a family other than the batch's, or a batch of host lliks (no "true observation"). */
+int svihmm_heldout_rows(svihmm_ctx* h, double out2[2], double* out_lp /*[nrows] or NULL*/);
+int svihmm_heldout_entries(svihmm_ctx* h, int64_t n, const int64_t* row /*[n]*/, const int32_t* col /*[n]*/,
+                           const double* val /*[n]*/, double out2[2], double* out_lp /*[n] or NULL*/);
 
 /* State decoding of the last estep/forward_backward call for the evaluation metrics
  * (hmmbase.py:346-355 hamming_dist; util.py:236-277 munkres_match's count matrix):

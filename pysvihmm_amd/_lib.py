@@ -106,6 +106,9 @@ SIGNATURES = {
                                               C.c_int32]),
     "svihmm_packed_len": (C.c_int64, [C.c_void_p]),
     "svihmm_pred_logprob": (C.c_int, [C.c_void_p, _c_int64_p, C.c_int32, C.c_int32, C.c_uint32, _c_double_p]),
+    "svihmm_heldout_rows": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p]),
+    "svihmm_heldout_entries": (C.c_int, [C.c_void_p, C.c_int64, _c_int64_p, C.POINTER(C.c_int32), _c_double_p,
+                                         _c_double_p, _c_double_p]),
     "svihmm_alloc_obs": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
     "svihmm_set_obs_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _c_double_p, C.c_void_p]),
     "svihmm_shift_obs": (C.c_int, [C.c_void_p, _c_double_p]),

@@ -174,6 +174,13 @@ struct svihmm_ctx {
   Buf dec_tab;
   std::vector<char> dec_host;
   int dec_result = 0;
+  // svihmm_heldout_rows / _entries score against the posterior batch an E-step-type call left: post_kind says which
+  // (0 none -- prepare_ll drops it, so every decoder / grow / loglik call does --, 1 a window batch, 2
+  // svihmm_estep_sequences, 3 svihmm_estep_sequence_subset), post_K / post_fam the K and the emission family
+  // (emission_family_id) it was computed with.  heldout: a device zero (the identity row map's one window start) |
+  // the entry lists | out_lp | the workgroups' partials
+  int post_kind = 0, post_K = 0, post_fam = -1;
+  Buf heldout;
   Buf vit;                         // svihmm_viterbi: score | z | final argmax | psi | path | chunk maps (launch_viterbi);
                                    // svihmm_ffbs_windows: logA | z | the caller's uniforms (launch_ffbs_windows);
                                    // svihmm_grow_windows: results / the rule's state (launch_grow_*)
@@ -306,6 +313,17 @@ inline size_t packed_len(const svihmm_ctx* h) {
   const size_t D = h->D > 0 ? h->D : 1;
   if (h->emis_diag) return (size_t)h->K * h->K + 2 * (size_t)h->K * D + h->K + 1;
   return (size_t)h->K * h->K + (size_t)h->K * D + h->K + (size_t)h->K * D * D + 1;
+}
+
+// the emission family in force: -1 none, 0 NIW, 1 diagonal Gaussian, 2 Categorical, 3 multi-column Categorical, 4 Poisson
+// (the numbering of svi_family)
+inline int emission_family_id(const svihmm_ctx* h) {
+  if (!h->have_emission) return -1;
+  return h->emis_pois ? 4 : h->emis_mcat ? 3 : h->emis_cat ? 2 : h->emis_diag ? 1 : 0;
+}
+// an E-step-type call has left its posterior batch (svihmm_ctx::post_kind)
+inline void note_posterior_batch(svihmm_ctx* h, int kind) {
+  h->post_kind = kind; h->post_K = h->K; h->post_fam = h->last_host_ll ? -1 : emission_family_id(h);
 }
 
 struct ProfScope {

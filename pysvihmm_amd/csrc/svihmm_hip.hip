@@ -23,6 +23,7 @@
 #include <algorithm>
 #include "device_helpers.h"
 #include "kernels_misc.h"
+#include "kernels_heldout.h"
 #include "kernels_svi.h"
 
 thread_local std::string g_err;
@@ -85,7 +86,7 @@ int svihmm_destroy(svihmm_ctx* h) {
                  &h->pipe_tabs[0].buf, &h->pipe_tabs[1].buf, &h->pipe_tabs[2].buf, &h->pipe_tabs[3].buf,
                  &h->pipe_tabs[4].buf, &h->pipe_tabs[5].buf, &h->pipe_tabs[6].buf, &h->pipe_tabs[7].buf,
                  &h->seq_off_d, &h->seq_q, &h->seq_work, &h->seq_ord, &h->seq_out, &h->dec_tab,
-                 &h->sub_obs, &h->sub_mask, &h->sub_tab};
+                 &h->sub_obs, &h->sub_mask, &h->sub_tab, &h->heldout};
   for (Buf* b : bufs) release(*b);
   if (h->vlb_host) { hipHostFree(h->vlb_host); h->vlb_host = nullptr; }
   if (h->svi_elbo) { hipHostFree(h->svi_elbo); h->svi_elbo = nullptr; }
@@ -177,6 +178,7 @@ int svihmm_set_obs(svihmm_ctx* h, const double* obs, int64_t T, int32_t D,
     HIPCK(hipMemcpyAsync(h->mask.p, mask, (size_t)T, hipMemcpyHostToDevice, h->stream));
   }
   h->T = T; h->D = D; h->gen_T = 0;
+  h->post_kind = 0;                    // (a held posterior batch described the previous rows)
   h->seq_off.clear();                  // (a declaration of sequences described the previous rows)
   h->svi_active = false;               // a resident SVI state belonged to the previous sequence
   h->center_pending = false;
@@ -358,6 +360,7 @@ int svihmm_alloc_obs(svihmm_ctx* h, int64_t T, int32_t D, int32_t with_mask) {
     HIPCK(hipMemsetAsync(h->mask.p, 0, (size_t)T, h->stream));
   }
   h->T = T; h->D = D; h->gen_T = 0;
+  h->post_kind = 0;
   h->seq_off.clear();
   h->svi_active = false;
   CK(reset_shift(h, std::vector<double>((size_t)D, 0.0), 0, 0));
@@ -1105,6 +1108,7 @@ int prepare_ll(svihmm_ctx* h, const int64_t* starts, int B, int Lm, uint32_t fla
   h->step_major = false;
   h->seq_result = false;
   h->dec_result = 0;
+  h->post_kind = 0;
   if (host_ll) {
     if (!h->have_host_ll || h->hostB != B || h->hostLm != Lm)
       return fail("SVIHMM_USE_HOST_LLIKS: no uploaded lliks of shape [B,Lm,K]");
@@ -1297,7 +1301,7 @@ static int estep_pipelined(svihmm_ctx* h, const int64_t* starts, int B, int Lm, 
   CK(ensure_stats(h, plan[0].nchunk + plan[1].nchunk));
   h->have_host_ll = false;
   h->lin_mode = true; h->lin_stale = false; h->last_host_ll = false; h->eh_in_llE = false; h->last_flags = flags;
-  h->cur_f32 = false; h->step_major = false; h->seq_result = false; h->dec_result = 0;
+  h->cur_f32 = false; h->step_major = false; h->seq_result = false; h->dec_result = 0; h->post_kind = 0;
   h->q_valid = false; h->curB = B;
   h->m_nb = 0; h->have_lb = true;
   hipStream_t A = h->stream, Bs = h->stream2;
@@ -1356,6 +1360,7 @@ int svihmm_forward_backward(svihmm_ctx* h, const int64_t* starts, int32_t B, int
   HIPCK(hipStreamSynchronize(h->stream));
   CK(check_emission_status(h));
   h->lastB = B; h->lastLm = Lm;
+  note_posterior_batch(h, 1);
   return 0;
 }
 
@@ -1435,6 +1440,7 @@ static int estep_core(svihmm_ctx* h, const int64_t* starts, int B, int Lm, int i
   h->have_packed = true;
   h->mirror_valid = false;
   h->lastB = B; h->lastLm = Lm;
+  note_posterior_batch(h, 1);
   return 0;
 }
 
@@ -1634,6 +1640,8 @@ static int estep_sequences_core(svihmm_ctx* h, uint32_t flags, bool subset = fal
   h->lastB = 1; h->lastLm = (int)T;
   h->seq_result = true;
   h->seq_subset = subset;
+  h->last_host_ll = false;
+  note_posterior_batch(h, subset ? 3 : 2);
   return 0;
 }
 
@@ -2890,6 +2898,175 @@ int svihmm_read_rows(svihmm_ctx* h, int32_t what, int64_t row0, int64_t nrows, d
   HIPCK(hipStreamSynchronize(h->stream));
   return 0;
 }
+
+// ---- held-out log-probability against the posterior batch held (kernels_heldout.h) -------------
+// Everything that can be wrong with a call is found before any device work.  The batch held: what the last
+// E-step-type call left (post_kind; prepare_ll drops it, so a decoder, svihmm_loglik or svihmm_grow_windows since
+// then means "none"), with the K it was computed with.
+static int heldout_batch(const svihmm_ctx* h, const char* fn, int64_t* nrows_out) {
+  const auto bad = [fn](const std::string& what) { return fail(std::string(fn) + ": " + what); };
+  if (h->post_kind == 0 || h->lastB <= 0 || h->dec_result)
+    return bad("no posterior batch held: call svihmm_forward_backward, svihmm_estep_minibatch(_ex), "
+               "svihmm_estep_sequences or svihmm_estep_sequence_subset first (a decoder, svihmm_loglik or "
+               "svihmm_grow_windows call since the last of them has dropped its batch)");
+  if (h->K != h->post_K)
+    return bad("the globals' K (" + std::to_string(h->K) + ") is not the K of the posterior batch held (" +
+               std::to_string(h->post_K) + "): run the E-step again");
+  if (h->K > 256) return bad("K = " + std::to_string(h->K) + " > 256 not supported");
+  *nrows_out = (int64_t)h->lastB * h->lastLm;
+  return 0;
+}
+// for the call's duration the handle's resident rows are the gathered copy svihmm_estep_sequence_subset left
+// (its own rows and mask bytes, R of them): what launch_emission reads
+struct GatheredRows {
+  svihmm_ctx* h; int64_t T; bool on;
+  GatheredRows(svihmm_ctx* h_, bool on_, int64_t R) : h(h_), T(h_->T), on(on_) {
+    if (on) { std::swap(h->obs, h->sub_obs); std::swap(h->mask, h->sub_mask); h->T = R; }
+  }
+  ~GatheredRows() {
+    if (on) { std::swap(h->obs, h->sub_obs); std::swap(h->mask, h->sub_mask); h->T = T; }
+  }
+};
+// the partials' sum and the results back: out2 = {mean, count}, out_lp[n] when asked for
+static int heldout_finish(svihmm_ctx* h, int nblk, double* part, const double* dlp, int64_t n, double out2[2], double* out_lp) {
+  hipLaunchKernelGGL(k_pred_final, dim3(1), dim3(64), 0, h->stream, (const double*)part, nblk, part + 2 * nblk);
+  HIPCK(hipGetLastError());
+  CK(d2h(h, out2, part + 2 * nblk, 2 * sizeof(double)));
+  if (out_lp) CK(d2h(h, out_lp, dlp, (size_t)n * sizeof(double)));
+  HIPCK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+#define HELDOUT_KT(L)                                                                                 \
+  do {                                                                                                \
+    if (K <= 16) L(1); else if (K <= 32) L(2); else if (K <= 48) L(3); else if (K <= 64) L(4);        \
+    else if (K <= 128) L(8); else L(16);                                                              \
+  } while (0)
+
+int svihmm_heldout_rows(svihmm_ctx* h, double out2[2], double* out_lp) {
+  const char* fn = "svihmm_heldout_rows";
+  const auto bad = [fn](const std::string& what) { return fail(std::string(fn) + ": " + what); };
+  if (!h) return bad("NULL handle");
+  if (!out2) return bad("out2 is NULL");
+  int64_t n = 0;
+  CK(heldout_batch(h, fn, &n));
+  if (h->last_host_ll)
+    return bad("the posterior batch held ran on host lliks (SVIHMM_USE_HOST_LLIKS): it has no true observation to score");
+  if (!h->have_emission)
+    return bad("no emission family: call svihmm_set_emission_niw / _diag / _cat / _mcat / _poisson first");
+  if (emission_family_id(h) != h->post_fam)
+    return bad("the emission family is not the one the posterior batch held was computed with: run the E-step again");
+  if (h->eK != h->K)
+    return bad("K of the globals (" + std::to_string(h->K) + ") differs from the emission family's K (" +
+               std::to_string(h->eK) + ")");
+  if (h->eD != h->D) return bad(emission_d_message(h));
+  if (!h->have_mask) {               // nothing can be masked: no launch
+    out2[0] = NAN; out2[1] = 0.0;
+    if (out_lp) for (int64_t g = 0; g < n; ++g) out_lp[g] = NAN;
+    return 0;
+  }
+  CK(set_device(h));
+  CK(wait_side_streams(h));
+  const int K = h->K;
+  const double* q = nullptr;
+  CK(intermediate_ptr(h, 3, 0, n, &q));
+  const int nblk = (int)((n + HELDOUT_PER_BLOCK - 1) / HELDOUT_PER_BLOCK);
+  // heldout: [ zero (the identity map's window start), 16 bytes | out_lp n | partials 2 nblk + 2 ]
+  CK(ensure(h->heldout, 16 + ((size_t)n + 2 * (size_t)nblk + 2) * sizeof(double)));
+  CK(ensure(h->m_ll, (size_t)n * K * sizeof(double)));
+  h->m_nb = 0;
+  const int64_t* zero = (const int64_t*)h->heldout.p;
+  double* dlp = (double*)((char*)h->heldout.p + 16);
+  double* part = dlp + n;
+  HIPCK(hipMemsetAsync(h->heldout.p, 0, 16, h->stream));
+  {
+    // the family's llik of the batch rows' true values (no masking), always fp64, into the side buffer; a window
+    // batch through its own starts, the two sequence kinds as one window over the rows from 0
+    GatheredRows view(h, h->post_kind == 3, n);
+    const bool windows = h->post_kind == 1;
+    if (windows) CK(ensure_starts_pulled(h));
+    const bool cur_f32 = h->cur_f32;
+    h->cur_f32 = false;
+    const uint32_t fl = windows ? h->last_flags & ~(uint32_t)(SVIHMM_MASK_AS_NAN | SVIHMM_USE_HOST_LLIKS) : 0u;
+    const int rc = launch_emission(h, windows ? h->lastB : 1, windows ? h->lastLm : (int)n, fl, false,
+                                   windows ? nullptr : zero, (double*)h->m_ll.p);
+    h->cur_f32 = cur_f32;
+    if (rc) return rc;
+    ProfScope ps(h, KS_MISC);
+#define HR(KT) hipLaunchKernelGGL(k_heldout_rows<KT>, dim3(nblk), dim3(256), 0, h->stream, q, (const double*)h->m_ll.p, \
+                                  (const uint8_t*)h->mask.p, windows ? (const int64_t*)h->starts.p : (const int64_t*)nullptr, \
+                                  n, h->lastLm, K, out_lp ? dlp : (double*)nullptr, part)
+    HELDOUT_KT(HR);
+#undef HR
+    HIPCK(hipGetLastError());
+  }
+  CK(heldout_finish(h, nblk, part, dlp, n, out2, out_lp));
+  return check_emission_status(h);
+}
+
+int svihmm_heldout_entries(svihmm_ctx* h, int64_t n, const int64_t* row, const int32_t* col, const double* val,
+                           double out2[2], double* out_lp) {
+  const char* fn = "svihmm_heldout_entries";
+  const auto bad = [fn](const std::string& what) { return fail(std::string(fn) + ": " + what); };
+  if (!h) return bad("NULL handle");
+  if (!out2) return bad("out2 is NULL");
+  if (n < 0) return bad("n = " + std::to_string(n) + " must not be negative");
+  if (n > 0 && (!row || !col || !val)) return bad("row, col and val must be given when n > 0");
+  int64_t nrows = 0;
+  CK(heldout_batch(h, fn, &nrows));
+  if (!h->have_emission || !(h->emis_mcat || h->emis_pois))
+    return bad("entry-wise scores are defined for the multi-column Categorical and the Poisson family only "
+               "(svihmm_set_emission_mcat / svihmm_set_emission_poisson); svihmm_heldout_rows takes every family");
+  if (h->eK != h->K)
+    return bad("K of the globals (" + std::to_string(h->K) + ") differs from the emission family's K (" +
+               std::to_string(h->eK) + ")");
+  const int K = h->K, D = h->eD;
+  for (int64_t e = 0; e < n; ++e) {
+    if (row[e] < 0 || row[e] >= nrows)
+      return bad("row[" + std::to_string(e) + "] = " + std::to_string(row[e]) + " is outside [0, nrows = " +
+                 std::to_string(nrows) + ")");
+    if (col[e] < 0 || col[e] >= D)
+      return bad("col[" + std::to_string(e) + "] = " + std::to_string(col[e]) + " is outside [0, D = " +
+                 std::to_string(D) + ")");
+  }
+  if (n == 0) { out2[0] = NAN; out2[1] = 0.0; return 0; }
+  CK(set_device(h));
+  CK(wait_side_streams(h));
+  const double* q = nullptr;
+  CK(intermediate_ptr(h, 3, 0, nrows, &q));
+  const int64_t nblk64 = (n + HELDOUT_PER_BLOCK - 1) / HELDOUT_PER_BLOCK;
+  if (nblk64 > 0x3fffffff) return bad("n = " + std::to_string(n) + " entries are too many for one launch");
+  const int nblk = (int)nblk64;
+  // heldout: [ zero, 16 bytes | out_lp n | partials 2 nblk + 2 | row n int64 | val n | col n int32 ]
+  CK(ensure(h->heldout, 16 + (3 * (size_t)n + 2 * (size_t)nblk + 2) * sizeof(double) + (size_t)n * sizeof(int32_t)));
+  double* dlp = (double*)((char*)h->heldout.p + 16);
+  double* part = dlp + n;
+  int64_t* drow = (int64_t*)(part + 2 * (size_t)nblk + 2);
+  double* dval = (double*)(drow + n);
+  int32_t* dcol = (int32_t*)(dval + n);
+  CK(upload_staged(h, drow, row, (size_t)n * sizeof(int64_t)));
+  CK(upload_staged(h, dval, val, (size_t)n * sizeof(double)));
+  CK(upload_staged(h, dcol, col, (size_t)n * sizeof(int32_t)));
+  {
+    ProfScope ps(h, KS_MISC);
+#define HE(KT)                                                                                                         \
+  do {                                                                                                                 \
+    if (h->emis_pois)                                                                                                  \
+      hipLaunchKernelGGL((k_heldout_entries<KT, true>), dim3(nblk), dim3(256), 0, h->stream, q, (const int64_t*)drow,  \
+                         (const int32_t*)dcol, (const double*)dval, n, K, D, (const double*)h->cat_table.p,            \
+                         (const int*)nullptr, (const double*)h->pois_logfact.p, h->pois_C,                             \
+                         out_lp ? dlp : (double*)nullptr, part);                                                       \
+    else                                                                                                               \
+      hipLaunchKernelGGL((k_heldout_entries<KT, false>), dim3(nblk), dim3(256), 0, h->stream, q, (const int64_t*)drow, \
+                         (const int32_t*)dcol, (const double*)dval, n, K, D, (const double*)h->cat_table.p,            \
+                         (const int*)h->mcat_meta.p, (const double*)nullptr, 0, out_lp ? dlp : (double*)nullptr, part); \
+  } while (0)
+    HELDOUT_KT(HE);
+#undef HE
+    HIPCK(hipGetLastError());
+  }
+  return heldout_finish(h, nblk, part, dlp, n, out2, out_lp);
+}
+#undef HELDOUT_KT
 
 int svihmm_state_argmax(svihmm_ctx* h, const int32_t* true_sts, int32_t* out_z,
                         int64_t* out_conf) {

@@ -358,6 +358,7 @@ class HipEngine(object):
         st = None if starts is None else self._starts(starts)
         B = len(st) if st is not None else int(B)
         self._rows = B * int(Lm)
+        self._held = None if st is None else ("windows", st, int(Lm))
         res = {}
         bufs = {}
         for name in ("lalpha", "lbeta", "var_x"):
@@ -381,6 +382,7 @@ class HipEngine(object):
         out = np.empty(self._packed_len()) if read else None
         off, ln = (0, int(Lm)) if inner is None else (int(inner[0]), int(inner[1]))
         self._rows = len(st) * int(Lm)
+        self._held = ("windows", st, int(Lm))
         L.check(self._lib.svihmm_estep_minibatch_ex(self._h, L.i64ptr(st), len(st), int(Lm),
                                                     off, ln, int(flags), L.dptr(out)),
                 "svihmm_estep_minibatch")
@@ -446,6 +448,7 @@ class HipEngine(object):
         L.check(self._lib.svihmm_estep_sequences(self._h, int(flags), L.dptr(out), L.dptr(seq_lb), L.dptr(q0)),
                 "svihmm_estep_sequences")
         self._rows = self.T
+        self._held = ("sequences",)
         return (self._wrap_packed(out) if read else None), seq_lb[:n], q0[:self.K]
 
     def estep_sequence_subset(self, idx, flags=0, read=True):
@@ -469,6 +472,7 @@ class HipEngine(object):
                 "svihmm_estep_sequence_subset")
         off = self.seq_off
         self._rows = int((off[ix + 1] - off[ix]).sum())
+        self._held = ("subset", ix)
         return (self._wrap_packed(out) if read else None), seq_lb, q0[:self.K]
 
     def _packed_len(self):
@@ -553,6 +557,94 @@ class HipEngine(object):
                                               L.dptr(out)), "svihmm_pred_logprob")
         n = int(out[1])
         return (float(out[0]) if n > 0 else None), n
+
+    def heldout_rows(self, want_lp=False):
+        """Held-out log-probability of the masked rows of the posterior batch the last E-step-type call left
+        (``svihmm_heldout_rows``; ``forward_backward``, ``estep``, ``estep_sequences``, ``estep_sequence_subset``),
+        every emission family, without another E-step: ``(mean or None, count)``, with ``want_lp`` also
+        ``lp[nrows]`` in batch-row order (NaN for the rows that are not masked).  The E-step is expected to have
+        run with ``MASK_AS_NAN``."""
+        out = np.empty(2)
+        lp = np.empty(max(int(getattr(self, "_rows", 0)), 1)) if want_lp else None
+        L.check(self._lib.svihmm_heldout_rows(self._h, L.dptr(out), L.dptr(lp)), "svihmm_heldout_rows")
+        n = int(out[1])
+        res = ((float(out[0]) if n > 0 else None), n)
+        return res + (lp[:int(self._rows)],) if want_lp else res
+
+    def _batch_rows_of(self, rows):
+        """Resident row numbers -> (batch rows, index of the entry each came from) under the last E-step's map."""
+        held = getattr(self, "_held", None)
+        if held is None:
+            raise RuntimeError("heldout_entries: no E-step batch of resident rows is known to this engine "
+                               "(forward_backward with starts, estep, estep_sequences, estep_sequence_subset)")
+        if held[0] == "sequences":
+            return rows, np.arange(len(rows), dtype=np.int64)
+
+        def expand(lo, hi, what):
+            # entry e owns positions lo[e] .. hi[e] - 1 of a sorted table: (e, position) of every pair
+            cnt = hi - lo
+            if len(cnt) and cnt.min() < 1:
+                bad = int(np.flatnonzero(cnt < 1)[0])
+                raise ValueError("heldout_entries: resident row %d (entry %d) lies in no %s of the batch held"
+                                 % (rows[bad], bad, what))
+            e = np.repeat(np.arange(len(lo), dtype=np.int64), cnt)
+            first = np.cumsum(cnt) - cnt
+            return e, np.arange(int(cnt.sum()), dtype=np.int64) - np.repeat(first, cnt) + np.repeat(lo, cnt)
+
+        if held[0] == "windows":
+            # every occurrence: window b holds resident row r at batch row b * Lm + (r - st[b]); the windows whose
+            # start lies in (r - Lm, r], found in the sorted starts, listed per entry in ascending b
+            st, Lm = held[1], held[2]
+            order = np.argsort(st, kind="stable")
+            ss = st[order]
+            e, p = expand(np.searchsorted(ss, rows - Lm, side="right"), np.searchsorted(ss, rows, side="right"), "window")
+            b = order[p]
+            o = np.lexsort((b, e))
+            e, b = e[o], b[o]
+            return b * Lm + (rows[e] - st[b]), e
+        # a subset: the declared sequence of every row, then its positions in idx (ascending), in the gathered order
+        ix, off = held[1].astype(np.int64), self.seq_off
+        s = np.searchsorted(off, rows, side="right") - 1
+        s[(rows < 0) | (rows >= off[-1])] = -1
+        order = np.argsort(ix, kind="stable")
+        si = ix[order]
+        e, p = expand(np.searchsorted(si, s, side="left"), np.searchsorted(si, s, side="right"), "listed sequence")
+        m = order[p]
+        dst = np.cumsum(off[ix + 1] - off[ix]) - (off[ix + 1] - off[ix])
+        return dst[m] + (rows[e] - off[ix[m]]), e
+
+    def heldout_entries(self, rows, cols, vals, resident=True, want_lp=False):
+        """Entry-wise held-out log-probability (``svihmm_heldout_entries``; multi-column Categorical and Poisson
+        families): entry ``e`` scores value ``vals[e]`` of column ``cols[e]`` against the posterior row
+        ``rows[e]`` of the batch the last E-step-type call left.  ``resident=True``: ``rows`` are resident row
+        numbers, mapped to batch rows from the last call -- after a window batch to every occurrence in the
+        windows (a row in no window raises ``ValueError``), after ``estep_sequences`` unchanged, after
+        ``estep_sequence_subset`` to its positions in the gathered order; ``resident=False``: batch rows as they
+        are.  Returns ``(mean or None, count)``; with ``want_lp`` also ``lp``, one value per entry passed to the
+        library (NaN for entries whose value is not present under the family's rule) and, when ``resident``
+        mapped them, ``src`` -- the index into ``rows`` each came from."""
+        r = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).ravel())
+        c = np.ascontiguousarray(np.asarray(cols, dtype=np.int32).ravel())
+        v = np.ascontiguousarray(np.asarray(vals, dtype=np.float64).ravel())
+        if not (len(r) == len(c) == len(v)):
+            raise ValueError("heldout_entries: rows, cols and vals must have one length")
+        src = None
+        if resident:
+            r, src = self._batch_rows_of(r)
+            r = np.ascontiguousarray(r, dtype=np.int64)
+            c, v = np.ascontiguousarray(c[src]), np.ascontiguousarray(v[src])
+        n = len(r)
+        out = np.empty(2)
+        lp = np.empty(max(n, 1)) if want_lp else None
+        L.check(self._lib.svihmm_heldout_entries(self._h, n, L.i64ptr(r) if n else None,
+                                                 c.ctypes.data_as(C.POINTER(C.c_int32)) if n else None,
+                                                 L.dptr(v) if n else None, L.dptr(out), L.dptr(lp)),
+                "svihmm_heldout_entries")
+        cnt = int(out[1])
+        res = ((float(out[0]) if cnt > 0 else None), cnt)
+        if not want_lp:
+            return res
+        return res + (lp[:n],) + ((src,) if resident else ())
 
     def state_argmax(self, true_sts=None, want_z=True):
         """``np.argmax(var_x, axis=1)`` over the rows of the last E-step (window-major) and, with
@@ -877,6 +969,7 @@ class HipEngine(object):
         st = self._starts(starts)
         off, ln = (0, int(Lm)) if inner is None else (int(inner[0]), int(inner[1]))
         self._rows = len(st) * int(Lm)
+        self._held = ("windows", st, int(Lm))
         L.check(self._lib.svihmm_svi_iteration(self._h, int(it), L.i64ptr(st), len(st), int(nwin_total),
                                                int(Lm), off, ln, int(flags), float(rho), float(bfactA),
                                                float(bfactE)), "svihmm_svi_iteration")
@@ -903,6 +996,7 @@ class HipEngine(object):
         off = getattr(self, "seq_off", None)
         if off is not None and len(ix):
             self._rows = int((off[ix + 1] - off[ix]).sum())
+            self._held = ("subset", ix)
 
     def svi_set_adagrad(self, ada_G):
         """AdaGrad accumulator of the transition factor joins the resident state (reference

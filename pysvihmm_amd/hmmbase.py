@@ -746,6 +746,100 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         flags = self._push_emission()
         self.engine.forward_backward([0], self.T, flags=flags, want=())
 
+    # -- held-out scores on the device ----------------------------------------------------
+    def _heldout_family(self):
+        """Emission family of the emitters as far as their types say (no engine is touched):
+        "niw", "diag", "cat", "mcat", "poisson" or None."""
+        from .distributions import ProductCategorical, ProductPoisson
+        ve = self.var_emit
+        if len(ve) and all(type(e) is ProductPoisson for e in ve):
+            return "poisson"
+        if len(ve) and all(type(e) is ProductCategorical for e in ve):
+            return "mcat"
+        if self._niw_fastpath():
+            return "niw"
+        if len(ve) and all(is_diag_gaussian(e) for e in ve):
+            return "diag"
+        if self._cat_fastpath():
+            return "cat"
+        return None
+
+    def _heldout_estep(self, what):
+        """The full E-step the held-out scores are taken against: the class's own ``_full_estep_device``
+        (the E-step of its ``full_local_update``: the whole chain, or every sequence from ``mod_init`` in
+        one device call; per-row results stay in HBM).  What that call writes on the way -- the
+        psi-expectations and the sequence bookkeeping -- is put back: no attribute of the model changes."""
+        if not self._device_family():
+            raise NotImplementedError("%s: the emitters are of a family this engine does not evaluate on the "
+                                      "device (the held-out kernels score against device lliks)" % what)
+        if not hasattr(self.engine, "heldout_rows"):
+            raise NotImplementedError("%s: this engine has no held-out kernels (heldout_rows / heldout_entries); "
+                                      "pred_logprob is the host route" % what)
+        names = ("mod_init", "mod_tran", "_seq_flags", "_seq_var_x", "_lZ")
+        none = object()
+        keep = {n: self.__dict__.get(n, none) for n in names}
+        try:
+            self._full_estep_device()
+        finally:
+            for n, v in keep.items():
+                if v is none:
+                    self.__dict__.pop(n, None)
+                else:
+                    self.__dict__[n] = v
+        return self.engine
+
+    def heldout_logprob(self):
+        """Mean predictive log-probability of the masked rows, the value ``pred_logprob_full`` defines
+        (``mean_t LSE_k(log(var_x[t, k] + 1e-9) + E_q log p(x_t | k))`` over the masked rows ``t``, ``var_x``
+        from the class's ``full_local_update`` E-step: ``hmmsgd_metaobs`` treats the masked rows as missing
+        there, the batch classes follow the reference's batch ``local_update``, which does not look at the
+        mask), computed on the device for every device family
+        (NIW, diagonal Gaussian, Categorical, ``ProductCategorical``, ``ProductPoisson``) and for a list
+        ``obs`` (every sequence from ``mod_init``, one device call): two doubles cross the bus instead of
+        ``var_x[T, K]``.  ``None`` without masked rows.  No attribute of the model changes.  Emitters without
+        a device family raise ``NotImplementedError``."""
+        if self._heldout_family() is None:
+            raise NotImplementedError("heldout_logprob: the emitters have no device family (NIW / diagonal "
+                                      "Gaussian, Categorical, ProductCategorical, ProductPoisson): their lliks "
+                                      "are evaluated on the host, use pred_logprob")
+        if not np.any(self.mask):
+            return None
+        val, _ = self._heldout_estep("heldout_logprob").heldout_rows()
+        return val
+
+    def heldout_entries_logprob(self, rows, cols, vals, per_entry=False):
+        """Entry-wise ("speckled") held-out score of a ``ProductCategorical`` / ``ProductPoisson`` model: the
+        entries ``(rows[e], cols[e])`` of ``obs`` (rows numbered over the concatenation when ``obs`` was a
+        list) were blanked -- set NaN, ``util.speckle_holdout`` -- before fitting; ``vals[e]`` is what stood
+        there.  Full E-step on the blanked data (the one ``heldout_logprob`` runs), then
+        ``lp_e = LSE_k(log(var_x[rows[e], k] + 1e-9) + E_q log p(vals[e] | k, column cols[e]))`` on the device:
+        the mean over the entries whose value is present under the family's rule (``None`` if there is none),
+        with ``per_entry`` ``(mean, lp[n])`` (NaN for the skipped ones).  ``ValueError`` unless every
+        ``obs[rows, cols]`` is NaN; ``NotImplementedError`` for other emitters (a NaN entry of a Gaussian row
+        blanks the whole row).  No attribute of the model changes."""
+        if self._heldout_family() not in ("mcat", "poisson"):
+            raise NotImplementedError("heldout_entries_logprob: entry-wise scores need ProductCategorical or "
+                                      "ProductPoisson emitters (columns independent given the state); other "
+                                      "families have no per-entry missingness")
+        r = np.asarray(rows, dtype=np.int64).ravel()
+        c = np.asarray(cols, dtype=np.int64).ravel()
+        v = np.asarray(vals, dtype=np.float64).ravel()
+        if not (len(r) == len(c) == len(v)):
+            raise ValueError("heldout_entries_logprob: rows, cols and vals must have one length")
+        obs = self.obs if self.obs.ndim == 2 else self.obs[:, None]
+        if len(r) and (r.min() < 0 or r.max() >= obs.shape[0] or c.min() < 0 or c.max() >= obs.shape[1]):
+            raise ValueError("heldout_entries_logprob: an entry lies outside obs %s" % (obs.shape,))
+        seen = obs[r, c]
+        if not np.all(np.isnan(seen)):
+            e = int(np.flatnonzero(~np.isnan(seen))[0])
+            raise ValueError("heldout_entries_logprob: obs[%d, %d] = %r is not blanked (entry %d): the posterior "
+                             "would have seen the value it is scored on" % (r[e], c[e], float(seen[e]), e))
+        eng = self._heldout_estep("heldout_entries_logprob")
+        res = eng.heldout_entries(r, c, v, resident=True, want_lp=per_entry)
+        if not per_entry:
+            return res[0]
+        return res[0], (res[2] if len(r) else np.empty(0))
+
     # -- Viterbi / MAP path -------------------------------------------------------------
     def viterbi(self, metaobs=None):
         """Most probable state sequence of the whole chain (or of one meta-observation

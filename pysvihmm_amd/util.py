@@ -107,6 +107,39 @@ def make_mask_prediction(sts, miss=0.):
     return out
 
 
+def speckle_holdout(obs, frac, seed, cols=None):
+    """Entry-wise ("speckled") hold-out for the product families: ``(obs_blanked, rows, cols, vals)``.
+    A ``frac`` fraction (rounded to the nearest count) of the non-NaN entries of ``obs`` -- of the columns
+    ``cols`` when given -- is drawn uniformly without replacement (``np.random.default_rng(seed)``) and set
+    NaN in a copy; ``obs`` itself is left as it is.  ``obs``: a ``[T, D]`` array or a list of ``[T_s, D]``
+    sequences (the copy is then a list of the same lengths); ``rows`` number the rows over the
+    concatenation, ``vals[e]`` is what stood at ``(rows[e], cols[e])``.  The triples come in ascending
+    (row, column) order.  Fit on ``obs_blanked``, then ``heldout_entries_logprob(rows, cols, vals)``."""
+    is_list = isinstance(obs, (list, tuple))
+    parts = [np.asarray(o, dtype=np.float64) for o in obs] if is_list else [np.asarray(obs, dtype=np.float64)]
+    parts = [p[:, None] if p.ndim == 1 else p for p in parts]
+    full = np.concatenate(parts, axis=0)          # (a copy: the caller's arrays are not written)
+    if not 0. <= frac <= 1.:
+        raise ValueError("speckle_holdout: frac = %r outside [0, 1]" % (frac,))
+    cand = ~np.isnan(full)
+    if cols is not None:
+        keep = np.zeros(full.shape[1], dtype=bool)
+        keep[np.asarray(cols, dtype=np.int64)] = True
+        cand &= keep[None, :]
+    flat = np.flatnonzero(cand)
+    n = int(round(frac * flat.size))
+    pick = np.sort(np.random.default_rng(seed).choice(flat, size=n, replace=False)) if n else flat[:0]
+    r, c = np.divmod(pick, full.shape[1])
+    vals = full[r, c].copy()
+    full[r, c] = np.nan
+    if is_list:
+        off = np.concatenate(([0], np.cumsum([p.shape[0] for p in parts])))
+        blanked = [full[off[s]:off[s + 1]] for s in range(len(parts))]
+    else:
+        blanked = full if np.ndim(obs) == 2 else full[:, 0]
+    return blanked, r.astype(np.int64), c.astype(np.int32), vals
+
+
 def munkres_match(sts_true, sts_pred, K):
     """Permutation of predicted labels minimising the Hamming distance
     (``util.py:236-277``); solved with ``scipy.optimize.linear_sum_assignment``."""
