@@ -639,6 +639,52 @@ int svihmm_set_emission_poisson(svihmm_ctx* h, int32_t K, int32_t D,
                                 const double* elog /*[K][D]*/, const double* erate /*[K][D]*/,
                                 const double* logfact /*[C + 1]*/, int32_t C);
 
+/* Gaussian tracks with missing entries: D real-valued columns per row, independent given the state,
+ *   p(x_t | z_t = k) = prod_{d present} N(x_t[d] | mu_{k,d}, sigma^2_{k,d}),  a normal-inverse-gamma mean-field factor
+ * (mu, nus, alphas, betas) per (k, d).  The host forms the three tables (SciPy), each [K][D]: mu,
+ * hprec[k][d] = -0.5 alphas / betas and cst[k][d] = -0.5 / nus - 0.5 (log betas - psi(alphas)) - 0.5 log 2 pi, so no
+ * digamma and no log of a parameter runs on the device.  obs is [T][D] doubles.
+ * Entry (t, d) is PRESENT when x > -SVIHMM_PGAUSS_ABSENT && x < SVIHMM_PGAUSS_ABSENT, compared as doubles: a NaN
+ * fails both, +-inf and 1e308-style sentinels are absent.  An absent entry adds nothing to the row's llik and nothing
+ * to the statistics; the row's other columns are not affected.  (svihmm_set_emission_diag, in contrast, gives a whole
+ * NaN row for one NaN entry.)
+ * lliks, for row t and state k: s = +0.0; for the present d in ascending order r = x - mu[k][d], p = r * r,
+ * p = p * hprec[k][d], s = s + p, s = s + cst[k][d], every operation rounded on its own (never fused); then
+ * ll[t][k] = s.  The centred form evaluated directly: it needs no centred resident copy.  Given the same tables and
+ * the same resident values this is bit-identical to that loop in NumPy.  A row masked under SVIHMM_MASK_AS_NAN, or
+ * one with no present entry, gives +0.0 for every k.
+ * Packed statistics (svihmm_packed_len): [A_raw K*K | stat K*3D | lb], stat[k] = [sxx[k][0..D) | sx[k][0..D) |
+ * n[k][0..D)], taken about the caller's origin[D] with r = x - origin[d]: sxx[k][d] = sum var_x[t][k] (r * r),
+ * sx[k][d] = sum var_x[t][k] r, n[k][d] = sum var_x[t][k], all over the rows t with mask[t] == 0 (whatever the
+ * flags) whose entry d is present.  An origin near the data (a column's mean over its present entries, say) keeps
+ * sxx - sx^2 / n from cancelling for data far from zero.  A_raw, lb, SVIHMM_TRANS_WRAP and the inner segment of
+ * svihmm_estep_minibatch_ex behave as for the Categorical families.  The statistics carry only the caller's own
+ * origin: export, import and all-reduce pass them through unchanged.
+ * Every entry point that dispatches on the emission family takes this one: loglik, forward_backward,
+ * estep_minibatch(_ex), suffstats, estep_sequences, estep_sequence_subset, viterbi(_sequences), ffbs, ffbs_windows,
+ * ffbs_sequences, grow_windows (both methods), state_argmax, read_intermediate / read_rows, read_packed, export /
+ * import / allreduce_packed, heldout_rows, heldout_entries.  Always fp64, K <= 256.
+ * The resident copy follows the rule of the symbol families: an upload while the family is in force is not centred;
+ * a copy an earlier Gaussian family centred is brought back by the plain shift before the first lookup, which
+ * restores the values to rounding only, NOT to the bit; a Gaussian family that follows centres again.  The
+ * bit-identity above therefore holds for rows uploaded while this family is in force (and for rows never centred);
+ * rows that went through a centring and back agree with the loop on the caller's values to rounding.  That rounding is
+ * relative to the centre: the Gaussian families centre on the mean of every entry below 1.7e308 in magnitude, so rows
+ * that hold 1e200-style sentinels belong uploaded while this family is in force (set the family, then the rows).
+ * Fails with a message before any device work, with the handle and the family set before still in force: a NULL mu,
+ * hprec, cst or origin; K < 1 or K > 256; D < 1 or D > SVIHMM_PGAUSS_MAX_D; a non-finite mu[k][d], hprec[k][d],
+ * cst[k][d] or origin[d]; a positive hprec[k][d]; a |mu[k][d]| or |origin[d]| at or above SVIHMM_PGAUSS_ABSENT (so
+ * no square can overflow; the message names the entry); and, at the first E-step-type call, resident observations
+ * whose D differs from the family's.
+ * Out of scope, each refused with a message: the resident SVI loop (svihmm_svi_begin_* replaces the family;
+ * svihmm_svi_iteration after this call alone refuses), svihmm_pred_logprob (NIW only) and the fp32 mode
+ * (svihmm_get_precision reports last_batch_f32 = 0). */
+#define SVIHMM_PGAUSS_MAX_D  128
+#define SVIHMM_PGAUSS_ABSENT 1e150
+int svihmm_set_emission_pgauss(svihmm_ctx* h, int32_t K, int32_t D, const double* mu /*[K][D]*/,
+                               const double* hprec /*[K][D]*/, const double* cst /*[K][D]*/,
+                               const double* origin /*[D]*/);
+
 /* ELBO bookkeeping of the SVI loop (hmmsgd_metaobs.py:273-296 global_lower_bound,
  * hmmbase.py:183-185: sum_k var_emit[k].get_vlb()): the data-dependent scalars of the NIW
  * factors' term for the given mean-field parameters (D <= SVIHMM_NIW_MAX_D; D <= 64 runs the
@@ -681,12 +727,14 @@ int svihmm_pred_logprob(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t
  * out_lp (host, [nrows], optional): lp_g for the masked rows, NaN elsewhere.  The E-step is expected to have run
  * with SVIHMM_MASK_AS_NAN; the call does not check that.
  *
- * svihmm_heldout_entries, the multi-column Categorical and the Poisson family: entry e is (g = row[e], d = col[e],
+ * svihmm_heldout_entries, the multi-column Categorical, the Poisson and the Gaussian-tracks family: entry e is (g = row[e], d = col[e],
  * x = val[e]), g a row of the batch held;
  *   lp_e = LSE_k( log(var_x[g][k] + 1e-9) + term_k ),
  *   multi-column Categorical: term_k = logp[k][off_d + (int)x]
  *   Poisson: t = (double)c * elog[k][d] (one rounded multiply, never fused), t = t - erate[k][d], t = t - logfact[c],
  *            c = (int)x.
+ *   Gaussian tracks (svihmm_set_emission_pgauss): t = x - mu[k][d], t = t * t, t = t * hprec[k][d],
+ *            t = t + cst[k][d], each rounded on its own.
  * An entry whose x is not PRESENT under the family's own rule (above, NaN included) is skipped: out_lp[e] = NaN, not
  * counted.  Duplicates count once each.  out2 = {mean over the counted entries, count}, {NaN, 0} when n = 0 (no
  * launch) or nothing is counted.  The resident value at (g, d) is not looked at: blanking it before the E-step is the
@@ -696,7 +744,7 @@ int svihmm_pred_logprob(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t
  * arrays with n > 0; a row[e] outside [0, nrows) or a col[e] outside [0, D) (the message gives e and the value); no
  * posterior batch held -- no E-step-type call yet, or svihmm_loglik, svihmm_pred_logprob, a decoder or
  * svihmm_grow_windows ran since, or new rows were uploaded (the message names the calls that leave one); K > 256 or
- * a K of the globals that is not the batch's; _entries: another family than the two above; _rows: no
+ * a K of the globals that is not the batch's; _entries: another family than the three above; _rows: no
  * emission family, a family other than the batch's, or a batch of host lliks (no "true observation"). */
 int svihmm_heldout_rows(svihmm_ctx* h, double out2[2], double* out_lp /*[nrows] or NULL*/);
 int svihmm_heldout_entries(svihmm_ctx* h, int64_t n, const int64_t* row /*[n]*/, const int32_t* col /*[n]*/,

@@ -27,6 +27,8 @@ MCAT_MAX_D = 128                  # multi-column Categorical family: columns ...
 MCAT_MAX_F = 1024                 # ... and features (sum of the columns' symbol counts)
 POISSON_MAX_D = 128               # Poisson count family: columns ...
 POISSON_MAX_COUNT = (1 << 20) - 1 # ... and the largest count the logfact table may reach
+PGAUSS_MAX_D = 128                # Gaussian tracks with missing entries: columns
+PGAUSS_ABSENT = 1e150             # ... an entry is present when -PGAUSS_ABSENT < x < PGAUSS_ABSENT
 LTRAN_F32_MIN = -60.0
 F64, F32 = 0, 1
 GROW_METHOD = {"auto": 0, "literal": 1, "products": 2}     # SVIHMM_GROW_* of include/svihmm.h
@@ -104,6 +106,8 @@ SIGNATURES = {
     "svihmm_set_emission_mcat": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_int32), _c_double_p]),
     "svihmm_set_emission_poisson": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _c_double_p, _c_double_p, _c_double_p,
                                               C.c_int32]),
+    "svihmm_set_emission_pgauss": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, _c_double_p, _c_double_p, _c_double_p,
+                                             _c_double_p]),
     "svihmm_packed_len": (C.c_int64, [C.c_void_p]),
     "svihmm_pred_logprob": (C.c_int, [C.c_void_p, _c_int64_p, C.c_int32, C.c_int32, C.c_uint32, _c_double_p]),
     "svihmm_heldout_rows": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p]),

@@ -127,6 +127,10 @@ struct svihmm_ctx {
   // Poisson counts (svihmm_set_emission_poisson): emis_cat is set as well, with V = F = 2 D statistics rows [sx | n];
   // cat_table = [D + 1][K] pairs (elog, erate) with row D all zeros, pois_logfact = lgamma(c + 1) for c = 0..pois_C (pois_lf_host: what it holds)
   bool emis_pois = false; int pois_C = 0; Buf pois_logfact; std::vector<double> pois_lf_host;
+  // Gaussian tracks with missing entries (svihmm_set_emission_pgauss): emis_cat is set as well, with V = F = 3 D statistics
+  // rows [sxx | sx | n]; cat_table = [D + 1][K] pairs (mu, hprec) followed by [D + 1][K] cst, row D of both all zeros;
+  // pg_origin: the origin[D] the statistics are taken about, on the device
+  bool emis_pgauss = false; Buf pg_origin;
   bool emis_diag = false;                    // diagonal Gaussian family: 2 D + 1 features, h->niw = [mu | nus | alphas | betas]
   bool tab_diag = false;                     // feature table currently on the device is the diagonal one
   void* theta_zero_p = nullptr; size_t theta_zero_n = 0;   // what the last theta memset covered
@@ -316,10 +320,10 @@ inline size_t packed_len(const svihmm_ctx* h) {
 }
 
 // the emission family in force: -1 none, 0 NIW, 1 diagonal Gaussian, 2 Categorical, 3 multi-column Categorical, 4 Poisson
-// (the numbering of svi_family)
+// (the numbering of svi_family), 5 Gaussian tracks with missing entries (no SVI loop of its own)
 inline int emission_family_id(const svihmm_ctx* h) {
   if (!h->have_emission) return -1;
-  return h->emis_pois ? 4 : h->emis_mcat ? 3 : h->emis_cat ? 2 : h->emis_diag ? 1 : 0;
+  return h->emis_pgauss ? 5 : h->emis_pois ? 4 : h->emis_mcat ? 3 : h->emis_cat ? 2 : h->emis_diag ? 1 : 0;
 }
 // an E-step-type call has left its posterior batch (svihmm_ctx::post_kind)
 inline void note_posterior_batch(svihmm_ctx* h, int kind) {
@@ -424,6 +428,9 @@ extern "C++" inline std::string emission_d_message(const svihmm_ctx* h) {
   if (h->emis_pois)
     return "svihmm_set_emission_poisson: the family has D = " + std::to_string(h->eD) +
            " count columns, the resident observations have " + std::to_string(h->D);
+  if (h->emis_pgauss)
+    return "svihmm_set_emission_pgauss: the family has D = " + std::to_string(h->eD) +
+           " columns, the resident observations have " + std::to_string(h->D);
   return "emission D does not match obs D";
 }
 int launch_fb_chain(svihmm_ctx* h, int Lm, bool total);

@@ -15,6 +15,9 @@
 //                         Poisson                   t = (double)c * elog[k][d]  (one rounded multiply: contraction is off),
 //                                                   t = t - erate[k][d],  t = t - logfact[c],  c = (int)x
 //                                                   (table [D + 1][K] pairs (elog, erate))
+//                         Gaussian tracks           t = x - mu[k][d], t = t * t, t = t * hprec[k][d], t = t + cst[k][d],
+//                                                   each rounded on its own (table [D + 1][K] pairs (mu, hprec), then
+//                                                   [D + 1][K] cst: kernels_pgauss.h)
 //                       Both tables are the transposed copies the emission kernels read (a feature's / a column's states
 //                       are contiguous; k_mcat_table / k_pois_table rebuild exactly these in the SVI loop), so the
 //                       table read of the 16 lanes is as coalesced as the q row read: 128 contiguous bytes of q and 128
@@ -85,9 +88,10 @@ __global__ __launch_bounds__(256) void k_heldout_rows(
   heldout_block_partial(acc, cnt, red, part);
 }
 
-// POIS: table = [D + 1][K] pairs (elog, erate) read as double2, logfact [C + 1]; otherwise table = [F][K] doubles and
+// FAM 1 (Poisson): table = [D + 1][K] pairs (elog, erate) read as double2, logfact [C + 1]; FAM 2 (Gaussian tracks):
+// table = [D + 1][K] pairs (mu, hprec) read as double2, then [D + 1][K] cst; FAM 0: table = [F][K] doubles and
 // meta = [off_d D | V_d D | ...] (svihmm_ctx::mcat_meta).  row[e] in [0, nrows) and col[e] in [0, D) are the host's check.
-template <int KT, bool POIS>
+template <int KT, int FAM>
 __global__ __launch_bounds__(256) void k_heldout_entries(
     const double* __restrict__ q, const int64_t* __restrict__ row, const int32_t* __restrict__ col,
     const double* __restrict__ val, int64_t n, int K, int D, const double* __restrict__ table,
@@ -103,16 +107,17 @@ __global__ __launch_bounds__(256) void k_heldout_entries(
     const double x = val[e];
     const int d = col[e];
     const int64_t g = row[e];
-    const double lim = POIS ? (double)(C + 1) : (double)meta[D + d];
-    const bool present = POIS ? (x >= 0.0 && x < lim) : (x == x && x > -1.0 && x < lim);
+    constexpr bool POIS = FAM == 1, PG = FAM == 2;
+    const double lim = PG ? 1e150 : POIS ? (double)(C + 1) : (double)meta[D + d];
+    const bool present = PG ? (x > -lim && x < lim) : POIS ? (x >= 0.0 && x < lim) : (x == x && x > -1.0 && x < lim);
     if (!present) {                        // uniform within the 16-lane row
       if (out_lp && li == 0) out_lp[e] = NAN;
       continue;
     }
-    const int c = (int)x;
+    const int c = PG ? 0 : (int)x;
     const double cd = (double)c;
     const double lf = POIS ? logfact[c] : 0.0;
-    const size_t trow = POIS ? (size_t)d * K : (size_t)(meta[d] + c) * K;
+    const size_t trow = (POIS || PG) ? (size_t)d * K : (size_t)(meta[d] + c) * K;
     double v[KT], mx = -INFINITY;
 #pragma unroll
     for (int j = 0; j < KT; ++j) {
@@ -120,7 +125,13 @@ __global__ __launch_bounds__(256) void k_heldout_entries(
       double vv = -INFINITY;
       if (k < K) {
         double t;
-        if (POIS) {
+        if (PG) {
+          const double2 mh = ((const double2*)table)[trow + k];
+          t = x - mh.x;
+          t = t * t;
+          t = t * mh.y;
+          t = t + (table + 2 * (size_t)(D + 1) * K)[trow + k];
+        } else if (POIS) {
           const double2 er = ((const double2*)table)[trow + k];
           t = cd * er.x;
           t = t - er.y;

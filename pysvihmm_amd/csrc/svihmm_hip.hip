@@ -80,7 +80,7 @@ int svihmm_destroy(svihmm_ctx* h) {
   Buf* bufs[] = {&h->obs, &h->mask, &h->mod_init, &h->ltran, &h->Aexp, &h->AexpT, &h->theta, &h->niw,
                  &h->fab, &h->starts, &h->user_q, &h->user_starts, &h->vit, &h->ll, &h->la, &h->lb, &h->q, &h->lse_part,
                  &h->local_lb, &h->logz, &h->part, &h->packed, &h->scratch, &h->kexp, &h->hx, &h->gx,
-                 &h->zfac, &h->llE, &h->m_ll, &h->m_la, &h->m_lb, &h->chain, &h->chain2, &h->cat_table, &h->mcat_meta, &h->pois_logfact, &h->partc, &h->theta_orb, &h->prior, &h->vlb_aux, &h->gen_z,
+                 &h->zfac, &h->llE, &h->m_ll, &h->m_la, &h->m_lb, &h->chain, &h->chain2, &h->cat_table, &h->mcat_meta, &h->pois_logfact, &h->pg_origin, &h->partc, &h->theta_orb, &h->prior, &h->vlb_aux, &h->gen_z,
                  &h->svi_state, &h->svi_prior, &h->svi_work, &h->commtmp, &h->ll0, &h->a0v, &h->a0e,
                  &h->shift_d, &h->uwb, &h->uwd, &h->AexpF, &h->AexpTF, &h->svi_sync, &h->pipe_cnt,
                  &h->pipe_tabs[0].buf, &h->pipe_tabs[1].buf, &h->pipe_tabs[2].buf, &h->pipe_tabs[3].buf,
@@ -701,14 +701,15 @@ int svihmm_niw_vlb_terms(svihmm_ctx* h, int32_t K, int32_t D, const double* mu, 
 // will read it; svihmm_shift_obs may have moved it) goes back to exact integers and stays uncentred.
 // Called when the table is set and again in front of every lookup / count launch.
 // counts: the family that reads the copy next is the Poisson one (-1: the family in force), whose fractional entries
-// keep their value (k_shift_obs<2>).
+// keep their value (k_shift_obs<2>); counts == 2: the real-valued one (svihmm_set_emission_pgauss), which takes the
+// plain shift back (k_shift_obs<0>: the values return to rounding, not to the bit).
 int cat_uncentre(svihmm_ctx* h, int counts) {
   if (h->T > 0) h->center_deferred = true;     // a Gaussian family that follows centres the copy again
   if (!h->shifted || h->T <= 0) return 0;
   std::vector<double> back(h->shift.size());
   for (size_t d = 0; d < back.size(); ++d) back[d] = -h->shift[d];
-  if (counts < 0) counts = h->emis_pois ? 1 : 0;
-  CK(shift_rows(h, back.data(), 0, h->T, counts ? 2 : 1));
+  if (counts < 0) counts = h->emis_pgauss ? 2 : h->emis_pois ? 1 : 0;
+  CK(shift_rows(h, back.data(), 0, h->T, counts == 2 ? 0 : counts ? 2 : 1));
   return store_shift(h, std::vector<double>((size_t)h->D, 0.0));
 }
 // feature table is also needed by the statistics kernels when only host lliks are used
@@ -733,7 +734,7 @@ int svihmm_set_emission_cat(svihmm_ctx* h, int32_t K, int32_t V, const double* l
     for (int v = 0; v < V; ++v) hp[(size_t)v * K + k] = logp[(size_t)k * V + v];
   HIPCK(hipMemcpyAsync(h->cat_table.p, hp, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
   CK(pin_release(h, slot));
-  h->eK = K; h->eD = 1; h->V = V; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16; h->have_emission = true; h->emis_cat = true; h->emis_mcat = false; h->emis_pois = false; h->emis_diag = false; h->uw_valid = false;
+  h->eK = K; h->eD = 1; h->V = V; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16; h->have_emission = true; h->emis_cat = true; h->emis_mcat = false; h->emis_pois = false; h->emis_pgauss = false; h->emis_diag = false; h->uw_valid = false;
   return 0;
 }
 // mcat_meta = [off_d D | V_d D | d(f) F | v(f) F]
@@ -790,7 +791,7 @@ int svihmm_set_emission_mcat(svihmm_ctx* h, int32_t K, int32_t D, const int32_t*
   HIPCK(hipMemcpyAsync(h->mcat_meta.p, mp, nmeta * sizeof(int), hipMemcpyHostToDevice, h->stream));
   CK(pin_release(h, slot));
   h->eK = K; h->eD = D; h->V = F; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16;
-  h->have_emission = true; h->emis_cat = true; h->emis_mcat = true; h->emis_pois = false; h->emis_diag = false; h->uw_valid = false;
+  h->have_emission = true; h->emis_cat = true; h->emis_mcat = true; h->emis_pois = false; h->emis_pgauss = false; h->emis_diag = false; h->uw_valid = false;
   return 0;
 }
 // D count columns, independent Poisson rates per state (kernels_poisson.h).  The family rides the Categorical branches
@@ -852,7 +853,67 @@ int svihmm_set_emission_poisson(svihmm_ctx* h, int32_t K, int32_t D, const doubl
   }
   CK(pin_release(h, slot));
   h->eK = K; h->eD = D; h->V = 2 * D; h->pois_C = C; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16;
-  h->have_emission = true; h->emis_cat = true; h->emis_mcat = false; h->emis_pois = true; h->emis_diag = false; h->uw_valid = false;
+  h->have_emission = true; h->emis_cat = true; h->emis_mcat = false; h->emis_pois = true; h->emis_pgauss = false; h->emis_diag = false; h->uw_valid = false;
+  return 0;
+}
+// D real-valued columns with missing entries, independent Gaussians per state (kernels_pgauss.h).  The family rides the
+// Categorical branches of the host code (emis_cat) with V = 3 D statistics rows [sxx | sx | n]; only the lookup and
+// the statistics launches differ (emis_pgauss).
+int svihmm_set_emission_pgauss(svihmm_ctx* h, int32_t K, int32_t D, const double* mu, const double* hprec,
+                               const double* cst, const double* origin) {
+  const std::string fn = "svihmm_set_emission_pgauss: ";
+  if (!h) return fail(fn + "handle is NULL");
+  if (!mu || !hprec || !cst || !origin) return fail(fn + "mu, hprec, cst and origin must not be NULL");
+  if (K < 1 || K > 256) return fail(fn + "K = " + std::to_string(K) + " outside [1, 256]");
+  if (D < 1 || D > SVIHMM_PGAUSS_MAX_D)
+    return fail(fn + "D = " + std::to_string(D) + " outside [1, SVIHMM_PGAUSS_MAX_D = " +
+                std::to_string(SVIHMM_PGAUSS_MAX_D) + "]");
+  auto finite = [](double v) { return v > -1.7e308 && v < 1.7e308; };
+  auto inside = [](double v) { return v > -SVIHMM_PGAUSS_ABSENT && v < SVIHMM_PGAUSS_ABSENT; };
+  const size_t n = (size_t)K * D;
+  for (size_t i = 0; i < n; ++i) {
+    const std::string at = "[" + std::to_string(i / D) + "][" + std::to_string(i % D) + "]";
+    if (!finite(mu[i])) return fail(fn + "mu" + at + " is not finite");
+    if (!finite(hprec[i])) return fail(fn + "hprec" + at + " is not finite");
+    if (!finite(cst[i])) return fail(fn + "cst" + at + " is not finite");
+    if (hprec[i] > 0.0) return fail(fn + "hprec" + at + " is positive (hprec = -0.5 alphas / betas)");
+    if (!inside(mu[i])) return fail(fn + "|mu" + at + "| is at or above SVIHMM_PGAUSS_ABSENT");
+  }
+  for (int d = 0; d < D; ++d) {
+    if (!finite(origin[d])) return fail(fn + "origin[" + std::to_string(d) + "] is not finite");
+    if (!inside(origin[d])) return fail(fn + "|origin[" + std::to_string(d) + "]| is at or above SVIHMM_PGAUSS_ABSENT");
+  }
+  CK(set_device(h));
+  h->lin_stale = true;
+  h->center_pending = false;
+  // (the resident SVI loop does not know this family: a running loop ends with this upload)
+  if (h->svi_active) CK(svi_flush_elbo(h));
+  h->svi_active = false;
+  if (h->vlb_pending) { HIPCK(hipStreamWaitEvent(h->stream, h->svi_ed, 0)); h->vlb_pending = false; }
+  CK(drop_auto_status(h));
+  CK(cat_uncentre(h, 2));
+  const size_t nr = n + (size_t)K;           // [D + 1][K]; row D, all +0.0, is what an absent column reads
+  const size_t nt = 3 * nr;                  // pairs (mu, hprec), then cst
+  CK(ensure(h->cat_table, nt * sizeof(double)));
+  CK(ensure(h->pg_origin, (size_t)D * sizeof(double)));
+  void* pin = nullptr;
+  int slot = 0;
+  CK(pinned(h, (nt + (size_t)D) * sizeof(double), &pin, &slot));
+  double* hp = (double*)pin;
+  for (int k = 0; k < K; ++k) {              // transposed: a column's states are contiguous
+    for (int d = 0; d < D; ++d) {
+      hp[2 * ((size_t)d * K + k)] = mu[(size_t)k * D + d];
+      hp[2 * ((size_t)d * K + k) + 1] = hprec[(size_t)k * D + d];
+      hp[2 * nr + (size_t)d * K + k] = cst[(size_t)k * D + d];
+    }
+    hp[2 * ((size_t)D * K + k)] = hp[2 * ((size_t)D * K + k) + 1] = hp[2 * nr + (size_t)D * K + k] = 0.0;
+  }
+  std::memcpy(hp + nt, origin, (size_t)D * sizeof(double));
+  HIPCK(hipMemcpyAsync(h->cat_table.p, hp, nt * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCK(hipMemcpyAsync(h->pg_origin.p, hp + nt, (size_t)D * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  CK(pin_release(h, slot));
+  h->eK = K; h->eD = D; h->V = 3 * D; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16;
+  h->have_emission = true; h->emis_cat = true; h->emis_mcat = false; h->emis_pois = false; h->emis_pgauss = true; h->emis_diag = false; h->uw_valid = false;
   return 0;
 }
 int64_t svihmm_packed_len(svihmm_ctx* h) { return h ? (int64_t)packed_len(h) : 0; }
@@ -1372,6 +1433,8 @@ int svihmm_pred_logprob(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t
     return fail("svihmm_pred_logprob: NIW emission only (the multi-column Categorical family of svihmm_set_emission_mcat is not taken)");
   if (h->have_emission && h->emis_pois)
     return fail("svihmm_pred_logprob: NIW emission only (the Poisson family of svihmm_set_emission_poisson is not taken)");
+  if (h->have_emission && h->emis_pgauss)
+    return fail("svihmm_pred_logprob: NIW emission only (the family of svihmm_set_emission_pgauss is not taken)");
   CK(set_device(h));
   if (!h->have_mask) { out2[0] = NAN; out2[1] = 0.0; return 0; }
   const int var = pick_fb(h, B, Lm, false);
@@ -1997,7 +2060,7 @@ static int svi_refresh_emission(svihmm_ctx* h, int elbo_it, int lb_slot, hipEven
                          (double2*)h->cat_table.p, tsy);
     HIPCK(hipGetLastError());
     h->eK = K; h->eD = D; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16;
-    h->have_emission = true; h->emis_cat = true; h->emis_mcat = fam == 3; h->emis_pois = fam == 4; h->emis_diag = false; h->uw_valid = false;
+    h->have_emission = true; h->emis_cat = true; h->emis_mcat = fam == 3; h->emis_pois = fam == 4; h->emis_pgauss = false; h->emis_diag = false; h->uw_valid = false;
   }
   h->theta_sy = SviSync{};
   h->lin_stale = true;
@@ -2454,6 +2517,9 @@ int svihmm_svi_iteration(svihmm_ctx* h, int32_t it, const int64_t* starts, int32
   if (h && !h->svi_active && h->have_emission && h->emis_pois)
     return fail("svihmm_svi_iteration: the resident SVI loop does not take the Poisson family "
                 "from svihmm_set_emission_poisson alone: the family enters the loop through svihmm_svi_begin_poisson");
+  if (h && !h->svi_active && h->have_emission && h->emis_pgauss)
+    return fail("svihmm_svi_iteration: the resident SVI loop does not take the family of svihmm_set_emission_pgauss; "
+                "step the globals on the host from svihmm_estep_minibatch's statistics");
   if (!h || !h->svi_active) return fail("svihmm_svi_iteration: call svihmm_svi_begin first");
   if (h->svi_seq)
     return fail("svihmm_svi_iteration: the loop steps on minibatches of whole sequences since svihmm_svi_sequences: "
@@ -2952,7 +3018,7 @@ int svihmm_heldout_rows(svihmm_ctx* h, double out2[2], double* out_lp) {
   if (h->last_host_ll)
     return bad("the posterior batch held ran on host lliks (SVIHMM_USE_HOST_LLIKS): it has no true observation to score");
   if (!h->have_emission)
-    return bad("no emission family: call svihmm_set_emission_niw / _diag / _cat / _mcat / _poisson first");
+    return bad("no emission family: call svihmm_set_emission_niw / _diag / _cat / _mcat / _poisson / _pgauss first");
   if (emission_family_id(h) != h->post_fam)
     return bad("the emission family is not the one the posterior batch held was computed with: run the E-step again");
   if (h->eK != h->K)
@@ -3013,8 +3079,9 @@ int svihmm_heldout_entries(svihmm_ctx* h, int64_t n, const int64_t* row, const i
   if (n > 0 && (!row || !col || !val)) return bad("row, col and val must be given when n > 0");
   int64_t nrows = 0;
   CK(heldout_batch(h, fn, &nrows));
-  if (!h->have_emission || !(h->emis_mcat || h->emis_pois))
-    return bad("entry-wise scores are defined for the multi-column Categorical and the Poisson family only "
+  if (!h->have_emission || !(h->emis_mcat || h->emis_pois || h->emis_pgauss))
+    return bad("entry-wise scores are defined for the families that skip single entries: besides the Gaussian tracks "
+               "of svihmm_set_emission_pgauss, the multi-column Categorical and the Poisson family only "
                "(svihmm_set_emission_mcat / svihmm_set_emission_poisson); svihmm_heldout_rows takes every family");
   if (h->eK != h->K)
     return bad("K of the globals (" + std::to_string(h->K) + ") differs from the emission family's K (" +
@@ -3050,15 +3117,19 @@ int svihmm_heldout_entries(svihmm_ctx* h, int64_t n, const int64_t* row, const i
     ProfScope ps(h, KS_MISC);
 #define HE(KT)                                                                                                         \
   do {                                                                                                                 \
-    if (h->emis_pois)                                                                                                  \
-      hipLaunchKernelGGL((k_heldout_entries<KT, true>), dim3(nblk), dim3(256), 0, h->stream, q, (const int64_t*)drow,  \
+    if (h->emis_pgauss)                                                                                                \
+      hipLaunchKernelGGL((k_heldout_entries<KT, 2>), dim3(nblk), dim3(256), 0, h->stream, q, (const int64_t*)drow,     \
+                         (const int32_t*)dcol, (const double*)dval, n, K, D, (const double*)h->cat_table.p,            \
+                         (const int*)nullptr, (const double*)nullptr, 0, out_lp ? dlp : (double*)nullptr, part);       \
+    else if (h->emis_pois)                                                                                             \
+      hipLaunchKernelGGL((k_heldout_entries<KT, 1>), dim3(nblk), dim3(256), 0, h->stream, q, (const int64_t*)drow,     \
                          (const int32_t*)dcol, (const double*)dval, n, K, D, (const double*)h->cat_table.p,            \
                          (const int*)nullptr, (const double*)h->pois_logfact.p, h->pois_C,                             \
                          out_lp ? dlp : (double*)nullptr, part);                                                       \
     else                                                                                                               \
-      hipLaunchKernelGGL((k_heldout_entries<KT, false>), dim3(nblk), dim3(256), 0, h->stream, q, (const int64_t*)drow, \
+      hipLaunchKernelGGL((k_heldout_entries<KT, 0>), dim3(nblk), dim3(256), 0, h->stream, q, (const int64_t*)drow,     \
                          (const int32_t*)dcol, (const double*)dval, n, K, D, (const double*)h->cat_table.p,            \
-                         (const int*)h->mcat_meta.p, (const double*)nullptr, 0, out_lp ? dlp : (double*)nullptr, part); \
+                         (const int*)h->mcat_meta.p, (const double*)nullptr, 0, out_lp ? dlp : (double*)nullptr, part);\
   } while (0)
     HELDOUT_KT(HE);
 #undef HE

@@ -7,6 +7,8 @@
 #include "kernels_mcat.h"
 #define SVIHMM_POISSON_EMISSION
 #include "kernels_poisson.h"
+#define SVIHMM_PGAUSS_EMISSION
+#include "kernels_pgauss.h"
 
 extern "C" {
 
@@ -138,7 +140,7 @@ int launch_niw_to_theta(svihmm_ctx* h, int K, int D, double* logdet_out, const S
   }
   // status comes back asynchronously; it is examined at the next synchronising call
   h->status_pending = true;
-  h->eK = K; h->eD = D; h->have_emission = true; h->emis_cat = false; h->emis_mcat = false; h->emis_pois = false; h->emis_diag = false;
+  h->eK = K; h->eD = D; h->have_emission = true; h->emis_cat = false; h->emis_mcat = false; h->emis_pois = false; h->emis_pgauss = false; h->emis_diag = false;
   h->orb_valid = orbp != nullptr;
   h->uw_valid = uwp != nullptr && !emd;
   h->uwd_valid = emd;
@@ -169,7 +171,7 @@ int launch_diag_to_theta(svihmm_ctx* h, int K, int D) {
     HIPCK(hipGetLastError());
   }
   h->status_pending = true;
-  h->eK = K; h->eD = D; h->have_emission = true; h->emis_cat = false; h->emis_mcat = false; h->emis_pois = false; h->emis_diag = true; h->uw_valid = false; h->uwd_valid = false;
+  h->eK = K; h->eD = D; h->have_emission = true; h->emis_cat = false; h->emis_mcat = false; h->emis_pois = false; h->emis_pgauss = false; h->emis_diag = true; h->uw_valid = false; h->uwd_valid = false;
   h->orb_valid = false;
   return 0;
 }
@@ -294,6 +296,28 @@ int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
         hipLaunchKernelGGL(k_emission_poisson<false>, grid, dim3(256), lds, stream, (const double*)h->obs.p, mk, starts_dev,
                            n, Lm, K, D, h->pois_C, (const double2*)h->cat_table.p, (const double*)h->pois_logfact.p, flags,
                            out, (int)rpw);
+      }
+      HIPCK(hipGetLastError());
+      return 0;
+    }
+    if (h->emis_pgauss) {      // D real-valued columns: five rounded operations per present column (kernels_pgauss.h)
+      const int DP = (D + 3) & ~3;
+      const size_t tb = 3 * (size_t)(D + 1) * K * sizeof(double);       // (with the zero row an absent column reads)
+      const size_t ib = (size_t)PG_EM_ROWS * DP * sizeof(double);
+      const bool tlds = tb <= 64 * 1024;
+      // rows per workgroup: as for k_emission_mcat (a staged table is paid once per workgroup)
+      int64_t rpw = (n + 8 * (int64_t)h->ncu - 1) / (8 * (int64_t)h->ncu);
+      rpw = std::max<int64_t>(tlds ? 256 : PG_EM_ROWS, (rpw + PG_EM_ROWS - 1) / PG_EM_ROWS * PG_EM_ROWS);
+      if (rpw > 1 << 20) rpw = 1 << 20;
+      const size_t lds = (tlds ? tb : 0) + ib;
+      const dim3 grid((unsigned)((n + rpw - 1) / rpw));
+      if (tlds) {
+        hipFuncSetAttribute((const void*)k_emission_pgauss<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(k_emission_pgauss<true>, grid, dim3(256), lds, stream, (const double*)h->obs.p, mk, starts_dev,
+                           n, Lm, K, D, (const double2*)h->cat_table.p, flags, out, (int)rpw);
+      } else {
+        hipLaunchKernelGGL(k_emission_pgauss<false>, grid, dim3(256), lds, stream, (const double*)h->obs.p, mk, starts_dev,
+                           n, Lm, K, D, (const double2*)h->cat_table.p, flags, out, (int)rpw);
       }
       HIPCK(hipGetLastError());
       return 0;

@@ -7,6 +7,8 @@
 #include "kernels_mcat.h"
 #define SVIHMM_POISSON_STATS
 #include "kernels_poisson.h"
+#define SVIHMM_PGAUSS_STATS
+#include "kernels_pgauss.h"
 
 extern "C" {
 
@@ -384,7 +386,8 @@ static int launch_stats_cat(svihmm_ctx* h, int B, int Lq, int off, int Lm, uint3
     return fail("Categorical statistics: window too long for the GEMM's 32-bit row offsets");
   // row chunks of the counts.  One column: k_stats_cat, one wave per chunk.  D columns (k_stats_onehot): whole stages
   // of MC_RB rows, two chunks per CU for each (feature group, state group) pair -- more only adds partial sums
-  const bool po = h->emis_pois, mc = h->emis_mcat || po;      // (Poisson: k_stats_poisson, the same tiling with V = 2 D)
+  // (Poisson: k_stats_poisson, the same tiling with V = 2 D; Gaussian tracks: k_stats_pgauss, V = 3 D)
+  const bool po = h->emis_pois, pg = h->emis_pgauss, mc = h->emis_mcat || po || pg;
   const int mcMT = V <= 64 ? 1 : V <= 128 ? 2 : 4;
   const int mcGy = (V + 64 * mcMT - 1) / (64 * mcMT), mcGz = (K + 63) / 64;
   int64_t rpcc = (n + 1023) / 1024 > 64 ? (n + 1023) / 1024 : 64;
@@ -408,7 +411,20 @@ static int launch_stats_cat(svihmm_ctx* h, int B, int Lq, int off, int Lm, uint3
                        (const int*)nullptr, qv, plan.rpc, flags, Lq, off,
                        (double*)h->part.p, KpT, 0, (const double*)nullptr, (const double*)nullptr,
                        (const double*)nullptr, (const double2*)nullptr, (double*)nullptr);
-    if (po) {
+    if (pg) {
+      const size_t ldsg = (size_t)MC_RB * MC_QS * sizeof(double) + MC_RB * sizeof(McRow) + MC_RB * sizeof(int) +
+                          (size_t)MC_RB * (D | 1) * sizeof(double);
+      const dim3 gm((unsigned)nchunkc, mcGy, mcGz);
+#define PGL(MTV)                                                                                                      \
+  do {                                                                                                                \
+    if (ldsg > 64 * 1024)                                                                                             \
+      hipFuncSetAttribute((const void*)k_stats_pgauss<MTV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsg);   \
+    hipLaunchKernelGGL(k_stats_pgauss<MTV>, gm, dim3(256), ldsg, stream, (const double*)h->obs.p, mk, sv, n, Lm, K,   \
+                       Kp, D, (const double*)h->pg_origin.p, qv, rpcc, Lq, off, (double*)h->partc.p);                 \
+  } while (0)
+      if (mcMT == 1) PGL(1); else if (mcMT == 2) PGL(2); else PGL(4);
+#undef PGL
+    } else if (po) {
       const size_t ldsp = (size_t)MC_RB * MC_QS * sizeof(double) + MC_RB * sizeof(McRow) + MC_RB * sizeof(int) +
                           (size_t)MC_RB * (D | 1) * sizeof(int);
       const dim3 gm((unsigned)nchunkc, mcGy, mcGz);

@@ -30,7 +30,7 @@ import numpy as np
 import scipy.linalg as sla
 from scipy.special import digamma, gammaln
 
-__all__ = ["Gaussian", "DiagonalGaussian", "Categorical", "ProductCategorical", "ProductPoisson", "sample_niw", "sample_invwishart",
+__all__ = ["Gaussian", "DiagonalGaussian", "Categorical", "ProductCategorical", "ProductPoisson", "ProductGaussian", "sample_niw", "sample_invwishart",
            "niw_quadratic_form", "niw_vlb_batch", "niw_prior_logpart", "vlb_logz_sign"]
 
 
@@ -703,3 +703,91 @@ class ProductPoisson(object):
         kl = ((a - a0) * digamma(a) - gammaln(a) + gammaln(a0) + a0 * (np.log(b) - np.log(b0))
               + a * (b0 - b) / b)
         return -kl.sum()
+
+
+PGAUSS_ABSENT = 1e150     # SVIHMM_PGAUSS_ABSENT of include/svihmm.h
+
+
+class ProductGaussian(DiagonalGaussian):
+    """``DiagonalGaussian`` whose rows may miss single entries: ``p(x | mu, sigma^2) = prod_{d present}
+    N(x[d] | mu_d, sigma_d^2)`` with the same normal-inverse-gamma prior and mean-field factor per
+    dimension.  An entry is *present* when ``-1e150 < x < 1e150`` (NaN, +-Inf and 1e308-style
+    sentinels are absent); an absent entry is skipped, the row's other columns are not affected.
+    The statistics are per dimension, ``(n[d], sx[d], sxx[d])`` of ``r = x - origin[d]``: the origin
+    keeps ``sxx - sx^2 / n`` from cancelling for data far from zero.  On the device the family is
+    ``svihmm_set_emission_pgauss``."""
+
+    svihmm_diag_fastpath = False
+
+    def rvs(self, size=None, missing=0.0):
+        """Draws as ``DiagonalGaussian.rvs``; ``missing``: the fraction of entries blanked with NaN."""
+        x = DiagonalGaussian.rvs(self, size)
+        if missing > 0.0:
+            x = np.where(np.random.random_sample(x.shape) < missing, np.nan, x)
+        return x
+
+    def _present(self, x):
+        """``(x float[n, D], ok bool[n, D])``: the rows and which of their entries are present."""
+        D = len(self.mf_mu)
+        x = np.reshape(np.asarray(x, dtype=np.float64), (-1, D))
+        with np.errstate(invalid="ignore"):
+            ok = (x > -PGAUSS_ABSENT) & (x < PGAUSS_ABSENT)
+        return x, ok
+
+    def data_origin(self, data):
+        """Each column's mean over its present entries (0 for a column without any): the origin the
+        classes take the statistics about."""
+        x, ok = self._present(data)
+        cnt = ok.sum(0)
+        return np.where(cnt > 0, np.where(ok, x, 0.0).sum(0) / np.maximum(cnt, 1), 0.0)
+
+    def expected_tables(self):
+        """``(mu[D], hprec[D], cst[D])``: ``hprec = -0.5 alphas / betas`` and
+        ``cst = -0.5 / nus - 0.5 (log betas - psi(alphas)) - 0.5 log 2 pi``."""
+        mu, nus, al, be = self.mf_mu, self.mf_nus, self.mf_alphas, self.mf_betas
+        return (np.array(mu, dtype=np.float64), -0.5 * al / be,
+                -0.5 / nus - 0.5 * (np.log(be) - digamma(al)) - 0.5 * np.log(2. * np.pi))
+
+    def _get_weighted_statistics(self, data, weights, origin=None):
+        """``(n[D], sx[D], sxx[D], origin[D])`` with ``r = x - origin[d]``: sums of ``w``, ``w r`` and
+        ``w (r r)`` over the rows whose entry d is present."""
+        x, ok = self._present(data)
+        origin = self.data_origin(x) if origin is None else np.asarray(origin, dtype=np.float64)
+        w = np.asarray(weights, dtype=np.float64).ravel()[:, None] * ok
+        r = np.where(ok, x - origin, 0.0)
+        return w.sum(0), (w * r).sum(0), (w * (r * r)).sum(0), origin
+
+    def _posterior_hypparams(self, n, sx, sxx, origin=None):
+        """The conjugate update from statistics about ``origin`` in the form that does not cancel:
+        ``betas_n = betas_0 + 1/2 [(sxx - sx^2 / n) + nus_0 n / (nus_0 + n) (sx / n - (mu_0 - o))^2]``;
+        a column with ``n = 0`` returns the prior."""
+        mu_0, nus_0, alphas_0, betas_0 = self.mu_0, self.nus_0, self.alphas_0, self.betas_0
+        n, sx, sxx = (np.asarray(a, dtype=np.float64) for a in (n, sx, sxx))
+        o = np.zeros_like(mu_0) if origin is None else np.asarray(origin, dtype=np.float64)
+        has = n > 0
+        ns = np.where(has, n, 1.0)
+        xbar = sx / ns
+        m0 = mu_0 - o
+        nus_n = nus_0 + n
+        mu_n = o + (nus_0 * m0 + sx) / nus_n
+        alphas_n = alphas_0 + 0.5 * n
+        betas_n = betas_0 + 0.5 * ((sxx - sx * xbar) + nus_0 * n / nus_n * (xbar - m0) ** 2)
+        return (np.where(has, mu_n, mu_0), np.where(has, nus_n, nus_0), np.where(has, alphas_n, alphas_0),
+                np.where(has, betas_n, betas_0))
+
+    def expected_log_likelihood(self, x):
+        """``s`` of the present columns in ascending d: ``r = x - mu[d]``, ``p = r r``, ``p = p hprec[d]``,
+        ``s = s + p``, ``s = s + cst[d]``, each rounded on its own; NaN where no column is present
+        (``nan_to_num`` then gives the 0 a missing row contributes)."""
+        x, ok = self._present(x)
+        mu, hprec, cst = self.expected_tables()
+        s = np.zeros(x.shape[0])
+        for d in range(x.shape[1]):
+            r = np.where(ok[:, d], x[:, d], 0.0) - mu[d]
+            p = r * r
+            p = p * hprec[d]
+            t = s + p
+            t = t + cst[d]
+            s = np.where(ok[:, d], t, s)
+        s[~ok.any(1)] = np.nan
+        return s

@@ -104,8 +104,31 @@ class PackedPoissonStats(object):
         return K * K + 2 * K * D + 1
 
 
+class PackedGaussTrackStats(object):
+    """View of the packed statistics of an E-step under ``set_emission_pgauss``
+    ``[A_raw K*K | stat K*3D | lb]``, ``stat[k] = [sxx[k] D | sx[k] D | n[k] D]``: sums of var_x[t, k] r r,
+    var_x[t, k] r and var_x[t, k] with ``r = x - origin[d]``, over the unmasked rows whose entry d is present;
+    ``flat`` is the whole ``[K, 3D]`` block, ``origin`` what the statistics were taken about."""
+
+    def __init__(self, buf, K, D, origin=None):
+        self.buf, self.K, self.D = buf, K, D
+        self.origin = np.zeros(D) if origin is None else origin
+        self.A_raw = buf[:K * K].reshape(K, K)
+        self.flat = buf[K * K:K * K + 3 * K * D].reshape(K, 3 * D)
+        self.sxx = self.flat[:, :D]
+        self.sx = self.flat[:, D:2 * D]
+        self.n = self.flat[:, 2 * D:]
+        self.lb = buf[K * K + 3 * K * D:K * K + 3 * K * D + 1]
+
+    @staticmethod
+    def size(K, D):
+        return K * K + 3 * K * D + 1
+
+
 def rewrap_packed(st, buf):
     """A view of ``st``'s type and shape over another buffer (sums / multiples of packed statistics)."""
+    if isinstance(st, PackedGaussTrackStats):
+        return PackedGaussTrackStats(buf, st.K, st.D, st.origin)
     if isinstance(st, PackedPoissonStats):
         return PackedPoissonStats(buf, st.K, st.D)
     if isinstance(st, PackedMCatStats):
@@ -133,6 +156,7 @@ class HipEngine(object):
         self.V = 0            # > 0: Categorical emission with V symbols is active
         self.Vs = None        # multi-column Categorical emission is active: the columns' symbol counts
         self.pois = 0         # Poisson count emission is active: its D
+        self.pgauss = 0        # Gaussian tracks with missing entries are active: their D
         self.diag = False     # diagonal-Gaussian emission is active (its own packed layout)
         self._comm = False
         self.seq_off = None   # offsets declared with set_sequences (every upload of rows removes them)
@@ -293,6 +317,7 @@ class HipEngine(object):
         self.diag = False
         self.Vs = None
         self.pois = 0
+        self.pgauss = 0
         if check:
             L.check(self._lib.svihmm_sync(self._h), "svihmm_set_emission_niw")
 
@@ -310,6 +335,7 @@ class HipEngine(object):
         self.diag = True
         self.Vs = None
         self.pois = 0
+        self.pgauss = 0
         if check:
             L.check(self._lib.svihmm_sync(self._h), "svihmm_set_emission_diag")
 
@@ -476,6 +502,8 @@ class HipEngine(object):
         return (self._wrap_packed(out) if read else None), seq_lb, q0[:self.K]
 
     def _packed_len(self):
+        if self.pgauss:
+            return PackedGaussTrackStats.size(self.K, self.pgauss)
         if self.pois:
             return PackedPoissonStats.size(self.K, self.pois)
         if self.Vs:
@@ -485,6 +513,8 @@ class HipEngine(object):
         return PackedDiagStats.size(self.K, self.D) if self.diag else PackedStats.size(self.K, self.D)
 
     def _wrap_packed(self, buf):
+        if self.pgauss:
+            return PackedGaussTrackStats(buf, self.K, self.pgauss, self._pg_origin)
         if self.pois:
             return PackedPoissonStats(buf, self.K, self.pois)
         if self.Vs:
@@ -503,6 +533,7 @@ class HipEngine(object):
         self.diag = False
         self.Vs = None
         self.pois = 0
+        self.pgauss = 0
 
     def set_emission_mcat(self, tables):
         """Multi-column Categorical emissions (``svihmm_set_emission_mcat``): ``tables`` is a list of D
@@ -521,6 +552,7 @@ class HipEngine(object):
         self.diag = False
         self.Vs = tuple(int(v) for v in Vs)
         self.pois = 0
+        self.pgauss = 0
 
     def set_emission_poisson(self, elog, erate, max_count):
         """Poisson count emissions (``svihmm_set_emission_poisson``): ``elog[k, d] = psi(a) - log(b)`` and
@@ -545,6 +577,30 @@ class HipEngine(object):
         self.diag = False
         self.Vs = None
         self.pois = D
+        self.pgauss = 0
+
+    def set_emission_pgauss(self, mu, hprec, cst, origin=None):
+        """Gaussian tracks with missing entries (``svihmm_set_emission_pgauss``): ``mu[k, d]``,
+        ``hprec[k, d] = -0.5 alphas / betas`` and ``cst[k, d] = -0.5 / nus - 0.5 (log betas - psi(alphas)) -
+        0.5 log 2 pi`` of the normal-inverse-gamma factors; obs is ``[T, D]``, an entry present when
+        ``-1e150 < x < 1e150``.  ``origin[d]`` (default zeros) is what the statistics are taken about; they then
+        come back as ``PackedGaussTrackStats``."""
+        self._pre_mutate()
+        mu, hprec, cst = L.as_f64(mu), L.as_f64(hprec), L.as_f64(cst)
+        if mu.ndim != 2 or hprec.shape != mu.shape or cst.shape != mu.shape:
+            raise RuntimeError("set_emission_pgauss: mu, hprec and cst must be [K, D] arrays of one shape")
+        K, D = mu.shape
+        origin = np.zeros(D) if origin is None else np.array(L.as_f64(origin)).ravel()
+        if origin.shape != (D,):
+            raise RuntimeError("set_emission_pgauss: origin must have one entry per column")
+        L.check(self._lib.svihmm_set_emission_pgauss(self._h, K, D, L.dptr(mu), L.dptr(hprec), L.dptr(cst),
+                                                     L.dptr(origin)), "svihmm_set_emission_pgauss")
+        self.V = 0
+        self.diag = False
+        self.Vs = None
+        self.pois = 0
+        self.pgauss = D
+        self._pg_origin = origin
 
     def pred_logprob(self, starts, Lm, flags=L.MASK_AS_NAN):
         """Mean predictive log-probability of the masked rows of the windows and their number
@@ -614,8 +670,8 @@ class HipEngine(object):
         return dst[m] + (rows[e] - off[ix[m]]), e
 
     def heldout_entries(self, rows, cols, vals, resident=True, want_lp=False):
-        """Entry-wise held-out log-probability (``svihmm_heldout_entries``; multi-column Categorical and Poisson
-        families): entry ``e`` scores value ``vals[e]`` of column ``cols[e]`` against the posterior row
+        """Entry-wise held-out log-probability (``svihmm_heldout_entries``; the multi-column Categorical, Poisson and
+        Gaussian-tracks families): entry ``e`` scores value ``vals[e]`` of column ``cols[e]`` against the posterior row
         ``rows[e]`` of the batch the last E-step-type call left.  ``resident=True``: ``rows`` are resident row
         numbers, mapped to batch rows from the last call -- after a window batch to every occurrence in the
         windows (a row in no window raises ``ValueError``), after ``estep_sequences`` unchanged, after
@@ -838,6 +894,7 @@ class HipEngine(object):
         self.diag = False
         self.Vs = None
         self.pois = 0
+        self.pgauss = 0
         self._svi_shape = (K, D)
         self._svi_family = "niw"
 
@@ -857,6 +914,7 @@ class HipEngine(object):
         self.diag = True
         self.Vs = None
         self.pois = 0
+        self.pgauss = 0
         self._svi_shape = (K, D)
         self._svi_family = "diag"
 
@@ -875,6 +933,7 @@ class HipEngine(object):
         self.diag = False
         self.Vs = None
         self.pois = 0
+        self.pgauss = 0
         self._svi_shape = (K, V)
         self._svi_family = "cat"
 
@@ -901,6 +960,7 @@ class HipEngine(object):
         self.diag = False
         self.Vs = tuple(int(v) for v in Vs)
         self.pois = 0
+        self.pgauss = 0
         self._svi_shape = (K, self.Vs)
         self._svi_family = "mcat"
 
@@ -930,6 +990,7 @@ class HipEngine(object):
         self.diag = False
         self.Vs = None
         self.pois = D
+        self.pgauss = 0
         self._svi_shape = (K, D)
         self._svi_family = "poisson"
 

@@ -212,6 +212,11 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         (include/svihmm.h, svihmm_set_obs)."""
         eng = self.engine
         if force or self._obs_dirty or getattr(eng, "_obs_owner", None) != id(self):
+            if self._pgauss_fastpath():
+                # the family goes in force before the rows do: an upload under it is not centred, so the device reads
+                # the caller's bits -- and a 1e308-style sentinel, finite to the Gaussian families' centring, cannot
+                # drag a centre that the way back would then have to undo in rounded arithmetic
+                self._push_emission()
             eng.set_obs(self.obs, self.mask)
             if self._multi() and hasattr(eng, "set_sequences"):
                 # (from here on the engine rejects windows that hold rows of two sequences)
@@ -263,8 +268,9 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         it, else one ``estep([off], len)`` per sequence with the sums formed here."""
         if not self._device_family():
             raise RuntimeError("several sequences need an emission family the device evaluates "
-                               "(NIW / diagonal Gaussian, Categorical, multi-column Categorical or Poisson on an "
-                               "engine with set_emission_mcat / _poisson): host lliks are not supported")
+                               "(NIW / diagonal Gaussian, Categorical, multi-column Categorical, Poisson or "
+                               "Gaussian tracks on an engine with set_emission_mcat / _poisson / _pgauss): host "
+                               "lliks are not supported")
         self._psi_expectations()
         self._upload_obs()
         self._push_globals()
@@ -297,8 +303,9 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         ``estep([off], len)`` per listed sequence with the sums formed here.  No per-row attribute is set."""
         if not self._device_family():
             raise RuntimeError("several sequences need an emission family the device evaluates "
-                               "(NIW / diagonal Gaussian, Categorical, multi-column Categorical or Poisson on an "
-                               "engine with set_emission_mcat / _poisson): host lliks are not supported")
+                               "(NIW / diagonal Gaussian, Categorical, multi-column Categorical, Poisson or "
+                               "Gaussian tracks on an engine with set_emission_mcat / _poisson / _pgauss): host "
+                               "lliks are not supported")
         self._psi_expectations()
         self._upload_obs()
         self._push_globals()
@@ -393,10 +400,32 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
                 and D <= L.POISSON_MAX_D and C <= L.POISSON_MAX_COUNT
                 and hasattr(self.engine, "set_emission_poisson"))
 
+    def _pgauss_fastpath(self):
+        """Gaussian tracks with missing entries (``ProductGaussian``: D real-valued columns, independent
+        given the state, single entries may be absent) on an engine that has the family: the device keeps
+        the (mu, hprec, cst) tables and sums (r r, r, 1) per column about an origin.  Other engines keep the
+        host-lliks route."""
+        from .distributions import ProductGaussian
+        ve = self.var_emit
+        if not all(type(e) is ProductGaussian for e in ve) or len(ve) < 1:
+            return False
+        D = len(ve[0].mf_mu)
+        return (all(len(e.mf_mu) == D for e in ve)
+                and self.obs.ndim == 2 and self.obs.shape[1] == D and D <= L.PGAUSS_MAX_D
+                and hasattr(self.engine, "set_emission_pgauss"))
+
+    def _pgauss_origin(self):
+        """Each column's mean over the present entries of the data, formed once per ``obs`` array: what the
+        device takes the family's statistics about."""
+        if getattr(self, "_pg_origin_obs", None) is not self.obs:
+            self._pg_origin = self.var_emit[0].data_origin(self.obs)
+            self._pg_origin_obs = self.obs
+        return self._pg_origin
+
     def _device_family(self):
         """Whether the device evaluates the emitters' family itself (no host lliks)."""
         return (self._niw_fastpath() or self._diag_fastpath() or self._cat_fastpath()
-                or self._mcat_fastpath() or self._poisson_fastpath())
+                or self._mcat_fastpath() or self._poisson_fastpath() or self._pgauss_fastpath())
 
     # -- the device-resident SVI loop: what its class surfaces share -------------------------
     # (hmmsgd_metaobs.VBHMM on windows of one chain, hmmbatchsgd.VBHMM(seq_minibatch=M) on whole sequences)
@@ -553,6 +582,13 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
             self.engine.set_emission_poisson(np.stack([t[0] for t in tabs]), np.stack([t[1] for t in tabs]),
                                              self.var_emit[0].max_count)
             return L.MASK_AS_NAN if nan_mask else 0
+        if self._pgauss_fastpath():
+            # D real-valued columns with missing entries: (mu, hprec, cst) per state and column; the squared
+            # residual of each present entry is formed on the device
+            tabs = [e.expected_tables() for e in self.var_emit]
+            self.engine.set_emission_pgauss(*[np.stack([t[i] for t in tabs]) for i in range(3)],
+                                            origin=self._pgauss_origin())
+            return L.MASK_AS_NAN if nan_mask else 0
         obs = self.obs if self.obs.ndim == 2 else self.obs[:, None]
         if windows is None:
             windows, Lm = [0], self.T
@@ -670,7 +706,7 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         self._q0 = self.engine.read_rows("var_x", 0, 1)[0]
         return st
 
-    def _batch_stats_route(self, literal_global_update, families=("niw", "diag", "cat", "mcat", "poisson")):
+    def _batch_stats_route(self, literal_global_update, families=("niw", "diag", "cat", "mcat", "poisson", "pgauss")):
         """Whether the host loop of a batch class (a ``local_update`` override, or
         ``infer(fused=False)``) may take the statistics of ``self.var_x`` on the device instead of
         the literal ``global_update``: only where that method is the class's own and the engine and
@@ -680,7 +716,7 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         if not hasattr(self.engine, "suffstats"):
             return False
         fam = {"niw": self._niw_fastpath, "diag": self._diag_fastpath, "cat": self._cat_fastpath,
-               "mcat": self._mcat_fastpath, "poisson": self._poisson_fastpath}
+               "mcat": self._mcat_fastpath, "poisson": self._poisson_fastpath, "pgauss": self._pgauss_fastpath}
         return any(fam[f]() for f in families)
 
     def _batch_suffstats(self):
@@ -749,9 +785,11 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
     # -- held-out scores on the device ----------------------------------------------------
     def _heldout_family(self):
         """Emission family of the emitters as far as their types say (no engine is touched):
-        "niw", "diag", "cat", "mcat", "poisson" or None."""
-        from .distributions import ProductCategorical, ProductPoisson
+        "niw", "diag", "cat", "mcat", "poisson", "pgauss" or None."""
+        from .distributions import ProductCategorical, ProductPoisson, ProductGaussian
         ve = self.var_emit
+        if len(ve) and all(type(e) is ProductGaussian for e in ve):
+            return "pgauss"
         if len(ve) and all(type(e) is ProductPoisson for e in ve):
             return "poisson"
         if len(ve) and all(type(e) is ProductCategorical for e in ve):
@@ -794,13 +832,14 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         from the class's ``full_local_update`` E-step: ``hmmsgd_metaobs`` treats the masked rows as missing
         there, the batch classes follow the reference's batch ``local_update``, which does not look at the
         mask), computed on the device for every device family
-        (NIW, diagonal Gaussian, Categorical, ``ProductCategorical``, ``ProductPoisson``) and for a list
+        (NIW, diagonal Gaussian, Categorical, ``ProductCategorical``, ``ProductPoisson``, ``ProductGaussian``) and
+        for a list
         ``obs`` (every sequence from ``mod_init``, one device call): two doubles cross the bus instead of
         ``var_x[T, K]``.  ``None`` without masked rows.  No attribute of the model changes.  Emitters without
         a device family raise ``NotImplementedError``."""
         if self._heldout_family() is None:
             raise NotImplementedError("heldout_logprob: the emitters have no device family (NIW / diagonal "
-                                      "Gaussian, Categorical, ProductCategorical, ProductPoisson): their lliks "
+                                      "Gaussian, Categorical, ProductCategorical, ProductPoisson, ProductGaussian): their lliks "
                                       "are evaluated on the host, use pred_logprob")
         if not np.any(self.mask):
             return None
@@ -808,18 +847,18 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         return val
 
     def heldout_entries_logprob(self, rows, cols, vals, per_entry=False):
-        """Entry-wise ("speckled") held-out score of a ``ProductCategorical`` / ``ProductPoisson`` model: the
-        entries ``(rows[e], cols[e])`` of ``obs`` (rows numbered over the concatenation when ``obs`` was a
+        """Entry-wise ("speckled") held-out score of a ``ProductCategorical`` / ``ProductPoisson`` /
+        ``ProductGaussian`` model: the entries ``(rows[e], cols[e])`` of ``obs`` (rows numbered over the concatenation when ``obs`` was a
         list) were blanked -- set NaN, ``util.speckle_holdout`` -- before fitting; ``vals[e]`` is what stood
         there.  Full E-step on the blanked data (the one ``heldout_logprob`` runs), then
         ``lp_e = LSE_k(log(var_x[rows[e], k] + 1e-9) + E_q log p(vals[e] | k, column cols[e]))`` on the device:
         the mean over the entries whose value is present under the family's rule (``None`` if there is none),
         with ``per_entry`` ``(mean, lp[n])`` (NaN for the skipped ones).  ``ValueError`` unless every
-        ``obs[rows, cols]`` is NaN; ``NotImplementedError`` for other emitters (a NaN entry of a Gaussian row
-        blanks the whole row).  No attribute of the model changes."""
-        if self._heldout_family() not in ("mcat", "poisson"):
-            raise NotImplementedError("heldout_entries_logprob: entry-wise scores need ProductCategorical or "
-                                      "ProductPoisson emitters (columns independent given the state); other "
+        ``obs[rows, cols]`` is NaN; ``NotImplementedError`` for other emitters (a NaN entry of a ``Gaussian`` or
+        ``DiagonalGaussian`` row blanks the whole row).  No attribute of the model changes."""
+        if self._heldout_family() not in ("mcat", "poisson", "pgauss"):
+            raise NotImplementedError("heldout_entries_logprob: entry-wise scores need ProductGaussian, "
+                                      "ProductCategorical or ProductPoisson emitters (columns independent given the state); other "
                                       "families have no per-entry missingness")
         r = np.asarray(rows, dtype=np.int64).ravel()
         c = np.asarray(cols, dtype=np.int64).ravel()

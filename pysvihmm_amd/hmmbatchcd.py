@@ -134,6 +134,12 @@ class VBHMM(VariationalHMMBase):
                 G = self.var_emit[k]
                 G._set_alpha(G._posterior_hypparams([c[k] for c in st.col_counts]))
             return
+        if hasattr(st, "sxx"):
+            # Gaussian tracks with missing entries: the per-column conjugate update from (n, sx, sxx) about the origin
+            for k in range(self.K):
+                G = self.var_emit[k]
+                G._set_mf(*G._posterior_hypparams(st.n[k], st.sx[k], st.sxx[k], st.origin))
+            return
         if hasattr(st, "sx"):
             # Poisson emitters: Gamma(alpha_0 + sx[k], beta_0 + n[k]) per column
             for k in range(self.K):

@@ -11,7 +11,7 @@ import time
 import numpy as np
 
 from .hmmbase import VariationalHMMBase, is_niw_gaussian, is_diag_gaussian
-from .distributions import ProductCategorical, ProductPoisson
+from .distributions import ProductCategorical, ProductPoisson, ProductGaussian
 from .engine import rewrap_packed
 from . import util
 from . import _lib as L
@@ -90,7 +90,7 @@ class VBHMM(VariationalHMMBase):
                        "_global_update_from_stats", "_natgrad_emissions", "_psi_expectations", "_emit_vlb",
                        "_push_globals", "_push_emission")
     _SEQ_ENGINE_CALLS = ("estep_sequence_subset", "set_globals", "set_emission_niw", "set_emission_diag",
-                         "set_emission_cat", "set_emission_mcat", "set_emission_poisson")
+                         "set_emission_cat", "set_emission_mcat", "set_emission_poisson", "set_emission_pgauss")
 
     def _svi_sequences_refusal(self):
         """Why ``infer`` cannot run in the engine's resident loop on sequence minibatches (None: it can)."""
@@ -99,6 +99,9 @@ class VBHMM(VariationalHMMBase):
         eng = self.engine
         if not (hasattr(eng, "svi_sequences") and hasattr(eng, "svi_iteration_sequences")):
             return "the engine has no svi_sequences / svi_iteration_sequences"
+        if self._pgauss_fastpath():
+            return ("the resident loop does not take ProductGaussian emitters (svihmm_set_emission_pgauss has no "
+                    "svi_begin of its own): the sequence minibatches step on the host route")
         fam = self._svi_family()
         if fam is None or not hasattr(eng, self._SVI_BEGIN[fam]):
             return "the emitters are none of the resident loop's families on this engine"
@@ -228,7 +231,7 @@ class VBHMM(VariationalHMMBase):
                 a, b = stats_for_k(G, k)
                 G._set_mf((1. - lrate) * G.alpha_mf + lrate * a, (1. - lrate) * G.beta_mf + lrate * b)
                 continue
-            if is_diag_gaussian(G):
+            if is_diag_gaussian(G) or type(G) is ProductGaussian:
                 # the same blend in the diagonal family's natural parameters (the reference's
                 # NIW arithmetic, util.py:28-60, has no counterpart for it)
                 new = stats_for_k(G, k)
@@ -268,6 +271,8 @@ class VBHMM(VariationalHMMBase):
         def from_stats(G, k):
             if hasattr(st, "col_counts"):
                 return G._posterior_hypparams([c[k] for c in st.col_counts])
+            if hasattr(st, "sxx"):
+                return G._posterior_hypparams(st.n[k], st.sx[k], st.sxx[k], st.origin)
             if hasattr(st, "sx"):
                 return G._posterior_hypparams(st.sx[k], st.n[k])
             if hasattr(st, "xsq"):
@@ -296,7 +301,7 @@ class VBHMM(VariationalHMMBase):
         inds = np.logical_not(self.mask)
         def from_rows(G, k):
             x, w = batch[inds, :], self.var_x[inds, k]
-            if is_diag_gaussian(G) or type(G) in (ProductCategorical, ProductPoisson):
+            if is_diag_gaussian(G) or type(G) in (ProductCategorical, ProductPoisson, ProductGaussian):
                 return G._posterior_hypparams(*G._get_weighted_statistics(x, w))
             return util.NIW_meanfield(G, x, w)
         self._natgrad_emissions(lrate, from_rows)

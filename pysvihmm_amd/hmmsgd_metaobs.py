@@ -559,6 +559,11 @@ class VBHMM(VariationalHMMBase):
                 getattr(self, name)
             self.__dict__.pop("_pending_rows", None)
 
+    def _pgauss_fastpath(self):
+        # ProductGaussian emitters keep the route of a plugin this class does not know: host lliks through
+        # expected_log_likelihood (the natural-gradient step here has no branch for the family)
+        return False
+
     def _suffstats_route(self):
         """Whether the host loop takes the statistics of its windows' posteriors on the device
         (one ``engine.suffstats`` call per minibatch) instead of ``intermediate_pars`` on the host:
