@@ -85,6 +85,36 @@ struct SviLogEntry {
   bool f32_ok_before = true;
   std::vector<int64_t> starts;
 };
+// The emission family in force is ONE tag ("the emission family is one tag").  The numbers are fixed: they
+// are what post_fam holds, what emission_family_id returns and what k_svi_global_step_simple and the finalize / mirror
+// kernels receive as an int.  Host code asks about the family through the predicates below or an equality test on the
+// tag, and enters a family through set_family alone.
+enum EmisFamily : int { EF_NIW = 0, EF_DIAG = 1, EF_CAT = 2, EF_MCAT = 3, EF_POIS = 4, EF_PGAUSS = 5 };
+constexpr int EF_COUNT = 6;
+// the family rides the table branches of the host code (lookup emission, no feature GEMM, uncentred rows)
+constexpr bool fam_table(EmisFamily f) { return f >= EF_CAT; }
+// NIW or diagonal: factors in h->niw with the means leading the block, feature GEMMs, centred rows
+constexpr bool fam_gaussian(EmisFamily f) { return f < EF_CAT; }
+// single entries of a row may be absent: the families svihmm_heldout_entries scores
+constexpr bool fam_entrywise(EmisFamily f) { return f >= EF_MCAT; }
+// What the host code says about and does for a family without branching on it, one row per tag.
+struct FamTraits {
+  const char* setter;      // the entry point that puts the family in force
+  const char* noun;        // how refusals name it (nullptr: svihmm_pred_logprob takes the family)
+  const char* columns;     // what emission_d_message calls its D columns (nullptr: the plain message)
+  const char* svi_begin;   // the entry point of its resident SVI loop (nullptr: there is none)
+  int uncentre;            // cat_uncentre's mode: 0 symbols (round), 1 counts (integers snap), 2 reals (plain shift back)
+  bool svi_width_D;        // the loop's simple step / ELBO kernels run over W = D columns (else W = V)
+};
+constexpr FamTraits FAM_TRAITS[EF_COUNT] = {
+    {"svihmm_set_emission_niw", nullptr, nullptr, "svihmm_svi_begin", 0, false},
+    {"svihmm_set_emission_diag", nullptr, nullptr, "svihmm_svi_begin_diag", 0, true},
+    {"svihmm_set_emission_cat", nullptr, nullptr, "svihmm_svi_begin_cat", 0, false},
+    {"svihmm_set_emission_mcat", "the multi-column Categorical family", "symbol columns", "svihmm_svi_begin_mcat", 0, false},
+    {"svihmm_set_emission_poisson", "the Poisson family", "count columns", "svihmm_svi_begin_poisson", 1, true},
+    {"svihmm_set_emission_pgauss", "the family", "columns", nullptr, 2, false},
+};
+
 struct svihmm_ctx {
   int device = 0;
   hipStream_t stream = nullptr;
@@ -120,19 +150,25 @@ struct svihmm_ctx {
   void* uwd_zero_p = nullptr; size_t uwd_zero_n = 0;
   bool uwd_valid = false, emd_attr_set[2] = {false, false};
   bool emb_attr_set = false;
-  bool emis_cat = false; int V = 0;          // Categorical emission: table [V][K] = E log theta
-  // multi-column Categorical (svihmm_set_emission_mcat): emis_cat is set as well -- every route the host picks by asking
-  // emis_cat is the one this family takes -- with V = F = sum_d V[d]; mcat_meta = [off_d D | V_d D | d(f) F | v(f) F] int32
-  bool emis_mcat = false; Buf mcat_meta;
-  // Poisson counts (svihmm_set_emission_poisson): emis_cat is set as well, with V = F = 2 D statistics rows [sx | n];
-  // cat_table = [D + 1][K] pairs (elog, erate) with row D all zeros, pois_logfact = lgamma(c + 1) for c = 0..pois_C (pois_lf_host: what it holds)
-  bool emis_pois = false; int pois_C = 0; Buf pois_logfact; std::vector<double> pois_lf_host;
-  // Gaussian tracks with missing entries (svihmm_set_emission_pgauss): emis_cat is set as well, with V = F = 3 D statistics
-  // rows [sxx | sx | n]; cat_table = [D + 1][K] pairs (mu, hprec) followed by [D + 1][K] cst, row D of both all zeros;
-  // pg_origin: the origin[D] the statistics are taken about, on the device
-  bool emis_pgauss = false; Buf pg_origin;
-  bool emis_diag = false;                    // diagonal Gaussian family: 2 D + 1 features, h->niw = [mu | nus | alphas | betas]
-  bool tab_diag = false;                     // feature table currently on the device is the diagonal one
+  // the family in force (meaningful while have_emission holds; a fresh handle reads as NIW).  Written by set_family only
+  EmisFamily fam = EF_NIW;
+  // EF_DIAG: 2 D + 1 features, h->niw = [mu | nus | alphas | betas]
+  // EF_CAT: table [V][K] = E log theta.  The families after it are table families too (fam_table): every route the host
+  // picks by asking fam_table is the one they take, with V = F statistics rows; only the lookup and the statistics
+  // launches differ
+  int V = 0;
+  // EF_MCAT (svihmm_set_emission_mcat): V = F = sum_d V[d]; mcat_meta = [off_d D | V_d D | d(f) F | v(f) F] int32
+  Buf mcat_meta;
+  // EF_POIS (svihmm_set_emission_poisson): V = F = 2 D statistics rows [sx | n]; cat_table = [D + 1][K] pairs (elog, erate)
+  // with row D all zeros, pois_logfact = lgamma(c + 1) for c = 0..pois_C (pois_lf_host: what it holds)
+  int pois_C = 0; Buf pois_logfact; std::vector<double> pois_lf_host;
+  // EF_PGAUSS (svihmm_set_emission_pgauss): V = F = 3 D statistics rows [sxx | sx | n]; cat_table = [D + 1][K] pairs
+  // (mu, hprec) followed by [D + 1][K] cst, row D of both all zeros; pg_origin: the origin[D] the statistics are taken
+  // about, on the device
+  Buf pg_origin;
+  // the feature table currently on the device is the diagonal one: a fact about that table (upload_feature_table keys
+  // on it), not about the family in force -- svihmm_niw_vlb_terms uploads the full table under any family
+  bool tab_diag = false;
   void* theta_zero_p = nullptr; size_t theta_zero_n = 0;   // what the last theta memset covered
   int tabD = -1;
   // pinned host staging: a ring of slots, each guarded by an event recorded after the copy
@@ -227,8 +263,8 @@ struct svihmm_ctx {
   // prior_logpart[K]; prior block [mu0 | sigma0 | kappa0 | nu0]; GTH scratch; elbo / event ring
   Buf svi_state, svi_prior, svi_work, commtmp;
   int svi_K = 0, svi_D = 0, svi_maxit = 0;
-  int svi_family = 0;       // 0 NIW, 1 diagonal Gaussian, 2 Categorical, 3 multi-column Categorical, 4 Poisson
-  std::vector<int> svi_mcat_V;   // family 3: the columns' symbol counts the loop was begun with
+  EmisFamily svi_family = EF_NIW;   // the family the loop was begun with (one whose FAM_TRAITS row names a svi_begin)
+  std::vector<int> svi_mcat_V;   // EF_MCAT: the columns' symbol counts the loop was begun with
   double svi_zsign = 1.0, svi_prior_const = 0.0;
   // svihmm_svi_sequences: the loop steps on minibatches of whole declared sequences (stream order and events only);
   // the prior-only constant of the learned initial-state factor's ELBO term (0 in the window loop)
@@ -313,18 +349,25 @@ struct svihmm_ctx {
 // length of the packed statistics in the layout of the current emission family:
 // NIW  [A_raw K*K | xbar K*D | neff K | S K*D*D | lb],  Categorical  [A_raw K*K | counts K*V | lb]
 inline size_t packed_len(const svihmm_ctx* h) {
-  if (h->emis_cat) return (size_t)h->K * h->K + (size_t)h->K * h->V + 1;
-  const size_t D = h->D > 0 ? h->D : 1;
-  if (h->emis_diag) return (size_t)h->K * h->K + 2 * (size_t)h->K * D + h->K + 1;
-  return (size_t)h->K * h->K + (size_t)h->K * D + h->K + (size_t)h->K * D * D + 1;
+  const size_t K = h->K, D = h->D > 0 ? h->D : 1;
+  switch (h->fam) {
+    case EF_NIW: return K * K + K * D + K + K * D * D + 1;
+    case EF_DIAG: return K * K + 2 * K * D + K + 1;
+    default: return K * K + K * (size_t)h->V + 1;      // the table families: V statistics rows
+  }
 }
 
-// the emission family in force: -1 none, 0 NIW, 1 diagonal Gaussian, 2 Categorical, 3 multi-column Categorical, 4 Poisson
-// (the numbering of svi_family), 5 Gaussian tracks with missing entries (no SVI loop of its own)
-inline int emission_family_id(const svihmm_ctx* h) {
-  if (!h->have_emission) return -1;
-  return h->emis_pgauss ? 5 : h->emis_pois ? 4 : h->emis_mcat ? 3 : h->emis_cat ? 2 : h->emis_diag ? 1 : 0;
+// every path into a family: the tag, and the invalidations the family's arrival implies -- the bf16 factor records
+// (uwb / uwd) describe NIW factors in h->niw: any other family's arrival outdates uwb, the diagonal family's (whose
+// block replaces the NIW one in h->niw) uwd as well; the NIW builder sets both flags itself after this call
+inline void set_family(svihmm_ctx* h, EmisFamily f) {
+  h->have_emission = true;
+  h->fam = f;
+  if (f != EF_NIW) h->uw_valid = false;
+  if (f == EF_DIAG) h->uwd_valid = false;
 }
+// the emission family in force as post_fam records it: -1 none, else the tag
+inline int emission_family_id(const svihmm_ctx* h) { return h->have_emission ? (int)h->fam : -1; }
 // an E-step-type call has left its posterior batch (svihmm_ctx::post_kind)
 inline void note_posterior_batch(svihmm_ctx* h, int kind) {
   h->post_kind = kind; h->post_K = h->K; h->post_fam = h->last_host_ll ? -1 : emission_family_id(h);
@@ -422,16 +465,10 @@ int ensure_starts_pulled(svihmm_ctx* h);
 int cat_uncentre(svihmm_ctx* h, int counts = -1);
 // what an E-step-type call says when the emission family's D is not the resident observations'
 extern "C++" inline std::string emission_d_message(const svihmm_ctx* h) {
-  if (h->emis_mcat)
-    return "svihmm_set_emission_mcat: the family has D = " + std::to_string(h->eD) +
-           " symbol columns, the resident observations have " + std::to_string(h->D);
-  if (h->emis_pois)
-    return "svihmm_set_emission_poisson: the family has D = " + std::to_string(h->eD) +
-           " count columns, the resident observations have " + std::to_string(h->D);
-  if (h->emis_pgauss)
-    return "svihmm_set_emission_pgauss: the family has D = " + std::to_string(h->eD) +
-           " columns, the resident observations have " + std::to_string(h->D);
-  return "emission D does not match obs D";
+  const FamTraits& t = FAM_TRAITS[h->fam];
+  if (!t.columns) return "emission D does not match obs D";
+  return std::string(t.setter) + ": the family has D = " + std::to_string(h->eD) + " " + t.columns +
+         ", the resident observations have " + std::to_string(h->D);
 }
 int launch_fb_chain(svihmm_ctx* h, int Lm, bool total);
 int launch_emission_deferred(svihmm_ctx* h);

@@ -200,7 +200,7 @@ static void sample_center(const svihmm_ctx* h, const double* obs, int64_t T, int
   // a Categorical table is the active emission: the column holds symbol indices, which the lookup
   // kernels truncate to int -- it stays exactly as uploaded (round-3 advisor finding: set_emission_cat
   // followed by set_obs centred the symbols)
-  if (h->have_emission && h->emis_cat) { const_cast<svihmm_ctx*>(h)->center_deferred = true; return; }
+  if (h->have_emission && fam_table(h->fam)) { const_cast<svihmm_ctx*>(h)->center_deferred = true; return; }
   int64_t nsamp = ((int64_t)4 << 20) / D;
   if (nsamp > 65536) nsamp = 65536;
   if (nsamp < 16) nsamp = 16;
@@ -271,8 +271,8 @@ static int params_follow_centre(svihmm_ctx* h, const double* delta) {
   const int D = h->D;
   bool any = false;
   for (int d = 0; d < D; ++d) any = any || delta[d] != 0.0;
-  const bool live = h->have_emission && !h->emis_cat && h->eD == D && h->niw.p;   // (NIW or diagonal: means lead the block)
-  const bool svi = h->svi_active && h->svi_D == D && h->svi_family < 2;    // (symbol and count families: no means)
+  const bool live = h->have_emission && fam_gaussian(h->fam) && h->eD == D && h->niw.p;   // (NIW or diagonal: means lead the block)
+  const bool svi = h->svi_active && h->svi_D == D && fam_gaussian(h->svi_family);    // (symbol and count families: no means)
   if (!any || (!live && !svi)) return 0;
   CK(wait_side_streams(h));
   if (live) CK(drop_auto_status(h));      // this rebuild supersedes what an earlier automatic one reported
@@ -294,7 +294,7 @@ static int params_follow_centre(svihmm_ctx* h, const double* delta) {
   }
   HIPCK(hipGetLastError());
   CK(pin_release(h, slot));
-  if (live && h->emis_diag) CK(launch_diag_to_theta(h, h->eK, D));
+  if (live && h->fam == EF_DIAG) CK(launch_diag_to_theta(h, h->eK, D));
   else if (live) CK(launch_niw_to_theta(h, h->eK, D, svi ? svi_ptr(h, 4) : nullptr));
   if (live) h->status_auto = true;
   return 0;
@@ -562,7 +562,7 @@ int svihmm_set_emission_niw(svihmm_ctx* h, int32_t K, int32_t D, const double* m
   h->lin_stale = true;
   if (h->D == D) CK(centre_deferred(h));
   // (a device loop of another family or shape kept its factors in h->niw: it ends here)
-  if (h->svi_active && !(h->svi_family == 0 && h->svi_K == K && h->svi_D == D)) h->svi_active = false;
+  if (h->svi_active && !(h->svi_family == EF_NIW && h->svi_K == K && h->svi_D == D)) h->svi_active = false;
   const size_t nmu = (size_t)K * D, nsg = (size_t)K * D * D;
   const size_t nin = nmu + nsg + 2 * (size_t)K;
   CK(ensure(h->niw, nin * sizeof(double) + 64));
@@ -614,7 +614,7 @@ int svihmm_set_emission_diag(svihmm_ctx* h, int32_t K, int32_t D, const double* 
   // a running device loop survives a re-push of ITS OWN family and shape (the loop's factor block IS
   // h->niw: the validation hooks of infer() -- full_predprob, adaptive L, growBuffer -- re-upload the
   // factors they just read back); any other loop's resident state is gone with this upload
-  if (!(h->svi_active && h->svi_family == 1 && h->svi_K == K && h->svi_D == D)) h->svi_active = false;
+  if (!(h->svi_active && h->svi_family == EF_DIAG && h->svi_K == K && h->svi_D == D)) h->svi_active = false;
   CK(drop_auto_status(h));
   CK(pull_small(h, h->niw.p, hp, 4 * n * sizeof(double)));
   CK(pin_release(h, slot));
@@ -708,7 +708,7 @@ int cat_uncentre(svihmm_ctx* h, int counts) {
   if (!h->shifted || h->T <= 0) return 0;
   std::vector<double> back(h->shift.size());
   for (size_t d = 0; d < back.size(); ++d) back[d] = -h->shift[d];
-  if (counts < 0) counts = h->emis_pgauss ? 2 : h->emis_pois ? 1 : 0;
+  if (counts < 0) counts = FAM_TRAITS[h->fam].uncentre;
   CK(shift_rows(h, back.data(), 0, h->T, counts == 2 ? 0 : counts ? 2 : 1));
   return store_shift(h, std::vector<double>((size_t)h->D, 0.0));
 }
@@ -719,7 +719,7 @@ int svihmm_set_emission_cat(svihmm_ctx* h, int32_t K, int32_t V, const double* l
   h->lin_stale = true;
   h->center_pending = false;
   // (a device loop of another family or shape ends with this upload, as in svihmm_set_emission_niw / _diag)
-  if (h->svi_active && !(h->svi_family == 2 && h->svi_K == K && h->V == V)) h->svi_active = false;
+  if (h->svi_active && !(h->svi_family == EF_CAT && h->svi_K == K && h->V == V)) h->svi_active = false;
   if (h->svi_active) CK(svi_flush_elbo(h));      // (as in svihmm_set_emission_niw)
   if (h->vlb_pending) { HIPCK(hipStreamWaitEvent(h->stream, h->svi_ed, 0)); h->vlb_pending = false; }
   CK(drop_auto_status(h));
@@ -734,7 +734,7 @@ int svihmm_set_emission_cat(svihmm_ctx* h, int32_t K, int32_t V, const double* l
     for (int v = 0; v < V; ++v) hp[(size_t)v * K + k] = logp[(size_t)k * V + v];
   HIPCK(hipMemcpyAsync(h->cat_table.p, hp, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
   CK(pin_release(h, slot));
-  h->eK = K; h->eD = 1; h->V = V; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16; h->have_emission = true; h->emis_cat = true; h->emis_mcat = false; h->emis_pois = false; h->emis_pgauss = false; h->emis_diag = false; h->uw_valid = false;
+  h->eK = K; h->eD = 1; h->V = V; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16; set_family(h, EF_CAT);
   return 0;
 }
 // mcat_meta = [off_d D | V_d D | d(f) F | v(f) F]
@@ -745,7 +745,7 @@ static void mcat_fill_meta(int* mp, int D, int F, const int32_t* V) {
   }
 }
 // D symbol columns, independent per state (kernels_mcat.h).  The family rides the Categorical branches of the host
-// code (emis_cat) with V = F features; only the lookup and the count launches differ (emis_mcat).
+// code (fam_table) with V = F features; only the lookup and the count launches differ (EF_MCAT).
 int svihmm_set_emission_mcat(svihmm_ctx* h, int32_t K, int32_t D, const int32_t* V, const double* logp) {
   if (!h) return fail("svihmm_set_emission_mcat: handle is NULL");
   if (!V || !logp) return fail("svihmm_set_emission_mcat: V and logp must not be NULL");
@@ -771,7 +771,7 @@ int svihmm_set_emission_mcat(svihmm_ctx* h, int32_t K, int32_t D, const int32_t*
   h->lin_stale = true;
   h->center_pending = false;
   // (a device loop of another family or shape ends with this upload, as in svihmm_set_emission_cat)
-  if (h->svi_active && !(h->svi_family == 3 && h->svi_K == K && h->svi_mcat_V == std::vector<int>(V, V + D))) h->svi_active = false;
+  if (h->svi_active && !(h->svi_family == EF_MCAT && h->svi_K == K && h->svi_mcat_V == std::vector<int>(V, V + D))) h->svi_active = false;
   if (h->svi_active) CK(svi_flush_elbo(h));
   if (h->vlb_pending) { HIPCK(hipStreamWaitEvent(h->stream, h->svi_ed, 0)); h->vlb_pending = false; }
   CK(drop_auto_status(h));
@@ -791,12 +791,12 @@ int svihmm_set_emission_mcat(svihmm_ctx* h, int32_t K, int32_t D, const int32_t*
   HIPCK(hipMemcpyAsync(h->mcat_meta.p, mp, nmeta * sizeof(int), hipMemcpyHostToDevice, h->stream));
   CK(pin_release(h, slot));
   h->eK = K; h->eD = D; h->V = F; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16;
-  h->have_emission = true; h->emis_cat = true; h->emis_mcat = true; h->emis_pois = false; h->emis_pgauss = false; h->emis_diag = false; h->uw_valid = false;
+  set_family(h, EF_MCAT);
   return 0;
 }
 // D count columns, independent Poisson rates per state (kernels_poisson.h).  The family rides the Categorical branches
-// of the host code (emis_cat) with V = 2 D statistics rows [sx | n]; only the lookup and the statistics launches
-// differ (emis_pois).
+// of the host code (fam_table) with V = 2 D statistics rows [sx | n]; only the lookup and the statistics launches
+// differ (EF_POIS).
 int svihmm_set_emission_poisson(svihmm_ctx* h, int32_t K, int32_t D, const double* elog, const double* erate,
                                 const double* logfact, int32_t C) {
   if (!h) return fail("svihmm_set_emission_poisson: handle is NULL");
@@ -823,7 +823,7 @@ int svihmm_set_emission_poisson(svihmm_ctx* h, int32_t K, int32_t D, const doubl
   h->lin_stale = true;
   h->center_pending = false;
   // (a device loop of another family or shape ends with this upload, as in svihmm_set_emission_cat)
-  if (h->svi_active && !(h->svi_family == 4 && h->svi_K == K && h->svi_D == D)) h->svi_active = false;
+  if (h->svi_active && !(h->svi_family == EF_POIS && h->svi_K == K && h->svi_D == D)) h->svi_active = false;
   if (h->svi_active) CK(svi_flush_elbo(h));
   if (h->vlb_pending) { HIPCK(hipStreamWaitEvent(h->stream, h->svi_ed, 0)); h->vlb_pending = false; }
   CK(drop_auto_status(h));
@@ -853,12 +853,12 @@ int svihmm_set_emission_poisson(svihmm_ctx* h, int32_t K, int32_t D, const doubl
   }
   CK(pin_release(h, slot));
   h->eK = K; h->eD = D; h->V = 2 * D; h->pois_C = C; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16;
-  h->have_emission = true; h->emis_cat = true; h->emis_mcat = false; h->emis_pois = true; h->emis_pgauss = false; h->emis_diag = false; h->uw_valid = false;
+  set_family(h, EF_POIS);
   return 0;
 }
 // D real-valued columns with missing entries, independent Gaussians per state (kernels_pgauss.h).  The family rides the
-// Categorical branches of the host code (emis_cat) with V = 3 D statistics rows [sxx | sx | n]; only the lookup and
-// the statistics launches differ (emis_pgauss).
+// Categorical branches of the host code (fam_table) with V = 3 D statistics rows [sxx | sx | n]; only the lookup and
+// the statistics launches differ (EF_PGAUSS).
 int svihmm_set_emission_pgauss(svihmm_ctx* h, int32_t K, int32_t D, const double* mu, const double* hprec,
                                const double* cst, const double* origin) {
   const std::string fn = "svihmm_set_emission_pgauss: ";
@@ -913,13 +913,13 @@ int svihmm_set_emission_pgauss(svihmm_ctx* h, int32_t K, int32_t D, const double
   HIPCK(hipMemcpyAsync(h->pg_origin.p, hp + nt, (size_t)D * sizeof(double), hipMemcpyHostToDevice, h->stream));
   CK(pin_release(h, slot));
   h->eK = K; h->eD = D; h->V = 3 * D; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16;
-  h->have_emission = true; h->emis_cat = true; h->emis_mcat = false; h->emis_pois = false; h->emis_pgauss = true; h->emis_diag = false; h->uw_valid = false;
+  set_family(h, EF_PGAUSS);
   return 0;
 }
 int64_t svihmm_packed_len(svihmm_ctx* h) { return h ? (int64_t)packed_len(h) : 0; }
 
 int ensure_feature_table(svihmm_ctx* h) {
-  return upload_feature_table(h, h->D, h->K, h->emis_diag);
+  return upload_feature_table(h, h->D, h->K, h->fam == EF_DIAG);
 }
 
 int svihmm_set_lliks(svihmm_ctx* h, const double* lliks, int32_t B, int32_t Lm) {
@@ -1150,7 +1150,7 @@ int64_t svihmm_packed_size(int32_t K, int32_t D) {
 // too (A/B runs, the bit-identity test).  (B + 18) Lm K < 2^31: the statistics GEMM's 32-bit message offsets.
 bool step_major_ok(const svihmm_ctx* h, int B, int Lm, uint32_t flags, bool lin) {
   if (!lin || h->variant[SVIHMM_VAR_MSG_LAYOUT] == SVIHMM_MSG_LAYOUT_ROW_MAJOR || h->K != 64 || h->Kp != 64) return false;
-  if ((flags & SVIHMM_USE_HOST_LLIKS) || h->emis_cat || (h->prec == 1 && h->f32_ok)) return false;
+  if ((flags & SVIHMM_USE_HOST_LLIKS) || fam_table(h->fam) || (h->prec == 1 && h->f32_ok)) return false;
   if (use_chain(h, B, Lm) || B < lin_wave_max(h)) return false;
   if ((int64_t)(B + 18) * Lm * h->K >= ((int64_t)1 << 31)) return false;
   return emission_row_tile_orbit(h, (int64_t)B * Lm);
@@ -1177,7 +1177,7 @@ int prepare_ll(svihmm_ctx* h, const int64_t* starts, int B, int Lm, uint32_t fla
   } else {
     // K <= 64: the emission kernel owns whole rows and writes (Eh, kexp) itself; wider
     // models take the plain kernel plus one scaling pass
-    const bool two_pass = lin && (h->Kp > 64 || h->emis_cat);
+    const bool two_pass = lin && (h->Kp > 64 || fam_table(h->fam));
     // fp32 mode: scaled messages stored as float + fp32 statistics GEMM, for what the mode
     // covers (NIW emission, K <= 64, window batches on the scaled sweeps; round 5: wide NIW models
     // up to K = 256, D = 64 in large batches, f32_wide_ok); everything else runs as fp64
@@ -1197,7 +1197,7 @@ int prepare_ll(svihmm_ctx* h, const int64_t* starts, int B, int Lm, uint32_t fla
     else if (two_pass) CK(launch_scale_ll(h, B, Lm));
     h->have_host_ll = false;
   }
-  h->eh_in_llE = lin && (host_ll || (h->Kp > 64 && !h->cur_f32) || h->emis_cat);
+  h->eh_in_llE = lin && (host_ll || (h->Kp > 64 && !h->cur_f32) || fam_table(h->fam));
   h->lin_mode = lin;
   h->lin_stale = false;
   h->q_valid = false;
@@ -1258,9 +1258,9 @@ static int launch_mirror(svihmm_ctx* h) {
   double* dev = nullptr;
   HIPCK(hipHostGetDevicePointer((void**)&dev, h->mirror, 0));
   ProfScope ps(h, KS_D2H);
-  if (h->shifted && !h->emis_cat)      // statistics leave in the caller's coordinates
+  if (h->shifted && fam_gaussian(h->fam))      // statistics leave in the caller's coordinates
     hipLaunchKernelGGL(k_packed_shift, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
-                       (const double*)h->packed.p, dev, (int)n, h->K, h->D, (const double*)h->shift_d.p, 1.0, h->emis_diag ? 1 : 0);
+                       (const double*)h->packed.p, dev, (int)n, h->K, h->D, (const double*)h->shift_d.p, 1.0, h->fam == EF_DIAG ? 1 : 0);
   else
     hipLaunchKernelGGL(k_mirror, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
                        (const double*)h->packed.p, dev, (int)n);
@@ -1283,7 +1283,7 @@ static int read_packed_host(svihmm_ctx* h, double* out) {
 // (svihmm_export_packed / svihmm_import_packed) run between the same two halves.
 static bool common_needs_shift(const svihmm_ctx* h, bool always) {
   // (the knob: rehearsal at one rank)
-  return h->shifted && !h->emis_cat &&
+  return h->shifted && fam_gaussian(h->fam) &&
          (always || h->nranks > 1 || h->variant[SVIHMM_VAR_ALLREDUCE_COORDS] == SVIHMM_ALLREDUCE_COORDS_ON);
 }
 static int packed_to_common(svihmm_ctx* h, bool always, double** buf_out) {
@@ -1293,7 +1293,7 @@ static int packed_to_common(svihmm_ctx* h, bool always, double** buf_out) {
   double* tmp = (double*)h->commtmp.p;
   hipLaunchKernelGGL(k_packed_shift, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream,
                      (const double*)h->packed.p, tmp, (int)n, h->K, h->D, (const double*)h->shift_d.p, 1.0,
-                     h->emis_diag ? 1 : 0);
+                     h->fam == EF_DIAG ? 1 : 0);
   HIPCK(hipGetLastError());
   *buf_out = tmp;
   return 0;
@@ -1303,7 +1303,7 @@ static int packed_from_common(svihmm_ctx* h, const double* buf) {
   const size_t n = (size_t)packed_len(h);
   hipLaunchKernelGGL(k_packed_shift, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, h->stream, buf,
                      (double*)h->packed.p, (int)n, h->K, h->D, (const double*)h->shift_d.p, -1.0,
-                     h->emis_diag ? 1 : 0);
+                     h->fam == EF_DIAG ? 1 : 0);
   HIPCK(hipGetLastError());
   return 0;
 }
@@ -1327,7 +1327,7 @@ static int allreduce_packed_dev(svihmm_ctx* h) {
 static bool use_pipeline(const svihmm_ctx* h, int B, int Lm, int fbvar, uint32_t flags) {
   const int v = h->variant[SVIHMM_VAR_PIPELINE];
   if (v == SVIHMM_PIPELINE_UNFUSED || fbvar != SVIHMM_FB_SCALED || (flags & SVIHMM_USE_HOST_LLIKS)) return false;
-  if (h->Kp > 64 || h->D > 64 || h->emis_cat) return false;
+  if (h->Kp > 64 || h->D > 64 || fam_table(h->fam)) return false;
   const int sv = h->variant[SVIHMM_VAR_STATS];
   if (sv != 0 && sv != SVIHMM_STATS_PIPELINED) return false;
   // opt-in only: on MI355X the sweeps' fp64 VALU work queues behind the GEMMs' MFMAs on a
@@ -1429,12 +1429,9 @@ int svihmm_pred_logprob(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t
                         uint32_t flags, double out2[2]) {
   if (!h || !starts || !out2) return fail("svihmm_pred_logprob: bad arguments");
   if (flags & SVIHMM_USE_HOST_LLIKS) return fail("svihmm_pred_logprob: NIW emission only");
-  if (h->have_emission && h->emis_mcat)
-    return fail("svihmm_pred_logprob: NIW emission only (the multi-column Categorical family of svihmm_set_emission_mcat is not taken)");
-  if (h->have_emission && h->emis_pois)
-    return fail("svihmm_pred_logprob: NIW emission only (the Poisson family of svihmm_set_emission_poisson is not taken)");
-  if (h->have_emission && h->emis_pgauss)
-    return fail("svihmm_pred_logprob: NIW emission only (the family of svihmm_set_emission_pgauss is not taken)");
+  if (h->have_emission && FAM_TRAITS[h->fam].noun)
+    return fail(std::string("svihmm_pred_logprob: NIW emission only (") + FAM_TRAITS[h->fam].noun + " of " +
+                FAM_TRAITS[h->fam].setter + " is not taken)");
   CK(set_device(h));
   if (!h->have_mask) { out2[0] = NAN; out2[1] = 0.0; return 0; }
   const int var = pick_fb(h, B, Lm, false);
@@ -1737,8 +1734,8 @@ static int check_estep_sequences(const svihmm_ctx* h, const char* fn, uint32_t f
 // ... the statistics pass addressing the call's R rows as one window (launch_stats_posteriors' limit; `rows`: their
 // name in the message) ...
 static int check_stats_rows(const svihmm_ctx* h, const char* fn, int64_t R, const std::string& rows) {
-  const int64_t rpc = h->emis_cat ? 0 : stats_plan(h, R, h->variant[SVIHMM_VAR_STATS_CHUNKS]).rpc;
-  if (R > 0x7fffffff || (R + rpc) * (int64_t)(h->emis_cat ? 1 : h->Kp) >= ((int64_t)1 << 31))
+  const int64_t rpc = fam_table(h->fam) ? 0 : stats_plan(h, R, h->variant[SVIHMM_VAR_STATS_CHUNKS]).rpc;
+  if (R > 0x7fffffff || (R + rpc) * (int64_t)(fam_table(h->fam) ? 1 : h->Kp) >= ((int64_t)1 << 31))
     return fail(std::string(fn) + ": " + rows + " are too many for the statistics GEMM's 32-bit row offsets");
   return 0;
 }
@@ -1825,7 +1822,7 @@ static int subset_enqueue(svihmm_ctx* h, const SubsetPlan& p, int M, uint32_t fl
   // the resident copy's lazily applied state first: symbol indices go back to exact integers before they are copied
   // (the lookup kernels would do that to the rows in place; a Gaussian family's centre is the handle's, and the copy
   // holds the same centred values)
-  if (h->emis_cat) CK(cat_uncentre(h));
+  if (fam_table(h->fam)) CK(cat_uncentre(h));
   CK(ensure(h->sub_obs, (size_t)R * D * sizeof(double)));
   if (h->have_mask) CK(ensure(h->sub_mask, (size_t)R));
   CK(ensure(h->sub_tab, p.tab.size() * sizeof(int64_t)));
@@ -2019,6 +2016,8 @@ static int svi_globals(svihmm_ctx* h, int slot, int for_it) {
 // their ELBO term vlb[] and, with elbo_it >= 0, elbo_vec[elbo_it] on the side stream -- only the
 // ELBO trace needs them, so they stay off the critical path of the iteration chain.
 static int svi_launch_elbo(svihmm_ctx* h, int elbo_it, int lb_slot, bool behind_sweeps, hipEvent_t after_theta);
+// columns the loop's simple step / ELBO kernels run over
+static int svi_step_width(const svihmm_ctx* h) { return FAM_TRAITS[h->svi_family].svi_width_D ? h->svi_D : h->V; }
 // what the step and ELBO kernels take for the loop on sequence minibatches (all nullptr: the window loop); M: the
 // minibatch's size -- q0 lies behind the M local bounds in h->seq_out
 static SviSeqStep svi_seq_args(svihmm_ctx* h, int M) {
@@ -2028,7 +2027,8 @@ static SviSeqStep svi_seq_args(svihmm_ctx* h, int M) {
 }
 static int svi_refresh_emission(svihmm_ctx* h, int elbo_it, int lb_slot, hipEvent_t after_theta = nullptr,
                                 bool defer_elbo = false, const SviStepArgs* step = nullptr) {
-  const int K = h->svi_K, D = h->svi_D, fam = h->svi_family;
+  const int K = h->svi_K, D = h->svi_D;
+  const EmisFamily fam = h->svi_family;
   if (!h->stream3) HIPCK(hipStreamCreateWithFlags(&h->stream3, hipStreamNonBlocking));
   if (!h->svi_ec) {
     HIPCK(hipEventCreateWithFlags(&h->svi_ec, hipEventDisableTiming));
@@ -2043,16 +2043,16 @@ static int svi_refresh_emission(svihmm_ctx* h, int elbo_it, int lb_slot, hipEven
     if (elbo_it >= 0) { tsy.stamp = svi_stamp_dev(h, 2 * elbo_it + 1); tsy.stamp_at = (unsigned)h->tgt_theta; }
   }
   h->theta_sy = tsy;
-  if (fam == 0) CK(launch_niw_to_theta(h, K, D, svi_ptr(h, 4), step));
-  else if (fam == 1) CK(launch_diag_to_theta(h, K, D));
+  if (fam == EF_NIW) CK(launch_niw_to_theta(h, K, D, svi_ptr(h, 4), step));
+  else if (fam == EF_DIAG) CK(launch_diag_to_theta(h, K, D));
   else {
     // E log theta[v][k] = psi(alpha_kv) - psi(sum_v alpha_kv) (what hmmbase._push_emission uploads); per column for
-    // fam 3; the pairs (psi(a) - log b, a / b) for fam 4
+    // EF_MCAT; the pairs (psi(a) - log b, a / b) for EF_POIS
     ProfScope ps(h, KS_MISC);
-    if (fam == 2)
+    if (fam == EF_CAT)
       hipLaunchKernelGGL(k_cat_table, dim3(K), dim3(64), 0, h->stream, (const double*)h->niw.p, K, h->V,
                          (double*)h->cat_table.p, tsy);
-    else if (fam == 3)
+    else if (fam == EF_MCAT)
       hipLaunchKernelGGL(k_mcat_table, dim3(K), dim3(256), 0, h->stream, (const double*)h->niw.p, K, D, h->V,
                          (const int*)h->mcat_meta.p, (double*)h->cat_table.p, tsy);
     else
@@ -2060,7 +2060,7 @@ static int svi_refresh_emission(svihmm_ctx* h, int elbo_it, int lb_slot, hipEven
                          (double2*)h->cat_table.p, tsy);
     HIPCK(hipGetLastError());
     h->eK = K; h->eD = D; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16;
-    h->have_emission = true; h->emis_cat = true; h->emis_mcat = fam == 3; h->emis_pois = fam == 4; h->emis_pgauss = false; h->emis_diag = false; h->uw_valid = false;
+    set_family(h, fam);
   }
   h->theta_sy = SviSync{};
   h->lin_stale = true;
@@ -2077,7 +2077,8 @@ static int svi_refresh_emission(svihmm_ctx* h, int elbo_it, int lb_slot, hipEven
 // The ELBO terms of the factors now in h->niw / theta (side stream).  `behind_sweeps`: additionally gated on the
 // start of the sweep launch that carries counter 4.
 static int svi_launch_elbo(svihmm_ctx* h, int elbo_it, int lb_slot, bool behind_sweeps, hipEvent_t after_theta) {
-  const int K = h->svi_K, D = h->svi_D, fam = h->svi_family;
+  const int K = h->svi_K, D = h->svi_D;
+  const EmisFamily fam = h->svi_family;
   hipStream_t s2 = h->stream3;
   // (the ELBO kernels follow their gate kernels in stream order: when a gate gave up they find the loop dead and
   //  leave the iteration's entry NaN -- svi_recover computes it again where the state still allows)
@@ -2105,17 +2106,17 @@ static int svi_launch_elbo(svihmm_ctx* h, int elbo_it, int lb_slot, bool behind_
     const SviSeqStep sq = svi_seq_args(h, 0);
     const unsigned nvlb = (unsigned)(2 * K) + (h->svi_seq ? 1u : 0u);
     const double prior_const = h->svi_seq ? h->svi_prior_const + h->svi_prior_const_init : h->svi_prior_const;
-    if (fam == 0)
+    if (fam == EF_NIW)
       hipLaunchKernelGGL(k_svi_vlb, dim3(nvlb), dim3(64), 0, s2, (const double*)h->theta.p,
                          (const int*)h->fab.p, h->F, D, h->Kp, (const double*)h->niw.p,
                          (const double*)svi_ptr(h, 4), (const double*)h->svi_prior.p,
                          (const double*)svi_ptr(h, 5), h->svi_zsign, K, svi_ptr(h, 3),
                          (const double*)svi_ptr(h, 1), (const double*)svi_ptr(h, 0), svi_ptr(h, 6), vsy, et, sq);
     else
-      hipLaunchKernelGGL(k_svi_vlb_simple, dim3(nvlb), dim3(64), 0, s2, fam, (const double*)h->niw.p,
-                         (const double*)h->svi_prior.p, K, fam == 1 || fam == 4 ? D : h->V, svi_ptr(h, 3),
+      hipLaunchKernelGGL(k_svi_vlb_simple, dim3(nvlb), dim3(64), 0, s2, (int)fam, (const double*)h->niw.p,
+                         (const double*)h->svi_prior.p, K, svi_step_width(h), svi_ptr(h, 3),
                          (const double*)svi_ptr(h, 1), (const double*)svi_ptr(h, 0), svi_ptr(h, 6),
-                         (const int*)(fam == 3 ? h->mcat_meta.p : nullptr), D, vsy, et, sq);
+                         (const int*)(fam == EF_MCAT ? h->mcat_meta.p : nullptr), D, vsy, et, sq);
     if (elbo_it >= 0 && !tail) {      // (stream-event choreography: no arrival counter to tell the last workgroup by)
       hipLaunchKernelGGL(k_svi_elbo, dim3(1), dim3(64), 0, s2, K, (const double*)svi_ptr(h, 3),
                          (const double*)svi_ptr(h, 6), prior_const, (const double*)svi_ptr(h, 8) + lb_slot,
@@ -2138,7 +2139,7 @@ int svi_flush_elbo(svihmm_ctx* h) {
 // state (var_tran | prior_tran | ...), the ELBO / event rings.  The caller uploads its prior / factor
 // blocks between svi_begin_common and svi_begin_finish.
 static int svi_begin_common(svihmm_ctx* h, int K, int D, const double* prior_tran, const double* var_tran,
-                            int maxit, int family) {
+                            int maxit, EmisFamily family) {
   if (K > 1024) return fail("svihmm_svi_begin: K > 1024 unsupported");
   if (h->D != D) return fail("svihmm_svi_begin: D does not match the resident observations");
   // from here on the previous loop's state is being overwritten: a begin that fails half way must not
@@ -2149,7 +2150,7 @@ static int svi_begin_common(svihmm_ctx* h, int K, int D, const double* prior_tra
   CK(set_device(h));
   CK(wait_side_streams(h));
   CK(drop_auto_status(h));
-  if (family < 2) CK(centre_deferred(h));       // (symbol and count families: the copy stays uncentred)
+  if (fam_gaussian(family)) CK(centre_deferred(h));       // (symbol and count families: the copy stays uncentred)
   const size_t kk = (size_t)K * K;
   {
     // The global step is var_tran <- (1 - rho) var_tran + rho (1 + bA (A_raw + nwin (prior_tran - 1)))
@@ -2274,7 +2275,7 @@ int svihmm_svi_begin(svihmm_ctx* h, int32_t K, int32_t D, const double* prior_tr
   if (!h || K <= 0 || D <= 0 || !prior_tran || !var_tran || !mu0 || !sigma0 || !kappa0 || !nu0 ||
       !prior_logpart || !mu || !sigma || !kappa || !nu || maxit <= 0)
     return fail("svihmm_svi_begin: bad arguments");
-  CK(svi_begin_common(h, K, D, prior_tran, var_tran, maxit, 0));
+  CK(svi_begin_common(h, K, D, prior_tran, var_tran, maxit, EF_NIW));
   h->svi_zsign = zsign;
   const size_t nmu = (size_t)K * D, nsg = (size_t)K * D * D;
   const size_t nin = nmu + nsg + 2 * (size_t)K;
@@ -2314,7 +2315,7 @@ int svihmm_svi_begin_diag(svihmm_ctx* h, int32_t K, int32_t D, const double* pri
   const size_t n4 = 4 * (size_t)K * D;
   for (size_t i = (size_t)K * D; i < n4; ++i)       // (validated before any state is touched)
     if (!(prior_blk[i] > 0.0) || !(factor_blk[i] > 0.0)) return fail("svihmm_svi_begin_diag: nus, alphas, betas must be positive");
-  CK(svi_begin_common(h, K, D, prior_tran, var_tran, maxit, 1));
+  CK(svi_begin_common(h, K, D, prior_tran, var_tran, maxit, EF_DIAG));
   CK(ensure(h->svi_prior, (n4 + 8) * sizeof(double)));
   CK(ensure(h->niw, n4 * sizeof(double) + 64));
   CK(svi_upload(h, h->svi_prior.p, prior_blk, n4, nullptr, 0, K, D));
@@ -2332,7 +2333,7 @@ int svihmm_svi_begin_cat(svihmm_ctx* h, int32_t K, int32_t V, const double* prio
   const size_t n = (size_t)K * V;
   for (size_t i = 0; i < n; ++i)
     if (!(alpha0[i] > 0.0) || !(alpha[i] > 0.0)) return fail("svihmm_svi_begin_cat: Dirichlet parameters must be positive");
-  CK(svi_begin_common(h, K, 1, prior_tran, var_tran, maxit, 2));
+  CK(svi_begin_common(h, K, 1, prior_tran, var_tran, maxit, EF_CAT));
   h->V = V;
   CK(cat_uncentre(h));
   CK(ensure(h->svi_prior, (n + 8) * sizeof(double)));
@@ -2370,7 +2371,7 @@ int svihmm_svi_begin_mcat(svihmm_ctx* h, int32_t K, int32_t D, const int32_t* V,
   const size_t n = (size_t)K * F;
   for (size_t i = 0; i < n; ++i)       // (validated before any state is touched)
     if (!(alpha0[i] > 0.0) || !(alpha[i] > 0.0)) return fail("svihmm_svi_begin_mcat: Dirichlet parameters must be positive");
-  CK(svi_begin_common(h, K, D, prior_tran, var_tran, maxit, 3));
+  CK(svi_begin_common(h, K, D, prior_tran, var_tran, maxit, EF_MCAT));
   h->V = F;
   h->svi_mcat_V.assign(V, V + D);
   CK(cat_uncentre(h, 0));
@@ -2415,7 +2416,7 @@ int svihmm_svi_begin_poisson(svihmm_ctx* h, int32_t K, int32_t D, const double* 
   const size_t n2 = 2 * (size_t)K * D;
   for (size_t i = 0; i < n2; ++i)      // (validated before any state is touched)
     if (!(prior_blk[i] > 0.0) || !(factor_blk[i] > 0.0)) return fail("svihmm_svi_begin_poisson: Gamma parameters must be positive");
-  CK(svi_begin_common(h, K, D, prior_tran, var_tran, maxit, 4));
+  CK(svi_begin_common(h, K, D, prior_tran, var_tran, maxit, EF_POIS));
   h->V = 2 * D;
   h->pois_C = C;
   CK(cat_uncentre(h, 1));
@@ -2444,7 +2445,6 @@ static int svi_iteration_impl(svihmm_ctx* h, int32_t it, const int64_t* starts, 
                               double bfactA, double bfactE);
 // elements per state of the element-wise global step: D (diagonal, Poisson: one thread per (k, d)), V (Categorical),
 // F (multi-column Categorical: h->V holds it)
-static int svi_step_width(const svihmm_ctx* h) { return h->svi_family == 1 || h->svi_family == 4 ? h->svi_D : h->V; }
 // Leave the counters in the middle of a loop and carry on with the stream-event choreography (round 6).  Two
 // callers: a gate of the loop gave up (the status word is set: a tool that serialises kernels attached after
 // svihmm_svi_begin's probe, another process time-slicing the device, a partition too small for the loop's
@@ -2511,15 +2511,13 @@ int svihmm_svi_recoveries(svihmm_ctx* h, int32_t* out) {
 int svihmm_svi_iteration(svihmm_ctx* h, int32_t it, const int64_t* starts, int32_t B, int32_t nwin_total,
                          int32_t Lm, int32_t inner_off, int32_t inner_len, uint32_t flags, double rho,
                          double bfactA, double bfactE) {
-  if (h && !h->svi_active && h->have_emission && h->emis_mcat)
-    return fail("svihmm_svi_iteration: the resident SVI loop does not take the multi-column Categorical family "
-                "from svihmm_set_emission_mcat alone: the family enters the loop through svihmm_svi_begin_mcat");
-  if (h && !h->svi_active && h->have_emission && h->emis_pois)
-    return fail("svihmm_svi_iteration: the resident SVI loop does not take the Poisson family "
-                "from svihmm_set_emission_poisson alone: the family enters the loop through svihmm_svi_begin_poisson");
-  if (h && !h->svi_active && h->have_emission && h->emis_pgauss)
-    return fail("svihmm_svi_iteration: the resident SVI loop does not take the family of svihmm_set_emission_pgauss; "
-                "step the globals on the host from svihmm_estep_minibatch's statistics");
+  if (h && !h->svi_active && h->have_emission && FAM_TRAITS[h->fam].noun) {
+    const FamTraits& t = FAM_TRAITS[h->fam];
+    const std::string head = std::string("svihmm_svi_iteration: the resident SVI loop does not take ") + t.noun;
+    if (t.svi_begin)
+      return fail(head + " from " + t.setter + " alone: the family enters the loop through " + t.svi_begin);
+    return fail(head + " of " + t.setter + "; step the globals on the host from svihmm_estep_minibatch's statistics");
+  }
   if (!h || !h->svi_active) return fail("svihmm_svi_iteration: call svihmm_svi_begin first");
   if (h->svi_seq)
     return fail("svihmm_svi_iteration: the loop steps on minibatches of whole sequences since svihmm_svi_sequences: "
@@ -2615,9 +2613,9 @@ static int svi_iteration_impl(svihmm_ctx* h, int32_t it, const int64_t* starts, 
   // which this global step and the NIW kernel after it rewrite (normally long finished): flags mode gates the
   // step kernel on their counter, the event mode waits for their event
   // (NIW factors of 17 .. 32 dimensions: the step rides in the theta builder's launch -- k_svi_step_theta32s)
-  const bool merged = h->svi_family == 0 && step_theta_ok(h, K, D);
+  const bool merged = h->svi_family == EF_NIW && step_theta_ok(h, K, D);
   const unsigned ntran = merged ? (unsigned)((K * K + 63) / 64) : (unsigned)((K * K + 255) / 256);
-  const unsigned step_grid = h->svi_family == 0 ? (unsigned)K + ntran
+  const unsigned step_grid = h->svi_family == EF_NIW ? (unsigned)K + ntran
                                                 : (unsigned)(((size_t)K * svi_step_width(h) + 255) / 256) + ntran;
   SviSync ssy = svi_sy(h);
   if (h->svi_flags) {
@@ -2642,7 +2640,7 @@ static int svi_iteration_impl(svihmm_ctx* h, int32_t it, const int64_t* starts, 
     if (h->svi_flags) h->tgt_step += ntran;          // (the merged kernel's transition workgroups: see k_svi_step_theta32s)
   } else {
     ProfScope ps(h, KS_MISC);
-    if (h->svi_family == 0)
+    if (h->svi_family == EF_NIW)
       hipLaunchKernelGGL(k_svi_global_step, dim3((unsigned)K + ntran), dim3(256), (size_t)3 * D * sizeof(double), h->stream,
                          (const double*)h->packed.p, (const double*)svi_ptr(h, 1), svi_ptr(h, 0),
                          (double*)h->niw.p, (const double*)h->svi_prior.p, K, D, rho, bfactA, bfactE,
@@ -2650,7 +2648,7 @@ static int svi_iteration_impl(svihmm_ctx* h, int32_t it, const int64_t* starts, 
     else {
       const int W = svi_step_width(h);
       const unsigned nem = (unsigned)(((size_t)K * W + 255) / 256);
-      hipLaunchKernelGGL(k_svi_global_step_simple, dim3(nem + ntran), dim3(256), 0, h->stream, h->svi_family,
+      hipLaunchKernelGGL(k_svi_global_step_simple, dim3(nem + ntran), dim3(256), 0, h->stream, (int)h->svi_family,
                          (const double*)h->packed.p, (const double*)svi_ptr(h, 1), svi_ptr(h, 0),
                          (double*)h->niw.p, (const double*)h->svi_prior.p, K, W, rho, bfactA, bfactE,
                          (double)nwin_total, svi_ptr(h, 8) + (it & 1), adag, (int)nem, ssy, sargs.sq);
@@ -2819,7 +2817,7 @@ int svihmm_svi_iteration_sequences(svihmm_ctx* h, int32_t it, const int32_t* idx
   // the previous iteration's ELBO kernels (their own stream) read var_tran / var_init / theta / logdet, which the step
   // and the theta builder rewrite: the stream waits for their event
   if (h->vlb_pending) { HIPCK(hipStreamWaitEvent(h->stream, h->svi_ed, 0)); h->vlb_pending = false; }
-  const bool merged = h->svi_family == 0 && step_theta_ok(h, K, D);
+  const bool merged = h->svi_family == EF_NIW && step_theta_ok(h, K, D);
   const unsigned ntran = (unsigned)((K * K + 255) / 256);
   const SviSeqStep sq = svi_seq_args(h, M);
   double* lb_keep = svi_ptr(h, 8) + (it & 1);
@@ -2827,14 +2825,14 @@ int svihmm_svi_iteration_sequences(svihmm_ctx* h, int32_t it, const int32_t* idx
                        rho, bfact, bfact, 1.0, lb_keep, (double*)nullptr, SviSync{}, sq};
   if (!merged) {
     ProfScope ps(h, KS_MISC);
-    if (h->svi_family == 0)
+    if (h->svi_family == EF_NIW)
       hipLaunchKernelGGL(k_svi_global_step, dim3((unsigned)K + ntran), dim3(256), (size_t)3 * D * sizeof(double), h->stream,
                          sargs.packed, sargs.prior_tran, sargs.var_tran, (double*)h->niw.p, sargs.prior, K, D, rho, bfact,
                          bfact, 1.0, lb_keep, (double*)nullptr, SviSync{}, sq);
     else {
       const int W = svi_step_width(h);
       const unsigned nem = (unsigned)(((size_t)K * W + 255) / 256);
-      hipLaunchKernelGGL(k_svi_global_step_simple, dim3(nem + ntran), dim3(256), 0, h->stream, h->svi_family,
+      hipLaunchKernelGGL(k_svi_global_step_simple, dim3(nem + ntran), dim3(256), 0, h->stream, (int)h->svi_family,
                          sargs.packed, sargs.prior_tran, sargs.var_tran, (double*)h->niw.p, sargs.prior, K, W, rho, bfact,
                          bfact, 1.0, lb_keep, (double*)nullptr, (int)nem, SviSync{}, sq);
     }
@@ -2874,7 +2872,7 @@ int svihmm_svi_read_elbo(svihmm_ctx* h, int32_t n, double* out_elbo, double* out
 int svihmm_svi_read_state(svihmm_ctx* h, double* var_tran, double* var_init, double* mu, double* sigma,
                           double* kappa, double* nu) {
   if (!h || !h->svi_active) return fail("svihmm_svi_read_state: no SVI state on the device");
-  if (h->svi_family != 0) return fail("svihmm_svi_read_state: NIW layout; this loop's family reads through svihmm_svi_read_factors");
+  if (h->svi_family != EF_NIW) return fail("svihmm_svi_read_state: NIW layout; this loop's family reads through svihmm_svi_read_factors");
   CK(set_device(h));
   CK(svi_settle(h));
   const size_t K = h->svi_K, D = h->svi_D, nmu = K * D, nsg = K * D * D;
@@ -2902,7 +2900,7 @@ int svihmm_svi_read_factors(svihmm_ctx* h, double* var_tran, double* var_init, d
   CK(set_device(h));
   CK(svi_settle(h));
   const size_t K = h->svi_K, D = h->svi_D;
-  const size_t n = h->svi_family == 0 ? K * D + K * D * D + 2 * K : h->svi_family == 1 ? 4 * K * D : K * (size_t)h->V;
+  const size_t n = h->svi_family == EF_NIW ? K * D + K * D * D + 2 * K : h->svi_family == EF_DIAG ? 4 * K * D : K * (size_t)h->V;
   if (var_tran) CK(d2h(h, var_tran, svi_ptr(h, 0), K * K * 8));
   CK(wait_globals(h));
   if (var_init) CK(d2h(h, var_init, svi_ptr(h, h->svi_vi_cur ? 7 : 2), K * 8));
@@ -2910,7 +2908,7 @@ int svihmm_svi_read_factors(svihmm_ctx* h, double* var_tran, double* var_init, d
   HIPCK(hipStreamSynchronize(h->stream));
   if (h->stream3) HIPCK(hipStreamSynchronize(h->stream3));   // ELBO kernels still reading the factors
   h->vlb_pending = false;
-  if (factors_out && h->svi_family < 2) from_centred(h, factors_out, (int)K, (int)D);
+  if (factors_out && fam_gaussian(h->svi_family)) from_centred(h, factors_out, (int)K, (int)D);
   CK(check_emission_status(h));
   return 0;
 }
@@ -3079,7 +3077,7 @@ int svihmm_heldout_entries(svihmm_ctx* h, int64_t n, const int64_t* row, const i
   if (n > 0 && (!row || !col || !val)) return bad("row, col and val must be given when n > 0");
   int64_t nrows = 0;
   CK(heldout_batch(h, fn, &nrows));
-  if (!h->have_emission || !(h->emis_mcat || h->emis_pois || h->emis_pgauss))
+  if (!h->have_emission || !fam_entrywise(h->fam))
     return bad("entry-wise scores are defined for the families that skip single entries: besides the Gaussian tracks "
                "of svihmm_set_emission_pgauss, the multi-column Categorical and the Poisson family only "
                "(svihmm_set_emission_mcat / svihmm_set_emission_poisson); svihmm_heldout_rows takes every family");
@@ -3117,11 +3115,11 @@ int svihmm_heldout_entries(svihmm_ctx* h, int64_t n, const int64_t* row, const i
     ProfScope ps(h, KS_MISC);
 #define HE(KT)                                                                                                         \
   do {                                                                                                                 \
-    if (h->emis_pgauss)                                                                                                \
+    if (h->fam == EF_PGAUSS)                                                                                           \
       hipLaunchKernelGGL((k_heldout_entries<KT, 2>), dim3(nblk), dim3(256), 0, h->stream, q, (const int64_t*)drow,     \
                          (const int32_t*)dcol, (const double*)dval, n, K, D, (const double*)h->cat_table.p,            \
                          (const int*)nullptr, (const double*)nullptr, 0, out_lp ? dlp : (double*)nullptr, part);       \
-    else if (h->emis_pois)                                                                                             \
+    else if (h->fam == EF_POIS)                                                                                        \
       hipLaunchKernelGGL((k_heldout_entries<KT, 1>), dim3(nblk), dim3(256), 0, h->stream, q, (const int64_t*)drow,     \
                          (const int32_t*)dcol, (const double*)dval, n, K, D, (const double*)h->cat_table.p,            \
                          (const int*)nullptr, (const double*)h->pois_logfact.p, h->pois_C,                             \
@@ -3502,8 +3500,8 @@ int svihmm_generate(svihmm_ctx* h, int64_t T, int32_t K, int32_t D, const double
   h->center_pending = false;
   {   // centre: the plain average of the state means (a point inside the data)
     std::vector<double> c((size_t)D, 0.0);
-    h->center_deferred = h->have_emission && h->emis_cat;
-    if (h->variant[SVIHMM_VAR_CENTRING] != SVIHMM_CENTRING_OFF && !(h->have_emission && h->emis_cat)) {
+    h->center_deferred = h->have_emission && fam_table(h->fam);
+    if (h->variant[SVIHMM_VAR_CENTRING] != SVIHMM_CENTRING_OFF && !(h->have_emission && fam_table(h->fam))) {
       for (int k = 0; k < K; ++k)
         for (int d = 0; d < D; ++d) c[d] += means[(size_t)k * D + d] / K;
       for (int d = 0; d < D; ++d) if (!(c[d] > -1.7e308 && c[d] < 1.7e308)) c[d] = 0.0;

@@ -50,7 +50,7 @@ static int emd_buffers(svihmm_ctx* h, int K, uint4** uwp) {
 // (the statistics side of the same decision is stats_bf16w_shape_ok, tu_stats.hip: a batch enters the fp32 format
 //  only when BOTH ends have their kernel -- otherwise it runs fp64, as the header promises)
 bool f32_wide_ok(const svihmm_ctx* h, int64_t n) {
-  return !h->emis_diag && !h->emis_cat && h->K > 64 && h->K <= 256 && h->D <= 64 && h->niw.p != nullptr &&
+  return h->fam == EF_NIW && h->K > 64 && h->K <= 256 && h->D <= 64 && h->niw.p != nullptr &&
          h->variant[SVIHMM_VAR_EMISSION_ORBIT] != SVIHMM_EMISSION_ORBIT_F64 &&
          h->variant[SVIHMM_VAR_STATS_TILING] != SVIHMM_STATS_TILING_F32_MFMA && bf16_batch_floor_ok(h, n) &&
          stats_bf16w_shape_ok(h, n);
@@ -140,7 +140,7 @@ int launch_niw_to_theta(svihmm_ctx* h, int K, int D, double* logdet_out, const S
   }
   // status comes back asynchronously; it is examined at the next synchronising call
   h->status_pending = true;
-  h->eK = K; h->eD = D; h->have_emission = true; h->emis_cat = false; h->emis_mcat = false; h->emis_pois = false; h->emis_pgauss = false; h->emis_diag = false;
+  h->eK = K; h->eD = D; set_family(h, EF_NIW);
   h->orb_valid = orbp != nullptr;
   h->uw_valid = uwp != nullptr && !emd;
   h->uwd_valid = emd;
@@ -171,7 +171,7 @@ int launch_diag_to_theta(svihmm_ctx* h, int K, int D) {
     HIPCK(hipGetLastError());
   }
   h->status_pending = true;
-  h->eK = K; h->eD = D; h->have_emission = true; h->emis_cat = false; h->emis_mcat = false; h->emis_pois = false; h->emis_pgauss = false; h->emis_diag = true; h->uw_valid = false; h->uwd_valid = false;
+  h->eK = K; h->eD = D; set_family(h, EF_DIAG);
   h->orb_valid = false;
   return 0;
 }
@@ -201,7 +201,7 @@ int launch_emission_deferred(svihmm_ctx* h) {
 // (k_emission_orbit: the only producer of the step-major layout)?  The same tests as in launch_emission below.
 bool emission_row_tile_orbit(const svihmm_ctx* h, int64_t n) {
   const int D = h->D;
-  if (h->emis_cat || h->emis_diag || h->K > 64 || D < 8 || D > 40 || D % 8 != 0 ||
+  if (h->fam != EF_NIW || h->K > 64 || D < 8 || D > 40 || D % 8 != 0 ||
       h->variant[SVIHMM_VAR_EMISSION_ORBIT] == SVIHMM_EMISSION_ORBIT_OFF)
     return false;
   return !((n + 127) / 128 < h->ncu && h->variant[SVIHMM_VAR_EMISSION_ORBIT] != SVIHMM_EMISSION_ORBIT_128 &&
@@ -247,14 +247,14 @@ int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
   const uint8_t* mk = h->have_mask ? (const uint8_t*)h->mask.p : nullptr;
   if (scaled && h->cur_f32) flags |= SVIHMM_INT_ST32;
   ProfScope ps(h, KS_EMISSION, stream);
-  if (h->emis_cat) {   // table lookup (scaled output: the caller adds the k_scale_ll pass)
+  if (fam_table(h->fam)) {   // table lookup (scaled output: the caller adds the k_scale_ll pass)
     if (scaled) return fail("internal: Categorical emission has no fused scaled output");
     CK(device_starts());
     if (h->shifted) {          // (a shift moved the symbol column after the table was set)
       if (stream != h->stream) return fail("internal: Categorical lookup on a side stream over a centred column");
       CK(cat_uncentre(h));
     }
-    if (h->emis_mcat) {        // D symbol columns: one lookup and one add per present column (kernels_mcat.h)
+    if (h->fam == EF_MCAT) {        // D symbol columns: one lookup and one add per present column (kernels_mcat.h)
       const int F = h->V;
       const size_t tb = (size_t)F * K * sizeof(double), ib = (size_t)MC_EM_ROWS * ((D + 7) & ~7) * sizeof(int);
       const bool tlds = tb <= 64 * 1024;
@@ -276,7 +276,7 @@ int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
       HIPCK(hipGetLastError());
       return 0;
     }
-    if (h->emis_pois) {        // D count columns: multiply, add, subtract per present column (kernels_poisson.h)
+    if (h->fam == EF_POIS) {        // D count columns: multiply, add, subtract per present column (kernels_poisson.h)
       const int DP = (D + 3) & ~3;
       const size_t tb = 2 * (size_t)(D + 1) * K * sizeof(double);       // (with the zero row an absent column reads)
       const size_t ib = PO_EM_ROWS * sizeof(double) + (size_t)PO_EM_ROWS * (DP + 4) * sizeof(int);
@@ -300,7 +300,7 @@ int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
       HIPCK(hipGetLastError());
       return 0;
     }
-    if (h->emis_pgauss) {      // D real-valued columns: five rounded operations per present column (kernels_pgauss.h)
+    if (h->fam == EF_PGAUSS) {      // D real-valued columns: five rounded operations per present column (kernels_pgauss.h)
       const int DP = (D + 3) & ~3;
       const size_t tb = 3 * (size_t)(D + 1) * K * sizeof(double);       // (with the zero row an absent column reads)
       const size_t ib = (size_t)PG_EM_ROWS * DP * sizeof(double);
@@ -330,7 +330,7 @@ int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
   }
   // fp32 mode, large batches of a NIW model with K <= 64, D <= 32: the centred bf16 x 3 kernel
   // (SVIHMM_EMISSION_ORBIT_F64: the fp64 feature GEMM also in this mode)
-  if (!h->emis_diag && scaled && (flags & SVIHMM_INT_ST32) && emb_shape_ok(K, D) && h->niw.p &&
+  if (h->fam != EF_DIAG && scaled && (flags & SVIHMM_INT_ST32) && emb_shape_ok(K, D) && h->niw.p &&
       h->variant[SVIHMM_VAR_EMISSION_ORBIT] != SVIHMM_EMISSION_ORBIT_F64 && min_lds == 0 &&
       (n >= 8192 || h->variant[SVIHMM_VAR_EMISSION_ORBIT] == SVIHMM_EMISSION_ORBIT_BF16_SMALL)) {
     uint4* uwp = nullptr;
@@ -390,7 +390,7 @@ int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
   // fp32 mode, 32 < D <= 64 (K <= 64: scaled output) and wide models (K > 64: plain float output, the
   // scaling pass follows): the centred bf16 x 3 kernel with 64-dimension pair records (round 5)
   const bool wide32 = !scaled && h->cur_f32 && K > 64;
-  if (!h->emis_diag && ((scaled && (flags & SVIHMM_INT_ST32) && K <= 64) || wide32) && emd_shape_ok(K, D) && h->niw.p &&
+  if (h->fam != EF_DIAG && ((scaled && (flags & SVIHMM_INT_ST32) && K <= 64) || wide32) && emd_shape_ok(K, D) && h->niw.p &&
       h->variant[SVIHMM_VAR_EMISSION_ORBIT] != SVIHMM_EMISSION_ORBIT_F64 && min_lds == 0 && bf16_batch_floor_ok(h, n)) {
     uint4* uwp = nullptr;
     CK(device_starts());
@@ -424,7 +424,7 @@ int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
   }
   int var = 2;      // (the VALU outer-product generation of round 1 is gone, and with it the knob that chose it)
   // scaled output, D % 8 == 0: the address-free orbit schedule (SVIHMM_EMISSION_ORBIT_OFF keeps K1b)
-  if (!h->emis_diag && scaled && K <= 64 && D >= 8 && D <= 40 && D % 8 == 0 &&
+  if (h->fam != EF_DIAG && scaled && K <= 64 && D >= 8 && D <= 40 && D % 8 == 0 &&
       h->variant[SVIHMM_VAR_EMISSION_ORBIT] != SVIHMM_EMISSION_ORBIT_OFF && min_lds == 0) {
     const int NT = Kp / 16, LEN = D + D / 2 + 1;
     const int nks = (D / 4) * (D / 2 + 1) + (D / 2 + 1 + 3) / 4;
@@ -494,7 +494,7 @@ int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
     if (lds > 150 * 1024 && MT == 4) { MT = 2; lds = (size_t)128 * DS * 8 + (size_t)h->Fp * 4 + 128 * 9; }
     if (lds < min_lds) lds = min_lds;   // occupancy cap: leave LDS for co-resident sweep workgroups
     if (lds > 150 * 1024 && scaled) return fail("emission: D too large for the scaled sweeps");
-    if (lds > 150 * 1024 && h->emis_diag) return fail("emission: D too large for the diagonal family's kernel");
+    if (lds > 150 * 1024 && h->fam == EF_DIAG) return fail("emission: D too large for the diagonal family's kernel");
     if (lds > 150 * 1024) return fail("emission: D too large for the LDS-staged GEMM kernel");
     {
       const int ntile = Kp / 16;

@@ -36,7 +36,7 @@ static bool stats_bf16_ok(const svihmm_ctx* h, int64_t n) {
   // (batches below 32 768 rows -- the 64-window minibatch -- keep the fp32-input kernel's many small
   //  workgroups: one 8-wave workgroup per chunk would leave most CUs idle)
   return h->cur_f32 && h->lin_mode && !h->q_valid && h->K == 64 && h->Kp == 64 && h->D <= 32 && h->Fp > 0 &&
-         h->Fp % 32 == 0 && !h->emis_cat && !h->emis_diag &&
+         h->Fp % 32 == 0 && h->fam == EF_NIW &&
          h->variant[SVIHMM_VAR_STATS_TILING] != SVIHMM_STATS_TILING_F32_MFMA && h->variant[SVIHMM_VAR_STATS] == 0 &&
          bf16_batch_floor_ok(h, n);     // (SVIHMM_STATS_TILING_BF16_SMALL: tests force it on small batches)
 }
@@ -65,8 +65,8 @@ bool stats_bf16w_shape_ok(const svihmm_ctx* h, int64_t n) {
   // (a wide model that runs in the fp32 format has no other statistics kernel: no batch-size floor there)
   // (D <= 64: the kernel stages x columns 0..63 from the observations and treats columns 64, 65 as the ones / zero
   //  columns -- found by the fuzz at K = 64, D = 79 with the floors lifted)
-  return h->K <= 256 && h->D <= 64 && h->Kp % 64 == 0 && h->Fp > 0 && !h->emis_cat &&
-         !h->emis_diag && h->variant[SVIHMM_VAR_STATS_TILING] != SVIHMM_STATS_TILING_F32_MFMA &&
+  return h->K <= 256 && h->D <= 64 && h->Kp % 64 == 0 && h->Fp > 0 && h->fam == EF_NIW &&
+         h->variant[SVIHMM_VAR_STATS_TILING] != SVIHMM_STATS_TILING_F32_MFMA &&
          h->variant[SVIHMM_VAR_STATS] == 0 && bw_lds(h) <= 160 * 1024 &&
          (h->K > 64 || ((h->Fp + 31) / 32 + 2 > 24 && bf16_batch_floor_ok(h, n)) ||
           // (minibatch-sized batches at K = 64: the six-tile groups)
@@ -97,7 +97,7 @@ StatsPlan stats_plan(const svihmm_ctx* h, int64_t n, int forced) {
     int64_t rpc = ((n + tc - 1) / tc + SB_ROWS - 1) / SB_ROWS * SB_ROWS;
     return {rpc, (n + rpc - 1) / rpc};
   }
-  if (forced <= 0 && h->Kp <= 64 && h->Fp > 0 && !h->emis_cat) {
+  if (forced <= 0 && h->Kp <= 64 && h->Fp > 0 && fam_gaussian(h->fam)) {
     const int gy = ((h->Fp + h->Kp) / 16 + 4 * stats_mt(h) - 1) / (4 * stats_mt(h));
     const int ncu = h->ncu;
     const int r = std::max(1, (ncu / 2 * gy + ncu / 2) / ncu);     // rounds: round((CUs / 2) gy / CUs)
@@ -357,7 +357,7 @@ int launch_stats_finalize(svihmm_ctx* h, int64_t nchunk, hipStream_t stream) {
   hipLaunchKernelGGL(k_finalize, dim3((unsigned)((tot + 63) / 64) + (lbB ? 1 : 0)), dim3(256), 0, stream,
                      (const double*)h->part.p, (int)nchunk, D, K, Kp, Fp, F,
                      (const int*)h->fab.p, (double*)h->packed.p,
-                     (const double*)(lbB ? h->local_lb.p : nullptr), lbB, h->emis_diag ? 1 : 0);
+                     (const double*)(lbB ? h->local_lb.p : nullptr), lbB, h->fam == EF_DIAG ? 1 : 0);
   HIPCK(hipGetLastError());
   return 0;
 }
@@ -387,7 +387,7 @@ static int launch_stats_cat(svihmm_ctx* h, int B, int Lq, int off, int Lm, uint3
   // row chunks of the counts.  One column: k_stats_cat, one wave per chunk.  D columns (k_stats_onehot): whole stages
   // of MC_RB rows, two chunks per CU for each (feature group, state group) pair -- more only adds partial sums
   // (Poisson: k_stats_poisson, the same tiling with V = 2 D; Gaussian tracks: k_stats_pgauss, V = 3 D)
-  const bool po = h->emis_pois, pg = h->emis_pgauss, mc = h->emis_mcat || po || pg;
+  const bool po = h->fam == EF_POIS, pg = h->fam == EF_PGAUSS, mc = h->fam == EF_MCAT || po || pg;
   const int mcMT = V <= 64 ? 1 : V <= 128 ? 2 : 4;
   const int mcGy = (V + 64 * mcMT - 1) / (64 * mcMT), mcGz = (K + 63) / 64;
   int64_t rpcc = (n + 1023) / 1024 > 64 ? (n + 1023) / 1024 : 64;
@@ -469,7 +469,7 @@ static int launch_stats_cat(svihmm_ctx* h, int B, int Lq, int off, int Lm, uint3
 }
 
 int launch_stats(svihmm_ctx* h, int B, int Lq, int off, int Lm, uint32_t flags) {
-  if (h->emis_cat) return launch_stats_cat(h, B, Lq, off, Lm, flags);
+  if (fam_table(h->fam)) return launch_stats_cat(h, B, Lq, off, Lm, flags);
   const StatsPlan plan = stats_plan(h, (int64_t)B * Lm, h->variant[SVIHMM_VAR_STATS_CHUNKS]);
   CK(ensure_stats(h, plan.nchunk));
   CK(launch_stats_range(h, 0, B, Lq, off, Lm, flags, plan, 0, h->stream));
@@ -482,7 +482,7 @@ int launch_stats(svihmm_ctx* h, int B, int Lq, int off, int Lm, uint32_t flags) 
 int launch_stats_posteriors(svihmm_ctx* h, const double* q, const int64_t* starts_dev, int B, int Lm,
                             uint32_t flags) {
   CK(flush_lb(h, h->stream));       // (a deferred ELBO total lands in the slot overwritten below)
-  if (h->emis_cat) {
+  if (fam_table(h->fam)) {
     CK(launch_stats_cat(h, B, Lm, 0, Lm, flags, q, starts_dev));
   } else {
     const StatsPlan plan = stats_plan(h, (int64_t)B * Lm, h->variant[SVIHMM_VAR_STATS_CHUNKS]);

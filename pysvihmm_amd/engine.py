@@ -6,6 +6,7 @@ reference's ``local_update`` / ``intermediate_pars`` (hmmsgd_metaobs.py:487-519,
 in a pickled ``__dict__`` (the reference pickles whole VBHMM objects,
 cluster/run_cluster_simple.py:32-37).
 """
+import collections
 import ctypes as C
 
 import numpy as np
@@ -125,15 +126,40 @@ class PackedGaussTrackStats(object):
         return K * K + 3 * K * D + 1
 
 
+def _split_niw(blk, K, D):
+    o1, o2 = K * D, K * D + K * D * D
+    return blk[:o1].reshape(K, D), blk[o1:o2].reshape(K, D, D), blk[o2:o2 + K], blk[o2 + K:]
+
+
+def _split_mcat(blk, K, Vs):
+    off = np.concatenate(([0], np.cumsum(Vs))).astype(int)
+    flat = blk.reshape(K, sum(Vs))
+    return [np.ascontiguousarray(flat[:, off[d]:off[d + 1]]) for d in range(len(Vs))]
+
+
+# One row per emission family (the names of hmmbase.FAMILIES): the view of its packed statistics and that view's
+# ``size(K, shape)``; ``fields``: the view's attributes that hold its constructor's arguments after ``K``; ``block`` /
+# ``split``: length of the resident SVI loop's factor block and its parts as ``svi_read_factors`` returns them, both of
+# ``(K, shape)`` (None: the family has no resident loop).  ``shape`` is D, V or the tuple Vs, as the family counts.
+FamilyStats = collections.namedtuple("FamilyStats", "stats size fields block split")
+FAMILY_STATS = {
+    "niw": FamilyStats(PackedStats, PackedStats.size, ("D",), lambda K, D: K * D + K * D * D + 2 * K, _split_niw),
+    "diag": FamilyStats(PackedDiagStats, PackedDiagStats.size, ("D",), lambda K, D: 4 * K * D,
+                        lambda blk, K, D: tuple(blk.reshape(4, K, D))),
+    "cat": FamilyStats(PackedCatStats, PackedCatStats.size, ("V",), lambda K, V: K * V,
+                       lambda blk, K, V: blk.reshape(K, V)),
+    "mcat": FamilyStats(PackedMCatStats, PackedMCatStats.size, ("Vs",), lambda K, Vs: K * sum(Vs), _split_mcat),
+    "poisson": FamilyStats(PackedPoissonStats, PackedPoissonStats.size, ("D",), lambda K, D: 2 * K * D,
+                           lambda blk, K, D: tuple(blk.reshape(2, K, D))),
+    "pgauss": FamilyStats(PackedGaussTrackStats, PackedGaussTrackStats.size, ("D", "origin"), None, None),
+}
+
+
 def rewrap_packed(st, buf):
     """A view of ``st``'s type and shape over another buffer (sums / multiples of packed statistics)."""
-    if isinstance(st, PackedGaussTrackStats):
-        return PackedGaussTrackStats(buf, st.K, st.D, st.origin)
-    if isinstance(st, PackedPoissonStats):
-        return PackedPoissonStats(buf, st.K, st.D)
-    if isinstance(st, PackedMCatStats):
-        return PackedMCatStats(buf, st.K, st.Vs)
-    return type(st)(buf, st.K, getattr(st, "V", None) if hasattr(st, "counts") else st.D)
+    fields = next((f.fields for f in FAMILY_STATS.values() if isinstance(st, f.stats)),
+                  ("V",) if hasattr(st, "counts") else ("D",))      # (another engine's view: told by its attributes)
+    return type(st)(buf, st.K, *[getattr(st, a) for a in fields])
 
 
 class HipEngine(object):
@@ -153,11 +179,10 @@ class HipEngine(object):
             self.set_precision("f32")
         self.device = int(device)
         self.T = self.D = self.K = 0
-        self.V = 0            # > 0: Categorical emission with V symbols is active
-        self.Vs = None        # multi-column Categorical emission is active: the columns' symbol counts
-        self.pois = 0         # Poisson count emission is active: its D
-        self.pgauss = 0        # Gaussian tracks with missing entries are active: their D
-        self.diag = False     # diagonal-Gaussian emission is active (its own packed layout)
+        # the emission family in force: (name in FAMILY_STATS, what its statistics view takes after K); () for the two
+        # Gaussian families, whose view takes the resident rows' D as it is when the statistics are wrapped
+        self.family = ("niw", ())
+        self._svi = None      # the resident SVI loop begun through this object: (family name, K, shape)
         self._comm = False
         self.seq_off = None   # offsets declared with set_sequences (every upload of rows removes them)
 
@@ -313,11 +338,7 @@ class HipEngine(object):
         L.check(self._lib.svihmm_set_emission_niw(self._h, K, D, L.dptr(mu), L.dptr(sigma),
                                                   L.dptr(kappa), L.dptr(nu)),
                 "svihmm_set_emission_niw")
-        self.V = 0
-        self.diag = False
-        self.Vs = None
-        self.pois = 0
-        self.pgauss = 0
+        self.family = ("niw", ())
         if check:
             L.check(self._lib.svihmm_sync(self._h), "svihmm_set_emission_niw")
 
@@ -331,11 +352,7 @@ class HipEngine(object):
         nus, alphas, betas = (L.as_f64(a, (K, D)) for a in (nus, alphas, betas))
         L.check(self._lib.svihmm_set_emission_diag(self._h, K, D, L.dptr(mu), L.dptr(nus), L.dptr(alphas),
                                                    L.dptr(betas)), "svihmm_set_emission_diag")
-        self.V = 0
-        self.diag = True
-        self.Vs = None
-        self.pois = 0
-        self.pgauss = 0
+        self.family = ("diag", ())
         if check:
             L.check(self._lib.svihmm_sync(self._h), "svihmm_set_emission_diag")
 
@@ -501,27 +518,17 @@ class HipEngine(object):
         self._held = ("subset", ix)
         return (self._wrap_packed(out) if read else None), seq_lb, q0[:self.K]
 
+    def _stats_args(self):
+        name, args = self.family
+        return FAMILY_STATS[name], (self.K,) + (args or (self.D,))
+
     def _packed_len(self):
-        if self.pgauss:
-            return PackedGaussTrackStats.size(self.K, self.pgauss)
-        if self.pois:
-            return PackedPoissonStats.size(self.K, self.pois)
-        if self.Vs:
-            return PackedMCatStats.size(self.K, self.Vs)
-        if self.V:
-            return PackedCatStats.size(self.K, self.V)
-        return PackedDiagStats.size(self.K, self.D) if self.diag else PackedStats.size(self.K, self.D)
+        fam, args = self._stats_args()
+        return fam.size(*args[:2])
 
     def _wrap_packed(self, buf):
-        if self.pgauss:
-            return PackedGaussTrackStats(buf, self.K, self.pgauss, self._pg_origin)
-        if self.pois:
-            return PackedPoissonStats(buf, self.K, self.pois)
-        if self.Vs:
-            return PackedMCatStats(buf, self.K, self.Vs)
-        if self.V:
-            return PackedCatStats(buf, self.K, self.V)
-        return PackedDiagStats(buf, self.K, self.D) if self.diag else PackedStats(buf, self.K, self.D)
+        fam, args = self._stats_args()
+        return fam.stats(buf, *args)
 
     def set_emission_cat(self, logp):
         """Categorical emissions: ``logp[k, v] = E_q log theta_k[v]`` (obs = symbol indices)."""
@@ -529,11 +536,7 @@ class HipEngine(object):
         logp = L.as_f64(logp)
         K, V = logp.shape
         L.check(self._lib.svihmm_set_emission_cat(self._h, K, V, L.dptr(logp)), "svihmm_set_emission_cat")
-        self.V = V
-        self.diag = False
-        self.Vs = None
-        self.pois = 0
-        self.pgauss = 0
+        self.family = ("cat", (V,))
 
     def set_emission_mcat(self, tables):
         """Multi-column Categorical emissions (``svihmm_set_emission_mcat``): ``tables`` is a list of D
@@ -548,11 +551,7 @@ class HipEngine(object):
         logp = np.ascontiguousarray(np.concatenate(tabs, axis=1))
         L.check(self._lib.svihmm_set_emission_mcat(self._h, K, len(tabs), Vs.ctypes.data_as(C.POINTER(C.c_int32)),
                                                    L.dptr(logp)), "svihmm_set_emission_mcat")
-        self.V = 0
-        self.diag = False
-        self.Vs = tuple(int(v) for v in Vs)
-        self.pois = 0
-        self.pgauss = 0
+        self.family = ("mcat", (tuple(int(v) for v in Vs),))
 
     def set_emission_poisson(self, elog, erate, max_count):
         """Poisson count emissions (``svihmm_set_emission_poisson``): ``elog[k, d] = psi(a) - log(b)`` and
@@ -573,11 +572,7 @@ class HipEngine(object):
         K, D = elog.shape
         L.check(self._lib.svihmm_set_emission_poisson(self._h, K, D, L.dptr(elog), L.dptr(erate),
                                                       L.dptr(self._logfact), C_), "svihmm_set_emission_poisson")
-        self.V = 0
-        self.diag = False
-        self.Vs = None
-        self.pois = D
-        self.pgauss = 0
+        self.family = ("poisson", (D,))
 
     def set_emission_pgauss(self, mu, hprec, cst, origin=None):
         """Gaussian tracks with missing entries (``svihmm_set_emission_pgauss``): ``mu[k, d]``,
@@ -595,12 +590,7 @@ class HipEngine(object):
             raise RuntimeError("set_emission_pgauss: origin must have one entry per column")
         L.check(self._lib.svihmm_set_emission_pgauss(self._h, K, D, L.dptr(mu), L.dptr(hprec), L.dptr(cst),
                                                      L.dptr(origin)), "svihmm_set_emission_pgauss")
-        self.V = 0
-        self.diag = False
-        self.Vs = None
-        self.pois = 0
-        self.pgauss = D
-        self._pg_origin = origin
+        self.family = ("pgauss", (D, origin))
 
     def pred_logprob(self, starts, Lm, flags=L.MASK_AS_NAN):
         """Mean predictive log-probability of the masked rows of the windows and their number
@@ -890,13 +880,7 @@ class HipEngine(object):
         L.check(self._lib.svihmm_svi_begin(self._h, K, D, L.dptr(prior_tran), L.dptr(var_tran),
                                            *([L.dptr(a) for a in arrs] + [int(maxit), float(zsign)])),
                 "svihmm_svi_begin")
-        self.K, self.V = K, 0
-        self.diag = False
-        self.Vs = None
-        self.pois = 0
-        self.pgauss = 0
-        self._svi_shape = (K, D)
-        self._svi_family = "niw"
+        self.K, self.family, self._svi = K, ("niw", ()), ("niw", K, D)
 
     def svi_begin_diag(self, prior_tran, var_tran, prior, factors, maxit):
         """The same loop for ``DiagonalGaussian`` emitters: ``prior`` / ``factors`` as
@@ -910,13 +894,7 @@ class HipEngine(object):
         fb = np.ascontiguousarray(np.stack([L.as_f64(a, (K, D)) for a in factors]))
         L.check(self._lib.svihmm_svi_begin_diag(self._h, K, D, L.dptr(prior_tran), L.dptr(var_tran), L.dptr(pb),
                                                 L.dptr(fb), int(maxit)), "svihmm_svi_begin_diag")
-        self.K, self.V = K, 0
-        self.diag = True
-        self.Vs = None
-        self.pois = 0
-        self.pgauss = 0
-        self._svi_shape = (K, D)
-        self._svi_family = "diag"
+        self.K, self.family, self._svi = K, ("diag", ()), ("diag", K, D)
 
     def svi_begin_cat(self, prior_tran, var_tran, alpha0, alpha, maxit):
         """The same loop for ``Categorical`` emitters over one symbol column: Dirichlet prior and
@@ -929,13 +907,7 @@ class HipEngine(object):
         alpha = L.as_f64(alpha, (K, V))
         L.check(self._lib.svihmm_svi_begin_cat(self._h, K, V, L.dptr(prior_tran), L.dptr(var_tran), L.dptr(alpha0),
                                                L.dptr(alpha), int(maxit)), "svihmm_svi_begin_cat")
-        self.K, self.V = K, V
-        self.diag = False
-        self.Vs = None
-        self.pois = 0
-        self.pgauss = 0
-        self._svi_shape = (K, V)
-        self._svi_family = "cat"
+        self.K, self.family, self._svi = K, ("cat", (V,)), ("cat", K, V)
 
     def svi_begin_mcat(self, prior_tran, var_tran, alpha0_cols, alpha_cols, maxit):
         """The same loop for ``ProductCategorical`` emitters over D symbol columns: Dirichlet priors and
@@ -956,13 +928,8 @@ class HipEngine(object):
         L.check(self._lib.svihmm_svi_begin_mcat(self._h, K, len(a0), Vs.ctypes.data_as(C.POINTER(C.c_int32)),
                                                 L.dptr(prior_tran), L.dptr(var_tran), L.dptr(p0), L.dptr(p1),
                                                 int(maxit)), "svihmm_svi_begin_mcat")
-        self.K, self.V = K, 0
-        self.diag = False
-        self.Vs = tuple(int(v) for v in Vs)
-        self.pois = 0
-        self.pgauss = 0
-        self._svi_shape = (K, self.Vs)
-        self._svi_family = "mcat"
+        Vs = tuple(int(v) for v in Vs)
+        self.K, self.family, self._svi = K, ("mcat", (Vs,)), ("mcat", K, Vs)
 
     def svi_begin_poisson(self, prior_tran, var_tran, prior, factors, max_count, maxit):
         """The same loop for ``ProductPoisson`` emitters over D count columns: Gamma ``prior = (a0, b0)`` and
@@ -986,43 +953,18 @@ class HipEngine(object):
         L.check(self._lib.svihmm_svi_begin_poisson(self._h, K, D, L.dptr(prior_tran), L.dptr(var_tran), L.dptr(pb),
                                                    L.dptr(fb), L.dptr(logfact), C_, int(maxit)),
                 "svihmm_svi_begin_poisson")
-        self.K, self.V = K, 0
-        self.diag = False
-        self.Vs = None
-        self.pois = D
-        self.pgauss = 0
-        self._svi_shape = (K, D)
-        self._svi_family = "poisson"
+        self.K, self.family, self._svi = K, ("poisson", (D,)), ("poisson", K, D)
 
     def svi_read_factors(self):
         """(var_tran, var_init, factors) with ``factors`` in the loop's family layout: NIW
         (mu, sigma, kappa, nu), diagonal (mu, nus, alphas, betas), Categorical alpha [K, V],
         multi-column Categorical the list of D arrays alpha_d [K, V_d], Poisson (a, b), each [K, D]."""
-        K, W = self._svi_shape
-        fam = getattr(self, "_svi_family", "niw")
-        if fam == "mcat":
-            n = K * sum(W)
-        elif fam == "poisson":
-            n = 2 * K * W
-        else:
-            n = {"niw": K * W + K * W * W + 2 * K, "diag": 4 * K * W, "cat": K * W}[fam]
-        vt, vi, blk = np.empty((K, K)), np.empty(K), np.empty(n)
+        name, K, W = self._svi
+        fam = FAMILY_STATS[name]
+        vt, vi, blk = np.empty((K, K)), np.empty(K), np.empty(fam.block(K, W))
         L.check(self._lib.svihmm_svi_read_factors(self._h, L.dptr(vt), L.dptr(vi), L.dptr(blk)),
                 "svihmm_svi_read_factors")
-        if fam == "diag":
-            fac = tuple(blk.reshape(4, K, W))
-        elif fam == "mcat":
-            off = np.concatenate(([0], np.cumsum(W))).astype(int)
-            flat = blk.reshape(K, sum(W))
-            fac = [np.ascontiguousarray(flat[:, off[d]:off[d + 1]]) for d in range(len(W))]
-        elif fam == "poisson":
-            fac = tuple(blk.reshape(2, K, W))
-        elif fam == "cat":
-            fac = blk.reshape(K, W)
-        else:
-            o1, o2 = K * W, K * W + K * W * W
-            fac = (blk[:o1].reshape(K, W), blk[o1:o2].reshape(K, W, W), blk[o2:o2 + K], blk[o2 + K:])
-        return vt, vi, fac
+        return vt, vi, fam.split(blk, K, W)
 
     def svi_iteration(self, it, starts, nwin_total, Lm, flags, rho, bfactA, bfactE, inner=None):
         """Enqueue iteration ``it`` on the windows ``starts`` (asynchronous)."""
@@ -1040,8 +982,7 @@ class HipEngine(object):
         (``svihmm_svi_sequences``); ``prior_init`` / ``var_init`` [K], the learned initial-state factor, join the
         resident state."""
         self._pre_mutate()
-        shape = getattr(self, "_svi_shape", None)      # (no loop begun through this object: the library says so)
-        K = shape[0] if shape else np.asarray(var_init).shape[0]
+        K = self._svi[1] if self._svi else np.asarray(var_init).shape[0]   # (no loop begun through this object: the library says so)
         p, v = L.as_f64(prior_init, (K,)), L.as_f64(var_init, (K,))
         L.check(self._lib.svihmm_svi_sequences(self._h, L.dptr(p), L.dptr(v)), "svihmm_svi_sequences")
 
@@ -1087,7 +1028,7 @@ class HipEngine(object):
 
     def svi_read_state(self):
         """Current (var_tran, var_init, mu, sigma, kappa, nu); waits for the device."""
-        K, D = self._svi_shape
+        _, K, D = self._svi
         if isinstance(D, tuple):                # (multi-column Categorical: the library refuses, NIW layout)
             D = len(D)
         out = [np.empty((K, K)), np.empty(K), np.empty((K, D)), np.empty((K, D, D)), np.empty(K), np.empty(K)]

@@ -18,6 +18,7 @@ no CPU fallback: constructing it without the built library / a GPU raises.
 from __future__ import division
 
 import abc
+import collections
 from copy import deepcopy
 
 import numpy as np
@@ -28,7 +29,8 @@ from scipy.special import digamma, gammaln
 
 from . import util
 from . import _lib as L
-from .distributions import Gaussian
+from .distributions import (Categorical, DiagonalGaussian, Gaussian, ProductCategorical, ProductGaussian, ProductPoisson,
+                            niw_prior_logpart, vlb_logz_sign)
 from .engine import rewrap_packed
 
 # This is for taking logs of things so we don't get -inf (reference hmmbase.py:30)
@@ -52,7 +54,6 @@ def is_niw_gaussian(e):
 def is_diag_gaussian(e):
     """Diagonal-covariance family (``distributions.DiagonalGaussian`` and subclasses that keep
     its ``expected_log_likelihood``): the device runs it on 2 D + 1 features per row."""
-    from .distributions import DiagonalGaussian
     t = type(e)
     return (isinstance(e, DiagonalGaussian)
             and t.expected_log_likelihood is DiagonalGaussian.expected_log_likelihood)
@@ -94,6 +95,113 @@ def dirichlet_elbo(prior, var):
     energy = lognorm(prior) + ((prior - 1.) * elog).sum(axis=1)
     entropy = -(lognorm(var) + ((var - 1.) * elog).sum(axis=1))
     return float(energy.sum() + entropy.sum())
+
+
+# ---- the emission families the device evaluates itself: one ordered table ------------------------------------------
+# A record per family, in the order the predicates are asked (``VariationalHMMBase._family``):
+#   name        the family's name, also its key in ``engine.FAMILY_STATS``
+#   pred        name of the model's predicate method (subclasses override these, so they are looked up by name)
+#   push        push(model, engine): upload the emitters' factors / tables through the engine's ``set_emission_*``
+#   emitter     the class whose ``get_vlb`` the resident SVI loop's ELBO kernels restate (None: no resident loop)
+#   svi_method  name of the engine's ``svi_begin*`` (None: no resident loop)
+#   svi_args    svi_args(model, maxit): that call's arguments after (prior_tran, var_tran)
+#   svi_pull    svi_pull(model): the loop's resident state -> the object's attributes (reference attribute names)
+#   heldout     "rows": only whole rows can be held out; "entries": single entries too (heldout_entries_logprob)
+#   by_type     by_type(model): the emitters are the family's as far as their types say (no engine is touched)
+Family = collections.namedtuple("Family", "name pred push emitter svi_method svi_args svi_pull heldout by_type")
+
+
+def _stack(ve, *names):
+    return tuple(np.array([getattr(g, n) for g in ve], dtype=np.float64) for n in names)
+
+
+def _all_exactly(cls):
+    return lambda m: len(m.var_emit) > 0 and all(type(e) is cls for e in m.var_emit)
+
+
+def _push_cat(m, eng):
+    # Categorical: E log theta table (pybasicbayes Categorical.expected_log_likelihood), looked up on the device
+    eng.set_emission_cat(np.stack([digamma(e.alpha_mf) - digamma(np.sum(e.alpha_mf)) for e in m.var_emit]))
+
+
+def _push_mcat(m, eng):
+    # D symbol columns: one E log theta table [K, V_d] per column, looked up and added on the device
+    per_state = [e.expected_log_tables() for e in m.var_emit]
+    eng.set_emission_mcat([np.stack([t[d] for t in per_state]) for d in range(len(per_state[0]))])
+
+
+def _push_poisson(m, eng):
+    # D count columns: (E log lambda, E lambda) per state and column, multiplied and added on the device
+    tabs = [e.expected_tables() for e in m.var_emit]
+    eng.set_emission_poisson(np.stack([t[0] for t in tabs]), np.stack([t[1] for t in tabs]), m.var_emit[0].max_count)
+
+
+def _push_pgauss(m, eng):
+    # D real-valued columns with missing entries: (mu, hprec, cst) per state and column; the squared residual of
+    # each present entry is formed on the device
+    tabs = [e.expected_tables() for e in m.var_emit]
+    eng.set_emission_pgauss(*[np.stack([t[i] for t in tabs]) for i in range(3)], origin=m._pgauss_origin())
+
+
+def _svi_args_niw(m, maxit):
+    prior = m._prior_arrays()
+    return prior, m._emission_arrays(), niw_prior_logpart(prior[1], prior[3]), maxit, vlb_logz_sign()
+
+
+def _svi_args_mcat(m, maxit):
+    ve = m.var_emit
+    stack = lambda name: [np.array([getattr(g, name)[d] for g in ve], dtype=np.float64) for d in range(ve[0].D)]
+    return stack("alphav_0"), stack("alpha_mf"), maxit
+
+
+def _svi_pull_niw(m):
+    vt, vi, mu, sg, ka, nu = m.engine.svi_read_state()
+    m.var_tran, m.var_init = vt, vi
+    D = m.D
+    for k, G in enumerate(m.var_emit):
+        G.mu_mf = mu[k]; G.sigma_mf = sg[k]
+        G.kappa_mf = ka[k]; G.nu_mf = nu[k]
+        G.mu = G.mu_mf
+        G.sigma = G.sigma_mf / (G.nu_mf - D - 1)
+
+
+def _svi_pull_factors(set_emitter):
+    def pull(m):
+        m.var_tran, m.var_init, fac = m.engine.svi_read_factors()
+        for k, G in enumerate(m.var_emit):
+            set_emitter(G, k, fac)
+    return pull
+
+
+def _set_cat(G, k, fac):
+    G._alpha_mf = fac[k].copy()
+    G.weights = G._alpha_mf / G._alpha_mf.sum()
+
+
+_svi_pull_mf = _svi_pull_factors(lambda G, k, fac: G._set_mf(*[a[k].copy() for a in fac]))
+
+FAMILIES = (
+    Family("niw", "_niw_fastpath", lambda m, eng: eng.set_emission_niw(*m._emission_arrays()), Gaussian,
+           "svi_begin", _svi_args_niw, _svi_pull_niw, "rows", lambda m: m._niw_fastpath()),
+    # diagonal family: the K x D normal-inverse-gamma factors; lliks on 2 D + 1 features
+    Family("diag", "_diag_fastpath", lambda m, eng: eng.set_emission_diag(*m._diag_arrays()), DiagonalGaussian,
+           "svi_begin_diag",
+           lambda m, maxit: (_stack(m.var_emit, "mu_0", "nus_0", "alphas_0", "betas_0"), m._diag_arrays(), maxit),
+           _svi_pull_mf, "rows", lambda m: len(m.var_emit) > 0 and all(is_diag_gaussian(e) for e in m.var_emit)),
+    Family("cat", "_cat_fastpath", _push_cat, Categorical, "svi_begin_cat",
+           lambda m, maxit: _stack(m.var_emit, "alphav_0", "alpha_mf") + (maxit,),
+           _svi_pull_factors(_set_cat), "rows", lambda m: m._cat_fastpath()),
+    Family("mcat", "_mcat_fastpath", _push_mcat, ProductCategorical, "svi_begin_mcat", _svi_args_mcat,
+           _svi_pull_factors(lambda G, k, fac: G._set_alpha([c[k] for c in fac])), "entries",
+           _all_exactly(ProductCategorical)),
+    Family("poisson", "_poisson_fastpath", _push_poisson, ProductPoisson, "svi_begin_poisson",
+           lambda m, maxit: (_stack(m.var_emit, "alpha_0", "beta_0"), _stack(m.var_emit, "alpha_mf", "beta_mf"),
+                             m.var_emit[0].max_count, maxit),
+           _svi_pull_mf, "entries", _all_exactly(ProductPoisson)),
+    Family("pgauss", "_pgauss_fastpath", _push_pgauss, None, None, None, None, "entries",
+           _all_exactly(ProductGaussian)),
+)
+FAMILY = {f.name: f for f in FAMILIES}
 
 
 class VariationalHMMBase(object, metaclass=abc.ABCMeta):
@@ -422,91 +530,37 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
             self._pg_origin_obs = self.obs
         return self._pg_origin
 
+    def _family(self, among=FAMILIES):
+        """The first record of ``among`` (hmmbase.FAMILIES, in its order) whose predicate holds for this model, or None:
+        the predicates after it are not asked."""
+        return next((f for f in among if getattr(self, f.pred)()), None)
+
     def _device_family(self):
         """Whether the device evaluates the emitters' family itself (no host lliks)."""
-        return (self._niw_fastpath() or self._diag_fastpath() or self._cat_fastpath()
-                or self._mcat_fastpath() or self._poisson_fastpath() or self._pgauss_fastpath())
+        return self._family() is not None
 
     # -- the device-resident SVI loop: what its class surfaces share -------------------------
     # (hmmsgd_metaobs.VBHMM on windows of one chain, hmmbatchsgd.VBHMM(seq_minibatch=M) on whole sequences)
-    _SVI_BEGIN = {"niw": "svi_begin", "diag": "svi_begin_diag", "cat": "svi_begin_cat", "mcat": "svi_begin_mcat",
-                  "poisson": "svi_begin_poisson"}
-
     def _svi_family(self):
         """Emission family the device-resident loop runs for this model (None: host loop)."""
-        if self._niw_fastpath():
-            return "niw"
-        if self._diag_fastpath():
-            return "diag"
-        if self._cat_fastpath():
-            return "cat"
-        if self._mcat_fastpath():
-            return "mcat"
-        if self._poisson_fastpath():
-            return "poisson"
-        return None
+        f = self._family([f for f in FAMILIES if f.svi_method])
+        return f and f.name
 
     def _svi_plain_vlb(self, fam):
         """The emitters' ``get_vlb`` is the family's own (the loop's ELBO kernels restate it)."""
-        from .distributions import Categorical, DiagonalGaussian, ProductCategorical, ProductPoisson
-        cls = {"niw": Gaussian, "diag": DiagonalGaussian, "cat": Categorical, "mcat": ProductCategorical,
-               "poisson": ProductPoisson}[fam]
-        return all(type(e).get_vlb is cls.get_vlb for e in self.var_emit)
+        return all(type(e).get_vlb is FAMILY[fam].emitter.get_vlb for e in self.var_emit)
 
     def _svi_begin(self, fam, maxit):
         """Upload the transition factor and the family's prior / factors: the engine's ``svi_begin*``."""
-        from .distributions import niw_prior_logpart, vlb_logz_sign
-        eng = self.engine
-        if fam == "niw":
-            prior = self._prior_arrays()
-            fac = self._emission_arrays()
-            eng.svi_begin(self.prior_tran, self.var_tran, prior, fac,
-                          niw_prior_logpart(prior[1], prior[3]), maxit, vlb_logz_sign())
-        elif fam == "diag":
-            ve = self.var_emit
-            prior = tuple(np.array([getattr(g, n) for g in ve], dtype=np.float64)
-                          for n in ("mu_0", "nus_0", "alphas_0", "betas_0"))
-            eng.svi_begin_diag(self.prior_tran, self.var_tran, prior, self._diag_arrays(), maxit)
-        elif fam == "mcat":
-            ve = self.var_emit
-            stack = lambda name: [np.array([getattr(g, name)[d] for g in ve], dtype=np.float64)
-                                  for d in range(ve[0].D)]
-            eng.svi_begin_mcat(self.prior_tran, self.var_tran, stack("alphav_0"), stack("alpha_mf"), maxit)
-        elif fam == "poisson":
-            ve = self.var_emit
-            stack = lambda *names: tuple(np.array([getattr(g, n) for g in ve], dtype=np.float64) for n in names)
-            eng.svi_begin_poisson(self.prior_tran, self.var_tran, stack("alpha_0", "beta_0"),
-                                  stack("alpha_mf", "beta_mf"), ve[0].max_count, maxit)
-        else:
-            ve = self.var_emit
-            eng.svi_begin_cat(self.prior_tran, self.var_tran, np.array([g.alphav_0 for g in ve], dtype=np.float64),
-                              np.array([g.alpha_mf for g in ve], dtype=np.float64), maxit)
+        f = FAMILY[fam]
+        getattr(self.engine, f.svi_method)(self.prior_tran, self.var_tran, *f.svi_args(self, maxit))
 
     def _svi_pull_state(self):
         """Device state -> the object's attributes (reference attribute names)."""
         fam = self._svi_family()
         if getattr(self, "adagrad", False):
             self.ada_G = self.engine.svi_read_adagrad()
-        if fam != "niw":
-            vt, vi, fac = self.engine.svi_read_factors()
-            self.var_tran, self.var_init = vt, vi
-            for k, G in enumerate(self.var_emit):
-                if fam in ("diag", "poisson"):
-                    G._set_mf(*[a[k].copy() for a in fac])
-                elif fam == "mcat":
-                    G._set_alpha([c[k] for c in fac])
-                else:
-                    G._alpha_mf = fac[k].copy()
-                    G.weights = G._alpha_mf / G._alpha_mf.sum()
-            return
-        vt, vi, mu, sg, ka, nu = self.engine.svi_read_state()
-        self.var_tran, self.var_init = vt, vi
-        D = self.D
-        for k, G in enumerate(self.var_emit):
-            G.mu_mf = mu[k]; G.sigma_mf = sg[k]
-            G.kappa_mf = ka[k]; G.nu_mf = nu[k]
-            G.mu = G.mu_mf
-            G.sigma = G.sigma_mf / (G.nu_mf - D - 1)
+        FAMILY[fam].svi_pull(self)
 
     def _prior_arrays(self):
         """Stacked NIW prior hyperparameters (mu_0 [K,D], sigma_0 [K,D,D], kappa_0 [K], nu_0 [K]).
@@ -557,37 +611,9 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         emission kernel.  Any other plugin object: evaluate
         ``expected_log_likelihood`` on the host (reference hmmbase.py:219-220) and
         upload ``lliks``.  Returns the flag word for the engine calls."""
-        if self._niw_fastpath():
-            mu, sg, ka, nu = self._emission_arrays()
-            self.engine.set_emission_niw(mu, sg, ka, nu)
-            return L.MASK_AS_NAN if nan_mask else 0
-        if self._diag_fastpath():
-            # diagonal family: the K x D normal-inverse-gamma factors; lliks on 2 D + 1 features
-            self.engine.set_emission_diag(*self._diag_arrays())
-            return L.MASK_AS_NAN if nan_mask else 0
-        if self._cat_fastpath():
-            # Categorical: E log theta table (pybasicbayes Categorical.expected_log_likelihood),
-            # looked up on the device
-            table = np.stack([digamma(e.alpha_mf) - digamma(np.sum(e.alpha_mf)) for e in self.var_emit])
-            self.engine.set_emission_cat(table)
-            return L.MASK_AS_NAN if nan_mask else 0
-        if self._mcat_fastpath():
-            # D symbol columns: one E log theta table [K, V_d] per column, looked up and added on the device
-            per_state = [e.expected_log_tables() for e in self.var_emit]
-            self.engine.set_emission_mcat([np.stack([t[d] for t in per_state]) for d in range(len(per_state[0]))])
-            return L.MASK_AS_NAN if nan_mask else 0
-        if self._poisson_fastpath():
-            # D count columns: (E log lambda, E lambda) per state and column, multiplied and added on the device
-            tabs = [e.expected_tables() for e in self.var_emit]
-            self.engine.set_emission_poisson(np.stack([t[0] for t in tabs]), np.stack([t[1] for t in tabs]),
-                                             self.var_emit[0].max_count)
-            return L.MASK_AS_NAN if nan_mask else 0
-        if self._pgauss_fastpath():
-            # D real-valued columns with missing entries: (mu, hprec, cst) per state and column; the squared
-            # residual of each present entry is formed on the device
-            tabs = [e.expected_tables() for e in self.var_emit]
-            self.engine.set_emission_pgauss(*[np.stack([t[i] for t in tabs]) for i in range(3)],
-                                            origin=self._pgauss_origin())
+        f = self._family()
+        if f is not None:
+            f.push(self, self.engine)
             return L.MASK_AS_NAN if nan_mask else 0
         obs = self.obs if self.obs.ndim == 2 else self.obs[:, None]
         if windows is None:
@@ -715,9 +741,7 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
             return False
         if not hasattr(self.engine, "suffstats"):
             return False
-        fam = {"niw": self._niw_fastpath, "diag": self._diag_fastpath, "cat": self._cat_fastpath,
-               "mcat": self._mcat_fastpath, "poisson": self._poisson_fastpath, "pgauss": self._pgauss_fastpath}
-        return any(fam[f]() for f in families)
+        return self._family([FAMILY[f] for f in families]) is not None
 
     def _batch_suffstats(self):
         """Statistics of the host posteriors ``self.var_x`` (whatever ``local_update`` left there)
@@ -786,21 +810,7 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
     def _heldout_family(self):
         """Emission family of the emitters as far as their types say (no engine is touched):
         "niw", "diag", "cat", "mcat", "poisson", "pgauss" or None."""
-        from .distributions import ProductCategorical, ProductPoisson, ProductGaussian
-        ve = self.var_emit
-        if len(ve) and all(type(e) is ProductGaussian for e in ve):
-            return "pgauss"
-        if len(ve) and all(type(e) is ProductPoisson for e in ve):
-            return "poisson"
-        if len(ve) and all(type(e) is ProductCategorical for e in ve):
-            return "mcat"
-        if self._niw_fastpath():
-            return "niw"
-        if len(ve) and all(is_diag_gaussian(e) for e in ve):
-            return "diag"
-        if self._cat_fastpath():
-            return "cat"
-        return None
+        return next((f.name for f in FAMILIES if f.by_type(self)), None)
 
     def _heldout_estep(self, what):
         """The full E-step the held-out scores are taken against: the class's own ``_full_estep_device``
@@ -856,7 +866,8 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         with ``per_entry`` ``(mean, lp[n])`` (NaN for the skipped ones).  ``ValueError`` unless every
         ``obs[rows, cols]`` is NaN; ``NotImplementedError`` for other emitters (a NaN entry of a ``Gaussian`` or
         ``DiagonalGaussian`` row blanks the whole row).  No attribute of the model changes."""
-        if self._heldout_family() not in ("mcat", "poisson", "pgauss"):
+        f = FAMILY.get(self._heldout_family())
+        if f is None or f.heldout != "entries":
             raise NotImplementedError("heldout_entries_logprob: entry-wise scores need ProductGaussian, "
                                       "ProductCategorical or ProductPoisson emitters (columns independent given the state); other "
                                       "families have no per-entry missingness")

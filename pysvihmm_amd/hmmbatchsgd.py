@@ -10,7 +10,7 @@ import time
 
 import numpy as np
 
-from .hmmbase import VariationalHMMBase, is_niw_gaussian, is_diag_gaussian
+from .hmmbase import FAMILY, VariationalHMMBase, is_niw_gaussian, is_diag_gaussian
 from .distributions import ProductCategorical, ProductPoisson, ProductGaussian
 from .engine import rewrap_packed
 from . import util
@@ -103,7 +103,7 @@ class VBHMM(VariationalHMMBase):
             return ("the resident loop does not take ProductGaussian emitters (svihmm_set_emission_pgauss has no "
                     "svi_begin of its own): the sequence minibatches step on the host route")
         fam = self._svi_family()
-        if fam is None or not hasattr(eng, self._SVI_BEGIN[fam]):
+        if fam is None or not hasattr(eng, FAMILY[fam].svi_method):
             return "the emitters are none of the resident loop's families on this engine"
         if not self._svi_plain_vlb(fam):
             return "an emitter overrides get_vlb"

@@ -27,7 +27,7 @@ import numpy.random as npr
 from numpy import newaxis as npa
 from scipy.special import digamma
 
-from .hmmbase import VariationalHMMBase, is_niw_gaussian, is_diag_gaussian, dirichlet_elbo
+from .hmmbase import FAMILY, VariationalHMMBase, is_niw_gaussian, is_diag_gaussian, dirichlet_elbo
 from .distributions import Gaussian, Categorical, DiagonalGaussian, ProductCategorical, ProductPoisson
 from . import util
 from . import _lib as L
@@ -397,7 +397,7 @@ class VBHMM(VariationalHMMBase):
     def _svi_device_ok(self):
         eng = self.engine
         fam = self._svi_family()
-        if fam is None or not hasattr(eng, self._SVI_BEGIN[fam]):
+        if fam is None or not hasattr(eng, FAMILY[fam].svi_method):
             return False
         if self.adagrad and not hasattr(eng, "svi_set_adagrad"):
             return False
