@@ -359,6 +359,39 @@ int svihmm_estep_sequences(svihmm_ctx* h, uint32_t flags, double* out_packed, do
 int svihmm_estep_sequence_subset(svihmm_ctx* h, const int32_t* idx, int32_t M, uint32_t flags,
                                  double* out_packed, double* out_seq_lb, double* out_q0);
 
+/* svihmm_set_labels: partially labelled rows -- the states of some resident rows are known (annotated regions,
+ *   behavioural epochs, trials whose condition fixes the state) and every E-step and decoder honours them.
+ *   labels: host int32 [T].  labels[t] = -1: row t is free; labels[t] = k >= 0: row t is known to be in state k.
+ *   NULL removes the labels.  svihmm_set_obs, svihmm_alloc_obs and svihmm_generate remove them as well (T changes);
+ *   svihmm_set_obs_rows and svihmm_set_sequences keep them.
+ *   Fails with a message, an earlier set staying in force: no observations; an entry below -1 (the message gives the
+ *   row and the value).
+ *   The labels live in HBM as int32 [T]; the host keeps the largest label and its first row only.
+ *   While labels are in force every call that evaluates lliks on the device sees
+ *       ll[t][k] = (labels[t] < 0 || k == labels[t]) ? ll[t][k] : -inf,
+ *   a select applied after the family's llik.  SVIHMM_MASK_AS_NAN is applied first, so the kept entry has its original
+ *   bits; a masked labelled row means "state known, observation missing": its ll is 0 at the label and -inf elsewhere,
+ *   and it stays out of the emission statistics as before.
+ *   Such a call is defined to give what the same call gives under SVIHMM_USE_HOST_LLIKS on exactly those clamped
+ *   lliks, wherever that call exists: svihmm_loglik, svihmm_read_intermediate / _read_rows with what = 0 and lalpha /
+ *   lbeta hand out the -inf values, var_x is 0.0 at forbidden pairs, lb keeps its formula (quirk Q4) on the clamped
+ *   lliks.
+ *   Honoured by: svihmm_loglik, _forward_backward, _estep_minibatch(_ex), _viterbi, _ffbs_windows, _ffbs,
+ *   _estep_sequences, _estep_sequence_subset (the listed sequences' labels are gathered with their rows),
+ *   _viterbi_sequences, _ffbs_sequences.
+ *   Unaffected: svihmm_suffstats (the caller's posteriors), svihmm_state_argmax, export / import / all-reduce, and
+ *   svihmm_heldout_rows / _entries -- their emission term is the family's own llik, unclamped; the posterior rows
+ *   they read already carry the labels.  Calls on host lliks (SVIHMM_USE_HOST_LLIKS) take the lliks as uploaded.
+ *   Refused with a message before any device work while labels are set (the handle and a running resident loop stay
+ *   intact): svihmm_svi_iteration, svihmm_svi_iteration_sequences, svihmm_grow_windows, svihmm_pred_logprob; and an
+ *   E-step-type call whose globals have K at or below the largest label (the message gives that label, its row and
+ *   K).
+ *   A label whose state has probability zero under mod_init, ltran and the row's llik leaves that window's results
+ *   unspecified (-inf or NaN, never a fault).
+ *   fp32 mode: a labelled batch runs in fp64 and svihmm_get_precision reports last_batch_f32 = 0; the mode itself
+ *   is left as set.  With no labels set nothing changes: the same kernels are chosen and the same bits result. */
+int svihmm_set_labels(svihmm_ctx* h, const int32_t* labels);
+
 /* svihmm_viterbi_sequences: the MAP state path of EVERY declared sequence (svihmm_set_sequences) in one call, under
  *   the globals currently set and the current emission family.
  *   out_z: host int32[T], row r holds the state of resident row r (the sequences laid end to end, as declared);

@@ -208,6 +208,12 @@ struct svihmm_ctx {
   // seq_off_d for its duration (SubsetView).  seq_subset: seq_result describes such a call (var_x of its R rows)
   Buf sub_obs, sub_mask, sub_tab;
   bool seq_subset = false;
+  // svihmm_set_labels: known states of the resident rows, int32 [T] in HBM (-1: the row is free).  The host keeps the
+  // largest label and its first row only (what an E-step-type call with too small a K says).  sub_labels: the listed
+  // sequences' labels in the compact copy's order, swapped in with sub_obs / sub_mask (SubsetView)
+  Buf labels, sub_labels;
+  bool have_labels = false;
+  int32_t label_max = -1; int64_t label_max_row = -1;
   // svihmm_viterbi_sequences / svihmm_ffbs_sequences: the launch tables (sequence orders, pad_off, chunk table) on the
   // device and their host image (alive until the call's final synchronisation); dec_result: the intermediates held are
   // such a call's -- the lliks of all T rows only (1: _viterbi_sequences, 2: _ffbs_sequences; prepare_ll drops it)
@@ -434,7 +440,8 @@ int ensure_q(svihmm_ctx* h, int B, int Lm, hipStream_t stream);
 int ensure_stats(svihmm_ctx* h, int64_t nchunk_total);
 int flush_lb(svihmm_ctx* h, hipStream_t stream);
 int launch_diag_to_theta(svihmm_ctx* h, int K, int D);
-int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled = false, const int64_t* starts_dev = nullptr, double* out = nullptr, double* kexp_out = nullptr, hipStream_t stream = nullptr, size_t min_lds = 0, double* ll0_out = nullptr);
+int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled = false, const int64_t* starts_dev = nullptr, double* out = nullptr, double* kexp_out = nullptr, hipStream_t stream = nullptr, size_t min_lds = 0, double* ll0_out = nullptr, bool clamp_labels = true);
+int check_labels_fit(const svihmm_ctx* h);
 int launch_fb(svihmm_ctx* h, int B, int Lm, int dir0, int ndir, const double* ll = nullptr, double* la = nullptr, double* lb = nullptr);
 int launch_fb_fused(svihmm_ctx* h, int B, int Lm, bool want_lb, bool total);
 bool emission_row_tile_orbit(const svihmm_ctx* h, int64_t n);
@@ -491,7 +498,8 @@ int launch_fb_sequences(svihmm_ctx* h, int nseq, const int32_t* order, const int
                         int64_t span, int maxlen, const double* ll, double* q, double* seq_lb);
 int launch_seq_finish(svihmm_ctx* h, int N, const int64_t* seq_off, bool wrap, const double* q, const double* seq_lb,
                       double* q0);
-int launch_seq_gather(svihmm_ctx* h, int M, const int64_t* tab, int maxlen, double* obs_out, uint8_t* mask_out);
+int launch_seq_gather(svihmm_ctx* h, int M, const int64_t* tab, int maxlen, double* obs_out, uint8_t* mask_out,
+                      int32_t* labels_out);
 int64_t viterbi_sequences_chunks(const svihmm_ctx* h);
 int launch_viterbi_sequences(svihmm_ctx* h, const double* ll, bool want_z, int32_t** dz_out, double** dscore_out);
 int launch_ffbs_sequences(svihmm_ctx* h, uint32_t flags, const double* logA, int S, const double* uniforms, uint64_t seed,

@@ -86,7 +86,7 @@ int svihmm_destroy(svihmm_ctx* h) {
                  &h->pipe_tabs[0].buf, &h->pipe_tabs[1].buf, &h->pipe_tabs[2].buf, &h->pipe_tabs[3].buf,
                  &h->pipe_tabs[4].buf, &h->pipe_tabs[5].buf, &h->pipe_tabs[6].buf, &h->pipe_tabs[7].buf,
                  &h->seq_off_d, &h->seq_q, &h->seq_work, &h->seq_ord, &h->seq_out, &h->dec_tab,
-                 &h->sub_obs, &h->sub_mask, &h->sub_tab, &h->heldout};
+                 &h->sub_obs, &h->sub_mask, &h->sub_tab, &h->heldout, &h->labels, &h->sub_labels};
   for (Buf* b : bufs) release(*b);
   if (h->vlb_host) { hipHostFree(h->vlb_host); h->vlb_host = nullptr; }
   if (h->svi_elbo) { hipHostFree(h->svi_elbo); h->svi_elbo = nullptr; }
@@ -125,6 +125,7 @@ static int store_shift(svihmm_ctx* h, const std::vector<double>& c);
 static int params_follow_centre(svihmm_ctx* h, const double* delta);
 static int drop_auto_status(svihmm_ctx* h);
 static int d2h_sync_small(svihmm_ctx* h, void* dst, const void* src, size_t bytes);
+static int upload_staged(svihmm_ctx* h, void* dst, const void* src, size_t bytes);
 int svihmm_set_precision(svihmm_ctx* h, int32_t mode) {
   if (!h || (mode != SVIHMM_F64 && mode != SVIHMM_F32)) return fail("svihmm_set_precision: mode must be SVIHMM_F64 or SVIHMM_F32");
   h->prec = mode;
@@ -178,6 +179,7 @@ int svihmm_set_obs(svihmm_ctx* h, const double* obs, int64_t T, int32_t D,
     HIPCK(hipMemcpyAsync(h->mask.p, mask, (size_t)T, hipMemcpyHostToDevice, h->stream));
   }
   h->T = T; h->D = D; h->gen_T = 0;
+  h->have_labels = false;              // (labels described the previous rows)
   h->post_kind = 0;                    // (a held posterior batch described the previous rows)
   h->seq_off.clear();                  // (a declaration of sequences described the previous rows)
   h->svi_active = false;               // a resident SVI state belonged to the previous sequence
@@ -360,6 +362,7 @@ int svihmm_alloc_obs(svihmm_ctx* h, int64_t T, int32_t D, int32_t with_mask) {
     HIPCK(hipMemsetAsync(h->mask.p, 0, (size_t)T, h->stream));
   }
   h->T = T; h->D = D; h->gen_T = 0;
+  h->have_labels = false;
   h->post_kind = 0;
   h->seq_off.clear();
   h->svi_active = false;
@@ -388,6 +391,32 @@ int svihmm_set_obs_rows(svihmm_ctx* h, int64_t row0, int64_t nrows, const double
   }
   CK(shift_rows(h, h->shift.data(), row0, nrows, 0));
   HIPCK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// Known states of the resident rows (include/svihmm.h).  Everything that can be wrong is found before the upload, so
+// a refused call leaves the labels in force as they were.
+int svihmm_set_labels(svihmm_ctx* h, const int32_t* labels) {
+  const char* fn = "svihmm_set_labels";
+  const auto bad = [fn](const std::string& what) { return fail(std::string(fn) + ": " + what); };
+  if (!h) return bad("NULL handle");
+  if (!labels) { h->have_labels = false; h->lin_stale = true; return 0; }
+  if (h->T <= 0 || !h->obs.p) return bad("no observations: call svihmm_set_obs first");
+  int32_t mx = -1;
+  int64_t mx_row = -1;
+  for (int64_t t = 0; t < h->T; ++t) {
+    if (labels[t] < -1)
+      return bad("labels[" + std::to_string(t) + "] = " + std::to_string(labels[t]) +
+                 " (-1 means free, a state index means known)");
+    if (labels[t] > mx) { mx = labels[t]; mx_row = t; }
+  }
+  CK(set_device(h));
+  CK(ensure(h->labels, (size_t)h->T * sizeof(int32_t)));
+  CK(upload_staged(h, h->labels.p, labels, (size_t)h->T * sizeof(int32_t)));
+  HIPCK(hipStreamSynchronize(h->stream));
+  h->have_labels = true;
+  h->label_max = mx; h->label_max_row = mx_row;
+  h->lin_stale = true;                 // (lliks held were evaluated under the previous labels)
   return 0;
 }
 
@@ -1161,6 +1190,7 @@ int prepare_ll(svihmm_ctx* h, const int64_t* starts, int B, int Lm, uint32_t fla
                       bool need_obs_for_stats, bool lin) {
   if (!h->have_globals) return fail("no globals: call svihmm_set_globals");
   const bool host_ll = flags & SVIHMM_USE_HOST_LLIKS;
+  if (!host_ll) CK(check_labels_fit(h));
   CK(check_windows(h, starts, B, Lm, !host_ll || need_obs_for_stats));
   if (starts) CK(upload_starts(h, starts, B));
   h->f32_report_hold = -1;
@@ -1177,11 +1207,14 @@ int prepare_ll(svihmm_ctx* h, const int64_t* starts, int B, int Lm, uint32_t fla
   } else {
     // K <= 64: the emission kernel owns whole rows and writes (Eh, kexp) itself; wider
     // models take the plain kernel plus one scaling pass
-    const bool two_pass = lin && (h->Kp > 64 || fam_table(h->fam));
+    // (a labelled batch -- svihmm_set_labels -- as well: the clamp follows the plain kernel, there is no scaled output
+    //  under labels; such a batch runs in fp64 and in the row-major layout)
+    const bool labelled = h->have_labels;
+    const bool two_pass = lin && (h->Kp > 64 || fam_table(h->fam) || labelled);
     // fp32 mode: scaled messages stored as float + fp32 statistics GEMM, for what the mode
     // covers (NIW emission, K <= 64, window batches on the scaled sweeps; round 5: wide NIW models
     // up to K = 256, D = 64 in large batches, f32_wide_ok); everything else runs as fp64
-    const bool wide32 = two_pass && lin && h->prec == 1 && h->f32_ok && !use_chain(h, B, Lm) &&
+    const bool wide32 = two_pass && !labelled && lin && h->prec == 1 && h->f32_ok && !use_chain(h, B, Lm) &&
                         f32_wide_ok(h, (int64_t)B * Lm);
     h->cur_f32 = lin && h->prec == 1 && h->f32_ok && (!two_pass || wide32) && !use_chain(h, B, Lm);
     h->step_major = !two_pass && !h->cur_f32 && step_major_ok(h, B, Lm, flags, lin);
@@ -1197,7 +1230,7 @@ int prepare_ll(svihmm_ctx* h, const int64_t* starts, int B, int Lm, uint32_t fla
     else if (two_pass) CK(launch_scale_ll(h, B, Lm));
     h->have_host_ll = false;
   }
-  h->eh_in_llE = lin && (host_ll || (h->Kp > 64 && !h->cur_f32) || fam_table(h->fam));
+  h->eh_in_llE = lin && (host_ll || (h->Kp > 64 && !h->cur_f32) || fam_table(h->fam) || h->have_labels);
   h->lin_mode = lin;
   h->lin_stale = false;
   h->q_valid = false;
@@ -1327,7 +1360,7 @@ static int allreduce_packed_dev(svihmm_ctx* h) {
 static bool use_pipeline(const svihmm_ctx* h, int B, int Lm, int fbvar, uint32_t flags) {
   const int v = h->variant[SVIHMM_VAR_PIPELINE];
   if (v == SVIHMM_PIPELINE_UNFUSED || fbvar != SVIHMM_FB_SCALED || (flags & SVIHMM_USE_HOST_LLIKS)) return false;
-  if (h->Kp > 64 || h->D > 64 || fam_table(h->fam)) return false;
+  if (h->Kp > 64 || h->D > 64 || fam_table(h->fam) || h->have_labels) return false;
   const int sv = h->variant[SVIHMM_VAR_STATS];
   if (sv != 0 && sv != SVIHMM_STATS_PIPELINED) return false;
   // opt-in only: on MI355X the sweeps' fp64 VALU work queues behind the GEMMs' MFMAs on a
@@ -1429,6 +1462,9 @@ int svihmm_pred_logprob(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t
                         uint32_t flags, double out2[2]) {
   if (!h || !starts || !out2) return fail("svihmm_pred_logprob: bad arguments");
   if (flags & SVIHMM_USE_HOST_LLIKS) return fail("svihmm_pred_logprob: NIW emission only");
+  if (h->have_labels)
+    return fail("svihmm_pred_logprob: labels are in force (svihmm_set_labels) and this call does not take them; "
+                "svihmm_heldout_rows scores masked rows against a labelled E-step's posteriors");
   if (h->have_emission && FAM_TRAITS[h->fam].noun)
     return fail(std::string("svihmm_pred_logprob: NIW emission only (") + FAM_TRAITS[h->fam].noun + " of " +
                 FAM_TRAITS[h->fam].setter + " is not taken)");
@@ -1444,7 +1480,8 @@ int svihmm_pred_logprob(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t
   const int64_t n = (int64_t)B * Lm;
   CK(ensure(h->m_ll, (size_t)n * K * sizeof(double)));
   h->m_nb = 0;
-  CK(launch_emission(h, B, Lm, flags & ~(uint32_t)SVIHMM_MASK_AS_NAN, false, nullptr, (double*)h->m_ll.p));
+  CK(launch_emission(h, B, Lm, flags & ~(uint32_t)SVIHMM_MASK_AS_NAN, false, nullptr, (double*)h->m_ll.p, nullptr, nullptr,
+                     0, nullptr, false));
   const int nblk = (int)((n + PRED_ROWS_PER_BLOCK - 1) / PRED_ROWS_PER_BLOCK);
   CK(ensure(h->scratch, ((size_t)2 * nblk + 2) * sizeof(double)));
   double* part = (double*)h->scratch.p;
@@ -1771,12 +1808,14 @@ struct SubsetView {
   svihmm_ctx* h; int64_t T; std::vector<int64_t> seq_off;
   SubsetView(svihmm_ctx* h_, int64_t R, std::vector<int64_t>& compact) : h(h_), T(h_->T) {
     std::swap(h->obs, h->sub_obs); std::swap(h->mask, h->sub_mask); std::swap(h->seq_off_d, h->sub_tab);
+    std::swap(h->labels, h->sub_labels);
     seq_off.swap(h->seq_off);
     h->seq_off.swap(compact);
     h->T = R;
   }
   ~SubsetView() {
     std::swap(h->obs, h->sub_obs); std::swap(h->mask, h->sub_mask); std::swap(h->seq_off_d, h->sub_tab);
+    std::swap(h->labels, h->sub_labels);
     h->seq_off.swap(seq_off);
     h->T = T;
   }
@@ -1827,7 +1866,9 @@ static int subset_enqueue(svihmm_ctx* h, const SubsetPlan& p, int M, uint32_t fl
   if (h->have_mask) CK(ensure(h->sub_mask, (size_t)R));
   CK(ensure(h->sub_tab, p.tab.size() * sizeof(int64_t)));
   CK(upload_staged(h, h->sub_tab.p, p.tab.data(), p.tab.size() * sizeof(int64_t)));
-  CK(launch_seq_gather(h, M, (const int64_t*)h->sub_tab.p, (int)p.maxlen, (double*)h->sub_obs.p, (uint8_t*)h->sub_mask.p));
+  if (h->have_labels) CK(ensure(h->sub_labels, (size_t)R * sizeof(int32_t)));
+  CK(launch_seq_gather(h, M, (const int64_t*)h->sub_tab.p, (int)p.maxlen, (double*)h->sub_obs.p, (uint8_t*)h->sub_mask.p,
+                       (int32_t*)h->sub_labels.p));
   std::vector<int64_t> compact(p.tab.begin(), p.tab.begin() + M + 1);
   {
     SubsetView view(h, R, compact);
@@ -2511,6 +2552,10 @@ int svihmm_svi_recoveries(svihmm_ctx* h, int32_t* out) {
 int svihmm_svi_iteration(svihmm_ctx* h, int32_t it, const int64_t* starts, int32_t B, int32_t nwin_total,
                          int32_t Lm, int32_t inner_off, int32_t inner_len, uint32_t flags, double rho,
                          double bfactA, double bfactE) {
+  if (h && h->have_labels)
+    return fail("svihmm_svi_iteration: labels are in force (svihmm_set_labels) and the resident SVI loop does not "
+                "take them; remove them with svihmm_set_labels(h, NULL) or step on the host from "
+                "svihmm_estep_minibatch's statistics");
   if (h && !h->svi_active && h->have_emission && FAM_TRAITS[h->fam].noun) {
     const FamTraits& t = FAM_TRAITS[h->fam];
     const std::string head = std::string("svihmm_svi_iteration: the resident SVI loop does not take ") + t.noun;
@@ -2787,6 +2832,10 @@ int svihmm_svi_iteration_sequences(svihmm_ctx* h, int32_t it, const int32_t* idx
   const char* fn = "svihmm_svi_iteration_sequences";
   const auto bad = [fn](const std::string& what) { return fail(std::string(fn) + ": " + what); };
   if (!h) return bad("NULL handle");
+  if (h->have_labels)
+    return fail("svihmm_svi_iteration_sequences: labels are in force (svihmm_set_labels) and the resident SVI loop does not "
+                "take them; remove them with svihmm_set_labels(h, NULL) or step on the host from "
+                "svihmm_estep_sequence_subset's statistics");
   if (!h->svi_active) return bad("no loop: call one of svihmm_svi_begin* and svihmm_svi_sequences first");
   if (!h->svi_seq) return bad("the loop steps on windows: call svihmm_svi_sequences first");
   if (it < 0 || it >= h->svi_maxit)
@@ -3052,7 +3101,8 @@ int svihmm_heldout_rows(svihmm_ctx* h, double out2[2], double* out_lp) {
     h->cur_f32 = false;
     const uint32_t fl = windows ? h->last_flags & ~(uint32_t)(SVIHMM_MASK_AS_NAN | SVIHMM_USE_HOST_LLIKS) : 0u;
     const int rc = launch_emission(h, windows ? h->lastB : 1, windows ? h->lastLm : (int)n, fl, false,
-                                   windows ? nullptr : zero, (double*)h->m_ll.p);
+                                   windows ? nullptr : zero, (double*)h->m_ll.p, nullptr, nullptr, 0, nullptr,
+                                   false);      // (the family's own llik of the true rows: no label clamp)
     h->cur_f32 = cur_f32;
     if (rc) return rc;
     ProfScope ps(h, KS_MISC);
@@ -3412,6 +3462,9 @@ int svihmm_grow_windows(svihmm_ctx* h, const int64_t* centers, int32_t n, int32_
   const char* fn = "svihmm_grow_windows";
   const auto bad = [fn](const std::string& what) { return fail(std::string(fn) + ": " + what); };
   if (!h) return bad("NULL handle");
+  if (h->have_labels)
+    return bad("labels are in force (svihmm_set_labels) and the growth rules do not take them; remove them with "
+               "svihmm_set_labels(h, NULL)");
   if (!centers || !out_half) return bad("centers and out_half must be given");
   if (n < 1) return bad("n must be positive");
   if (increment < 1) return bad("increment must be positive");
@@ -3495,6 +3548,7 @@ int svihmm_generate(svihmm_ctx* h, int64_t T, int32_t K, int32_t D, const double
     HIPCK(hipGetLastError());
   }
   h->T = T; h->D = D; h->gen_T = T;
+  h->have_labels = false;
   h->seq_off.clear();
   h->svi_active = false;
   h->center_pending = false;

@@ -9,6 +9,8 @@
 #include "kernels_poisson.h"
 #define SVIHMM_PGAUSS_EMISSION
 #include "kernels_pgauss.h"
+#define SVIHMM_LABELS_CLAMP
+#include "kernels_labels.h"
 
 extern "C" {
 
@@ -209,7 +211,7 @@ bool emission_row_tile_orbit(const svihmm_ctx* h, int64_t n) {
 }
 // scaled: write (Eh, kexp) for the linear-domain sweeps instead of ll (K <= 64 only).
 // starts_dev / out: window starts and destination (default: the handle's buffers).
-int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
+static int launch_emission_family(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
                            const int64_t* starts_dev, double* out,
                            double* kexp_out, hipStream_t stream,
                            size_t min_lds, double* ll0_out) {
@@ -527,6 +529,39 @@ int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
 #undef EMM_LAUNCH
     }
   }
+  HIPCK(hipGetLastError());
+  return 0;
+}
+
+// an E-step-type call under labels: every label must name a state of the globals
+int check_labels_fit(const svihmm_ctx* h) {
+  if (h->have_labels && h->label_max >= h->K)
+    return fail("svihmm_set_labels: row " + std::to_string(h->label_max_row) + " is labelled with state " +
+                std::to_string(h->label_max) + ", the globals have K = " + std::to_string(h->K) + " states");
+  return 0;
+}
+// Where every route gets its lliks: the family's kernel (launch_emission_family), then, while labels are in force
+// (svihmm_set_labels) and the caller has not opted out, the clamp of `out` (k_label_clamp).  The callers that score
+// true observations opt out (clamp_labels = false).  Under labels there is no scaled output: the routes that ask for
+// one stay off a labelled batch (prepare_ll, use_pipeline, fused_shape_ok, the resident loops' refusals).
+int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
+                           const int64_t* starts_dev, double* out,
+                           double* kexp_out, hipStream_t stream,
+                           size_t min_lds, double* ll0_out, bool clamp_labels) {
+  const bool clamp = clamp_labels && h->have_labels;
+  if (clamp) {
+    if (scaled || h->cur_f32) return fail("internal: scaled emission output requested for a labelled batch");
+    CK(check_labels_fit(h));
+  }
+  CK(launch_emission_family(h, B, Lm, flags, scaled, starts_dev, out, kexp_out, stream, min_lds, ll0_out));
+  if (!clamp) return 0;
+  if (!starts_dev) { CK(ensure_starts_pulled(h)); starts_dev = (const int64_t*)h->starts.p; }
+  if (!out) out = (double*)h->ll.p;
+  if (!stream) stream = h->stream;
+  const int64_t n = (int64_t)B * Lm;
+  ProfScope ps(h, KS_EMISSION, stream);
+  hipLaunchKernelGGL(k_label_clamp, dim3((unsigned)((n + LC_ROWS - 1) / LC_ROWS)), dim3(256), 0, stream,
+                     (const int32_t*)h->labels.p, starts_dev, n, Lm, h->K, out);
   HIPCK(hipGetLastError());
   return 0;
 }

@@ -10,6 +10,8 @@
 #include "kernels_grow.h"
 #include "kernels_sequences.h"
 #include "kernels_decode_sequences.h"
+#define SVIHMM_LABELS_GATHER
+#include "kernels_labels.h"
 
 // The Viterbi forward sweep of n units addressed by `units` (kernels_viterbi.h: VitWindows / VitSequences): the one
 // dispatch on the model's width.  LDSBT: psi in LDS, the launch writes z itself (z null: score only); otherwise psi
@@ -1173,7 +1175,8 @@ int launch_seq_finish(svihmm_ctx* h, int N, const int64_t* seq_off, bool wrap, c
 }
 // svihmm_estep_sequence_subset: the M listed sequences of the resident rows (and mask bytes) into the compact copy
 // obs_out [R][D] / mask_out [R].  tab (device): dst_off [M + 1] | src_off [M], in rows.  maxlen: the longest of them.
-int launch_seq_gather(svihmm_ctx* h, int M, const int64_t* tab, int maxlen, double* obs_out, uint8_t* mask_out) {
+int launch_seq_gather(svihmm_ctx* h, int M, const int64_t* tab, int maxlen, double* obs_out, uint8_t* mask_out,
+                      int32_t* labels_out) {
   // 8 KiB of rows per workgroup and pass, at most 1024 workgroups per occurrence
   int64_t nseg = ((int64_t)maxlen * h->D * 8 + 8191) / 8192;
   if (nseg > 1024) nseg = 1024;
@@ -1182,6 +1185,10 @@ int launch_seq_gather(svihmm_ctx* h, int M, const int64_t* tab, int maxlen, doub
   hipLaunchKernelGGL(k_seq_gather, dim3((unsigned)M, (unsigned)nseg), dim3(256), 0, h->stream,
                      (const unsigned long long*)h->obs.p, h->have_mask ? (const uint8_t*)h->mask.p : nullptr, tab,
                      tab + M + 1, h->D, (unsigned long long*)obs_out, h->have_mask ? mask_out : nullptr);
+  // labels in force: the listed sequences' labels travel the same way (k_label_gather, the same grid)
+  if (h->have_labels)
+    hipLaunchKernelGGL(k_label_gather, dim3((unsigned)M, (unsigned)nseg), dim3(256), 0, h->stream,
+                       (const int32_t*)h->labels.p, tab, tab + M + 1, labels_out);
   HIPCK(hipGetLastError());
   return 0;
 }

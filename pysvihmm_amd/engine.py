@@ -475,6 +475,27 @@ class HipEngine(object):
         L.check(self._lib.svihmm_set_sequences(self._h, L.i64ptr(off), len(off) - 1), "svihmm_set_sequences")
         self.seq_off = off
 
+    def set_labels(self, labels):
+        """Known states of the resident rows (``svihmm_set_labels``): an int-valued array of length ``T``,
+        ``-1`` where the row is free, the state index where it is known.  ``None`` removes the labels, as every
+        upload of new rows does.  While they are in force every E-step and decoder on the device sees
+        ``-inf`` lliks at a labelled row's other states; the resident SVI loops, ``grow_windows`` and
+        ``pred_logprob`` refuse."""
+        self._pre_mutate()
+        if labels is None:
+            L.check(self._lib.svihmm_set_labels(self._h, None), "svihmm_set_labels")
+            return
+        a = np.asarray(labels)
+        if a.ndim != 1 or a.shape[0] != getattr(self, "T", 0):
+            raise RuntimeError("set_labels: labels must have shape (T,) = (%d,), got %s"
+                               % (getattr(self, "T", 0), a.shape))
+        if not (np.issubdtype(a.dtype, np.integer) or np.all(a == np.rint(a))):
+            raise RuntimeError("set_labels: labels must be int-valued")
+        if a.size and (a.min() < -(2 ** 31) or a.max() >= 2 ** 31):
+            raise RuntimeError("set_labels: labels must fit int32")
+        a = np.ascontiguousarray(a.astype(np.int32))
+        L.check(self._lib.svihmm_set_labels(self._h, a.ctypes.data_as(C.POINTER(C.c_int32))), "svihmm_set_labels")
+
     def estep_sequences(self, flags=0, read=True):
         """Whole E-step of all declared sequences in one device call (``svihmm_estep_sequences``):
         ``(stats, seq_lb[N], q0[K])`` -- ``stats`` as ``estep`` wraps them (None with read=False: they

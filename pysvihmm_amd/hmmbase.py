@@ -229,6 +229,59 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
             self.mask = np.asarray(mask).astype('bool')
         self._obs_dirty = True
 
+    def set_labels(self, labels):
+        """Partially labelled rows: ``labels[t] = -1`` leaves row ``t`` free, ``labels[t] = k`` says the row is
+        known to be in state ``k``.  One int-valued array over the rows, or -- when ``obs`` was a list -- a list with
+        one array per sequence.  ``None`` removes the labels.  Every E-step and decoder of the model then sees
+        ``lliks[t, j] = -inf`` for ``j != labels[t]`` at the labelled rows (``local_update``, the batch ``infer()``
+        loops, ``viterbi()``, ``ffbs_windows()``, ``heldout_logprob()``): on the device where the engine has
+        ``set_labels``, else through host lliks clamped here.  A label whose state is impossible under the initial
+        and transition factors leaves that chain's results unspecified (``-inf`` / NaN)."""
+        if labels is None:
+            self.labels = None
+            self._obs_dirty = True
+            return
+        so = self.__dict__.get("seq_off")
+        if isinstance(labels, (list, tuple)) and len(labels) and np.ndim(labels[0]) >= 1:
+            lens = [len(a) for a in labels]
+            want = [int(n) for n in np.diff(so)] if so is not None else [self.obs.shape[0]]
+            if lens != want:
+                raise ValueError("set_labels: the list's lengths %s do not match the sequences' %s" % (lens, want))
+            labels = np.concatenate([np.asarray(a).ravel() for a in labels])
+        a = np.asarray(labels)
+        if a.ndim != 1 or a.shape[0] != self.obs.shape[0]:
+            raise ValueError("set_labels: labels must have shape (%d,), got %s" % (self.obs.shape[0], a.shape))
+        if not np.issubdtype(a.dtype, np.integer):
+            if not (np.issubdtype(a.dtype, np.floating) and np.all(a == np.rint(a))):
+                raise ValueError("set_labels: labels must be int-valued")
+        a = a.astype(np.int64)
+        if a.size and a.min() < -1:
+            t = int(np.flatnonzero(a < -1)[0])
+            raise ValueError("set_labels: labels[%d] = %d (-1 means free, a state index means known)" % (t, a[t]))
+        if a.size and a.max() >= self.K:
+            t = int(np.argmax(a))
+            raise ValueError("set_labels: labels[%d] = %d, the model has K = %d states" % (t, a[t], self.K))
+        self.labels = a.astype(np.int32)
+        self._obs_dirty = True
+
+    def _clamp_lliks(self, ll, windows, Lm):
+        """The labels' clamp of host lliks ``ll`` [B, Lm, K] of the windows ``windows`` (in place): at a labelled
+        row every state but the label gets ``-inf``, the label's entry keeps its bits."""
+        lab = self.__dict__.get("labels")
+        if lab is None:
+            return ll
+        for b, s in enumerate(windows):
+            l = lab[s:s + Lm]
+            rows = np.flatnonzero(l >= 0)
+            keep = ll[b, rows, l[rows]].copy()
+            ll[b, rows, :] = -np.inf
+            ll[b, rows, l[rows]] = keep
+        return ll
+
+    def _labels_on_host(self):
+        """Labels are set and the engine does not take them: lliks are evaluated and clamped on the host."""
+        return self.__dict__.get("labels") is not None and not hasattr(self.engine, "set_labels")
+
     def __init__(self, obs, prior_init, prior_tran, prior_emit, mask=None,
                  init_init=None, init_tran=None, verbose=False, sts=None,
                  engine=None, device=0, dtype="f64"):
@@ -264,6 +317,7 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
             self.T, self.D = obs.shape
         else:
             raise RuntimeError("obs must have 1 or 2 dimensions")
+        self.labels = None
         self.set_mask(mask)
 
         self.elbo = -np.inf
@@ -309,6 +363,9 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
             self.mask = np.zeros(self.obs.shape[0], dtype='bool')
         else:
             self.mask = mask
+        lab = self.__dict__.get("labels")
+        if lab is not None and len(lab) != self.obs.shape[0]:
+            self.labels = None                  # (labels described the previous rows)
         self._obs_dirty = True
 
     def _upload_obs(self, force=False):
@@ -329,6 +386,9 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
             if self._multi() and hasattr(eng, "set_sequences"):
                 # (from here on the engine rejects windows that hold rows of two sequences)
                 eng.set_sequences(np.diff(self.seq_off))
+            if self.__dict__.get("labels") is not None and hasattr(eng, "set_labels"):
+                # (the upload above removed whatever labels the handle held)
+                eng.set_labels(self.labels)
             eng._obs_owner = id(self)
             self._obs_dirty = False
             self._obs_print = self._obs_fingerprint()
@@ -374,7 +434,7 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         the statistics summed over the sequences (batch transition form), ``lb = sum_s local_lb[s]``
         and ``q0 = sum_s var_x[first row of s]``.  One ``estep_sequences`` call where the engine has
         it, else one ``estep([off], len)`` per sequence with the sums formed here."""
-        if not self._device_family():
+        if not self._device_family() and not self._labels_on_host():
             raise RuntimeError("several sequences need an emission family the device evaluates "
                                "(NIW / diagonal Gaussian, Categorical, multi-column Categorical, Poisson or "
                                "Gaussian tracks on an engine with set_emission_mcat / _poisson / _pgauss): host "
@@ -386,7 +446,7 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         self._seq_flags = flags
         eng = self.engine
         self._seq_var_x = None
-        if hasattr(eng, "estep_sequences"):
+        if hasattr(eng, "estep_sequences") and not flags & L.USE_HOST_LLIKS:
             st, seq_lb, q0 = eng.estep_sequences(flags=flags)
             return st, float(st.lb[0]), q0
         so = self.seq_off
@@ -394,6 +454,8 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         var_x = np.empty((self.T, self.K))
         for s in range(len(so) - 1):
             off, ln = int(so[s]), int(so[s + 1] - so[s])
+            if flags & L.USE_HOST_LLIKS:        # (labels clamped on the host: the sequence's slice of the [1, T, K] batch)
+                eng.set_lliks(self._host_lliks[:, off:off + ln])
             st = eng.estep([off], ln, flags=flags)
             total = st.buf.copy() if total is None else total + st.buf
             lb += float(st.lb[0])
@@ -409,7 +471,7 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         occurs twice counts twice): ``(stats, lb, q0)`` as ``_sequences_estep`` returns them, summed over the
         listed sequences.  One ``estep_sequence_subset`` call where the engine has it, else one
         ``estep([off], len)`` per listed sequence with the sums formed here.  No per-row attribute is set."""
-        if not self._device_family():
+        if not self._device_family() and not self._labels_on_host():
             raise RuntimeError("several sequences need an emission family the device evaluates "
                                "(NIW / diagonal Gaussian, Categorical, multi-column Categorical, Poisson or "
                                "Gaussian tracks on an engine with set_emission_mcat / _poisson / _pgauss): host "
@@ -421,13 +483,15 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         self._seq_flags = flags
         eng = self.engine
         self._seq_var_x = None
-        if hasattr(eng, "estep_sequence_subset"):
+        if hasattr(eng, "estep_sequence_subset") and not flags & L.USE_HOST_LLIKS:
             st, seq_lb, q0 = eng.estep_sequence_subset(idx, flags=flags)
             return st, float(st.lb[0]), q0
         so = self.seq_off
         total, lb, q0 = None, 0., np.zeros(self.K)
         for s in idx:
             off, ln = int(so[s]), int(so[s + 1] - so[s])
+            if flags & L.USE_HOST_LLIKS:        # (labels clamped on the host: the sequence's slice of the [1, T, K] batch)
+                eng.set_lliks(self._host_lliks[:, off:off + ln])
             st = eng.estep([off], ln, flags=flags)
             total = st.buf.copy() if total is None else total + st.buf
             lb += float(st.lb[0])
@@ -532,7 +596,10 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
 
     def _family(self, among=FAMILIES):
         """The first record of ``among`` (hmmbase.FAMILIES, in its order) whose predicate holds for this model, or None:
-        the predicates after it are not asked."""
+        the predicates after it are not asked.  Labels on an engine that does not take them: None, so that no
+        device family evaluates unclamped lliks (the host-lliks route clamps them)."""
+        if self._labels_on_host():
+            return None
         return next((f for f in among if getattr(self, f.pred)()), None)
 
     def _device_family(self):
@@ -626,6 +693,7 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
                 x[self.mask[s:s + Lm]] = np.nan
             for k, odist in enumerate(self.var_emit):
                 ll[b, :, k] = np.nan_to_num(odist.expected_log_likelihood(x))
+        self._clamp_lliks(ll, windows, Lm)
         self.engine.set_lliks(ll)
         self._host_lliks = ll
         return L.USE_HOST_LLIKS
@@ -766,6 +834,8 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
             self.lliks, self.lalpha, self.lbeta = (np.empty((T, self.K)) for _ in range(3))
             for s in range(len(so) - 1):
                 off, ln = int(so[s]), int(so[s + 1] - so[s])
+                if self._seq_flags & L.USE_HOST_LLIKS:
+                    eng.set_lliks(self._host_lliks[:, off:off + ln])
                 r = eng.forward_backward([off], ln, flags=self._seq_flags, want=("lalpha", "lbeta"))
                 self.lalpha[off:off + ln] = r["lalpha"][0]
                 self.lbeta[off:off + ln] = r["lbeta"][0]

@@ -96,6 +96,9 @@ class VBHMM(VariationalHMMBase):
         """Why ``infer`` cannot run in the engine's resident loop on sequence minibatches (None: it can)."""
         if self.seq_minibatch is None:
             return "seq_minibatch is not set"
+        if self.__dict__.get("labels") is not None:
+            return ("labels are set (set_labels): the resident loop does not take them; the host route steps "
+                    "on estep_sequence_subset, which honours them")
         eng = self.engine
         if not (hasattr(eng, "svi_sequences") and hasattr(eng, "svi_iteration_sequences")):
             return "the engine has no svi_sequences / svi_iteration_sequences"

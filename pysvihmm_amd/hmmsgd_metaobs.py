@@ -99,6 +99,16 @@ class VBHMM(VariationalHMMBase):
                 'prior_emit': prior_emit, 'mask': mask, 'tau': tau,
                 'kappa': kappa, 'metaobs_half': metaobs_half, 'mb_sz': mb_sz}
 
+    def set_labels(self, labels):
+        """Not supported by this class: its iterations run in the engine's resident SVI loop and its adaptive
+        windows through ``grow_windows``, and neither takes labels.  ``hmmbatchcd.VBHMM`` and
+        ``hmmbatchsgd.VBHMM`` honour them."""
+        if labels is None:
+            self.labels = None
+            return
+        raise NotImplementedError("hmmsgd_metaobs.VBHMM.set_labels: the resident SVI loop and grow_windows do not "
+                                  "take labels; use hmmbatchcd.VBHMM or hmmbatchsgd.VBHMM")
+
     def set_metaobs_fun(self):
         if self.metaobs_fun_name == 'unif':
             self.metaobs_fun = self.metaobs_unif
