@@ -372,6 +372,15 @@ inline void set_family(svihmm_ctx* h, EmisFamily f) {
   if (f != EF_NIW) h->uw_valid = false;
   if (f == EF_DIAG) h->uwd_valid = false;
 }
+// padded state count: tiles of 16; wide models in groups of 64 (the statistics GEMM's state groups)
+inline int padded_K(int K) { return K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16; }
+// a table family arrives with K states, D columns and V statistics rows
+inline void enter_table_family(svihmm_ctx* h, EmisFamily f, int K, int D, int V) {
+  h->eK = K; h->eD = D; h->V = V; h->Kp = padded_K(K);
+  set_family(h, f);
+}
+// what the argument checks call finite: neither NaN nor an infinity
+inline bool finite_val(double v) { return v > -1.7e308 && v < 1.7e308; }
 // the emission family in force as post_fam records it: -1 none, else the tag
 inline int emission_family_id(const svihmm_ctx* h) { return h->have_emission ? (int)h->fam : -1; }
 // an E-step-type call has left its posterior batch (svihmm_ctx::post_kind)

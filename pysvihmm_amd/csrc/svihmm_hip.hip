@@ -126,6 +126,30 @@ static int params_follow_centre(svihmm_ctx* h, const double* delta);
 static int drop_auto_status(svihmm_ctx* h);
 static int d2h_sync_small(svihmm_ctx* h, void* dst, const void* src, size_t bytes);
 static int upload_staged(svihmm_ctx* h, void* dst, const void* src, size_t bytes);
+static void to_centred(const svihmm_ctx* h, double* mu, int K, int D);
+// The side-stream ELBO kernels in flight read niw / theta / logdet / var_tran: the stream waits for their event before
+// any of those is rewritten
+static int wait_vlb(svihmm_ctx* h) {
+  if (h->vlb_pending) { HIPCK(hipStreamWaitEvent(h->stream, h->svi_ed, 0)); h->vlb_pending = false; }
+  return 0;
+}
+// Upload the pieces, end to end, into dst through one pinned staging slot: pulled by a kernel, no stream
+// synchronisation.  centre_K > 0: the leading [centre_K][centre_D] block is means in the caller's coordinates and
+// travels centred (to_centred).  On a failure the slot is simply not marked busy.
+struct Piece { const double* p; size_t n; };
+static int upload_blocks(svihmm_ctx* h, void* dst, std::initializer_list<Piece> pieces, int centre_K = 0,
+                         int centre_D = 0) {
+  size_t n = 0;
+  for (const Piece& q : pieces) n += q.n;
+  void* pin = nullptr;
+  int slot = 0;
+  CK(pinned(h, n * sizeof(double), &pin, &slot));
+  double* hp = (double*)pin;
+  for (const Piece& q : pieces) { std::memcpy(hp, q.p, q.n * sizeof(double)); hp += q.n; }
+  if (centre_K > 0) to_centred(h, (double*)pin, centre_K, centre_D);
+  CK(pull_small(h, dst, pin, n * sizeof(double)));
+  return pin_release(h, slot);
+}
 int svihmm_set_precision(svihmm_ctx* h, int32_t mode) {
   if (!h || (mode != SVIHMM_F64 && mode != SVIHMM_F32)) return fail("svihmm_set_precision: mode must be SVIHMM_F64 or SVIHMM_F32");
   h->prec = mode;
@@ -213,12 +237,12 @@ static void sample_center(const svihmm_ctx* h, const double* obs, int64_t T, int
     const double* row = obs + (size_t)(i * stride) * D;
     for (int d = 0; d < D; ++d) {
       const double v = row[d];
-      if (v > -1.7e308 && v < 1.7e308) { c[d] += v; ++cnt[d]; }
+      if (finite_val(v)) { c[d] += v; ++cnt[d]; }
     }
   }
   for (int d = 0; d < D; ++d) {
     c[d] = cnt[d] > 0 ? c[d] / (double)cnt[d] : 0.0;
-    if (!(c[d] > -1.7e308 && c[d] < 1.7e308)) c[d] = 0.0;
+    if (!finite_val(c[d])) c[d] = 0.0;
   }
 }
 // rows [row0, row0 + nrows) of the resident copy -= delta[D] (host vector)
@@ -258,13 +282,7 @@ static int store_shift(svihmm_ctx* h, const std::vector<double>& c) {
   for (int d = 0; d < D; ++d) h->shifted = h->shifted || c[d] != 0.0;
   ++h->shift_epoch;
   CK(ensure(h->shift_d, (size_t)D * sizeof(double)));
-  void* pin = nullptr;
-  int slot = 0;
-  CK(pinned(h, (size_t)D * sizeof(double), &pin, &slot));
-  std::memcpy(pin, c.data(), (size_t)D * sizeof(double));
-  CK(pull_small(h, h->shift_d.p, pin, (size_t)D * sizeof(double)));
-  CK(pin_release(h, slot));
-  return 0;
+  return upload_blocks(h, h->shift_d.p, {{c.data(), (size_t)D}});
 }
 // The centre moved by delta[D]: device-side parameters kept in centred coordinates follow -- the
 // means of the NIW / diagonal factors in h->niw (theta is rebuilt), the prior means of a running
@@ -330,7 +348,7 @@ int svihmm_shift_obs(svihmm_ctx* h, const double* shift) {
   h->lin_stale = true;
   const int D = h->D;
   for (int d = 0; d < D; ++d)
-    if (!(shift[d] > -1.7e308 && shift[d] < 1.7e308)) return fail("svihmm_shift_obs: shift must be finite");
+    if (!finite_val(shift[d])) return fail("svihmm_shift_obs: shift must be finite");
   CK(wait_side_streams(h));
   CK(shift_rows(h, shift, 0, h->T, 0));
   std::vector<double> c = h->shift;
@@ -466,7 +484,7 @@ int svihmm_set_globals(svihmm_ctx* h, int32_t K, const double* mod_init, const d
   bool finite = true;
   for (size_t i = 0; i < (size_t)K * K; ++i) {
     const double v = ltran[i];
-    if (!(v > -1.7e308 && v < 1.7e308)) finite = false;
+    if (!finite_val(v)) finite = false;
     else if (v < lmin) lmin = v;
   }
   h->exact_log = !finite || lmin < SVIHMM_LTRAN_LINEAR_MIN;
@@ -529,8 +547,7 @@ static inline int feat_index(int a, int b, int D) {  // 0 <= a <= b <= D
 // the table, so the family only changes the table and the theta builder.
 int upload_feature_table(svihmm_ctx* h, int D, int K, bool diag) {
   const int F = diag ? 2 * D + 1 : (D + 1) * (D + 2) / 2, Fp = (F + 15) / 16 * 16;
-  // padded state count: tiles of 16; wide models in groups of 64 (the statistics GEMM's state groups)
-  const int Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16;
+  const int Kp = padded_K(K);
   if (h->tabD == D && h->Fp == Fp && h->tab_diag == diag) { h->F = F; h->Kp = Kp; return 0; }
   std::vector<int> fab(Fp, (D + 1) | ((D + 1) << 16));  // padding -> zero slot
   if (diag) {
@@ -580,6 +597,39 @@ static int centre_deferred(svihmm_ctx* h) {
   return reset_shift(h, c, 0, h->T);
 }
 
+// ---- what every svihmm_set_emission_* does between its argument checks and its first ensure ---------------------
+// The live device loop is of this family and this shape: the upload re-pushes the loop's own factors' table (the
+// validation hooks of infer() -- full_predprob, adaptive L, growBuffer -- re-upload what they just read back) and the
+// loop survives it.  W: the columns D, for EF_CAT the symbols V; V: the columns' symbol counts (EF_MCAT only).
+static bool own_loop(const svihmm_ctx* h, EmisFamily fam, int K, int W, const int32_t* V = nullptr) {
+  if (!h->svi_active || h->svi_family != fam || h->svi_K != K) return false;
+  switch (fam) {
+    case EF_NIW: case EF_DIAG: case EF_POIS: return h->svi_D == W;
+    case EF_CAT: return h->V == W;
+    case EF_MCAT: return h->svi_mcat_V == std::vector<int>(V, V + W);
+    default: return false;             // (the resident loop does not know the family)
+  }
+}
+// The emission is about to be rewritten, in this order ("putting a family in force"):
+//   1. device, stale logs;
+//   2. the centring the family wants (Gaussian: the one an upload under a table family deferred; table: none pending);
+//   3. a live loop's deferred ELBO kernels, launched while the factors they read are still whole -- only then does a
+//      loop that is not `own` end (it kept its factors in h->niw, which any family's arrival may rewrite or reallocate);
+//   4. the stream behind the ELBO kernels in flight;  5. an automatic rebuild's status word dropped;
+//   6. table families: the resident rows back in the caller's coordinates (uncentre: cat_uncentre's mode).
+static int begin_emission_upload(svihmm_ctx* h, EmisFamily fam, int D, bool own, int uncentre = -1) {
+  CK(set_device(h));
+  h->lin_stale = true;
+  if (fam_table(fam)) h->center_pending = false;
+  else if (h->D == D) CK(centre_deferred(h));
+  if (h->svi_active) CK(svi_flush_elbo(h));
+  if (!own) h->svi_active = false;
+  CK(wait_vlb(h));
+  CK(drop_auto_status(h));
+  if (fam_table(fam)) CK(cat_uncentre(h, uncentre));
+  return 0;
+}
+
 int svihmm_set_emission_niw(svihmm_ctx* h, int32_t K, int32_t D, const double* mu,
                             const double* sigma, const double* kappa, const double* nu) {
   if (!h || K <= 0 || D <= 0 || !mu || !sigma || !kappa || !nu)
@@ -587,34 +637,12 @@ int svihmm_set_emission_niw(svihmm_ctx* h, int32_t K, int32_t D, const double* m
   if (D > SVIHMM_NIW_MAX_D)   // (k_niw_to_theta_generic keeps two D x (D+1) matrices in LDS)
     return fail("svihmm_set_emission_niw: D > SVIHMM_NIW_MAX_D: evaluate the expected log-likelihoods on the "
                 "host and pass them with svihmm_set_lliks / SVIHMM_USE_HOST_LLIKS");
-  CK(set_device(h));
-  h->lin_stale = true;
-  if (h->D == D) CK(centre_deferred(h));
-  // (a device loop of another family or shape kept its factors in h->niw: it ends here)
-  if (h->svi_active && !(h->svi_family == EF_NIW && h->svi_K == K && h->svi_D == D)) h->svi_active = false;
+  CK(begin_emission_upload(h, EF_NIW, D, own_loop(h, EF_NIW, K, D)));
   const size_t nmu = (size_t)K * D, nsg = (size_t)K * D * D;
-  const size_t nin = nmu + nsg + 2 * (size_t)K;
-  CK(ensure(h->niw, nin * sizeof(double) + 64));
-  double* dmu = (double*)h->niw.p;
-  // one pinned staging slot, pulled by a kernel, no stream synchronisation
-  void* pin = nullptr;
-  int slot = 0;
-  CK(pinned(h, (nin + 1) * sizeof(double), &pin, &slot));
-  double* hp = (double*)pin;
-  std::memcpy(hp, mu, nmu * sizeof(double));
-  to_centred(h, hp, K, D);             // the resident observations are x - shift: so are the means
-  std::memcpy(hp + nmu, sigma, nsg * sizeof(double));
-  std::memcpy(hp + nmu + nsg, kappa, K * sizeof(double));
-  std::memcpy(hp + nmu + nsg + K, nu, K * sizeof(double));
-  // (a live loop whose own family and shape are re-pushed: the previous iteration's ELBO kernels may still be
-  //  deferred -- they read the factors this upload rewrites, so they go first)
-  if (h->svi_active) CK(svi_flush_elbo(h));
-  if (h->vlb_pending) { HIPCK(hipStreamWaitEvent(h->stream, h->svi_ed, 0)); h->vlb_pending = false; }
-  CK(drop_auto_status(h));
-  CK(pull_small(h, dmu, hp, nin * sizeof(double)));
-  CK(pin_release(h, slot));
-  CK(launch_niw_to_theta(h, K, D, nullptr));
-  return 0;
+  CK(ensure(h->niw, (nmu + nsg + 2 * (size_t)K) * sizeof(double) + 64));
+  // (the resident observations are x - shift: so are the means)
+  CK(upload_blocks(h, h->niw.p, {{mu, nmu}, {sigma, nsg}, {kappa, (size_t)K}, {nu, (size_t)K}}, K, D));
+  return launch_niw_to_theta(h, K, D, nullptr);
 }
 
 int svihmm_set_emission_diag(svihmm_ctx* h, int32_t K, int32_t D, const double* mu, const double* nus,
@@ -624,29 +652,10 @@ int svihmm_set_emission_diag(svihmm_ctx* h, int32_t K, int32_t D, const double* 
   if (D > SVIHMM_DIAG_MAX_D)
     return fail("svihmm_set_emission_diag: D > SVIHMM_DIAG_MAX_D: evaluate the expected log-likelihoods on the "
                 "host and pass them with svihmm_set_lliks / SVIHMM_USE_HOST_LLIKS");
-  CK(set_device(h));
-  h->lin_stale = true;
-  if (h->D == D) CK(centre_deferred(h));
+  CK(begin_emission_upload(h, EF_DIAG, D, own_loop(h, EF_DIAG, K, D)));
   const size_t n = (size_t)K * D;
   CK(ensure(h->niw, 4 * n * sizeof(double) + 64));
-  void* pin = nullptr;
-  int slot = 0;
-  CK(pinned(h, 4 * n * sizeof(double), &pin, &slot));
-  double* hp = (double*)pin;
-  std::memcpy(hp, mu, n * sizeof(double));
-  to_centred(h, hp, K, D);
-  std::memcpy(hp + n, nus, n * sizeof(double));
-  std::memcpy(hp + 2 * n, alphas, n * sizeof(double));
-  std::memcpy(hp + 3 * n, betas, n * sizeof(double));
-  if (h->svi_active) CK(svi_flush_elbo(h));      // (as in svihmm_set_emission_niw)
-  if (h->vlb_pending) { HIPCK(hipStreamWaitEvent(h->stream, h->svi_ed, 0)); h->vlb_pending = false; }
-  // a running device loop survives a re-push of ITS OWN family and shape (the loop's factor block IS
-  // h->niw: the validation hooks of infer() -- full_predprob, adaptive L, growBuffer -- re-upload the
-  // factors they just read back); any other loop's resident state is gone with this upload
-  if (!(h->svi_active && h->svi_family == EF_DIAG && h->svi_K == K && h->svi_D == D)) h->svi_active = false;
-  CK(drop_auto_status(h));
-  CK(pull_small(h, h->niw.p, hp, 4 * n * sizeof(double)));
-  CK(pin_release(h, slot));
+  CK(upload_blocks(h, h->niw.p, {{mu, n}, {nus, n}, {alphas, n}, {betas, n}}, K, D));
   return launch_diag_to_theta(h, K, D);
 }
 
@@ -656,14 +665,7 @@ int svihmm_set_emission_prior(svihmm_ctx* h, int32_t K, int32_t D, const double*
   CK(set_device(h));
   const size_t nmu = (size_t)K * D, nsg = (size_t)K * D * D;
   CK(ensure(h->prior, (nmu + nsg) * sizeof(double)));
-  void* pin = nullptr;
-  int slot = 0;
-  CK(pinned(h, (nmu + nsg) * sizeof(double), &pin, &slot));
-  std::memcpy(pin, mu0, nmu * sizeof(double));
-  to_centred(h, (double*)pin, K, D);
-  std::memcpy((double*)pin + nmu, sigma0, nsg * sizeof(double));
-  CK(pull_small(h, h->prior.p, pin, (nmu + nsg) * sizeof(double)));
-  CK(pin_release(h, slot));
+  CK(upload_blocks(h, h->prior.p, {{mu0, nmu}, {sigma0, nsg}}, K, D));
   h->prior_K = K; h->prior_D = D;
   h->prior_mu0.assign(mu0, mu0 + nmu);     // re-centred when the handle's shift has moved since
   h->prior_epoch = h->shift_epoch;
@@ -698,25 +700,10 @@ int svihmm_niw_vlb_terms(svihmm_ctx* h, int32_t K, int32_t D, const double* mu, 
   double* th2 = dnu + K;
   double* ld = th2 + nth;
   int* dstat = (int*)(ld + K);
-  void* pin = nullptr;
-  int slot = 0;
-  CK(pinned(h, nin * sizeof(double), &pin, &slot));
-  double* hp = (double*)pin;
-  std::memcpy(hp, mu, nmu * sizeof(double));
-  to_centred(h, hp, K, D);     // (only differences mu - mu_0 enter; both travel centred)
-  std::memcpy(hp + nmu, sigma, nsg * sizeof(double));
-  std::memcpy(hp + nmu + nsg, kappa, K * sizeof(double));
-  std::memcpy(hp + nmu + nsg + K, nu, K * sizeof(double));
-  CK(pull_small(h, dmu, hp, nin * sizeof(double)));
-  CK(pin_release(h, slot));
+  // (only differences mu - mu_0 enter; both travel centred)
+  CK(upload_blocks(h, dmu, {{mu, nmu}, {sigma, nsg}, {kappa, (size_t)K}, {nu, (size_t)K}}, K, D));
   if (h->prior_epoch != h->shift_epoch) {
-    void* pin2 = nullptr;
-    int slot2 = 0;
-    CK(pinned(h, nmu * sizeof(double), &pin2, &slot2));
-    std::memcpy(pin2, h->prior_mu0.data(), nmu * sizeof(double));
-    to_centred(h, (double*)pin2, K, D);
-    CK(pull_small(h, h->prior.p, pin2, nmu * sizeof(double)));
-    CK(pin_release(h, slot2));
+    CK(upload_blocks(h, h->prior.p, {{h->prior_mu0.data(), nmu}}, K, D));
     h->prior_epoch = h->shift_epoch;
   }
   const double* p0 = (const double*)h->prior.p;
@@ -744,15 +731,7 @@ int cat_uncentre(svihmm_ctx* h, int counts) {
 // feature table is also needed by the statistics kernels when only host lliks are used
 int svihmm_set_emission_cat(svihmm_ctx* h, int32_t K, int32_t V, const double* logp) {
   if (!h || K <= 0 || V <= 0 || !logp) return fail("svihmm_set_emission_cat: bad arguments");
-  CK(set_device(h));
-  h->lin_stale = true;
-  h->center_pending = false;
-  // (a device loop of another family or shape ends with this upload, as in svihmm_set_emission_niw / _diag)
-  if (h->svi_active && !(h->svi_family == EF_CAT && h->svi_K == K && h->V == V)) h->svi_active = false;
-  if (h->svi_active) CK(svi_flush_elbo(h));      // (as in svihmm_set_emission_niw)
-  if (h->vlb_pending) { HIPCK(hipStreamWaitEvent(h->stream, h->svi_ed, 0)); h->vlb_pending = false; }
-  CK(drop_auto_status(h));
-  CK(cat_uncentre(h));
+  CK(begin_emission_upload(h, EF_CAT, 1, own_loop(h, EF_CAT, K, V)));
   const size_t n = (size_t)K * V;
   CK(ensure(h->cat_table, n * sizeof(double)));
   void* pin = nullptr;
@@ -763,64 +742,94 @@ int svihmm_set_emission_cat(svihmm_ctx* h, int32_t K, int32_t V, const double* l
     for (int v = 0; v < V; ++v) hp[(size_t)v * K + k] = logp[(size_t)k * V + v];
   HIPCK(hipMemcpyAsync(h->cat_table.p, hp, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
   CK(pin_release(h, slot));
-  h->eK = K; h->eD = 1; h->V = V; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16; set_family(h, EF_CAT);
+  enter_table_family(h, EF_CAT, K, 1, V);
   return 0;
 }
-// mcat_meta = [off_d D | V_d D | d(f) F | v(f) F]
-static void mcat_fill_meta(int* mp, int D, int F, const int32_t* V) {
+// What svihmm_set_emission_mcat and svihmm_svi_begin_mcat (`fn`) ask of K, D and the columns' symbol counts, in the
+// order both have always asked it; *F_out = sum of V
+static int check_mcat_shape(const char* fn, int K, int D, const int32_t* V, int* F_out) {
+  const std::string p = std::string(fn) + ": ";
+  if (K < 1 || K > 256) return fail(p + "K = " + std::to_string(K) + " outside [1, 256]");
+  if (D < 1 || D > SVIHMM_MCAT_MAX_D)
+    return fail(p + "D = " + std::to_string(D) + " outside [1, SVIHMM_MCAT_MAX_D = " + std::to_string(SVIHMM_MCAT_MAX_D) + "]");
+  int64_t F = 0;
+  for (int d = 0; d < D; ++d) {
+    if (V[d] < 1)
+      return fail(p + "V[" + std::to_string(d) + "] = " + std::to_string(V[d]) + " (every column needs at least one symbol)");
+    F += V[d];
+  }
+  if (F > SVIHMM_MCAT_MAX_F)
+    return fail(p + "F = sum of V = " + std::to_string(F) + " exceeds SVIHMM_MCAT_MAX_F = " + std::to_string(SVIHMM_MCAT_MAX_F));
+  *F_out = (int)F;
+  return 0;
+}
+// mcat_meta = [off_d D | V_d D | d(f) F | v(f) F] int32, built in a staging slot
+static int upload_mcat_meta(svihmm_ctx* h, int D, int F, const int32_t* V) {
+  const size_t nb = (2 * (size_t)D + 2 * (size_t)F) * sizeof(int);
+  CK(ensure(h->mcat_meta, nb));
+  void* pin = nullptr;
+  int slot = 0;
+  CK(pinned(h, nb, &pin, &slot));
+  int* mp = (int*)pin;
   for (int d = 0, o = 0; d < D; o += V[d], ++d) {
     mp[d] = o; mp[D + d] = V[d];
     for (int v = 0; v < V[d]; ++v) { mp[2 * D + o + v] = d; mp[2 * D + F + o + v] = v; }
   }
+  HIPCK(hipMemcpyAsync(h->mcat_meta.p, pin, nb, hipMemcpyHostToDevice, h->stream));
+  return pin_release(h, slot);
 }
 // D symbol columns, independent per state (kernels_mcat.h).  The family rides the Categorical branches of the host
 // code (fam_table) with V = F features; only the lookup and the count launches differ (EF_MCAT).
 int svihmm_set_emission_mcat(svihmm_ctx* h, int32_t K, int32_t D, const int32_t* V, const double* logp) {
   if (!h) return fail("svihmm_set_emission_mcat: handle is NULL");
   if (!V || !logp) return fail("svihmm_set_emission_mcat: V and logp must not be NULL");
-  if (K < 1 || K > 256) return fail("svihmm_set_emission_mcat: K = " + std::to_string(K) + " outside [1, 256]");
-  if (D < 1 || D > SVIHMM_MCAT_MAX_D)
-    return fail("svihmm_set_emission_mcat: D = " + std::to_string(D) + " outside [1, SVIHMM_MCAT_MAX_D = " +
-                std::to_string(SVIHMM_MCAT_MAX_D) + "]");
-  int64_t F64 = 0;
-  for (int d = 0; d < D; ++d) {
-    if (V[d] < 1)
-      return fail("svihmm_set_emission_mcat: V[" + std::to_string(d) + "] = " + std::to_string(V[d]) + " (every column needs at least one symbol)");
-    F64 += V[d];
-  }
-  if (F64 > SVIHMM_MCAT_MAX_F)
-    return fail("svihmm_set_emission_mcat: F = sum of V = " + std::to_string(F64) + " exceeds SVIHMM_MCAT_MAX_F = " +
-                std::to_string(SVIHMM_MCAT_MAX_F));
-  const int F = (int)F64;
+  int F = 0;
+  CK(check_mcat_shape("svihmm_set_emission_mcat", K, D, V, &F));
   const size_t n = (size_t)K * F;
   for (size_t i = 0; i < n; ++i)
-    if (!(logp[i] > -1.7e308 && logp[i] < 1.7e308))
+    if (!finite_val(logp[i]))
       return fail("svihmm_set_emission_mcat: logp[" + std::to_string(i / F) + "][" + std::to_string(i % F) + "] is not finite");
-  CK(set_device(h));
-  h->lin_stale = true;
-  h->center_pending = false;
-  // (a device loop of another family or shape ends with this upload, as in svihmm_set_emission_cat)
-  if (h->svi_active && !(h->svi_family == EF_MCAT && h->svi_K == K && h->svi_mcat_V == std::vector<int>(V, V + D))) h->svi_active = false;
-  if (h->svi_active) CK(svi_flush_elbo(h));
-  if (h->vlb_pending) { HIPCK(hipStreamWaitEvent(h->stream, h->svi_ed, 0)); h->vlb_pending = false; }
-  CK(drop_auto_status(h));
-  CK(cat_uncentre(h));
-  const size_t nmeta = 2 * (size_t)D + 2 * (size_t)F;
+  CK(begin_emission_upload(h, EF_MCAT, D, own_loop(h, EF_MCAT, K, D, V)));
   CK(ensure(h->cat_table, n * sizeof(double)));
-  CK(ensure(h->mcat_meta, nmeta * sizeof(int)));
   void* pin = nullptr;
   int slot = 0;
-  CK(pinned(h, n * sizeof(double) + nmeta * sizeof(int), &pin, &slot));
+  CK(pinned(h, n * sizeof(double), &pin, &slot));
   double* hp = (double*)pin;
   for (int k = 0; k < K; ++k)              // transpose to [F][K]: a feature's states are contiguous
     for (int f = 0; f < F; ++f) hp[(size_t)f * K + k] = logp[(size_t)k * F + f];
-  int* mp = (int*)(hp + n);
-  mcat_fill_meta(mp, D, F, V);
   HIPCK(hipMemcpyAsync(h->cat_table.p, hp, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCK(hipMemcpyAsync(h->mcat_meta.p, mp, nmeta * sizeof(int), hipMemcpyHostToDevice, h->stream));
   CK(pin_release(h, slot));
-  h->eK = K; h->eD = D; h->V = F; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16;
-  set_family(h, EF_MCAT);
+  CK(upload_mcat_meta(h, D, F, V));
+  enter_table_family(h, EF_MCAT, K, D, F);
+  return 0;
+}
+// What svihmm_set_emission_poisson and svihmm_svi_begin_poisson (`fn`) ask of K, D, C and the logfact table, in the
+// order both have always asked it; elog / erate [K][D]: the setter's tables, which it checks in front of logfact
+static int check_poisson_shape(const char* fn, int K, int D, int C, const double* logfact, const double* elog = nullptr,
+                               const double* erate = nullptr) {
+  const std::string p = std::string(fn) + ": ";
+  if (K < 1 || K > 256) return fail(p + "K = " + std::to_string(K) + " outside [1, 256]");
+  if (D < 1 || D > SVIHMM_POISSON_MAX_D)
+    return fail(p + "D = " + std::to_string(D) + " outside [1, SVIHMM_POISSON_MAX_D = " + std::to_string(SVIHMM_POISSON_MAX_D) + "]");
+  if (C < 0 || C > SVIHMM_POISSON_MAX_COUNT)
+    return fail(p + "C = " + std::to_string(C) + " outside [0, SVIHMM_POISSON_MAX_COUNT = " + std::to_string(SVIHMM_POISSON_MAX_COUNT) + "]");
+  for (size_t i = 0; elog && i < (size_t)K * D; ++i) {
+    const std::string at = "[" + std::to_string(i / D) + "][" + std::to_string(i % D) + "] is not finite";
+    if (!finite_val(elog[i])) return fail(p + "elog" + at);
+    if (!finite_val(erate[i])) return fail(p + "erate" + at);
+  }
+  for (int c = 0; c <= C; ++c)
+    if (!finite_val(logfact[c])) return fail(p + "logfact[" + std::to_string(c) + "] is not finite");
+  return 0;
+}
+// the logfact table changes only with C: the device copy stays while the caller's holds the same bits
+static int upload_logfact(svihmm_ctx* h, const double* logfact, int C) {
+  const size_t nlf = (size_t)C + 1;
+  if (h->pois_lf_host.size() == nlf && std::memcmp(h->pois_lf_host.data(), logfact, nlf * sizeof(double)) == 0) return 0;
+  CK(ensure(h->pois_logfact, nlf * sizeof(double)));
+  h->pois_lf_host.clear();               // (stays empty if the upload below fails)
+  CK(upload_blocks(h, h->pois_logfact.p, {{logfact, nlf}}));
+  h->pois_lf_host.assign(logfact, logfact + nlf);
   return 0;
 }
 // D count columns, independent Poisson rates per state (kernels_poisson.h).  The family rides the Categorical branches
@@ -830,41 +839,14 @@ int svihmm_set_emission_poisson(svihmm_ctx* h, int32_t K, int32_t D, const doubl
                                 const double* logfact, int32_t C) {
   if (!h) return fail("svihmm_set_emission_poisson: handle is NULL");
   if (!elog || !erate || !logfact) return fail("svihmm_set_emission_poisson: elog, erate and logfact must not be NULL");
-  if (K < 1 || K > 256) return fail("svihmm_set_emission_poisson: K = " + std::to_string(K) + " outside [1, 256]");
-  if (D < 1 || D > SVIHMM_POISSON_MAX_D)
-    return fail("svihmm_set_emission_poisson: D = " + std::to_string(D) + " outside [1, SVIHMM_POISSON_MAX_D = " +
-                std::to_string(SVIHMM_POISSON_MAX_D) + "]");
-  if (C < 0 || C > SVIHMM_POISSON_MAX_COUNT)
-    return fail("svihmm_set_emission_poisson: C = " + std::to_string(C) + " outside [0, SVIHMM_POISSON_MAX_COUNT = " +
-                std::to_string(SVIHMM_POISSON_MAX_COUNT) + "]");
-  auto finite = [](double v) { return v > -1.7e308 && v < 1.7e308; };
+  CK(check_poisson_shape("svihmm_set_emission_poisson", K, D, C, logfact, elog, erate));
+  CK(begin_emission_upload(h, EF_POIS, D, own_loop(h, EF_POIS, K, D), 1));
   const size_t n = (size_t)K * D;
-  for (size_t i = 0; i < n; ++i) {
-    if (!finite(elog[i]))
-      return fail("svihmm_set_emission_poisson: elog[" + std::to_string(i / D) + "][" + std::to_string(i % D) + "] is not finite");
-    if (!finite(erate[i]))
-      return fail("svihmm_set_emission_poisson: erate[" + std::to_string(i / D) + "][" + std::to_string(i % D) + "] is not finite");
-  }
-  const size_t nlf = (size_t)C + 1;
-  for (size_t c = 0; c < nlf; ++c)
-    if (!finite(logfact[c])) return fail("svihmm_set_emission_poisson: logfact[" + std::to_string(c) + "] is not finite");
-  CK(set_device(h));
-  h->lin_stale = true;
-  h->center_pending = false;
-  // (a device loop of another family or shape ends with this upload, as in svihmm_set_emission_cat)
-  if (h->svi_active && !(h->svi_family == EF_POIS && h->svi_K == K && h->svi_D == D)) h->svi_active = false;
-  if (h->svi_active) CK(svi_flush_elbo(h));
-  if (h->vlb_pending) { HIPCK(hipStreamWaitEvent(h->stream, h->svi_ed, 0)); h->vlb_pending = false; }
-  CK(drop_auto_status(h));
-  CK(cat_uncentre(h, 1));
-  // the logfact table changes only with C: the device copy stays while the caller's holds the same bits
-  const bool lf_new = h->pois_lf_host.size() != nlf || std::memcmp(h->pois_lf_host.data(), logfact, nlf * sizeof(double)) != 0;
   const size_t nt = 2 * (n + (size_t)K);     // [D + 1][K] pairs (elog, erate); row D, all +0.0, is what an absent column reads
   CK(ensure(h->cat_table, nt * sizeof(double)));
-  if (lf_new) CK(ensure(h->pois_logfact, nlf * sizeof(double)));
   void* pin = nullptr;
   int slot = 0;
-  CK(pinned(h, (nt + (lf_new ? nlf : 0)) * sizeof(double), &pin, &slot));
+  CK(pinned(h, nt * sizeof(double), &pin, &slot));
   double* hp = (double*)pin;
   for (int k = 0; k < K; ++k) {            // transposed: a column's states are contiguous
     for (int d = 0; d < D; ++d) {
@@ -874,15 +856,10 @@ int svihmm_set_emission_poisson(svihmm_ctx* h, int32_t K, int32_t D, const doubl
     hp[2 * ((size_t)D * K + k)] = hp[2 * ((size_t)D * K + k) + 1] = 0.0;
   }
   HIPCK(hipMemcpyAsync(h->cat_table.p, hp, nt * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  if (lf_new) {
-    std::memcpy(hp + nt, logfact, nlf * sizeof(double));
-    h->pois_lf_host.clear();             // (stays empty if the copy below fails)
-    HIPCK(hipMemcpyAsync(h->pois_logfact.p, hp + nt, nlf * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    h->pois_lf_host.assign(logfact, logfact + nlf);
-  }
   CK(pin_release(h, slot));
-  h->eK = K; h->eD = D; h->V = 2 * D; h->pois_C = C; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16;
-  set_family(h, EF_POIS);
+  CK(upload_logfact(h, logfact, C));
+  h->pois_C = C;
+  enter_table_family(h, EF_POIS, K, D, 2 * D);
   return 0;
 }
 // D real-valued columns with missing entries, independent Gaussians per state (kernels_pgauss.h).  The family rides the
@@ -897,30 +874,22 @@ int svihmm_set_emission_pgauss(svihmm_ctx* h, int32_t K, int32_t D, const double
   if (D < 1 || D > SVIHMM_PGAUSS_MAX_D)
     return fail(fn + "D = " + std::to_string(D) + " outside [1, SVIHMM_PGAUSS_MAX_D = " +
                 std::to_string(SVIHMM_PGAUSS_MAX_D) + "]");
-  auto finite = [](double v) { return v > -1.7e308 && v < 1.7e308; };
-  auto inside = [](double v) { return v > -SVIHMM_PGAUSS_ABSENT && v < SVIHMM_PGAUSS_ABSENT; };
+  auto inside =[](double v) { return v > -SVIHMM_PGAUSS_ABSENT && v < SVIHMM_PGAUSS_ABSENT; };
   const size_t n = (size_t)K * D;
   for (size_t i = 0; i < n; ++i) {
     const std::string at = "[" + std::to_string(i / D) + "][" + std::to_string(i % D) + "]";
-    if (!finite(mu[i])) return fail(fn + "mu" + at + " is not finite");
-    if (!finite(hprec[i])) return fail(fn + "hprec" + at + " is not finite");
-    if (!finite(cst[i])) return fail(fn + "cst" + at + " is not finite");
+    if (!finite_val(mu[i])) return fail(fn + "mu" + at + " is not finite");
+    if (!finite_val(hprec[i])) return fail(fn + "hprec" + at + " is not finite");
+    if (!finite_val(cst[i])) return fail(fn + "cst" + at + " is not finite");
     if (hprec[i] > 0.0) return fail(fn + "hprec" + at + " is positive (hprec = -0.5 alphas / betas)");
     if (!inside(mu[i])) return fail(fn + "|mu" + at + "| is at or above SVIHMM_PGAUSS_ABSENT");
   }
   for (int d = 0; d < D; ++d) {
-    if (!finite(origin[d])) return fail(fn + "origin[" + std::to_string(d) + "] is not finite");
+    if (!finite_val(origin[d])) return fail(fn + "origin[" + std::to_string(d) + "] is not finite");
     if (!inside(origin[d])) return fail(fn + "|origin[" + std::to_string(d) + "]| is at or above SVIHMM_PGAUSS_ABSENT");
   }
-  CK(set_device(h));
-  h->lin_stale = true;
-  h->center_pending = false;
   // (the resident SVI loop does not know this family: a running loop ends with this upload)
-  if (h->svi_active) CK(svi_flush_elbo(h));
-  h->svi_active = false;
-  if (h->vlb_pending) { HIPCK(hipStreamWaitEvent(h->stream, h->svi_ed, 0)); h->vlb_pending = false; }
-  CK(drop_auto_status(h));
-  CK(cat_uncentre(h, 2));
+  CK(begin_emission_upload(h, EF_PGAUSS, D, own_loop(h, EF_PGAUSS, K, D), 2));
   const size_t nr = n + (size_t)K;           // [D + 1][K]; row D, all +0.0, is what an absent column reads
   const size_t nt = 3 * nr;                  // pairs (mu, hprec), then cst
   CK(ensure(h->cat_table, nt * sizeof(double)));
@@ -941,8 +910,7 @@ int svihmm_set_emission_pgauss(svihmm_ctx* h, int32_t K, int32_t D, const double
   HIPCK(hipMemcpyAsync(h->cat_table.p, hp, nt * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCK(hipMemcpyAsync(h->pg_origin.p, hp + nt, (size_t)D * sizeof(double), hipMemcpyHostToDevice, h->stream));
   CK(pin_release(h, slot));
-  h->eK = K; h->eD = D; h->V = 3 * D; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16;
-  set_family(h, EF_PGAUSS);
+  enter_table_family(h, EF_PGAUSS, K, D, 3 * D);
   return 0;
 }
 int64_t svihmm_packed_len(svihmm_ctx* h) { return h ? (int64_t)packed_len(h) : 0; }
@@ -1122,8 +1090,7 @@ static int wait_side_streams(svihmm_ctx* h) {
   if (h->svi_flags && h->in_svi_estep) return 0;
   CK(svi_flush_elbo(h));
   CK(wait_globals(h));
-  if (h->vlb_pending) { HIPCK(hipStreamWaitEvent(h->stream, h->svi_ed, 0)); h->vlb_pending = false; }
-  return 0;
+  return wait_vlb(h);
 }
 static int run_fb(svihmm_ctx* h, int B, int Lm, int var, bool want_lb, bool total) {
   h->m_nb = 0;
@@ -2100,8 +2067,7 @@ static int svi_refresh_emission(svihmm_ctx* h, int elbo_it, int lb_slot, hipEven
       hipLaunchKernelGGL(k_pois_table, dim3(K), dim3(64), 0, h->stream, (const double*)h->niw.p, K, D,
                          (double2*)h->cat_table.p, tsy);
     HIPCK(hipGetLastError());
-    h->eK = K; h->eD = D; h->Kp = K > 64 ? (K + 63) / 64 * 64 : (K + 15) / 16 * 16;
-    set_family(h, fam);
+    enter_table_family(h, fam, K, D, h->V);
   }
   h->theta_sy = SviSync{};
   h->lin_stale = true;
@@ -2222,13 +2188,7 @@ static int svi_begin_common(svihmm_ctx* h, int K, int D, const double* prior_tra
   }
   CK(ensure(h->svi_state, (3 * kk + 7 * (size_t)K + 16) * sizeof(double)));
   h->svi_adagrad = false;
-  void* pin = nullptr;
-  int slot = 0;
-  CK(pinned(h, 2 * kk * sizeof(double), &pin, &slot));
-  double* hp = (double*)pin;
-  std::memcpy(hp, var_tran, kk * 8); std::memcpy(hp + kk, prior_tran, kk * 8);
-  CK(pull_small(h, svi_ptr(h, 0), hp, 2 * kk * 8));
-  CK(pin_release(h, slot));
+  CK(upload_blocks(h, svi_ptr(h, 0), {{var_tran, kk}, {prior_tran, kk}}));
   if (h->svi_elbo_cap < maxit) {
     if (h->svi_elbo) hipHostFree(h->svi_elbo);
     h->svi_elbo = nullptr; h->svi_elbo_cap = 0;
@@ -2295,19 +2255,6 @@ static int svi_begin_finish(svihmm_ctx* h) {
   h->svi_active = true;
   return 0;
 }
-// upload `n` doubles through a pinned slot into dst (asynchronous, pulled by a kernel)
-static int svi_upload(svihmm_ctx* h, void* dst, const double* a, size_t na, const double* b, size_t nb2,
-                      int centre_K, int centre_D) {
-  void* pin = nullptr;
-  int slot = 0;
-  CK(pinned(h, (na + nb2) * sizeof(double), &pin, &slot));
-  double* hp = (double*)pin;
-  std::memcpy(hp, a, na * 8);
-  if (b) std::memcpy(hp + na, b, nb2 * 8);
-  if (centre_K > 0) to_centred(h, hp, centre_K, centre_D);     // leading [K][D] block = means
-  CK(pull_small(h, dst, hp, (na + nb2) * 8));
-  return pin_release(h, slot);
-}
 
 int svihmm_svi_begin(svihmm_ctx* h, int32_t K, int32_t D, const double* prior_tran, const double* var_tran,
                      const double* mu0, const double* sigma0, const double* kappa0, const double* nu0,
@@ -2322,25 +2269,11 @@ int svihmm_svi_begin(svihmm_ctx* h, int32_t K, int32_t D, const double* prior_tr
   const size_t nin = nmu + nsg + 2 * (size_t)K;
   CK(ensure(h->svi_prior, (nin + 8) * sizeof(double)));
   CK(ensure(h->niw, nin * sizeof(double) + 64));
-  // one staging slot: [prior_logpart | prior block | niw block]
-  const size_t tot = K + 2 * nin;
-  void* pin = nullptr;
-  int slot = 0;
-  CK(pinned(h, tot * sizeof(double), &pin, &slot));
-  double* hp = (double*)pin;
-  std::memcpy(hp, prior_logpart, K * 8);
-  double* pp = hp + K;
-  std::memcpy(pp, mu0, nmu * 8); std::memcpy(pp + nmu, sigma0, nsg * 8);
-  to_centred(h, pp, K, D);             // the loop's state lives in the resident copy's coordinates
-  std::memcpy(pp + nmu + nsg, kappa0, K * 8); std::memcpy(pp + nmu + nsg + K, nu0, K * 8);
-  double* np_ = pp + nin;
-  std::memcpy(np_, mu, nmu * 8); std::memcpy(np_ + nmu, sigma, nsg * 8);
-  to_centred(h, np_, K, D);
-  std::memcpy(np_ + nmu + nsg, kappa, K * 8); std::memcpy(np_ + nmu + nsg + K, nu, K * 8);
-  CK(pull_small(h, svi_ptr(h, 5), hp, K * 8));
-  CK(pull_small(h, h->svi_prior.p, pp, nin * 8));
-  CK(pull_small(h, h->niw.p, np_, nin * 8));
-  CK(pin_release(h, slot));
+  // (the loop's state lives in the resident copy's coordinates: both blocks' means travel centred)
+  const size_t k = (size_t)K;
+  CK(upload_blocks(h, svi_ptr(h, 5), {{prior_logpart, k}}));
+  CK(upload_blocks(h, h->svi_prior.p, {{mu0, nmu}, {sigma0, nsg}, {kappa0, k}, {nu0, k}}, K, D));
+  CK(upload_blocks(h, h->niw.p, {{mu, nmu}, {sigma, nsg}, {kappa, k}, {nu, k}}, K, D));
   return svi_begin_finish(h);
 }
 
@@ -2359,8 +2292,8 @@ int svihmm_svi_begin_diag(svihmm_ctx* h, int32_t K, int32_t D, const double* pri
   CK(svi_begin_common(h, K, D, prior_tran, var_tran, maxit, EF_DIAG));
   CK(ensure(h->svi_prior, (n4 + 8) * sizeof(double)));
   CK(ensure(h->niw, n4 * sizeof(double) + 64));
-  CK(svi_upload(h, h->svi_prior.p, prior_blk, n4, nullptr, 0, K, D));
-  CK(svi_upload(h, h->niw.p, factor_blk, n4, nullptr, 0, K, D));
+  CK(upload_blocks(h, h->svi_prior.p, {{prior_blk, n4}}, K, D));
+  CK(upload_blocks(h, h->niw.p, {{factor_blk, n4}}, K, D));
   return svi_begin_finish(h);
 }
 
@@ -2380,8 +2313,8 @@ int svihmm_svi_begin_cat(svihmm_ctx* h, int32_t K, int32_t V, const double* prio
   CK(ensure(h->svi_prior, (n + 8) * sizeof(double)));
   CK(ensure(h->niw, n * sizeof(double) + 64));
   CK(ensure(h->cat_table, n * sizeof(double)));
-  CK(svi_upload(h, h->svi_prior.p, alpha0, n, nullptr, 0, 0, 0));
-  CK(svi_upload(h, h->niw.p, alpha, n, nullptr, 0, 0, 0));
+  CK(upload_blocks(h, h->svi_prior.p, {{alpha0, n}}));
+  CK(upload_blocks(h, h->niw.p, {{alpha, n}}));
   return svi_begin_finish(h);
 }
 
@@ -2392,23 +2325,11 @@ int svihmm_svi_begin_mcat(svihmm_ctx* h, int32_t K, int32_t D, const int32_t* V,
                           const double* var_tran, const double* alpha0, const double* alpha, int32_t maxit) {
   if (!h || !V || !prior_tran || !var_tran || !alpha0 || !alpha || maxit <= 0)
     return fail("svihmm_svi_begin_mcat: bad arguments");
-  if (K < 1 || K > 256) return fail("svihmm_svi_begin_mcat: K = " + std::to_string(K) + " outside [1, 256]");
-  if (D < 1 || D > SVIHMM_MCAT_MAX_D)
-    return fail("svihmm_svi_begin_mcat: D = " + std::to_string(D) + " outside [1, SVIHMM_MCAT_MAX_D = " +
-                std::to_string(SVIHMM_MCAT_MAX_D) + "]");
-  int64_t F64 = 0;
-  for (int d = 0; d < D; ++d) {
-    if (V[d] < 1)
-      return fail("svihmm_svi_begin_mcat: V[" + std::to_string(d) + "] = " + std::to_string(V[d]) + " (every column needs at least one symbol)");
-    F64 += V[d];
-  }
-  if (F64 > SVIHMM_MCAT_MAX_F)
-    return fail("svihmm_svi_begin_mcat: F = sum of V = " + std::to_string(F64) + " exceeds SVIHMM_MCAT_MAX_F = " +
-                std::to_string(SVIHMM_MCAT_MAX_F));
+  int F = 0;
+  CK(check_mcat_shape("svihmm_svi_begin_mcat", K, D, V, &F));
   if (h->D != D)
     return fail("svihmm_svi_begin_mcat: the family has D = " + std::to_string(D) + " symbol columns, the resident observations have " +
                 std::to_string(h->D));
-  const int F = (int)F64;
   const size_t n = (size_t)K * F;
   for (size_t i = 0; i < n; ++i)       // (validated before any state is touched)
     if (!(alpha0[i] > 0.0) || !(alpha[i] > 0.0)) return fail("svihmm_svi_begin_mcat: Dirichlet parameters must be positive");
@@ -2416,19 +2337,12 @@ int svihmm_svi_begin_mcat(svihmm_ctx* h, int32_t K, int32_t D, const int32_t* V,
   h->V = F;
   h->svi_mcat_V.assign(V, V + D);
   CK(cat_uncentre(h, 0));
-  const size_t nmeta = 2 * (size_t)D + 2 * (size_t)F;
   CK(ensure(h->svi_prior, (n + 8) * sizeof(double)));
   CK(ensure(h->niw, n * sizeof(double) + 64));
   CK(ensure(h->cat_table, n * sizeof(double)));
-  CK(ensure(h->mcat_meta, nmeta * sizeof(int)));
-  void* pin = nullptr;
-  int slot = 0;
-  CK(pinned(h, nmeta * sizeof(int), &pin, &slot));
-  mcat_fill_meta((int*)pin, D, F, V);
-  HIPCK(hipMemcpyAsync(h->mcat_meta.p, pin, nmeta * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  CK(pin_release(h, slot));
-  CK(svi_upload(h, h->svi_prior.p, alpha0, n, nullptr, 0, 0, 0));
-  CK(svi_upload(h, h->niw.p, alpha, n, nullptr, 0, 0, 0));
+  CK(upload_mcat_meta(h, D, F, V));
+  CK(upload_blocks(h, h->svi_prior.p, {{alpha0, n}}));
+  CK(upload_blocks(h, h->niw.p, {{alpha, n}}));
   return svi_begin_finish(h);
 }
 
@@ -2440,17 +2354,7 @@ int svihmm_svi_begin_poisson(svihmm_ctx* h, int32_t K, int32_t D, const double* 
                              int32_t maxit) {
   if (!h || !prior_tran || !var_tran || !prior_blk || !factor_blk || !logfact || maxit <= 0)
     return fail("svihmm_svi_begin_poisson: bad arguments");
-  if (K < 1 || K > 256) return fail("svihmm_svi_begin_poisson: K = " + std::to_string(K) + " outside [1, 256]");
-  if (D < 1 || D > SVIHMM_POISSON_MAX_D)
-    return fail("svihmm_svi_begin_poisson: D = " + std::to_string(D) + " outside [1, SVIHMM_POISSON_MAX_D = " +
-                std::to_string(SVIHMM_POISSON_MAX_D) + "]");
-  if (C < 0 || C > SVIHMM_POISSON_MAX_COUNT)
-    return fail("svihmm_svi_begin_poisson: C = " + std::to_string(C) + " outside [0, SVIHMM_POISSON_MAX_COUNT = " +
-                std::to_string(SVIHMM_POISSON_MAX_COUNT) + "]");
-  const size_t nlf = (size_t)C + 1;
-  for (size_t c = 0; c < nlf; ++c)
-    if (!(logfact[c] > -1.7e308 && logfact[c] < 1.7e308))
-      return fail("svihmm_svi_begin_poisson: logfact[" + std::to_string(c) + "] is not finite");
+  CK(check_poisson_shape("svihmm_svi_begin_poisson", K, D, C, logfact));
   if (h->D != D)
     return fail("svihmm_svi_begin_poisson: the family has D = " + std::to_string(D) + " count columns, the resident observations have " +
                 std::to_string(h->D));
@@ -2464,20 +2368,9 @@ int svihmm_svi_begin_poisson(svihmm_ctx* h, int32_t K, int32_t D, const double* 
   CK(ensure(h->svi_prior, (n2 + 8) * sizeof(double)));
   CK(ensure(h->niw, n2 * sizeof(double) + 64));
   CK(ensure(h->cat_table, (n2 + 2 * (size_t)K) * sizeof(double)));
-  // (the device copy of the logfact table stays while the caller's holds the same bits: svihmm_set_emission_poisson)
-  if (h->pois_lf_host.size() != nlf || std::memcmp(h->pois_lf_host.data(), logfact, nlf * sizeof(double)) != 0) {
-    CK(ensure(h->pois_logfact, nlf * sizeof(double)));
-    void* pin = nullptr;
-    int slot = 0;
-    CK(pinned(h, nlf * sizeof(double), &pin, &slot));
-    std::memcpy(pin, logfact, nlf * sizeof(double));
-    h->pois_lf_host.clear();             // (stays empty if the copy below fails)
-    HIPCK(hipMemcpyAsync(h->pois_logfact.p, pin, nlf * sizeof(double), hipMemcpyHostToDevice, h->stream));
-    h->pois_lf_host.assign(logfact, logfact + nlf);
-    CK(pin_release(h, slot));
-  }
-  CK(svi_upload(h, h->svi_prior.p, prior_blk, n2, nullptr, 0, 0, 0));
-  CK(svi_upload(h, h->niw.p, factor_blk, n2, nullptr, 0, 0, 0));
+  CK(upload_logfact(h, logfact, C));
+  CK(upload_blocks(h, h->svi_prior.p, {{prior_blk, n2}}));
+  CK(upload_blocks(h, h->niw.p, {{factor_blk, n2}}));
   return svi_begin_finish(h);
 }
 
@@ -2676,7 +2569,7 @@ static int svi_iteration_impl(svihmm_ctx* h, int32_t it, const int64_t* starts, 
       HIPCK(hipStreamWaitEvent(h->stream, h->svi_ed, 0));
       ssy.gate = nullptr;
     }
-  } else if (h->vlb_pending) { HIPCK(hipStreamWaitEvent(h->stream, h->svi_ed, 0)); h->vlb_pending = false; }
+  } else CK(wait_vlb(h));
   double* adag = h->svi_adagrad ? svi_ptr(h, 9) : (double*)nullptr;
   SviStepArgs sargs = {(const double*)h->packed.p, (const double*)svi_ptr(h, 1), svi_ptr(h, 0), (const double*)h->svi_prior.p,
                        rho, bfactA, bfactE, (double)nwin_total, svi_ptr(h, 8) + (it & 1), adag, ssy,
@@ -2738,12 +2631,7 @@ int svihmm_svi_set_adagrad(svihmm_ctx* h, const double* ada_G) {
   // var_tran leave the range svi_begin_common checked for the linear-domain recursions
   for (size_t i = 0; i < kk; ++i)
     if (!(ada_G[i] >= 1.0 && ada_G[i] < 1.7e308)) return fail("svihmm_svi_set_adagrad: ada_G must be finite and >= 1");
-  void* pin = nullptr;
-  int slot = 0;
-  CK(pinned(h, kk * sizeof(double), &pin, &slot));
-  std::memcpy(pin, ada_G, kk * sizeof(double));
-  CK(pull_small(h, svi_ptr(h, 9), pin, kk * sizeof(double)));
-  CK(pin_release(h, slot));
+  CK(upload_blocks(h, svi_ptr(h, 9), {{ada_G, kk}}));
   h->svi_adagrad = true;               // (only once the accumulator is on its way)
   return 0;
 }
@@ -2797,8 +2685,8 @@ int svihmm_svi_sequences(svihmm_ctx* h, const double* prior_init, const double* 
   // everything in flight first: begin's globals kernel writes the stationary vector into the slot var_init takes
   CK(svi_settle(h));
   if (h->svi_flags) CK(svi_leave_counters(h));
-  CK(svi_upload(h, svi_ptr(h, 2), var_init, (size_t)K, nullptr, 0, 0, 0));
-  CK(svi_upload(h, svi_ptr(h, 10), prior_init, (size_t)K, nullptr, 0, 0, 0));
+  CK(upload_blocks(h, svi_ptr(h, 2), {{var_init, (size_t)K}}));
+  CK(upload_blocks(h, svi_ptr(h, 10), {{prior_init, (size_t)K}}));
   {   // lgamma(sum_k p_k + eps) - sum_k lgamma(p_k + eps): the prior-only part of the initial factor's energy
     double sum = 0.0, lg = 0.0;
     for (int k = 0; k < K; ++k) { sum += prior_init[k]; lg += std::lgamma(prior_init[k] + 1e-9); }
@@ -2865,7 +2753,7 @@ int svihmm_svi_iteration_sequences(svihmm_ctx* h, int32_t it, const int32_t* idx
   CK(subset_enqueue(h, p, M, flags, true));
   // the previous iteration's ELBO kernels (their own stream) read var_tran / var_init / theta / logdet, which the step
   // and the theta builder rewrite: the stream waits for their event
-  if (h->vlb_pending) { HIPCK(hipStreamWaitEvent(h->stream, h->svi_ed, 0)); h->vlb_pending = false; }
+  CK(wait_vlb(h));
   const bool merged = h->svi_family == EF_NIW && step_theta_ok(h, K, D);
   const unsigned ntran = (unsigned)((K * K + 255) / 256);
   const SviSeqStep sq = svi_seq_args(h, M);
@@ -3558,7 +3446,7 @@ int svihmm_generate(svihmm_ctx* h, int64_t T, int32_t K, int32_t D, const double
     if (h->variant[SVIHMM_VAR_CENTRING] != SVIHMM_CENTRING_OFF && !(h->have_emission && fam_table(h->fam))) {
       for (int k = 0; k < K; ++k)
         for (int d = 0; d < D; ++d) c[d] += means[(size_t)k * D + d] / K;
-      for (int d = 0; d < D; ++d) if (!(c[d] > -1.7e308 && c[d] < 1.7e308)) c[d] = 0.0;
+      for (int d = 0; d < D; ++d) if (!finite_val(c[d])) c[d] = 0.0;
     }
     CK(reset_shift(h, c, 0, T));
   }
@@ -3649,12 +3537,7 @@ int svihmm_import_packed(svihmm_ctx* h, const double* packed_in) {
   const bool sh = common_needs_shift(h, true);
   if (sh) CK(ensure(h->commtmp, nb));
   double* dst = sh ? (double*)h->commtmp.p : (double*)h->packed.p;
-  void* pin = nullptr;
-  int slot = 0;
-  CK(pinned(h, nb, &pin, &slot));
-  std::memcpy(pin, packed_in, nb);
-  CK(pull_small(h, dst, pin, nb));
-  CK(pin_release(h, slot));
+  CK(upload_blocks(h, dst, {{packed_in, packed_len(h)}}));
   CK(packed_from_common(h, dst));
   h->have_packed = true;
   h->mirror_valid = false;
