@@ -392,6 +392,33 @@ int svihmm_estep_sequence_subset(svihmm_ctx* h, const int32_t* idx, int32_t M, u
  *   is left as set.  With no labels set nothing changes: the same kernels are chosen and the same bits result. */
 int svihmm_set_labels(svihmm_ctx* h, const int32_t* labels);
 
+/* svihmm_set_state_sets: allowed-state sets per resident row -- the weaker statement than a label: "this region is one
+ *   of these three states", "this epoch is anything but state 0", "these trials never visit states 4-7".
+ *   allowed: host uint64 [T][W], W = (K + 63) / 64.  Bit k % 64 of word k / 64 of row t says that state k is allowed
+ *   at row t; a row with all K bits set is free.  NULL removes the sets (K is then ignored).  svihmm_set_obs,
+ *   svihmm_alloc_obs and svihmm_generate remove them as well; svihmm_set_obs_rows and svihmm_set_sequences keep them.
+ *   Sets and labels are alternatives: a successful call with a non-NULL array removes labels, a successful
+ *   svihmm_set_labels with a non-NULL array removes sets; NULL to either removes only its own kind.
+ *   Fails with a message, whatever was in force staying in force: no observations; K outside [1, 256]; a row that
+ *   allows no state; a bit at or beyond K set in a row's last word (the message gives the first offending row, found
+ *   in one pass over the array).
+ *   The sets live in HBM as uint64 [T][W]; the host keeps K only.
+ *   While sets are in force every call that evaluates lliks on the device sees
+ *       ll[t][k] = allowed(t, k) ? ll[t][k] : -inf,
+ *   a select applied after the family's llik and after SVIHMM_MASK_AS_NAN, so the kept entries have their original
+ *   bits; a masked constrained row means "state in this set, observation missing".  As with labels, such a call is
+ *   defined to give what the same call gives under SVIHMM_USE_HOST_LLIKS on exactly those clamped lliks, wherever that
+ *   call exists; a row whose set holds one state is a labelled row, bit for bit.
+ *   Honoured by, unaffected by and refused by the same calls as labels (svihmm_set_labels above); the refusals of
+ *   svihmm_svi_iteration, svihmm_svi_iteration_sequences, svihmm_grow_windows and svihmm_pred_logprob name this call,
+ *   and an E-step-type call whose globals have a K other than the sets' K fails with a message that gives both.
+ *   svihmm_estep_sequence_subset gathers the listed sequences' mask rows with their rows.
+ *   A set none of whose states has positive probability under mod_init, ltran and the row's llik leaves that window's
+ *   results unspecified (-inf or NaN, never a fault).
+ *   fp32 mode: a constrained batch runs in fp64 and svihmm_get_precision reports last_batch_f32 = 0; the mode itself
+ *   is left as set.  With neither labels nor sets nothing changes: the same kernels and the same bits. */
+int svihmm_set_state_sets(svihmm_ctx* h, const uint64_t* allowed, int32_t K);
+
 /* svihmm_viterbi_sequences: the MAP state path of EVERY declared sequence (svihmm_set_sequences) in one call, under
  *   the globals currently set and the current emission family.
  *   out_z: host int32[T], row r holds the state of resident row r (the sequences laid end to end, as declared);

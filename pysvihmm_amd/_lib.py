@@ -82,6 +82,7 @@ SIGNATURES = {
     "svihmm_estep_sequence_subset": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32, C.c_uint32, _c_double_p,
                                                _c_double_p, _c_double_p]),
     "svihmm_set_labels": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32)]),
+    "svihmm_set_state_sets": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int32]),
     "svihmm_viterbi_sequences": (C.c_int, [C.c_void_p, C.c_uint32, C.c_void_p, _c_double_p]),
     "svihmm_ffbs_sequences": (C.c_int, [C.c_void_p, C.c_uint32, _c_double_p, C.c_int32, _c_double_p, C.c_uint64,
                                         C.c_void_p, _c_double_p]),

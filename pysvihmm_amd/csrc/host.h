@@ -214,6 +214,12 @@ struct svihmm_ctx {
   Buf labels, sub_labels;
   bool have_labels = false;
   int32_t label_max = -1; int64_t label_max_row = -1;
+  // svihmm_set_state_sets: allowed-state sets of the resident rows, uint64 [T][sets_W] in HBM, sets_W =
+  // (sets_K + 63) / 64, bit k % 64 of word k / 64 set where state k is allowed.  The alternative to labels: at most one
+  // of have_labels / have_sets holds.  sub_sets: the listed sequences' mask rows, as sub_labels
+  Buf sets, sub_sets;
+  bool have_sets = false;
+  int32_t sets_K = 0, sets_W = 0;
   // svihmm_viterbi_sequences / svihmm_ffbs_sequences: the launch tables (sequence orders, pad_off, chunk table) on the
   // device and their host image (alive until the call's final synchronisation); dec_result: the intermediates held are
   // such a call's -- the lliks of all T rows only (1: _viterbi_sequences, 2: _ffbs_sequences; prepare_ll drops it)
@@ -440,6 +446,10 @@ inline int lin_wave_max(const svihmm_ctx* h) { return 4 * h->ncu + 1; }
 inline int lin_wave4_max(const svihmm_ctx* h) { return h->ncu; }
 // up to this many windows: the register-resident one-wave kernel (k_wave_linr; round 5)
 inline int lin_waver_max(const svihmm_ctx* h) { return h->ncu; }
+// a clamp of the device lliks is in force: labels (svihmm_set_labels) or allowed-state sets (svihmm_set_state_sets).
+// Every routing decision and every clearing site asks this, or calls drop_clamp, so that none forgets one of the kinds
+inline bool clamp_in_force(const svihmm_ctx* h) { return h->have_labels || h->have_sets; }
+inline void drop_clamp(svihmm_ctx* h) { h->have_labels = false; h->have_sets = false; }
 
 extern "C" {
 int d2h(svihmm_ctx* h, void* dst, const void* src, size_t bytes);
@@ -451,6 +461,8 @@ int flush_lb(svihmm_ctx* h, hipStream_t stream);
 int launch_diag_to_theta(svihmm_ctx* h, int K, int D);
 int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled = false, const int64_t* starts_dev = nullptr, double* out = nullptr, double* kexp_out = nullptr, hipStream_t stream = nullptr, size_t min_lds = 0, double* ll0_out = nullptr, bool clamp_labels = true);
 int check_labels_fit(const svihmm_ctx* h);
+int check_sets_fit(const svihmm_ctx* h);
+int check_clamp_fit(const svihmm_ctx* h);
 int launch_fb(svihmm_ctx* h, int B, int Lm, int dir0, int ndir, const double* ll = nullptr, double* la = nullptr, double* lb = nullptr);
 int launch_fb_fused(svihmm_ctx* h, int B, int Lm, bool want_lb, bool total);
 bool emission_row_tile_orbit(const svihmm_ctx* h, int64_t n);
@@ -508,7 +520,7 @@ int launch_fb_sequences(svihmm_ctx* h, int nseq, const int32_t* order, const int
 int launch_seq_finish(svihmm_ctx* h, int N, const int64_t* seq_off, bool wrap, const double* q, const double* seq_lb,
                       double* q0);
 int launch_seq_gather(svihmm_ctx* h, int M, const int64_t* tab, int maxlen, double* obs_out, uint8_t* mask_out,
-                      int32_t* labels_out);
+                      int32_t* labels_out, uint64_t* sets_out);
 int64_t viterbi_sequences_chunks(const svihmm_ctx* h);
 int launch_viterbi_sequences(svihmm_ctx* h, const double* ll, bool want_z, int32_t** dz_out, double** dscore_out);
 int launch_ffbs_sequences(svihmm_ctx* h, uint32_t flags, const double* logA, int S, const double* uniforms, uint64_t seed,

@@ -4,6 +4,10 @@
 //                     has its original bits, and a free row costs its label load alone.
 //   k_label_gather    svihmm_estep_sequence_subset: the listed sequences' labels into the compact copy's order
 //                     (k_seq_gather's sibling, launched with its grid)
+// and allowed-state sets (svihmm_set_state_sets): a K-bit mask per resident row, uint64 [T][W], W = (K + 63) / 64,
+// bit k % 64 of word k / 64 set where state k is allowed
+//   k_set_clamp       k_label_clamp's sibling in the same frame: ll[g][k] = -inf wherever bit k of row g is clear
+//   k_set_gather      k_label_gather's sibling: W words per row
 // Each kernel is compiled into the one translation unit that launches it: tu_emission.hip defines
 // SVIHMM_LABELS_CLAMP, tu_recursion.hip SVIHMM_LABELS_GATHER (as kernels_mcat.h splits its halves).
 #pragma once
@@ -43,6 +47,54 @@ __global__ __launch_bounds__(256) void k_label_clamp(const int32_t* __restrict__
   }
 }
 
+// grid ceil(n / LC_ROWS), block 256, rows found as in k_label_clamp.  W = (K + 63) / 64 <= SC_WMAX words per row.  The
+// workgroup's LC_ROWS * W mask words are read once into LDS, one word per thread.  Each wave owns 16 rows: its lanes
+// 0 .. 15 test one row each for a word that is not all ones within K, and the ballot of those tests is the wave's list
+// of constrained rows -- a free row costs its word loads and that one test, no trip of a loop.  The wave then visits
+// the listed rows only, lane = state within a group of 64: the group's word is uniform over the wave, the lane tests
+// its own bit and stores -inf where it is clear.  The bits of the last word at or beyond K are zero by contract; the
+// k < K test keeps those lanes from storing.  A row past n is never listed.  Nothing is read from ll.  64-bit element
+// offsets throughout.
+constexpr int SC_WMAX = 4;       // K <= 256
+__global__ __launch_bounds__(256) void k_set_clamp(const unsigned long long* __restrict__ sets,
+                                                   const int64_t* __restrict__ starts, int64_t n, int Lm, int K, int W,
+                                                   double* __restrict__ ll) {
+  __shared__ unsigned long long msk[LC_ROWS * SC_WMAX];
+  const int64_t g0 = (int64_t)blockIdx.x * LC_ROWS;
+  if ((int)threadIdx.x < LC_ROWS * W) {
+    const int r = threadIdx.x / W, j = threadIdx.x - r * W;
+    const int64_t g = g0 + r;
+    unsigned long long v = ~0ull;
+    if (g < n) {
+      const int64_t w = g / Lm;
+      v = sets[(starts[w] + (g - w * Lm)) * (int64_t)W + j];
+    }
+    msk[threadIdx.x] = v;
+  }
+  __syncthreads();
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int r0 = wave * (LC_ROWS / 4);
+  const int tail = K - (W - 1) * 64;            // states of the last word: 1 .. 64
+  const unsigned long long full_tail = tail == 64 ? ~0ull : (1ull << tail) - 1ull;
+  bool constrained = false;
+  if (lane < LC_ROWS / 4 && g0 + r0 + lane < n) {
+    const unsigned long long* m = msk + (r0 + lane) * W;
+    for (int j = 0; j < W; ++j) constrained |= m[j] != (j == W - 1 ? full_tail : ~0ull);
+  }
+  unsigned long long todo = __ballot(constrained);       // (uniform over the wave: bit i stands for row r0 + i)
+  const double ninf = -__builtin_huge_val();
+  while (todo) {
+    const int r = r0 + __builtin_ctzll(todo);
+    todo &= todo - 1;
+    double* __restrict__ row = ll + (g0 + r) * (int64_t)K;
+    for (int j = 0; j < W; ++j) {
+      const unsigned long long word = msk[r * W + j];
+      const int k = j * 64 + lane;
+      if (k < K && !((word >> lane) & 1ull)) row[k] = ninf;
+    }
+  }
+}
+
 #endif  // SVIHMM_LABELS_CLAMP
 
 #ifdef SVIHMM_LABELS_GATHER
@@ -56,5 +108,15 @@ __global__ __launch_bounds__(256) void k_label_gather(const int32_t* __restrict_
   const int64_t d0 = dst_off[m], len = dst_off[m + 1] - d0, s0 = src_off[m];
   const int64_t tid = (int64_t)blockIdx.y * 256 + threadIdx.x, nthr = (int64_t)gridDim.y * 256;
   for (int64_t i = tid; i < len; i += nthr) labels_out[d0 + i] = labels[s0 + i];
+}
+// the same grid; occurrence m's len * W words are contiguous in both copies
+__global__ __launch_bounds__(256) void k_set_gather(const unsigned long long* __restrict__ sets,
+                                                    const int64_t* __restrict__ dst_off,
+                                                    const int64_t* __restrict__ src_off, int W,
+                                                    unsigned long long* __restrict__ sets_out) {
+  const int m = blockIdx.x;
+  const int64_t d0 = dst_off[m] * W, len = dst_off[m + 1] * W - d0, s0 = src_off[m] * W;
+  const int64_t tid = (int64_t)blockIdx.y * 256 + threadIdx.x, nthr = (int64_t)gridDim.y * 256;
+  for (int64_t i = tid; i < len; i += nthr) sets_out[d0 + i] = sets[s0 + i];
 }
 #endif  // SVIHMM_LABELS_GATHER

@@ -86,7 +86,8 @@ int svihmm_destroy(svihmm_ctx* h) {
                  &h->pipe_tabs[0].buf, &h->pipe_tabs[1].buf, &h->pipe_tabs[2].buf, &h->pipe_tabs[3].buf,
                  &h->pipe_tabs[4].buf, &h->pipe_tabs[5].buf, &h->pipe_tabs[6].buf, &h->pipe_tabs[7].buf,
                  &h->seq_off_d, &h->seq_q, &h->seq_work, &h->seq_ord, &h->seq_out, &h->dec_tab,
-                 &h->sub_obs, &h->sub_mask, &h->sub_tab, &h->heldout, &h->labels, &h->sub_labels};
+                 &h->sub_obs, &h->sub_mask, &h->sub_tab, &h->heldout, &h->labels, &h->sub_labels,
+                 &h->sets, &h->sub_sets};
   for (Buf* b : bufs) release(*b);
   if (h->vlb_host) { hipHostFree(h->vlb_host); h->vlb_host = nullptr; }
   if (h->svi_elbo) { hipHostFree(h->svi_elbo); h->svi_elbo = nullptr; }
@@ -203,7 +204,7 @@ int svihmm_set_obs(svihmm_ctx* h, const double* obs, int64_t T, int32_t D,
     HIPCK(hipMemcpyAsync(h->mask.p, mask, (size_t)T, hipMemcpyHostToDevice, h->stream));
   }
   h->T = T; h->D = D; h->gen_T = 0;
-  h->have_labels = false;              // (labels described the previous rows)
+  drop_clamp(h);                       // (labels / allowed-state sets described the previous rows)
   h->post_kind = 0;                    // (a held posterior batch described the previous rows)
   h->seq_off.clear();                  // (a declaration of sequences described the previous rows)
   h->svi_active = false;               // a resident SVI state belonged to the previous sequence
@@ -380,7 +381,7 @@ int svihmm_alloc_obs(svihmm_ctx* h, int64_t T, int32_t D, int32_t with_mask) {
     HIPCK(hipMemsetAsync(h->mask.p, 0, (size_t)T, h->stream));
   }
   h->T = T; h->D = D; h->gen_T = 0;
-  h->have_labels = false;
+  drop_clamp(h);
   h->post_kind = 0;
   h->seq_off.clear();
   h->svi_active = false;
@@ -433,8 +434,43 @@ int svihmm_set_labels(svihmm_ctx* h, const int32_t* labels) {
   CK(upload_staged(h, h->labels.p, labels, (size_t)h->T * sizeof(int32_t)));
   HIPCK(hipStreamSynchronize(h->stream));
   h->have_labels = true;
+  h->have_sets = false;                // (labels and allowed-state sets are alternatives)
   h->label_max = mx; h->label_max_row = mx_row;
   h->lin_stale = true;                 // (lliks held were evaluated under the previous labels)
+  return 0;
+}
+
+// Allowed-state sets of the resident rows (include/svihmm.h): one pass over the host array finds the first offending
+// row before the upload, so a refused call leaves whatever was in force as it was.
+int svihmm_set_state_sets(svihmm_ctx* h, const uint64_t* allowed, int32_t K) {
+  const char* fn = "svihmm_set_state_sets";
+  const auto bad = [fn](const std::string& what) { return fail(std::string(fn) + ": " + what); };
+  if (!h) return bad("NULL handle");
+  if (!allowed) { h->have_sets = false; h->lin_stale = true; return 0; }
+  if (h->T <= 0 || !h->obs.p) return bad("no observations: call svihmm_set_obs first");
+  if (K < 1 || K > 256) return bad("K = " + std::to_string(K) + " is outside [1, 256]");
+  const int W = (K + 63) / 64, tail = K - (W - 1) * 64;
+  const uint64_t beyond = tail == 64 ? 0ull : ~0ull << tail;       // the last word's bits at or beyond K
+  for (int64_t t = 0; t < h->T; ++t) {
+    const uint64_t* row = allowed + t * W;
+    if (row[W - 1] & beyond) {
+      const int k = (W - 1) * 64 + __builtin_ctzll(row[W - 1] & beyond);
+      return bad("row " + std::to_string(t) + " has bit " + std::to_string(k) + " set, at or beyond K = " +
+                 std::to_string(K) + " (the padding bits of the last word must be zero)");
+    }
+    uint64_t any = 0;
+    for (int j = 0; j < W; ++j) any |= row[j];
+    if (!any) return bad("row " + std::to_string(t) + " allows no state (a free row has all K bits set)");
+  }
+  const size_t bytes = (size_t)h->T * W * sizeof(uint64_t);
+  CK(set_device(h));
+  CK(ensure(h->sets, bytes));
+  CK(upload_staged(h, h->sets.p, allowed, bytes));
+  HIPCK(hipStreamSynchronize(h->stream));
+  h->have_sets = true;
+  h->have_labels = false;              // (labels and allowed-state sets are alternatives)
+  h->sets_K = K; h->sets_W = W;
+  h->lin_stale = true;                 // (lliks held were evaluated under the previous clamp)
   return 0;
 }
 
@@ -1157,7 +1193,7 @@ int prepare_ll(svihmm_ctx* h, const int64_t* starts, int B, int Lm, uint32_t fla
                       bool need_obs_for_stats, bool lin) {
   if (!h->have_globals) return fail("no globals: call svihmm_set_globals");
   const bool host_ll = flags & SVIHMM_USE_HOST_LLIKS;
-  if (!host_ll) CK(check_labels_fit(h));
+  if (!host_ll) CK(check_clamp_fit(h));
   CK(check_windows(h, starts, B, Lm, !host_ll || need_obs_for_stats));
   if (starts) CK(upload_starts(h, starts, B));
   h->f32_report_hold = -1;
@@ -1174,9 +1210,10 @@ int prepare_ll(svihmm_ctx* h, const int64_t* starts, int B, int Lm, uint32_t fla
   } else {
     // K <= 64: the emission kernel owns whole rows and writes (Eh, kexp) itself; wider
     // models take the plain kernel plus one scaling pass
-    // (a labelled batch -- svihmm_set_labels -- as well: the clamp follows the plain kernel, there is no scaled output
-    //  under labels; such a batch runs in fp64 and in the row-major layout)
-    const bool labelled = h->have_labels;
+    // (a labelled batch -- svihmm_set_labels -- or one under allowed-state sets -- svihmm_set_state_sets -- as well: the
+    //  clamp follows the plain kernel, there is no scaled output under a clamp; such a batch runs in fp64 and in the
+    //  row-major layout)
+    const bool labelled = clamp_in_force(h);
     const bool two_pass = lin && (h->Kp > 64 || fam_table(h->fam) || labelled);
     // fp32 mode: scaled messages stored as float + fp32 statistics GEMM, for what the mode
     // covers (NIW emission, K <= 64, window batches on the scaled sweeps; round 5: wide NIW models
@@ -1197,7 +1234,7 @@ int prepare_ll(svihmm_ctx* h, const int64_t* starts, int B, int Lm, uint32_t fla
     else if (two_pass) CK(launch_scale_ll(h, B, Lm));
     h->have_host_ll = false;
   }
-  h->eh_in_llE = lin && (host_ll || (h->Kp > 64 && !h->cur_f32) || fam_table(h->fam) || h->have_labels);
+  h->eh_in_llE = lin && (host_ll || (h->Kp > 64 && !h->cur_f32) || fam_table(h->fam) || clamp_in_force(h));
   h->lin_mode = lin;
   h->lin_stale = false;
   h->q_valid = false;
@@ -1327,7 +1364,7 @@ static int allreduce_packed_dev(svihmm_ctx* h) {
 static bool use_pipeline(const svihmm_ctx* h, int B, int Lm, int fbvar, uint32_t flags) {
   const int v = h->variant[SVIHMM_VAR_PIPELINE];
   if (v == SVIHMM_PIPELINE_UNFUSED || fbvar != SVIHMM_FB_SCALED || (flags & SVIHMM_USE_HOST_LLIKS)) return false;
-  if (h->Kp > 64 || h->D > 64 || fam_table(h->fam) || h->have_labels) return false;
+  if (h->Kp > 64 || h->D > 64 || fam_table(h->fam) || clamp_in_force(h)) return false;
   const int sv = h->variant[SVIHMM_VAR_STATS];
   if (sv != 0 && sv != SVIHMM_STATS_PIPELINED) return false;
   // opt-in only: on MI355X the sweeps' fp64 VALU work queues behind the GEMMs' MFMAs on a
@@ -1432,6 +1469,9 @@ int svihmm_pred_logprob(svihmm_ctx* h, const int64_t* starts, int32_t B, int32_t
   if (h->have_labels)
     return fail("svihmm_pred_logprob: labels are in force (svihmm_set_labels) and this call does not take them; "
                 "svihmm_heldout_rows scores masked rows against a labelled E-step's posteriors");
+  if (h->have_sets)
+    return fail("svihmm_pred_logprob: allowed-state sets are in force (svihmm_set_state_sets) and this call does not "
+                "take them; svihmm_heldout_rows scores masked rows against a constrained E-step's posteriors");
   if (h->have_emission && FAM_TRAITS[h->fam].noun)
     return fail(std::string("svihmm_pred_logprob: NIW emission only (") + FAM_TRAITS[h->fam].noun + " of " +
                 FAM_TRAITS[h->fam].setter + " is not taken)");
@@ -1775,14 +1815,14 @@ struct SubsetView {
   svihmm_ctx* h; int64_t T; std::vector<int64_t> seq_off;
   SubsetView(svihmm_ctx* h_, int64_t R, std::vector<int64_t>& compact) : h(h_), T(h_->T) {
     std::swap(h->obs, h->sub_obs); std::swap(h->mask, h->sub_mask); std::swap(h->seq_off_d, h->sub_tab);
-    std::swap(h->labels, h->sub_labels);
+    std::swap(h->labels, h->sub_labels); std::swap(h->sets, h->sub_sets);
     seq_off.swap(h->seq_off);
     h->seq_off.swap(compact);
     h->T = R;
   }
   ~SubsetView() {
     std::swap(h->obs, h->sub_obs); std::swap(h->mask, h->sub_mask); std::swap(h->seq_off_d, h->sub_tab);
-    std::swap(h->labels, h->sub_labels);
+    std::swap(h->labels, h->sub_labels); std::swap(h->sets, h->sub_sets);
     h->seq_off.swap(seq_off);
     h->T = T;
   }
@@ -1834,8 +1874,9 @@ static int subset_enqueue(svihmm_ctx* h, const SubsetPlan& p, int M, uint32_t fl
   CK(ensure(h->sub_tab, p.tab.size() * sizeof(int64_t)));
   CK(upload_staged(h, h->sub_tab.p, p.tab.data(), p.tab.size() * sizeof(int64_t)));
   if (h->have_labels) CK(ensure(h->sub_labels, (size_t)R * sizeof(int32_t)));
+  if (h->have_sets) CK(ensure(h->sub_sets, (size_t)R * h->sets_W * sizeof(uint64_t)));
   CK(launch_seq_gather(h, M, (const int64_t*)h->sub_tab.p, (int)p.maxlen, (double*)h->sub_obs.p, (uint8_t*)h->sub_mask.p,
-                       (int32_t*)h->sub_labels.p));
+                       (int32_t*)h->sub_labels.p, (uint64_t*)h->sub_sets.p));
   std::vector<int64_t> compact(p.tab.begin(), p.tab.begin() + M + 1);
   {
     SubsetView view(h, R, compact);
@@ -2449,6 +2490,10 @@ int svihmm_svi_iteration(svihmm_ctx* h, int32_t it, const int64_t* starts, int32
     return fail("svihmm_svi_iteration: labels are in force (svihmm_set_labels) and the resident SVI loop does not "
                 "take them; remove them with svihmm_set_labels(h, NULL) or step on the host from "
                 "svihmm_estep_minibatch's statistics");
+  if (h && h->have_sets)
+    return fail("svihmm_svi_iteration: allowed-state sets are in force (svihmm_set_state_sets) and the resident SVI "
+                "loop does not take them; remove them with svihmm_set_state_sets(h, NULL, 0) or step on the host from "
+                "svihmm_estep_minibatch's statistics");
   if (h && !h->svi_active && h->have_emission && FAM_TRAITS[h->fam].noun) {
     const FamTraits& t = FAM_TRAITS[h->fam];
     const std::string head = std::string("svihmm_svi_iteration: the resident SVI loop does not take ") + t.noun;
@@ -2724,6 +2769,10 @@ int svihmm_svi_iteration_sequences(svihmm_ctx* h, int32_t it, const int32_t* idx
     return fail("svihmm_svi_iteration_sequences: labels are in force (svihmm_set_labels) and the resident SVI loop does not "
                 "take them; remove them with svihmm_set_labels(h, NULL) or step on the host from "
                 "svihmm_estep_sequence_subset's statistics");
+  if (h->have_sets)
+    return fail("svihmm_svi_iteration_sequences: allowed-state sets are in force (svihmm_set_state_sets) and the "
+                "resident SVI loop does not take them; remove them with svihmm_set_state_sets(h, NULL, 0) or step on "
+                "the host from svihmm_estep_sequence_subset's statistics");
   if (!h->svi_active) return bad("no loop: call one of svihmm_svi_begin* and svihmm_svi_sequences first");
   if (!h->svi_seq) return bad("the loop steps on windows: call svihmm_svi_sequences first");
   if (it < 0 || it >= h->svi_maxit)
@@ -3353,6 +3402,9 @@ int svihmm_grow_windows(svihmm_ctx* h, const int64_t* centers, int32_t n, int32_
   if (h->have_labels)
     return bad("labels are in force (svihmm_set_labels) and the growth rules do not take them; remove them with "
                "svihmm_set_labels(h, NULL)");
+  if (h->have_sets)
+    return bad("allowed-state sets are in force (svihmm_set_state_sets) and the growth rules do not take them; remove "
+               "them with svihmm_set_state_sets(h, NULL, 0)");
   if (!centers || !out_half) return bad("centers and out_half must be given");
   if (n < 1) return bad("n must be positive");
   if (increment < 1) return bad("increment must be positive");
@@ -3436,7 +3488,7 @@ int svihmm_generate(svihmm_ctx* h, int64_t T, int32_t K, int32_t D, const double
     HIPCK(hipGetLastError());
   }
   h->T = T; h->D = D; h->gen_T = T;
-  h->have_labels = false;
+  drop_clamp(h);
   h->seq_off.clear();
   h->svi_active = false;
   h->center_pending = false;

@@ -540,18 +540,30 @@ int check_labels_fit(const svihmm_ctx* h) {
                 std::to_string(h->label_max) + ", the globals have K = " + std::to_string(h->K) + " states");
   return 0;
 }
-// Where every route gets its lliks: the family's kernel (launch_emission_family), then, while labels are in force
-// (svihmm_set_labels) and the caller has not opted out, the clamp of `out` (k_label_clamp).  The callers that score
-// true observations opt out (clamp_labels = false).  Under labels there is no scaled output: the routes that ask for
-// one stay off a labelled batch (prepare_ll, use_pipeline, fused_shape_ok, the resident loops' refusals).
+// an E-step-type call under allowed-state sets: the masks were packed for one K, the globals must have it
+int check_sets_fit(const svihmm_ctx* h) {
+  if (h->have_sets && h->sets_K != h->K)
+    return fail("svihmm_set_state_sets: the sets were given for K = " + std::to_string(h->sets_K) +
+                " states, the globals have K = " + std::to_string(h->K) + " states");
+  return 0;
+}
+int check_clamp_fit(const svihmm_ctx* h) {
+  CK(check_labels_fit(h));
+  return check_sets_fit(h);
+}
+// Where every route gets its lliks: the family's kernel (launch_emission_family), then, while labels or allowed-state
+// sets are in force (svihmm_set_labels / svihmm_set_state_sets) and the caller has not opted out, the clamp of `out`
+// (k_label_clamp / k_set_clamp).  The callers that score true observations opt out (clamp_labels = false).  Under a
+// clamp there is no scaled output: the routes that ask for one stay off such a batch (prepare_ll, use_pipeline,
+// fused_shape_ok, the resident loops' refusals).
 int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
                            const int64_t* starts_dev, double* out,
                            double* kexp_out, hipStream_t stream,
                            size_t min_lds, double* ll0_out, bool clamp_labels) {
-  const bool clamp = clamp_labels && h->have_labels;
+  const bool clamp = clamp_labels && clamp_in_force(h);
   if (clamp) {
     if (scaled || h->cur_f32) return fail("internal: scaled emission output requested for a labelled batch");
-    CK(check_labels_fit(h));
+    CK(check_clamp_fit(h));
   }
   CK(launch_emission_family(h, B, Lm, flags, scaled, starts_dev, out, kexp_out, stream, min_lds, ll0_out));
   if (!clamp) return 0;
@@ -560,8 +572,13 @@ int launch_emission(svihmm_ctx* h, int B, int Lm, uint32_t flags, bool scaled,
   if (!stream) stream = h->stream;
   const int64_t n = (int64_t)B * Lm;
   ProfScope ps(h, KS_EMISSION, stream);
-  hipLaunchKernelGGL(k_label_clamp, dim3((unsigned)((n + LC_ROWS - 1) / LC_ROWS)), dim3(256), 0, stream,
-                     (const int32_t*)h->labels.p, starts_dev, n, Lm, h->K, out);
+  const dim3 grid((unsigned)((n + LC_ROWS - 1) / LC_ROWS));
+  if (h->have_labels)
+    hipLaunchKernelGGL(k_label_clamp, grid, dim3(256), 0, stream, (const int32_t*)h->labels.p, starts_dev, n, Lm, h->K,
+                       out);
+  else
+    hipLaunchKernelGGL(k_set_clamp, grid, dim3(256), 0, stream, (const unsigned long long*)h->sets.p, starts_dev, n,
+                       Lm, h->K, h->sets_W, out);
   HIPCK(hipGetLastError());
   return 0;
 }

@@ -52,7 +52,7 @@ static bool fused_shape_ok(const svihmm_ctx* h, int B, int Lq, int off, int Lm, 
       h->variant[SVIHMM_VAR_WIDE_POSTERIOR] != 0)
     return false;
   if ((flags & SVIHMM_USE_HOST_LLIKS) || h->fam != EF_NIW) return false;
-  if (h->have_labels) return false;            // (svihmm_set_labels: the fused launch reads scaled emission rows)
+  if (clamp_in_force(h)) return false;         // (labels / state sets: the fused launch reads scaled emission rows)
   if (K != 64 || h->Fp <= 0 || !five_tile_shape(h)) return false;      // (the sweep workgroups run the all-lanes-valid body)
   if (B < 1 || B > lin_waver_max(h) || Lq > (1 << 20) || use_chain(h, B, Lq)) return false;
   if (off != 0 || Lm != Lq) return false;      // (the local bound covers the whole window: its log terms come from the statistics rows)

@@ -1176,7 +1176,7 @@ int launch_seq_finish(svihmm_ctx* h, int N, const int64_t* seq_off, bool wrap, c
 // svihmm_estep_sequence_subset: the M listed sequences of the resident rows (and mask bytes) into the compact copy
 // obs_out [R][D] / mask_out [R].  tab (device): dst_off [M + 1] | src_off [M], in rows.  maxlen: the longest of them.
 int launch_seq_gather(svihmm_ctx* h, int M, const int64_t* tab, int maxlen, double* obs_out, uint8_t* mask_out,
-                      int32_t* labels_out) {
+                      int32_t* labels_out, uint64_t* sets_out) {
   // 8 KiB of rows per workgroup and pass, at most 1024 workgroups per occurrence
   int64_t nseg = ((int64_t)maxlen * h->D * 8 + 8191) / 8192;
   if (nseg > 1024) nseg = 1024;
@@ -1189,6 +1189,10 @@ int launch_seq_gather(svihmm_ctx* h, int M, const int64_t* tab, int maxlen, doub
   if (h->have_labels)
     hipLaunchKernelGGL(k_label_gather, dim3((unsigned)M, (unsigned)nseg), dim3(256), 0, h->stream,
                        (const int32_t*)h->labels.p, tab, tab + M + 1, labels_out);
+  if (h->have_sets)
+    hipLaunchKernelGGL(k_set_gather, dim3((unsigned)M, (unsigned)nseg), dim3(256), 0, h->stream,
+                       (const unsigned long long*)h->sets.p, tab, tab + M + 1, h->sets_W,
+                       (unsigned long long*)sets_out);
   HIPCK(hipGetLastError());
   return 0;
 }

@@ -496,6 +496,47 @@ class HipEngine(object):
         a = np.ascontiguousarray(a.astype(np.int32))
         L.check(self._lib.svihmm_set_labels(self._h, a.ctypes.data_as(C.POINTER(C.c_int32))), "svihmm_set_labels")
 
+    def set_state_sets(self, allowed, K=None):
+        """Allowed-state sets of the resident rows (``svihmm_set_state_sets``): a bool array ``[T, K]``, True where
+        state ``k`` is allowed at row ``t`` (a row of all True is free), or the packed ``uint64 [T, W]`` of
+        ``util.pack_state_sets`` together with ``K=``.  ``None`` removes the sets, as every upload of new rows does.
+        Sets and labels are alternatives: setting one kind removes the other.  While sets are in force every E-step
+        and decoder on the device sees ``-inf`` lliks at the states a row does not allow; the resident SVI loops,
+        ``grow_windows`` and ``pred_logprob`` refuse.  The library refuses a row that allows no state, a padding bit
+        at or beyond ``K`` and ``K`` outside ``[1, 256]``, whatever was in force staying in force."""
+        from .util import pack_state_sets
+        self._pre_mutate()
+        if allowed is None:
+            L.check(self._lib.svihmm_set_state_sets(self._h, None, 0), "svihmm_set_state_sets")
+            return
+        a = np.asarray(allowed)
+        T = getattr(self, "T", 0)
+        if a.dtype == np.uint64:
+            if K is None:
+                raise RuntimeError("set_state_sets: packed uint64 sets need K=")
+            K = int(K)
+            if a.ndim != 2 or a.shape[1] != (K + 63) // 64:
+                raise RuntimeError("set_state_sets: packed sets for K = %d must have shape (T, %d), got %s"
+                                   % (K, (K + 63) // 64, a.shape))
+        elif a.dtype == np.bool_:
+            if a.ndim != 2 or a.shape[1] < 1:
+                raise RuntimeError("set_state_sets: allowed must have shape (T, K), got %s" % (a.shape,))
+            if K is not None and int(K) != a.shape[1]:
+                raise RuntimeError("set_state_sets: K = %d, allowed has %d columns" % (int(K), a.shape[1]))
+            K = a.shape[1]
+            if 1 <= K <= 256:                   # (outside it the library refuses before it reads the array)
+                a = pack_state_sets(a)
+            else:
+                a = np.zeros((a.shape[0], (K + 63) // 64), dtype=np.uint64)
+        else:
+            raise RuntimeError("set_state_sets: allowed must be a bool [T, K] array or packed uint64 [T, W] with "
+                               "K=, got dtype %s" % a.dtype)
+        if T and a.shape[0] != T:               # (no rows resident: the library says so)
+            raise RuntimeError("set_state_sets: allowed must have T = %d rows, got %d" % (T, a.shape[0]))
+        a = np.ascontiguousarray(a)
+        L.check(self._lib.svihmm_set_state_sets(self._h, a.ctypes.data_as(C.POINTER(C.c_uint64)), K),
+                "svihmm_set_state_sets")
+
     def estep_sequences(self, flags=0, read=True):
         """Whole E-step of all declared sequences in one device call (``svihmm_estep_sequences``):
         ``(stats, seq_lb[N], q0[K])`` -- ``stats`` as ``estep`` wraps them (None with read=False: they

@@ -262,11 +262,57 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
             t = int(np.argmax(a))
             raise ValueError("set_labels: labels[%d] = %d, the model has K = %d states" % (t, a[t], self.K))
         self.labels = a.astype(np.int32)
+        self.state_sets = None                  # (labels and allowed-state sets are alternatives)
+        self._obs_dirty = True
+
+    def set_state_sets(self, allowed):
+        """Allowed-state sets per row, the weaker statement than a label: ``allowed[t, k]`` is True where row ``t``
+        may be in state ``k``; a row of all True is free.  One bool array ``[T, K]`` over the rows, or -- when ``obs``
+        was a list -- a list with one bool array ``[T_s, K]`` per sequence.  ``None`` removes the sets.  Sets replace
+        labels, as ``set_labels`` replaces sets.  Every E-step and decoder of the model then sees
+        ``lliks[t, k] = -inf`` wherever ``allowed[t, k]`` is False, in the places ``set_labels`` lists: on the device
+        where the engine has ``set_state_sets``, else through host lliks clamped here.  A set none of whose states is
+        possible under the initial and transition factors leaves that chain's results unspecified."""
+        if allowed is None:
+            self.state_sets = None
+            self._obs_dirty = True
+            return
+        so = self.__dict__.get("seq_off")
+        T = self.obs.shape[0]
+        if isinstance(allowed, (list, tuple)) and len(allowed) and np.ndim(allowed[0]) >= 2:
+            lens = [len(a) for a in allowed]
+            want = [int(n) for n in np.diff(so)] if so is not None else [T]
+            if lens != want:
+                raise ValueError("set_state_sets: the list's lengths %s do not match the sequences' %s" % (lens, want))
+            widths = sorted(set(np.shape(a)[1] for a in allowed))
+            if widths != [self.K]:
+                raise ValueError("set_state_sets: the arrays have %s columns, the model has K = %d states"
+                                 % (widths, self.K))
+            allowed = np.concatenate([np.asarray(a) for a in allowed])
+        a = np.asarray(allowed)
+        if a.ndim != 2 or a.shape[0] != T:
+            raise ValueError("set_state_sets: allowed must have shape (%d, %d), got %s" % (T, self.K, a.shape))
+        if a.shape[1] != self.K:
+            raise ValueError("set_state_sets: allowed has %d columns, the model has K = %d states"
+                             % (a.shape[1], self.K))
+        if a.dtype != np.bool_:
+            raise ValueError("set_state_sets: allowed must be a bool array, got dtype %s" % a.dtype)
+        empty = np.flatnonzero(~a.any(axis=1))
+        if empty.size:
+            raise ValueError("set_state_sets: row %d allows no state (a free row is all True)" % int(empty[0]))
+        self.state_sets = np.ascontiguousarray(a)
+        self.labels = None                      # (sets and labels are alternatives)
         self._obs_dirty = True
 
     def _clamp_lliks(self, ll, windows, Lm):
         """The labels' clamp of host lliks ``ll`` [B, Lm, K] of the windows ``windows`` (in place): at a labelled
-        row every state but the label gets ``-inf``, the label's entry keeps its bits."""
+        row every state but the label gets ``-inf``, the label's entry keeps its bits.  Allowed-state sets
+        (``set_state_sets``): ``-inf`` wherever the row does not allow the state."""
+        sets = self.__dict__.get("state_sets")
+        if sets is not None:
+            for b, s in enumerate(windows):
+                ll[b][~sets[s:s + Lm]] = -np.inf
+            return ll
         lab = self.__dict__.get("labels")
         if lab is None:
             return ll
@@ -279,7 +325,10 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         return ll
 
     def _labels_on_host(self):
-        """Labels are set and the engine does not take them: lliks are evaluated and clamped on the host."""
+        """Labels or allowed-state sets are set and the engine does not take them: lliks are evaluated and clamped
+        on the host."""
+        if self.__dict__.get("state_sets") is not None:
+            return not hasattr(self.engine, "set_state_sets")
         return self.__dict__.get("labels") is not None and not hasattr(self.engine, "set_labels")
 
     def __init__(self, obs, prior_init, prior_tran, prior_emit, mask=None,
@@ -318,6 +367,7 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         else:
             raise RuntimeError("obs must have 1 or 2 dimensions")
         self.labels = None
+        self.state_sets = None
         self.set_mask(mask)
 
         self.elbo = -np.inf
@@ -366,6 +416,9 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
         lab = self.__dict__.get("labels")
         if lab is not None and len(lab) != self.obs.shape[0]:
             self.labels = None                  # (labels described the previous rows)
+        sets = self.__dict__.get("state_sets")
+        if sets is not None and len(sets) != self.obs.shape[0]:
+            self.state_sets = None
         self._obs_dirty = True
 
     def _upload_obs(self, force=False):
@@ -389,6 +442,8 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
             if self.__dict__.get("labels") is not None and hasattr(eng, "set_labels"):
                 # (the upload above removed whatever labels the handle held)
                 eng.set_labels(self.labels)
+            if self.__dict__.get("state_sets") is not None and hasattr(eng, "set_state_sets"):
+                eng.set_state_sets(self.state_sets)
             eng._obs_owner = id(self)
             self._obs_dirty = False
             self._obs_print = self._obs_fingerprint()

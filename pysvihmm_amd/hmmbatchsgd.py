@@ -99,6 +99,9 @@ class VBHMM(VariationalHMMBase):
         if self.__dict__.get("labels") is not None:
             return ("labels are set (set_labels): the resident loop does not take them; the host route steps "
                     "on estep_sequence_subset, which honours them")
+        if self.__dict__.get("state_sets") is not None:
+            return ("allowed-state sets are set (set_state_sets): the resident loop does not take them; the host "
+                    "route steps on estep_sequence_subset, which honours them")
         eng = self.engine
         if not (hasattr(eng, "svi_sequences") and hasattr(eng, "svi_iteration_sequences")):
             return "the engine has no svi_sequences / svi_iteration_sequences"

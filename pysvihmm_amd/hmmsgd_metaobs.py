@@ -109,6 +109,14 @@ class VBHMM(VariationalHMMBase):
         raise NotImplementedError("hmmsgd_metaobs.VBHMM.set_labels: the resident SVI loop and grow_windows do not "
                                   "take labels; use hmmbatchcd.VBHMM or hmmbatchsgd.VBHMM")
 
+    def set_state_sets(self, allowed):
+        """Not supported by this class, for the reason ``set_labels`` gives."""
+        if allowed is None:
+            self.state_sets = None
+            return
+        raise NotImplementedError("hmmsgd_metaobs.VBHMM.set_state_sets: the resident SVI loop and grow_windows do "
+                                  "not take allowed-state sets; use hmmbatchcd.VBHMM or hmmbatchsgd.VBHMM")
+
     def set_metaobs_fun(self):
         if self.metaobs_fun_name == 'unif':
             self.metaobs_fun = self.metaobs_unif

@@ -164,3 +164,33 @@ def match_from_counts(DM):
 
 
 match_state_seq = munkres_match
+
+
+def pack_state_sets(allowed):
+    """Allowed-state sets ``allowed`` (bool ``[T, K]``, True where state ``k`` is allowed at row ``t``) in the layout
+    ``svihmm_set_state_sets`` takes: ``uint64 [T, W]``, ``W = (K + 63) // 64``, bit ``k % 64`` of word ``k // 64`` of
+    row ``t`` for state ``k``; the bits of the last word at or beyond ``K`` are zero."""
+    a = np.asarray(allowed)
+    if a.ndim != 2 or a.shape[1] < 1:
+        raise ValueError("pack_state_sets: allowed must have shape (T, K) with K >= 1, got %s" % (a.shape,))
+    a = a.astype(bool)
+    T, K = a.shape
+    W = (K + 63) // 64
+    padded = np.zeros((T, W * 64), dtype=np.uint64)
+    padded[:, :K] = a
+    weights = np.left_shift(np.uint64(1), np.arange(64, dtype=np.uint64))
+    # (distinct bits: the sum is the bitwise or, and stays inside uint64)
+    return np.ascontiguousarray((padded.reshape(T, W, 64) * weights).sum(axis=2, dtype=np.uint64))
+
+
+def unpack_state_sets(packed, K):
+    """The inverse of ``pack_state_sets``: bool ``[T, K]`` from ``uint64 [T, W]``."""
+    p = np.asarray(packed)
+    K = int(K)
+    W = (K + 63) // 64
+    if p.dtype != np.uint64 or p.ndim != 2 or K < 1 or p.shape[1] != W:
+        raise ValueError("unpack_state_sets: packed must be uint64 of shape (T, %d) for K = %d, got %s %s"
+                         % (W, K, p.dtype, p.shape))
+    shifts = np.arange(64, dtype=np.uint64)
+    bits = (np.right_shift(p[:, :, None], shifts) & np.uint64(1)).astype(bool)
+    return bits.reshape(p.shape[0], W * 64)[:, :K]
