@@ -65,9 +65,10 @@ enum {
    *    that is ahead, else one launch after the other; 4: as 0).  Whatever this slot says, the fused launch needs STATS,
    *    SWEEP_FAMILY, STATS_CHUNKS, STATS_TILING and WIDE_POSTERIOR at 0 and FB at 0 or 3 */
   SVIHMM_VAR_PIPELINE = 4,
-  /* 5: emission kernel choice.  Two switches: codes 1 / 2 / 5 shape the fp64 orbit-schedule kernels (K <= 64,
-   *    D % 8 == 0, 8 <= D <= 40), codes 3 / 4 / 8 the fp32 mode's bf16 x 3 kernels.  The emission tiles inside the
-   *    fused E-step launch (PIPELINE 3 / 5) need this slot at 0 */
+  /* 5: emission kernel choice.  Two switches: codes 1 / 2 / 5 / 6 / 7 shape the fp64 orbit-schedule kernels (K <= 64,
+   *    D % 8 == 0, 8 <= D <= 40; 6 / 7 keep the row-tile kernel's generic staging and epilogue in every workgroup),
+   *    codes 3 / 4 / 8 the fp32 mode's bf16 x 3 kernels.  The emission tiles inside the fused E-step launch
+   *    (PIPELINE 3 / 5) need this slot at 0 */
   SVIHMM_VAR_EMISSION_ORBIT = 5,
   /* 6: blocked scan for one long window (B = 1, Lm >= 2048, K <= 256) and blocked backward sampling of the FFBS
    *    entry points (chains / windows of at least 1024 rows) */
@@ -146,7 +147,12 @@ enum {
   SVIHMM_EMISSION_ORBIT_BF16_SMALL = 4,  /* fp32 mode, K <= 64, D <= 32: the bf16 x 3 kernel also below 8192 rows */
   SVIHMM_EMISSION_ORBIT_64 = 5,          /* minibatches: the 64-row k_emission_orbit of round 3 instead of the 16-row
                                             k_emission_orbit_ks */
-  SVIHMM_EMISSION_ORBIT_BF16_128 = 8,    /* fp32 mode minibatches: k_emission_bf16x3<1>, one group of four waves on 128
+  SVIHMM_EMISSION_ORBIT_GENERIC_EDGES = 6,       /* default dispatch, but the row-tile kernel k_emission_orbit runs its
+                                                    generic staging and epilogue in every workgroup instead of the lean
+                                                    ones in workgroups wholly inside the batch (K = Kp, fp64 storage;
+                                                    csrc/kernels_emission.h) -- same results bit for bit */
+  SVIHMM_EMISSION_ORBIT_128_GENERIC_EDGES = 7,   /* codes 2 and 6 together (tests: batches below one workgroup per CU) */
+  SVIHMM_EMISSION_ORBIT_BF16_128 = 8,   /* fp32 mode minibatches: k_emission_bf16x3<1>, one group of four waves on 128
                                             rows, instead of k_emission_bf16x3h */
   /* CHAIN */
   SVIHMM_CHAIN_OFF = 1,

@@ -40,6 +40,10 @@ VARIANT = {
     "stats_lds3": 12, "wide_sweeps": 13, "wide_tran_block": 14, "wide_posterior": 15, "renorm4": 16,
     "msg_layout": 17,
 }
+# codes of slot "emission_orbit" the tests name (include/svihmm_debug.h: SVIHMM_EMISSION_ORBIT_*)
+EMISSION_ORBIT_128 = 2
+EMISSION_ORBIT_GENERIC_EDGES = 6       # k_emission_orbit: the generic staging and epilogue in every workgroup
+EMISSION_ORBIT_128_GENERIC_EDGES = 7   # 2 and 6 together
 
 _lib = None
 

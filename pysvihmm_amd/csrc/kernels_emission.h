@@ -103,6 +103,83 @@ __device__ __forceinline__ void emission_scaled_epilogue(
     }
 }
 
+// The same epilogue for a workgroup of the row-tile orbit kernel that lies wholly inside the batch, with K = 16 NT
+// and fp64 storage (k_emission_orbit, `lean`): every value goes through the operations above in the same order --
+// the results are the same bit for bit -- and only the work around them differs.
+//  * No store guards (all rows valid, K full) and no float path.
+//  * Addresses: workgroup-uniform bases (llb = Eh at the workgroup's base row, kexpb = kexp at its first row, ll0b =
+//    ll0 at its first window) plus one 32-bit byte offset per row; the row's record word `rec_hi` (LDS, written by the
+//    kernel's first stage) holds the Eh offset of the row, a multiple of 128, and in its low seven bits the row's window
+//    relative to the workgroup's first.
+//  * The clamps and the NaN / masked-row select are identities on a finite value of a row that is not masked: one
+//    class test per value and the rows' bad_s bits are OR-ed over the wave, and only a wave that holds a special
+//    value runs them.  The unscaled rows of window starts (ll0) likewise only in waves that hold one.
+template <int NT, int MT>
+__device__ __forceinline__ void emission_scaled_epilogue_lean(
+    double (&outv)[MT][NT][4], const unsigned char* bad_s, const uint32_t* rec_hi, int wave, int li, int lg,
+    double* __restrict__ llb, double* __restrict__ kexpb, double* __restrict__ ll0b) {
+    constexpr int KP = 16 * NT;
+    ExpConsts ek;
+    exp_consts_init(ek);
+    double big = 1.7976931348623157e308, l2e = 1.4426950408889634074;
+    asm volatile("" : "+v"(big));
+    asm volatile("" : "+v"(l2e));
+    const int rl0 = wave * 16 * MT + lg;
+    const uint32_t li8 = (uint32_t)li * 8u;
+    unsigned bits = 0;
+    bool sp = false;
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        bits |= bad_s[rl0 + m * 16 + 4 * r];
+#pragma unroll
+        for (int n = 0; n < NT; ++n) sp |= __builtin_amdgcn_class(outv[m][n][r], 0x207);   // NaN, -inf, +inf
+      }
+    if (__builtin_amdgcn_ballot_w64(sp || (bits & 1)) != 0) {     // (wave-uniform) the sequence of the generic epilogue
+#pragma unroll
+      for (int m = 0; m < MT; ++m)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const bool bd = (bad_s[rl0 + m * 16 + 4 * r] & 1) != 0;
+#pragma unroll
+          for (int n = 0; n < NT; ++n) {
+            double x = outv[m][n][r];
+            x = fmax_raw(-big, x);
+            x = -fmax_raw(-big, -x);
+            outv[m][n][r] = (outv[m][n][r] != outv[m][n][r] || bd) ? 0.0 : x;
+          }
+        }
+    }
+    const bool st0 = ll0b && __builtin_amdgcn_ballot_w64((bits & 2) != 0) != 0;
+    char* kxp = reinterpret_cast<char*>(kexpb) + (uint32_t)rl0 * 8u;
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int rl = rl0 + m * 16 + 4 * r;
+        const uint32_t hi = rec_hi[2 * rl];
+        double mx = outv[m][0][r];       // (= fmax_raw(-inf, v) of a value that is no NaN)
+#pragma unroll
+        for (int n = 1; n < NT; ++n) mx = fmax_raw(mx, outv[m][n][r]);
+        mx = row16_max(mx);
+        const double kx = (mx > -1e300 && mx < 1e300) ? ceil(mx * l2e) : 0.0;
+        char* orow = reinterpret_cast<char*>(llb) + ((hi & ~127u) | li8);
+#pragma unroll
+        for (int n = 0; n < NT; ++n)
+          *reinterpret_cast<double*>(orow + n * 128) = fast_exp_k(fma(kx, ek.c[13], fma(kx, ek.c[12], outv[m][n][r])), ek);
+        if (li == 0) *reinterpret_cast<double*>(kxp + (m * 16 + 4 * r) * 8) = kx;
+        if (st0) {                       // (wave-uniform)
+          if (bad_s[rl] & 2) {
+            char* o0 = reinterpret_cast<char*>(ll0b) + ((hi & 127u) * (uint32_t)(KP * 8) | li8);
+#pragma unroll
+            for (int n = 0; n < NT; ++n) *reinterpret_cast<double*>(o0 + n * 128) = outv[m][n][r];
+          }
+        }
+      }
+    }
+}
+
 template <int NT, int MT, bool SCALED>
 __global__ __launch_bounds__(256) void k_emission_mfma(
     const double* __restrict__ obs, const uint8_t* __restrict__ mask,
@@ -297,6 +374,13 @@ __global__ void k_theta_orbit(const double* __restrict__ theta, int D, int Kp, i
   if (k < Kp) orb[(size_t)fo * Kp + (k & 15) * NT + (k >> 4)] = valid ? theta[(size_t)f * Kp + k] : 0.0;
 }
 
+// Measurement-only knock-outs of k_emission_orbit (a library built with -DSVIHMM_KO_EMO=n next to the product: make
+// ko_emo; never set in the product; results are meaningless, every address stays valid): bit 0 = the epilogue stores
+// the raw accumulators (no clamp, exponential, kexp, ll0), bit 1 = the staging writes constants to LDS instead of the
+// loaded rows.  They bound what the code around the k-loop costs.
+#ifndef SVIHMM_KO_EMO
+#define SVIHMM_KO_EMO 0
+#endif
 // MT = row tiles per wave: 2 (128 rows per workgroup) for batches that fill the chip, 1 (64 rows,
 // round 3) for minibatches with fewer than one 128-row workgroup per CU -- the SVI iteration of 64
 // windows is 129 workgroups of 128 rows on 256 CUs.
@@ -306,8 +390,11 @@ __global__ __launch_bounds__(256) void k_emission_orbit(
     const int64_t* __restrict__ starts, int64_t nrows, int Lm, int D, int K,
     const double* __restrict__ orb, uint32_t flags, double* __restrict__ ll,
     double* __restrict__ kexp, double* __restrict__ ll0,
-    int64_t* __restrict__ starts_copy = nullptr, int nstarts = 0, int smB = 0) {
+    int64_t* __restrict__ starts_copy = nullptr, int nstarts = 0, int smB = 0, int lean_ok = 0) {
   // smB: window count of the batch whose Eh rows leave in the step-major layout (kernels_msg_layout.h), 0 = row-major
+  // lean_ok (the launcher: K = 16 NT, fp64 storage, 32-bit byte offsets reach every row of obs and of a workgroup's Eh
+  // rows, SVIHMM_EMISSION_ORBIT_GENERIC_EDGES not set): a workgroup wholly inside the batch takes the lean staging
+  // and epilogue below -- same bits, less work around them
   constexpr int ROWS = 64 * MT, KP = 16 * NT;
   // SVI loop (round 5): `starts` is the host's pinned, device-visible slot -- the window starts are read over
   // PCIe here once (a separate k_pull launch in front of this kernel cost 6 us + a 7 us dispatch gap on the
@@ -335,16 +422,26 @@ __global__ __launch_bounds__(256) void k_emission_orbit(
   unsigned char* bad_s = (unsigned char*)(rowoff + ROWS);
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int64_t g0 = (int64_t)blockIdx.x * ROWS;
+  // (workgroup-uniform; the knock-outs are measured against the generic edges)
+#ifdef SVIHMM_EMO_LEAN_LISTING   // assembly listings only (tools/isa_loop_hist.py): the lean path without the generic one
+  const bool lean = true;
+#else
+  const bool lean = !SVIHMM_KO_EMO && lean_ok && g0 + ROWS <= nrows;
+#endif
   double* xs1 = (double*)xs2;
   long long omap_r = 0;
+  int64_t base_row = g0, bw0 = 0;
   // row r of the tile -> wave r >> 5, row tile (r >> 4) & 1, lane row r & 15
   auto slot = [&](int r, int idx) {
     return MT == 2 ? ((((r >> 5) * 16 + (r & 15)) * LEN + EO_SHIFT((r >> 5) * 16 + (r & 15)) + idx + 1) << 1) + ((r >> 4) & 1)
                    : r * LEN + idx + 1;
   };
   {
-    const int64_t bw0 = g0 / Lm;
+    bw0 = g0 / Lm;
     const unsigned t0 = (unsigned)(g0 - bw0 * Lm);
+    // lean: Eh rows are addressed from the first row of the workgroup's first 16-window group (step-major) / its own
+    // first row (row-major)
+    if (smB) base_row = (bw0 & ~(int64_t)15) * Lm;
     for (int r = tid; r < ROWS; r += 256) {
       const bool valid = g0 + r < nrows;
       const unsigned x = t0 + (unsigned)(valid ? r : 0);
@@ -353,13 +450,66 @@ __global__ __launch_bounds__(256) void k_emission_orbit(
       omap_r = msg_row(smB, Lm, bw0 + bwr, x - bwr * (unsigned)Lm);     // (ROWS <= 256: one row per thread)
       unsigned char bd = 0;
       if (valid && (flags & SVIHMM_MASK_AS_NAN) && mask) bd = mask[orow] != 0;
-      rowoff[r] = valid ? orow * D : -1;
+      // lean row record: byte offset of the obs row | (byte offset of the Eh row + window inside the workgroup) << 32
+      if (lean) rowoff[r] = (long long)((uint64_t)(uint32_t)(orow * D * 8) |
+                                        ((uint64_t)((uint32_t)(omap_r - base_row) * (uint32_t)(KP * 8) + bwr) << 32));
+      else rowoff[r] = valid ? orow * D : -1;
       bad_s[r] = bd | ((valid && x == bwr * (unsigned)Lm) ? 2 : 0);   // bit 1: step 0 of its window
       xs1[slot(r, -1)] = 1.0;
       xs1[slot(r, D)] = 1.0;
     }
   }
   __syncthreads();
+  // Lean staging (MT = 2, D = 16 / 32, compile-time DD): thread (rr, i) loads column i of the rows rr + RPP j.  The
+  // slot of row RPP j + rr differs from the slot of row rr by a compile-time number of doubles -- wave, row tile,
+  // lane row and EO_SHIFT of a row are affine in j because rr < RPP <= 16 carries into none of them -- so the
+  // ds_writes are one base register plus immediates; the loads take the scalar obs base and the record's 32-bit
+  // byte offset.  All rows are valid: no selects.  The NaN test and the bad_s update stay.
+  auto lean_stage = [&](auto dd) {
+    constexpr int DD = decltype(dd)::value, SH = DD == 32 ? 5 : 4, RPP = 256 >> SH, NL = ROWS / RPP;
+    constexpr int LENC = DD + DD / 2 + 1, NC = DD + 1;
+#ifdef SVIHMM_AB_EMIS_OLD
+    constexpr int S8 = 0;
+#else
+    constexpr int S8 = DD == 32 ? 8 : 0;
+#endif
+    const int i = tid & (DD - 1), rr = tid >> SH;
+    double* w0 = xs1 + (((rr * LENC + S8 * (rr >> 3) + i + 1) << 1));
+    const uint32_t* rec = reinterpret_cast<const uint32_t*>(rowoff) + 2 * rr;
+    unsigned char* bs = bad_s + rr;
+    const char* ob = reinterpret_cast<const char*>(obs);
+    const uint32_t i8 = (uint32_t)i * 8u;
+    double v[NL];
+#pragma unroll
+    for (int j = 0; j < NL; ++j) v[j] = *reinterpret_cast<const double*>(ob + (rec[2 * RPP * j] + i8));
+#pragma unroll
+    for (int j = 0; j < NL; ++j)
+      if (v[j] != v[j]) { bs[RPP * j] |= 1; v[j] = 0.0; }
+    // doubles from the slot of row rr to the slot of row RPP j + rr
+    auto delta = [](int j) {
+      const int r0 = RPP * j, lr = (r0 >> 5) * 16 + (r0 & 15);
+      return ((lr * LENC + S8 * (lr >> 3)) << 1) + ((r0 >> 4) & 1);
+    };
+#pragma unroll
+    for (int j = 0; j < NL; ++j) w0[delta(j)] = v[j];
+    if (i + NC <= LENC - 2) {
+#pragma unroll
+      for (int j = 0; j < NL; ++j) w0[2 * NC + delta(j)] = v[j];
+    }
+  };
+  const bool lean_st = lean && MT == 2 && (D == 32 || D == 16);
+#if SVIHMM_KO_EMO & 2
+  if (true) {
+    for (int q = tid; q < ROWS * LEN + 16 * SHIFT8; q += 256) xs1[q] = 0.5;
+  } else
+#else
+  if (lean_st) {
+    if constexpr (MT == 2) {
+      if (D == 32) lean_stage(std::integral_constant<int, 32>());
+      else lean_stage(std::integral_constant<int, 16>());
+    }
+  } else
+#endif
   {
     const int sh = 32 - __builtin_clz((unsigned)(D - 1));
     const int rpp = 256 >> sh, i = tid & ((1 << sh) - 1), rr = tid >> sh;
@@ -369,7 +519,8 @@ __global__ __launch_bounds__(256) void k_emission_orbit(
 #pragma unroll
       for (int j = 0; j < CH; ++j) {
         const int r = rb + j * rpp + rr;
-        const long long o = r < ROWS ? rowoff[r] : -1;
+        // (a lean workgroup on this staging: all rows valid, the record's low word is the obs row's byte offset)
+        const long long o = r < ROWS ? (lean ? (long long)((uint32_t)rowoff[r] >> 3) : rowoff[r]) : -1;
         const bool ok = i < D && o >= 0;
         const double t = obs[ok ? o + i : 0];
         v[j] = ok ? t : 0.0;
@@ -387,7 +538,8 @@ __global__ __launch_bounds__(256) void k_emission_orbit(
   }
   __syncthreads();
   // the observation offsets are consumed: their slots carry the rows' storage rows to the epilogue
-  if (smB && tid < ROWS) rowoff[tid] = omap_r;
+  // (a lean workgroup's records carry them already)
+  if (smB && !lean && tid < ROWS) rowoff[tid] = omap_r;
 
   const int li = lane & 15, lg = lane >> 4;
   double4_t acc[MT][NT];
@@ -474,6 +626,25 @@ __global__ __launch_bounds__(256) void k_emission_orbit(
 #pragma unroll
       for (int r = 0; r < 4; ++r) outv[m][n][r] = acc[m][n][r];
   __builtin_amdgcn_sched_barrier(0);
+#if SVIHMM_KO_EMO & 1
+  if (!((flags >> 16) & 1)) {   // raw accumulators to valid row-major addresses; no clamp, no exponential, no kexp / ll0
+    char* o = reinterpret_cast<char*>(ll + g0 * K) + (uint32_t)((wave * 16 * MT + lg) * K + li) * 8u;
+#pragma unroll
+    for (int m = 0; m < MT; ++m)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        if (g0 + wave * 16 * MT + m * 16 + lg + 4 * r < nrows)
+#pragma unroll
+          for (int n = 0; n < NT; ++n)
+            if (n * 16 + li < K) *reinterpret_cast<double*>(o + (uint32_t)((m * 16 + 4 * r) * K + n * 16) * 8u) = outv[m][n][r];
+    return;
+  }
+#endif
+  if (lean) {
+    emission_scaled_epilogue_lean<NT, MT>(outv, bad_s, reinterpret_cast<const uint32_t*>(rowoff) + 1, wave, li, lg,
+                                          ll + base_row * KP, kexp + g0, ll0 ? ll0 + bw0 * KP : (double*)nullptr);
+    return;
+  }
   if (smB) __syncthreads();     // (uniform) the map rows of the other waves' threads
   emission_scaled_epilogue<NT, MT>(outv, bad_s, wave, li, lg, g0, nrows, K, 0, ll, kexp, (flags >> 16) & 1, ll0, Lm,
                                    smB ? rowoff : (const long long*)nullptr);

@@ -199,6 +199,11 @@ int launch_emission_deferred(svihmm_ctx* h) {
 }
 
 
+// always the 128-row form of k_emission_orbit (with or without the lean edges)
+static bool orbit_128(const svihmm_ctx* h) {
+  return h->variant[SVIHMM_VAR_EMISSION_ORBIT] == SVIHMM_EMISSION_ORBIT_128 ||
+         h->variant[SVIHMM_VAR_EMISSION_ORBIT] == SVIHMM_EMISSION_ORBIT_128_GENERIC_EDGES;
+}
 // Does a scaled fp64 emission of n rows into the handle's own buffers take the row-tile orbit kernel
 // (k_emission_orbit: the only producer of the step-major layout)?  The same tests as in launch_emission below.
 bool emission_row_tile_orbit(const svihmm_ctx* h, int64_t n) {
@@ -206,7 +211,7 @@ bool emission_row_tile_orbit(const svihmm_ctx* h, int64_t n) {
   if (h->fam != EF_NIW || h->K > 64 || D < 8 || D > 40 || D % 8 != 0 ||
       h->variant[SVIHMM_VAR_EMISSION_ORBIT] == SVIHMM_EMISSION_ORBIT_OFF)
     return false;
-  return !((n + 127) / 128 < h->ncu && h->variant[SVIHMM_VAR_EMISSION_ORBIT] != SVIHMM_EMISSION_ORBIT_128 &&
+  return !((n + 127) / 128 < h->ncu && !orbit_128(h) &&
            h->variant[SVIHMM_VAR_EMISSION_ORBIT] != SVIHMM_EMISSION_ORBIT_64);
 }
 // scaled: write (Eh, kexp) for the linear-domain sweeps instead of ll (K <= 64 only).
@@ -445,7 +450,7 @@ static int launch_emission_family(svihmm_ctx* h, int B, int Lm, uint32_t flags, 
     }
     // minibatches (fewer than 32768 rows): 16-row workgroups, the four waves split the k-steps
     // (k_emission_orbit_ks; SVIHMM_EMISSION_ORBIT_64: the 64-row form of round 3, _128: always 128 rows)
-    if ((n + 127) / 128 < h->ncu && h->variant[SVIHMM_VAR_EMISSION_ORBIT] != SVIHMM_EMISSION_ORBIT_128 &&
+    if ((n + 127) / 128 < h->ncu && !orbit_128(h) &&
         h->variant[SVIHMM_VAR_EMISSION_ORBIT] != SVIHMM_EMISSION_ORBIT_64) {
       const int R0 = 3 * NT * 256 > 16 * LEN + 1 ? 3 * NT * 256 : ((16 * LEN + 1) & ~1);
       const size_t lds = (size_t)(R0 + 16 * NT + 16) * 8 + 16;
@@ -468,17 +473,27 @@ static int launch_emission_family(svihmm_ctx* h, int B, int Lm, uint32_t flags, 
       return 0;
     }
     // fewer than one 128-row workgroup per CU: 64-row workgroups
-    const int MTo = ((n + 127) / 128 < h->ncu && h->variant[SVIHMM_VAR_EMISSION_ORBIT] != SVIHMM_EMISSION_ORBIT_128) ? 1 : 2;
+    const int MTo = ((n + 127) / 128 < h->ncu && !orbit_128(h)) ? 1 : 2;
     const int rows = 64 * MTo;
     // step-major Eh rows (prepare_ll: step_major_ok) leave only from here, for the whole batch into the handle's buffer
     const int smB = (h->step_major && own_out && own_starts) ? B : 0;
     // (+ 1 KB at D = 32 with two row tiles per wave: every second block of eight rows starts eight slots later, EO_SHIFT)
     const size_t lds = (size_t)rows * LEN * 8 + rows * 9 + ((MTo == 2 && D == 32) ? 1024 : 0);
     dim3 grid((unsigned)((n + rows - 1) / rows));
+    // Workgroups wholly inside the batch take the lean staging and epilogue (kernels_emission.h; same results bit for
+    // bit) where K fills its tiles, Eh is stored as fp64 and 32-bit byte offsets reach every resident observation and,
+    // from the first row of a workgroup's first 16-window group, every Eh row of the workgroup (a row's group ends less
+    // than 16 Lm rows behind it and starts less than 16 Lm rows before it: 32 Lm + rows rows).
+    // SVIHMM_EMISSION_ORBIT_GENERIC_EDGES / _128_GENERIC_EDGES: the generic staging and epilogue everywhere
+    const int lean = K == Kp && !(flags & SVIHMM_INT_ST32) &&
+                     h->variant[SVIHMM_VAR_EMISSION_ORBIT] != SVIHMM_EMISSION_ORBIT_GENERIC_EDGES &&
+                     h->variant[SVIHMM_VAR_EMISSION_ORBIT] != SVIHMM_EMISSION_ORBIT_128_GENERIC_EDGES &&
+                     (int64_t)h->T * D * 8 < ((int64_t)1 << 32) &&
+                     ((int64_t)32 * Lm + rows) * K * 8 < ((int64_t)1 << 32);
 #define EMO(NTV, UV, MTV) hipLaunchKernelGGL((k_emission_orbit<NTV, UV, MTV>), grid, dim3(256), lds, stream,  \
                                         (const double*)h->obs.p, mk, starts_dev, n, Lm, D, K,               \
                                         (const double*)h->theta_orb.p, flags, out, kexp_out, ll0_out,               \
-                                        pend ? (int64_t*)h->starts.p : (int64_t*)nullptr, pend_n, smB)
+                                        pend ? (int64_t*)h->starts.p : (int64_t*)nullptr, pend_n, smB, lean)
 #define EMOM(NTV, UV) do { if (MTo == 1) EMO(NTV, UV, 1); else EMO(NTV, UV, 2); } while (0)
     if (D % 16 == 0) { if (NT == 4) EMOM(4, 4); else if (NT == 3) EMOM(3, 4); else if (NT == 2) EMOM(2, 4); else EMOM(1, 4); }
     else             { if (NT == 4) EMOM(4, 2); else if (NT == 3) EMOM(3, 2); else if (NT == 2) EMOM(2, 2); else EMOM(1, 2); }
