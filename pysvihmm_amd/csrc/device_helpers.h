@@ -29,6 +29,13 @@ __device__ __forceinline__ int64_t obs_row(const int64_t* __restrict__ starts, i
   return starts[b] + (g - b * Lm);
 }
 
+// one double, the same in every lane, moved to the scalar side
+__device__ __forceinline__ double wave_uniform(double v) {
+  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
+  const int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
+  return __hiloint2double(hi, lo);
+}
+
 // fp64 transcendentals for the fused sweeps.  On gfx950 fp64 MFMA and fp64 VALU share one
 // pipe (tools/peak_probe.py: their times add), so every fp64 VALU instruction in the time
 // loop costs matrix throughput; ocml's log() alone is ~90 of them.  These are plain

@@ -11,16 +11,13 @@
 //                     column, so the result is bit-identical to the same loop on the host.  A row masked under
 //                     SVIHMM_MASK_AS_NAN is all zeros.  Output in the layout / scaling convention of k_emission_cat
 //                     (unscaled lliks: the k_scale_ll pass and the sweeps follow unchanged).
-//   k_stats_onehot    counts as a GEMM on v_mfma_f64_16x16x4_f64:
+//   k_stats_onehot    the counts as a GEMM, the scheme of k_stats_columns (kernels_columns.h) in a kernel of its own:
 //                       out[f][k] = sum_t 1[x_t,d(f) = v(f) and row t unmasked] q[t][k]
 //                     A operand formed on the fly from 16-bit staged symbols (-1: absent or masked row): every
-//                     product is 1.0 q or 0.0 q, exact, so the only rounding is the fp64 accumulation.  Per-chunk
-//                     partials [chunk][F][Kp] (the layout k_stats_cat writes), reduced in chunk order by
-//                     k_finalize_cat: no atomics, a run is bit-reproducible.
+//                     product is 1.0 q or 0.0 q, exact, so the only rounding is the fp64 accumulation.
 //
 // Shapes: every F <= SVIHMM_MCAT_MAX_F, D <= SVIHMM_MCAT_MAX_D, K <= 256 runs on these two kernels (no fallback
-// kernel).  A workgroup of the GEMM always carries four state tiles (64 states): models with K < 64 run the
-// remaining tiles on zero columns.
+// kernel).
 //
 // The resident SVI loop takes the family as its family 3 (svihmm_svi_begin_mcat; kernels_svi.h: k_mcat_table rebuilds
 // the table these kernels read, the step and the ELBO term are the Categorical family's, column by column), and
@@ -31,11 +28,8 @@
 
 // meta (int32, device): [ off_d  D | V_d  D | d(f)  F | v(f)  F ]
 #define MC_EM_ROWS 32          // rows whose symbols k_emission_mcat stages at a time
-#define MC_RB 64               // rows per stage of k_stats_onehot
-#define MC_QS 80               // doubles per staged q row: 64 states + 16, so that rows r and r + 1 of a 32-lane
-                               // group sit on the two halves of the LDS banks (stride = 32 dwords mod 64)
 
-// (tu_emission.hip takes the lookup, tu_stats.hip -- after kernels_stats.h, for MF<double> -- the GEMM)
+// (tu_emission.hip takes the lookup, tu_stats.hip -- after kernels_stats.h and kernels_columns.h -- the GEMM)
 #ifdef SVIHMM_MCAT_EMISSION
 // lane = state (strided for K > 64); a wave owns every fourth row of the staged block.
 // TLDS: the table sits in LDS (the host picks it when F K doubles fit 64 KB), otherwise it is read through L2.
@@ -65,9 +59,7 @@ __global__ __launch_bounds__(256) void k_emission_mcat(
       const int r = e / DP, d = e - r * DP;
       int f = -1;
       if (d < D) {
-        const int64_t g = base + r;
-        const int64_t b = g / Lm;
-        const int64_t orow = starts[b] + (g - b * Lm);
+        const int64_t orow = obs_row(starts, Lm, base + r);
         const double x = obs[orow * D + d];
         const bool bad = (x != x) || (use_mask && mask[orow]);
         const int v = bad ? -1 : (int)x;
@@ -102,18 +94,11 @@ __global__ __launch_bounds__(256) void k_emission_mcat(
 #endif  // SVIHMM_MCAT_EMISSION
 
 #ifdef SVIHMM_MCAT_STATS
-// Workgroup (blockIdx.x = row chunk, .y = group of 64 MT features, .z = group of 64 states), 4 waves; wave w owns
-// the feature tiles 4 m + w (m < MT) of its group against the four state tiles.
-// Operand layout of v_mfma_f64_16x16x4_f64 (MF<double> / k_stats_mfma4, svihmm_selftest_mfma): A lane l ->
-// [feature l & 15][row l >> 4], B lane l -> [row l >> 4][state l & 15], C lane l register r -> [feature (l >> 4) + 4 r]
-// [state l & 15].
-// A row that is masked, or whose every entry is absent, contributes nothing whatever its posterior holds (the rule of
-// k_stats_cat, which skips such rows): its posterior is staged as zeros, so a NaN or Inf a svihmm_suffstats caller left
-// there stays out of the counts.  A row with some entries present is a GEMM row: a non-finite posterior of such a row
-// reaches, through 0.0 x NaN, every feature of its state's column in the tiles that stage it, not only the present ones
-// (k_stats_cat has one column, so the case does not arise there).
-// LDS: [ q MC_RB * MC_QS doubles | row records MC_RB * 2 int64 | row-has-a-present-entry MC_RB ints | symbols MC_RB * DS int16 ]
-struct McRow { int64_t orow, qrow; };       // orow < 0: no such row / masked
+// k_stats_columns's scheme, operand layout, row records and posterior staging (kernels_columns.h, included before this
+// file: COL_RB, COL_QS, ColRow) in a kernel of its own: as a policy of the frame this family's statistics slot measured
+// about 1 % above this kernel's, more than the run-to-run spread, in three samples, so it stays on the code it had.
+// A masked row, or one without a present entry, is staged with zero posteriors (the frame's rule).
+// LDS: [ q COL_RB * COL_QS doubles | row records COL_RB ColRow | row-has-a-present-entry COL_RB ints | symbols COL_RB * DS int16 ]
 template <int MT>
 __global__ __launch_bounds__(256) void k_stats_onehot(
     const double* __restrict__ obs, const uint8_t* __restrict__ mask, const int64_t* __restrict__ starts,
@@ -121,9 +106,9 @@ __global__ __launch_bounds__(256) void k_stats_onehot(
     const double* __restrict__ q, int64_t rows_per_chunk, int Lq, int off, double* __restrict__ partc) {
   extern __shared__ __attribute__((aligned(16))) char mc_smem[];
   double* qs = (double*)mc_smem;
-  McRow* rows = (McRow*)(mc_smem + (size_t)MC_RB * MC_QS * sizeof(double));
-  int* present = (int*)(mc_smem + (size_t)MC_RB * MC_QS * sizeof(double) + MC_RB * sizeof(McRow));
-  short* sym = (short*)(mc_smem + (size_t)MC_RB * MC_QS * sizeof(double) + MC_RB * sizeof(McRow) + MC_RB * sizeof(int));
+  ColRow* rows = (ColRow*)(mc_smem + (size_t)COL_RB * COL_QS * sizeof(double));
+  int* present = (int*)(mc_smem + (size_t)COL_RB * COL_QS * sizeof(double) + COL_RB * sizeof(ColRow));
+  short* sym = (short*)(mc_smem + (size_t)COL_RB * COL_QS * sizeof(double) + COL_RB * sizeof(ColRow) + COL_RB * sizeof(int));
   const int DS = D | 1;            // (odd row stride of the 16-bit symbols)
   const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
   const int li = lane & 15, lg = lane >> 4;
@@ -148,11 +133,11 @@ __global__ __launch_bounds__(256) void k_stats_onehot(
     for (int n = 0; n < 4; ++n) acc[m][n] = v4{0.0, 0.0, 0.0, 0.0};
   const int64_t c0 = (int64_t)blockIdx.x * rows_per_chunk;
   const int64_t c1 = imin64(nrows, c0 + rows_per_chunk);
-  for (int64_t s0 = c0; s0 < c1; s0 += MC_RB) {
+  for (int64_t s0 = c0; s0 < c1; s0 += COL_RB) {
     __syncthreads();                 // (the previous stage is consumed)
-    if (tid < MC_RB) {
+    if (tid < COL_RB) {
       const int64_t g = s0 + tid;
-      McRow rr = {-1, -1};
+      ColRow rr = {-1, -1};
       if (g < c1) {
         const int64_t bw = g / Lm;
         const int64_t t = g - bw * Lm;
@@ -164,17 +149,17 @@ __global__ __launch_bounds__(256) void k_stats_onehot(
       present[tid] = 0;
     }
     __syncthreads();
-    // posteriors: MC_RB rows x the group's 64 states, loaded now and committed once the symbols have said which
+    // posteriors: COL_RB rows x the group's 64 states, loaded now and committed once the symbols have said which
     // rows count (zeros beyond K, beyond the chunk, for masked rows and for rows without a present entry)
     const int qc = tid & 63;
-    double qreg[MC_RB / 4];
+    double qreg[COL_RB / 4];
 #pragma unroll
-    for (int i = 0; i < MC_RB / 4; ++i) {
-      const McRow rr = rows[(tid >> 6) + 4 * i];
+    for (int i = 0; i < COL_RB / 4; ++i) {
+      const ColRow rr = rows[(tid >> 6) + 4 * i];
       qreg[i] = (rr.orow >= 0 && kbase + qc < K) ? q[rr.qrow * K + kbase + qc] : 0.0;
     }
     // symbols: 16-bit, -1 for an absent entry and for every entry of a masked / missing row
-    for (int e = tid; e < MC_RB * D; e += 256) {
+    for (int e = tid; e < COL_RB * D; e += 256) {
       const int r = e / D, d = e - r * D;
       const int64_t orow = rows[r].orow;
       int v = -1;
@@ -188,17 +173,17 @@ __global__ __launch_bounds__(256) void k_stats_onehot(
     }
     __syncthreads();
 #pragma unroll
-    for (int i = 0; i < MC_RB / 4; ++i) {
+    for (int i = 0; i < COL_RB / 4; ++i) {
       const int r = (tid >> 6) + 4 * i;
-      qs[r * MC_QS + qc] = present[r] ? qreg[i] : 0.0;
+      qs[r * COL_QS + qc] = present[r] ? qreg[i] : 0.0;
     }
     __syncthreads();
 #pragma unroll 2
-    for (int ks = 0; ks < MC_RB / 4; ++ks) {
+    for (int ks = 0; ks < COL_RB / 4; ++ks) {
       const int r = 4 * ks + lg;
       double Bv[4];
 #pragma unroll
-      for (int n = 0; n < 4; ++n) Bv[n] = qs[r * MC_QS + 16 * n + li];
+      for (int n = 0; n < 4; ++n) Bv[n] = qs[r * COL_QS + 16 * n + li];
 #pragma unroll
       for (int m = 0; m < MT; ++m) {
         const double A = ((int)sym[r * DS + myd[m]] == myv[m]) ? 1.0 : 0.0;

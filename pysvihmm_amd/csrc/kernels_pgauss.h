@@ -16,16 +16,14 @@
 //                        loop on the host.  The centred form evaluated directly: no centred resident copy is needed.
 //                        A row masked under SVIHMM_MASK_AS_NAN, or without a present entry, is all +0.0.  Output in the
 //                        layout / scaling convention of k_emission_cat.
-//   k_stats_pgauss       [sxx | sx | n] about origin[D] as a GEMM on v_mfma_f64_16x16x4_f64 with F = 3 D feature rows,
-//                        r = x - origin[d]:
+//   PgaussStats          the family's policy of k_stats_columns (kernels_columns.h): [sxx | sx | n] about origin[D]
+//                        as a GEMM with F = 3 D feature rows, r = x - origin[d]:
 //                          out[d][k]       = sum_t (r * r) q[t][k]      (the square a rounded product of its own)
 //                          out[D + d][k]   = sum_t r q[t][k]
 //                          out[2 D + d][k] = sum_t 1[entry (t, d) present] q[t][k]
-//                        over the unmasked rows.  Per-chunk partials [chunk][F][Kp] (the layout k_stats_cat writes),
-//                        reduced in chunk order by k_finalize_cat with V = 3 D: no atomics, a run is bit-reproducible.
+//                        over the unmasked rows; k_finalize_cat reduces the partials with V = 3 D.
 //
-// Shapes: every D <= SVIHMM_PGAUSS_MAX_D, K <= 256 runs on these two kernels.  The GEMM's operand layout, chunking and
-// posterior staging are k_stats_onehot's (kernels_mcat.h: MC_RB, MC_QS, McRow).
+// Shapes: every D <= SVIHMM_PGAUSS_MAX_D, K <= 256 runs on these two kernels.
 //
 // Out of scope for this family, each refused by the host: the resident SVI loop, svihmm_pred_logprob, the fp32 mode.
 #pragma once
@@ -36,12 +34,6 @@
 __device__ __forceinline__ bool pg_present(double x) { return x > -PG_ABSENT && x < PG_ABSENT; }
 
 #ifdef SVIHMM_PGAUSS_EMISSION
-// one double, the same in every lane, moved to the scalar side
-__device__ __forceinline__ double pg_uniform(double v) {
-  const int lo = __builtin_amdgcn_readfirstlane(__double2loint(v));
-  const int hi = __builtin_amdgcn_readfirstlane(__double2hiint(v));
-  return __hiloint2double(hi, lo);
-}
 // lane = state (strided for K > 64); a wave owns every fourth row of the staged block.
 // Tables: mh [D + 1][K] pairs (mu, hprec), one aligned 16-byte read, followed by cst [D + 1][K]; row D of both is all
 // +0.0.  (Three doubles per (column, state): K = 64, D = 32 is 50 KB and stays in LDS, which a padded 32-byte record
@@ -83,9 +75,7 @@ __global__ __launch_bounds__(256) void k_emission_pgauss(
       const int r = e / DP, d = e - r * DP;
       double v = NAN;
       if (d < D) {
-        const int64_t g = base + r;
-        const int64_t b = g / Lm;
-        const int64_t orow = starts[b] + (g - b * Lm);
+        const int64_t orow = obs_row(starts, Lm, base + r);
         const double x = obs[orow * D + d];
         if (pg_present(x) && !(use_mask && mask[orow])) v = x;
       }
@@ -100,7 +90,7 @@ __global__ __launch_bounds__(256) void k_emission_pgauss(
           double p[4], c[4];
 #pragma unroll
           for (int j = 0; j < 4; ++j) {
-            const double xv = pg_uniform(xr[d0 + j]);     // the row's entry: one value for the wave
+            const double xv = wave_uniform(xr[d0 + j]);     // the row's entry: one value for the wave
             const bool absent = xv != xv;
             const size_t ti = (size_t)(absent ? D : d0 + j) * K + k;
             const double2 v = MH[ti];
@@ -124,118 +114,31 @@ __global__ __launch_bounds__(256) void k_emission_pgauss(
 #endif  // SVIHMM_PGAUSS_EMISSION
 
 #ifdef SVIHMM_PGAUSS_STATS
-// Workgroup (blockIdx.x = row chunk, .y = group of 64 MT features, .z = group of 64 states), 4 waves; wave w owns
-// the feature tiles 4 m + w (m < MT) of its group against the four state tiles: the scheme, the operand layout and
-// the posterior staging of k_stats_onehot (kernels_mcat.h, included before this file).
-// Staged per row and column: r = x - origin[d] as fp64, NaN for an absent entry, a masked row or a row beyond the
-// chunk.  A operand of feature f for a row: r * r (f < D), r (D <= f < 2 D), 1.0 (2 D <= f < 3 D), each 0.0 where the
-// staged value is NaN.  A row that is masked, or whose every entry is absent, is staged with zero posteriors
-// (k_stats_onehot's rule): a NaN or Inf a svihmm_suffstats caller left there stays out.
-// LDS: [ q MC_RB * MC_QS doubles | row records MC_RB * 2 int64 | row-has-a-present-entry MC_RB ints | r MC_RB * (D | 1) doubles ]
-//      = 42240 + 512 (D | 1) bytes: 108288 (106 KB) at D = 128 (the launch raises the dynamic limit), 59136 at D = 32.
-template <int MT>
-__global__ __launch_bounds__(256) void k_stats_pgauss(
-    const double* __restrict__ obs, const uint8_t* __restrict__ mask, const int64_t* __restrict__ starts,
-    int64_t nrows, int Lm, int K, int Kp, int D, const double* __restrict__ origin, const double* __restrict__ q,
-    int64_t rows_per_chunk, int Lq, int off, double* __restrict__ partc) {
+// The policy of k_stats_columns (kernels_columns.h, included before this file).  Staged per row and column:
+// r = x - origin[d] as fp64, NaN for absent.  A operand of feature f for a staged r: r * r (f < D), r (D <= f < 2 D),
+// 1.0 (2 D <= f < 3 D), each 0.0 where r is NaN.  Contraction is off where the policy computes: the difference and the
+// square are rounded operations of their own.
+struct PgaussStats {
+  typedef double Staged;
+  typedef double Aux;              // origin
+  struct Feat { int d, third; };   // column and third (0 r * r, 1 r, 2 one, 3 none)
+  static __device__ Staged absent() { return NAN; }
+  __device__ int features(int D) const { return 3 * D; }
+  __device__ Feat feature(int f, int D, const double*) const {
+    const int third = f < D ? 0 : f < 2 * D ? 1 : f < 3 * D ? 2 : 3;
+    return Feat{third < 3 ? f - third * D : 0, third};
+  }
+  __device__ Staged stage(double x, int d, int, const double* __restrict__ origin, int* row_present) const {
 #pragma clang fp contract(off)
-  extern __shared__ __attribute__((aligned(16))) char pg_smem[];
-  double* qs = (double*)pg_smem;
-  McRow* rows = (McRow*)(pg_smem + (size_t)MC_RB * MC_QS * sizeof(double));
-  int* present = (int*)(pg_smem + (size_t)MC_RB * MC_QS * sizeof(double) + MC_RB * sizeof(McRow));
-  double* rs = (double*)(present + MC_RB);
-  const int DS = D | 1;            // (odd row stride of the staged values)
-  const int F = 3 * D;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int li = lane & 15, lg = lane >> 4;
-  const int kbase = 64 * blockIdx.z;
-  const int fbase = 64 * MT * blockIdx.y;
-  // this lane's feature of each tile: its column and its third (0 r * r, 1 r, 2 one, 3 none)
-  int myd[MT], third[MT];
-#pragma unroll
-  for (int m = 0; m < MT; ++m) {
-    const int f = fbase + 16 * (4 * m + w) + li;
-    third[m] = f < D ? 0 : f < 2 * D ? 1 : f < F ? 2 : 3;
-    myd[m] = third[m] < 3 ? f - third[m] * D : 0;
+    if (!pg_present(x)) return NAN;
+    *row_present = 1;                    // (every writer stores the same value)
+    return x - origin[d];
   }
-  typedef MF<double>::v4 v4;
-  v4 acc[MT][4];
-#pragma unroll
-  for (int m = 0; m < MT; ++m)
-#pragma unroll
-    for (int n = 0; n < 4; ++n) acc[m][n] = v4{0.0, 0.0, 0.0, 0.0};
-  const int64_t c0 = (int64_t)blockIdx.x * rows_per_chunk;
-  const int64_t c1 = imin64(nrows, c0 + rows_per_chunk);
-  for (int64_t s0 = c0; s0 < c1; s0 += MC_RB) {
-    __syncthreads();                 // (the previous stage is consumed)
-    if (tid < MC_RB) {
-      const int64_t g = s0 + tid;
-      McRow rr = {-1, -1};
-      if (g < c1) {
-        const int64_t bw = g / Lm;
-        const int64_t t = g - bw * Lm;
-        const int64_t orow = starts[bw] + off + t;
-        rr.qrow = bw * Lq + off + t;
-        rr.orow = (mask && mask[orow]) ? -1 : orow;
-      }
-      rows[tid] = rr;
-      present[tid] = 0;
-    }
-    __syncthreads();
-    // posteriors: MC_RB rows x the group's 64 states, loaded now and committed once the entries have said which
-    // rows count (zeros beyond K, beyond the chunk, for masked rows and for rows without a present entry)
-    const int qc = tid & 63;
-    double qreg[MC_RB / 4];
-#pragma unroll
-    for (int i = 0; i < MC_RB / 4; ++i) {
-      const McRow rr = rows[(tid >> 6) + 4 * i];
-      qreg[i] = (rr.orow >= 0 && kbase + qc < K) ? q[rr.qrow * K + kbase + qc] : 0.0;
-    }
-    // r = x - origin[d]; NaN for an absent entry and for every entry of a masked / missing row
-    for (int e = tid; e < MC_RB * D; e += 256) {
-      const int r = e / D, d = e - r * D;
-      const int64_t orow = rows[r].orow;
-      double v = NAN;
-      if (orow >= 0) {
-        const double x = obs[orow * D + d];
-        if (pg_present(x)) { v = x - origin[d]; present[r] = 1; }      // (every writer stores the same value)
-      }
-      rs[r * DS + d] = v;
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < MC_RB / 4; ++i) {
-      const int r = (tid >> 6) + 4 * i;
-      qs[r * MC_QS + qc] = present[r] ? qreg[i] : 0.0;
-    }
-    __syncthreads();
-#pragma unroll 2
-    for (int ks = 0; ks < MC_RB / 4; ++ks) {
-      const int r = 4 * ks + lg;
-      double Bv[4];
-#pragma unroll
-      for (int n = 0; n < 4; ++n) Bv[n] = qs[r * MC_QS + 16 * n + li];
-#pragma unroll
-      for (int m = 0; m < MT; ++m) {
-        const double v = rs[r * DS + myd[m]];
-        const double sq = v * v;
-        const double a = third[m] == 0 ? sq : third[m] == 1 ? v : 1.0;
-        const double A = (v != v || third[m] == 3) ? 0.0 : a;
-#pragma unroll
-        for (int n = 0; n < 4; ++n) acc[m][n] = MF<double>::mma(A, Bv[n], acc[m][n]);
-      }
-    }
+  static __device__ double operand(Staged v, const Feat& ft) {
+#pragma clang fp contract(off)
+    const double sq = v * v;
+    const double a = ft.third == 0 ? sq : ft.third == 1 ? v : 1.0;
+    return (v != v || ft.third == 3) ? 0.0 : a;
   }
-  double* __restrict__ out = partc + (size_t)blockIdx.x * F * Kp;
-#pragma unroll
-  for (int m = 0; m < MT; ++m)
-#pragma unroll
-    for (int n = 0; n < 4; ++n)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int f = fbase + 16 * (4 * m + w) + MF<double>::crow(lg, r);
-        const int k = kbase + 16 * n + li;
-        if (f < F && k < Kp) out[(size_t)f * Kp + k] = acc[m][n][r];
-      }
-}
+};
 #endif  // SVIHMM_PGAUSS_STATS

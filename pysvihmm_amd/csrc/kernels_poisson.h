@@ -14,15 +14,14 @@
 //                        contraction is off in the kernel, so the result is bit-identical to that loop on the host.
 //                        g is formed once per row.  A row masked under SVIHMM_MASK_AS_NAN, or without a present
 //                        entry, is all +0.0.  Output in the layout / scaling convention of k_emission_cat.
-//   k_stats_poisson      [sx | n] as a GEMM on v_mfma_f64_16x16x4_f64 with F = 2 D feature rows:
+//   PoissonStats         the family's policy of k_stats_columns (kernels_columns.h): [sx | n] as a GEMM with F = 2 D
+//                        feature rows,
 //                          out[f][k]     = sum_t c_tf q[t][k]                     (f < D)
 //                          out[D + d][k] = sum_t 1[entry (t, d) present] q[t][k]
 //                        over the unmasked rows.  A operand formed on the fly from 32-bit staged counts (-1: absent or
-//                        masked row).  Per-chunk partials [chunk][F][Kp] (the layout k_stats_cat writes), reduced in
-//                        chunk order by k_finalize_cat with V = 2 D: no atomics, a run is bit-reproducible.
+//                        masked row); k_finalize_cat reduces the partials with V = 2 D.
 //
-// Shapes: every D <= SVIHMM_POISSON_MAX_D, C <= SVIHMM_POISSON_MAX_COUNT, K <= 256 runs on these two kernels.  The
-// GEMM's operand layout, chunking and posterior staging are k_stats_onehot's (kernels_mcat.h: MC_RB, MC_QS, McRow).
+// Shapes: every D <= SVIHMM_POISSON_MAX_D, C <= SVIHMM_POISSON_MAX_COUNT, K <= 256 runs on these two kernels.
 //
 // The resident SVI loop takes the family as its family 4 (svihmm_svi_begin_poisson; kernels_svi.h: k_pois_table
 // rebuilds the pairs these kernels read, svi_pois_step blends the Gamma factors), and hmmsgd_metaobs.VBHMM runs on it.
@@ -66,9 +65,7 @@ __global__ __launch_bounds__(256) void k_emission_poisson(
       const int r = e / DP, d = e - r * DP;
       int c = -1;
       if (d < D) {
-        const int64_t g = base + r;
-        const int64_t b = g / Lm;
-        const int64_t orow = starts[b] + (g - b * Lm);
+        const int64_t orow = obs_row(starts, Lm, base + r);
         const double x = obs[orow * D + d];
         if (x >= 0.0 && x < lim && !(use_mask && mask[orow])) c = (int)x;
       }
@@ -123,118 +120,23 @@ __global__ __launch_bounds__(256) void k_emission_poisson(
 #endif  // SVIHMM_POISSON_EMISSION
 
 #ifdef SVIHMM_POISSON_STATS
-// Workgroup (blockIdx.x = row chunk, .y = group of 64 MT features, .z = group of 64 states), 4 waves; wave w owns
-// the feature tiles 4 m + w (m < MT) of its group against the four state tiles: the scheme, the operand layout and
-// the posterior staging of k_stats_onehot (kernels_mcat.h, included before this file).
-// A operand of feature f for row r: (double)c_rf for f < D, 1.0 for D <= f < 2 D, either 0.0 when the entry is absent,
-// the row masked or beyond the chunk.  A row that is masked, or whose every entry is absent, is staged with zero
-// posteriors (k_stats_onehot's rule): a NaN or Inf a svihmm_suffstats caller left there stays out.
-// LDS: [ q MC_RB * MC_QS doubles | row records MC_RB * 2 int64 | row-has-a-present-entry MC_RB ints | counts MC_RB * (D | 1) ints ]
-template <int MT>
-__global__ __launch_bounds__(256) void k_stats_poisson(
-    const double* __restrict__ obs, const uint8_t* __restrict__ mask, const int64_t* __restrict__ starts,
-    int64_t nrows, int Lm, int K, int Kp, int D, int C, const double* __restrict__ q, int64_t rows_per_chunk,
-    int Lq, int off, double* __restrict__ partc) {
-  extern __shared__ __attribute__((aligned(16))) char po_smem[];
-  double* qs = (double*)po_smem;
-  McRow* rows = (McRow*)(po_smem + (size_t)MC_RB * MC_QS * sizeof(double));
-  int* present = (int*)(po_smem + (size_t)MC_RB * MC_QS * sizeof(double) + MC_RB * sizeof(McRow));
-  int* cnt = present + MC_RB;
-  const int DS = D | 1;            // (odd row stride of the counts)
-  const int F = 2 * D;
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int li = lane & 15, lg = lane >> 4;
-  const int kbase = 64 * blockIdx.z;
-  const int fbase = 64 * MT * blockIdx.y;
-  const double lim = (double)(C + 1);
-  // this lane's feature of each tile: its column, and what a present entry contributes (the count, or one)
-  int myd[MT];
-  bool issx[MT];
-  double one[MT];
-#pragma unroll
-  for (int m = 0; m < MT; ++m) {
-    const int f = fbase + 16 * (4 * m + w) + li;
-    myd[m] = f < D ? f : f < F ? f - D : 0;
-    issx[m] = f < D;
-    one[m] = (f >= D && f < F) ? 1.0 : 0.0;
+// The policy of k_stats_columns (kernels_columns.h, included before this file): 32-bit staged counts, -1 for absent.
+// A operand of feature f for a staged count c: (double)c for f < D, 1.0 for D <= f < 2 D, either 0.0 when c is absent.
+struct PoissonStats {
+  double lim;                      // (double)(C + 1)
+  typedef int Staged;
+  typedef void Aux;
+  struct Feat { int d; bool issx; double one; };      // column, and what a present entry contributes (the count, or one)
+  static __device__ Staged absent() { return -1; }
+  __device__ int features(int D) const { return 2 * D; }
+  __device__ Feat feature(int f, int D, const void*) const {
+    return Feat{f < D ? f : f < 2 * D ? f - D : 0, f < D, (f >= D && f < 2 * D) ? 1.0 : 0.0};
   }
-  typedef MF<double>::v4 v4;
-  v4 acc[MT][4];
-#pragma unroll
-  for (int m = 0; m < MT; ++m)
-#pragma unroll
-    for (int n = 0; n < 4; ++n) acc[m][n] = v4{0.0, 0.0, 0.0, 0.0};
-  const int64_t c0 = (int64_t)blockIdx.x * rows_per_chunk;
-  const int64_t c1 = imin64(nrows, c0 + rows_per_chunk);
-  for (int64_t s0 = c0; s0 < c1; s0 += MC_RB) {
-    __syncthreads();                 // (the previous stage is consumed)
-    if (tid < MC_RB) {
-      const int64_t g = s0 + tid;
-      McRow rr = {-1, -1};
-      if (g < c1) {
-        const int64_t bw = g / Lm;
-        const int64_t t = g - bw * Lm;
-        const int64_t orow = starts[bw] + off + t;
-        rr.qrow = bw * Lq + off + t;
-        rr.orow = (mask && mask[orow]) ? -1 : orow;
-      }
-      rows[tid] = rr;
-      present[tid] = 0;
-    }
-    __syncthreads();
-    // posteriors: MC_RB rows x the group's 64 states, loaded now and committed once the counts have said which
-    // rows count (zeros beyond K, beyond the chunk, for masked rows and for rows without a present entry)
-    const int qc = tid & 63;
-    double qreg[MC_RB / 4];
-#pragma unroll
-    for (int i = 0; i < MC_RB / 4; ++i) {
-      const McRow rr = rows[(tid >> 6) + 4 * i];
-      qreg[i] = (rr.orow >= 0 && kbase + qc < K) ? q[rr.qrow * K + kbase + qc] : 0.0;
-    }
-    // counts: -1 for an absent entry and for every entry of a masked / missing row
-    for (int e = tid; e < MC_RB * D; e += 256) {
-      const int r = e / D, d = e - r * D;
-      const int64_t orow = rows[r].orow;
-      int c = -1;
-      if (orow >= 0) {
-        const double x = obs[orow * D + d];
-        if (x >= 0.0 && x < lim) c = (int)x;
-      }
-      cnt[r * DS + d] = c;
-      if (c >= 0) present[r] = 1;        // (every writer stores the same value)
-    }
-    __syncthreads();
-#pragma unroll
-    for (int i = 0; i < MC_RB / 4; ++i) {
-      const int r = (tid >> 6) + 4 * i;
-      qs[r * MC_QS + qc] = present[r] ? qreg[i] : 0.0;
-    }
-    __syncthreads();
-#pragma unroll 2
-    for (int ks = 0; ks < MC_RB / 4; ++ks) {
-      const int r = 4 * ks + lg;
-      double Bv[4];
-#pragma unroll
-      for (int n = 0; n < 4; ++n) Bv[n] = qs[r * MC_QS + 16 * n + li];
-#pragma unroll
-      for (int m = 0; m < MT; ++m) {
-        const int c = cnt[r * DS + myd[m]];
-        const double A = c < 0 ? 0.0 : issx[m] ? (double)c : one[m];
-#pragma unroll
-        for (int n = 0; n < 4; ++n) acc[m][n] = MF<double>::mma(A, Bv[n], acc[m][n]);
-      }
-    }
+  __device__ Staged stage(double x, int, int, const void*, int* row_present) const {
+    const int c = (x >= 0.0 && x < lim) ? (int)x : -1;
+    if (c >= 0) *row_present = 1;        // (every writer stores the same value)
+    return c;
   }
-  double* __restrict__ out = partc + (size_t)blockIdx.x * F * Kp;
-#pragma unroll
-  for (int m = 0; m < MT; ++m)
-#pragma unroll
-    for (int n = 0; n < 4; ++n)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int f = fbase + 16 * (4 * m + w) + MF<double>::crow(lg, r);
-        const int k = kbase + 16 * n + li;
-        if (f < F && k < Kp) out[(size_t)f * Kp + k] = acc[m][n][r];
-      }
-}
+  static __device__ double operand(Staged c, const Feat& ft) { return c < 0 ? 0.0 : ft.issx ? (double)c : ft.one; }
+};
 #endif  // SVIHMM_POISSON_STATS

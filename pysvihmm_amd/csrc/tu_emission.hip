@@ -12,6 +12,26 @@
 #define SVIHMM_LABELS_CLAMP
 #include "kernels_labels.h"
 
+// One launch of a column family's lookup kernel (k_emission_mcat / _poisson / _pgauss): `staged` is the TLDS form, its
+// table of tb bytes in LDS, chosen when tlds; ib bytes of staged entries either way; args are the kernel's up to its
+// last, the rows per workgroup.  Those come in whole blocks of rb rows, enough for eight workgroups per CU; a staged
+// table is paid once per workgroup, so then at least 256 rows; at most 2^20.
+template <class Kern, class... Args>
+static void launch_lookup_columns(svihmm_ctx* h, hipStream_t stream, int64_t n, Kern staged, Kern through_l2, bool tlds,
+                                  int rb, size_t tb, size_t ib, Args... args) {
+  int64_t rpw = (n + 8 * (int64_t)h->ncu - 1) / (8 * (int64_t)h->ncu);
+  rpw = std::max<int64_t>(tlds ? 256 : rb, (rpw + rb - 1) / rb * rb);
+  if (rpw > 1 << 20) rpw = 1 << 20;
+  const size_t lds = (tlds ? tb : 0) + ib;
+  const dim3 grid((unsigned)((n + rpw - 1) / rpw));
+  if (tlds) {
+    hipFuncSetAttribute((const void*)staged, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    hipLaunchKernelGGL(staged, grid, dim3(256), lds, stream, args..., (int)rpw);
+  } else {
+    hipLaunchKernelGGL(through_l2, grid, dim3(256), lds, stream, args..., (int)rpw);
+  }
+}
+
 extern "C" {
 
 // NIW parameter block in h->niw ([mu | sigma | kappa | nu], on the device) -> theta (both layouts);
@@ -261,25 +281,13 @@ static int launch_emission_family(svihmm_ctx* h, int B, int Lm, uint32_t flags, 
       if (stream != h->stream) return fail("internal: Categorical lookup on a side stream over a centred column");
       CK(cat_uncentre(h));
     }
+    const double* ob = (const double*)h->obs.p;
     if (h->fam == EF_MCAT) {        // D symbol columns: one lookup and one add per present column (kernels_mcat.h)
       const int F = h->V;
       const size_t tb = (size_t)F * K * sizeof(double), ib = (size_t)MC_EM_ROWS * ((D + 7) & ~7) * sizeof(int);
-      const bool tlds = tb <= 64 * 1024;
-      // rows per workgroup: blocks of MC_EM_ROWS; a staged table is paid once per workgroup, so at least 256 rows,
-      // more once the launch has eight workgroups per CU
-      int64_t rpw = (n + 8 * (int64_t)h->ncu - 1) / (8 * (int64_t)h->ncu);
-      rpw = std::max<int64_t>(tlds ? 256 : MC_EM_ROWS, (rpw + MC_EM_ROWS - 1) / MC_EM_ROWS * MC_EM_ROWS);
-      if (rpw > 1 << 20) rpw = 1 << 20;
-      const size_t lds = (tlds ? tb : 0) + ib;
-      const dim3 grid((unsigned)((n + rpw - 1) / rpw));
-      if (tlds) {
-        hipFuncSetAttribute((const void*)k_emission_mcat<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(k_emission_mcat<true>, grid, dim3(256), lds, stream, (const double*)h->obs.p, mk, starts_dev,
-                           n, Lm, K, D, F, (const int*)h->mcat_meta.p, (const double*)h->cat_table.p, flags, out, (int)rpw);
-      } else {
-        hipLaunchKernelGGL(k_emission_mcat<false>, grid, dim3(256), lds, stream, (const double*)h->obs.p, mk, starts_dev,
-                           n, Lm, K, D, F, (const int*)h->mcat_meta.p, (const double*)h->cat_table.p, flags, out, (int)rpw);
-      }
+      launch_lookup_columns(h, stream, n, k_emission_mcat<true>, k_emission_mcat<false>, tb <= 64 * 1024, MC_EM_ROWS,
+                            tb, ib, ob, mk, starts_dev, n, Lm, K, D, F, (const int*)h->mcat_meta.p,
+                            (const double*)h->cat_table.p, flags, out);
       HIPCK(hipGetLastError());
       return 0;
     }
@@ -287,23 +295,11 @@ static int launch_emission_family(svihmm_ctx* h, int B, int Lm, uint32_t flags, 
       const int DP = (D + 3) & ~3;
       const size_t tb = 2 * (size_t)(D + 1) * K * sizeof(double);       // (with the zero row an absent column reads)
       const size_t ib = PO_EM_ROWS * sizeof(double) + (size_t)PO_EM_ROWS * (DP + 4) * sizeof(int);
-      const bool tlds = 2 * (size_t)D * K * sizeof(double) <= 64 * 1024;
-      // rows per workgroup: as for k_emission_mcat (a staged table is paid once per workgroup)
-      int64_t rpw = (n + 8 * (int64_t)h->ncu - 1) / (8 * (int64_t)h->ncu);
-      rpw = std::max<int64_t>(tlds ? 256 : PO_EM_ROWS, (rpw + PO_EM_ROWS - 1) / PO_EM_ROWS * PO_EM_ROWS);
-      if (rpw > 1 << 20) rpw = 1 << 20;
-      const size_t lds = (tlds ? tb : 0) + ib;
-      const dim3 grid((unsigned)((n + rpw - 1) / rpw));
-      if (tlds) {
-        hipFuncSetAttribute((const void*)k_emission_poisson<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(k_emission_poisson<true>, grid, dim3(256), lds, stream, (const double*)h->obs.p, mk, starts_dev,
-                           n, Lm, K, D, h->pois_C, (const double2*)h->cat_table.p, (const double*)h->pois_logfact.p, flags,
-                           out, (int)rpw);
-      } else {
-        hipLaunchKernelGGL(k_emission_poisson<false>, grid, dim3(256), lds, stream, (const double*)h->obs.p, mk, starts_dev,
-                           n, Lm, K, D, h->pois_C, (const double2*)h->cat_table.p, (const double*)h->pois_logfact.p, flags,
-                           out, (int)rpw);
-      }
+      // (staged when the D rows of pairs fit 64 KB: the zero row is not counted)
+      launch_lookup_columns(h, stream, n, k_emission_poisson<true>, k_emission_poisson<false>,
+                            2 * (size_t)D * K * sizeof(double) <= 64 * 1024, PO_EM_ROWS, tb, ib, ob, mk, starts_dev, n,
+                            Lm, K, D, h->pois_C, (const double2*)h->cat_table.p, (const double*)h->pois_logfact.p, flags,
+                            out);
       HIPCK(hipGetLastError());
       return 0;
     }
@@ -311,21 +307,8 @@ static int launch_emission_family(svihmm_ctx* h, int B, int Lm, uint32_t flags, 
       const int DP = (D + 3) & ~3;
       const size_t tb = 3 * (size_t)(D + 1) * K * sizeof(double);       // (with the zero row an absent column reads)
       const size_t ib = (size_t)PG_EM_ROWS * DP * sizeof(double);
-      const bool tlds = tb <= 64 * 1024;
-      // rows per workgroup: as for k_emission_mcat (a staged table is paid once per workgroup)
-      int64_t rpw = (n + 8 * (int64_t)h->ncu - 1) / (8 * (int64_t)h->ncu);
-      rpw = std::max<int64_t>(tlds ? 256 : PG_EM_ROWS, (rpw + PG_EM_ROWS - 1) / PG_EM_ROWS * PG_EM_ROWS);
-      if (rpw > 1 << 20) rpw = 1 << 20;
-      const size_t lds = (tlds ? tb : 0) + ib;
-      const dim3 grid((unsigned)((n + rpw - 1) / rpw));
-      if (tlds) {
-        hipFuncSetAttribute((const void*)k_emission_pgauss<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        hipLaunchKernelGGL(k_emission_pgauss<true>, grid, dim3(256), lds, stream, (const double*)h->obs.p, mk, starts_dev,
-                           n, Lm, K, D, (const double2*)h->cat_table.p, flags, out, (int)rpw);
-      } else {
-        hipLaunchKernelGGL(k_emission_pgauss<false>, grid, dim3(256), lds, stream, (const double*)h->obs.p, mk, starts_dev,
-                           n, Lm, K, D, (const double2*)h->cat_table.p, flags, out, (int)rpw);
-      }
+      launch_lookup_columns(h, stream, n, k_emission_pgauss<true>, k_emission_pgauss<false>, tb <= 64 * 1024, PG_EM_ROWS,
+                            tb, ib, ob, mk, starts_dev, n, Lm, K, D, (const double2*)h->cat_table.p, flags, out);
       HIPCK(hipGetLastError());
       return 0;
     }

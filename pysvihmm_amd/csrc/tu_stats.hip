@@ -3,12 +3,26 @@
 #include "host.h"
 #include "device_helpers.h"
 #include "kernels_stats.h"
+#include "kernels_columns.h"
 #define SVIHMM_MCAT_STATS
 #include "kernels_mcat.h"
 #define SVIHMM_POISSON_STATS
 #include "kernels_poisson.h"
 #define SVIHMM_PGAUSS_STATS
 #include "kernels_pgauss.h"
+
+// One launch of a column family's statistics GEMM (k_stats_columns<P, MT>, k_stats_onehot<MT>; k1 / k2 / k4: its
+// instantiations for MT = 1 / 2 / 4 feature tiles per wave): the LDS of the frame plus a stage of staged_bytes entries,
+// the dynamic limit raised where that passes 64 KB.  args: the kernel's.
+template <class Kern, class... Args>
+static void launch_stats_columns(svihmm_ctx* h, size_t staged_bytes, int MT, Kern k1, Kern k2, Kern k4, const dim3& grid,
+                                 Args... args) {
+  const size_t lds = (size_t)COL_RB * COL_QS * sizeof(double) + COL_RB * sizeof(ColRow) + COL_RB * sizeof(int) +
+                     (size_t)COL_RB * (h->D | 1) * staged_bytes;
+  Kern kernel = MT == 1 ? k1 : MT == 2 ? k2 : k4;
+  if (lds > 64 * 1024) hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  hipLaunchKernelGGL(kernel, grid, dim3(256), lds, h->stream, args...);
+}
 
 extern "C" {
 
@@ -384,16 +398,16 @@ static int launch_stats_cat(svihmm_ctx* h, int B, int Lq, int off, int Lm, uint3
   const StatsPlan plan = stats_plan(h, n);
   if (qsrc && (int64_t)(Lq + plan.rpc) * KpT >= ((int64_t)1 << 31))
     return fail("Categorical statistics: window too long for the GEMM's 32-bit row offsets");
-  // row chunks of the counts.  One column: k_stats_cat, one wave per chunk.  D columns (k_stats_onehot): whole stages
-  // of MC_RB rows, two chunks per CU for each (feature group, state group) pair -- more only adds partial sums
-  // (Poisson: k_stats_poisson, the same tiling with V = 2 D; Gaussian tracks: k_stats_pgauss, V = 3 D)
+  // row chunks of the counts.  One column: k_stats_cat, one wave per chunk.  D columns (k_stats_columns, k_stats_onehot): whole stages
+  // of COL_RB rows, two chunks per CU for each (feature group, state group) pair -- more only adds partial sums
+  // (V features: F symbols, Poisson 2 D, Gaussian tracks 3 D)
   const bool po = h->fam == EF_POIS, pg = h->fam == EF_PGAUSS, mc = h->fam == EF_MCAT || po || pg;
   const int mcMT = V <= 64 ? 1 : V <= 128 ? 2 : 4;
   const int mcGy = (V + 64 * mcMT - 1) / (64 * mcMT), mcGz = (K + 63) / 64;
   int64_t rpcc = (n + 1023) / 1024 > 64 ? (n + 1023) / 1024 : 64;
   if (mc) {
     const int64_t tc = std::max<int64_t>(1, 2 * (int64_t)h->ncu / (mcGy * mcGz));
-    rpcc = std::max<int64_t>(MC_RB, ((n + tc - 1) / tc + MC_RB - 1) / MC_RB * MC_RB);
+    rpcc = std::max<int64_t>(COL_RB, ((n + tc - 1) / tc + COL_RB - 1) / COL_RB * COL_RB);
   }
   const int nchunkc = (int)((n + rpcc - 1) / rpcc);
   CK(ensure(h->part, (size_t)plan.nchunk * KpT * KpT * sizeof(double)));
@@ -411,41 +425,20 @@ static int launch_stats_cat(svihmm_ctx* h, int B, int Lq, int off, int Lm, uint3
                        (const int*)nullptr, qv, plan.rpc, flags, Lq, off,
                        (double*)h->part.p, KpT, 0, (const double*)nullptr, (const double*)nullptr,
                        (const double*)nullptr, (const double2*)nullptr, (double*)nullptr);
+    const dim3 gm((unsigned)nchunkc, mcGy, mcGz);
+    const double* ob = (const double*)h->obs.p;
+    double* pc = (double*)h->partc.p;
     if (pg) {
-      const size_t ldsg = (size_t)MC_RB * MC_QS * sizeof(double) + MC_RB * sizeof(McRow) + MC_RB * sizeof(int) +
-                          (size_t)MC_RB * (D | 1) * sizeof(double);
-      const dim3 gm((unsigned)nchunkc, mcGy, mcGz);
-#define PGL(MTV)                                                                                                      \
-  do {                                                                                                                \
-    if (ldsg > 64 * 1024)                                                                                             \
-      hipFuncSetAttribute((const void*)k_stats_pgauss<MTV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsg);   \
-    hipLaunchKernelGGL(k_stats_pgauss<MTV>, gm, dim3(256), ldsg, stream, (const double*)h->obs.p, mk, sv, n, Lm, K,   \
-                       Kp, D, (const double*)h->pg_origin.p, qv, rpcc, Lq, off, (double*)h->partc.p);                 \
-  } while (0)
-      if (mcMT == 1) PGL(1); else if (mcMT == 2) PGL(2); else PGL(4);
-#undef PGL
+      launch_stats_columns(h, sizeof(PgaussStats::Staged), mcMT, k_stats_columns<PgaussStats, 1>,
+                           k_stats_columns<PgaussStats, 2>, k_stats_columns<PgaussStats, 4>, gm, ob, mk, sv, n, Lm, K, Kp, D,
+                           PgaussStats{}, (const double*)h->pg_origin.p, qv, rpcc, Lq, off, pc);
     } else if (po) {
-      const size_t ldsp = (size_t)MC_RB * MC_QS * sizeof(double) + MC_RB * sizeof(McRow) + MC_RB * sizeof(int) +
-                          (size_t)MC_RB * (D | 1) * sizeof(int);
-      const dim3 gm((unsigned)nchunkc, mcGy, mcGz);
-#define POL(MTV)                                                                                                      \
-  do {                                                                                                                \
-    if (ldsp > 64 * 1024)                                                                                             \
-      hipFuncSetAttribute((const void*)k_stats_poisson<MTV>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsp);  \
-    hipLaunchKernelGGL(k_stats_poisson<MTV>, gm, dim3(256), ldsp, stream, (const double*)h->obs.p, mk, sv, n, Lm, K,  \
-                       Kp, D, h->pois_C, qv, rpcc, Lq, off, (double*)h->partc.p);                                     \
-  } while (0)
-      if (mcMT == 1) POL(1); else if (mcMT == 2) POL(2); else POL(4);
-#undef POL
+      launch_stats_columns(h, sizeof(PoissonStats::Staged), mcMT, k_stats_columns<PoissonStats, 1>,
+                           k_stats_columns<PoissonStats, 2>, k_stats_columns<PoissonStats, 4>, gm, ob, mk, sv, n, Lm, K, Kp,
+                           D, PoissonStats{(double)(h->pois_C + 1)}, (const void*)nullptr, qv, rpcc, Lq, off, pc);
     } else if (mc) {
-      const size_t ldsm = (size_t)MC_RB * MC_QS * sizeof(double) + MC_RB * sizeof(McRow) + MC_RB * sizeof(int) +
-                          (size_t)MC_RB * (D | 1) * sizeof(short);
-      const dim3 gm((unsigned)nchunkc, mcGy, mcGz);
-#define MCL(MTV)                                                                                                   \
-  hipLaunchKernelGGL(k_stats_onehot<MTV>, gm, dim3(256), ldsm, stream, (const double*)h->obs.p, mk, sv, n, Lm, K, Kp, \
-                     D, V, (const int*)h->mcat_meta.p, qv, rpcc, Lq, off, (double*)h->partc.p)
-      if (mcMT == 1) MCL(1); else if (mcMT == 2) MCL(2); else MCL(4);
-#undef MCL
+      launch_stats_columns(h, sizeof(short), mcMT, k_stats_onehot<1>, k_stats_onehot<2>, k_stats_onehot<4>, gm, ob, mk,
+                           sv, n, Lm, K, Kp, D, V, (const int*)h->mcat_meta.p, qv, rpcc, Lq, off, pc);
     } else {
       const size_t ldsc = (size_t)V * Kp * sizeof(double);
       if (ldsc > 150 * 1024) return fail("Categorical statistics: V * K too large for the LDS table");

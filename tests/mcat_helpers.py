@@ -93,3 +93,24 @@ def make_model(K, V, rng):
 def split_tables(logp, V):
     off = offsets_of(V)
     return [np.ascontiguousarray(logp[:, off[d]:off[d + 1]]) for d in range(len(V))]
+
+
+# ---- the problems the GPU tests and tools/ab_columns.py share
+# K = 3: one ragged state tile; (16, 7 x 3): F = 21, no multiple of 16; 65: a second state group of one state, a
+# one-symbol column; 256 with F = 96: the table beyond 64 KB (read through L2), four state groups; (16, 13 x 20): F = 260,
+# four feature tiles per wave and a second feature group of four features, the 33 KB table staged
+SHAPES = [(3, (2, 5)), (16, (3,) * 7), (64, (2,) * 12), (65, (4, 1, 7)), (256, (8,) * 12), (16, (20,) * 13)]
+IDS = ["K3", "K16", "K64", "K65", "K256", "F260"]
+T = 700
+LENGTHS = (1, 2, 63, 64, 65, 257, 1)
+_cache = {}
+
+
+def problem(i):
+    if i not in _cache:
+        K, V = SHAPES[i]
+        rng = np.random.default_rng(100 + i)
+        x, mask = make_data(T, V, rng)
+        logp, mod_init, ltran = make_model(K, V, rng)
+        _cache[i] = dict(K=K, V=V, x=x, mask=mask, logp=logp, mod_init=mod_init, ltran=ltran)
+    return _cache[i]

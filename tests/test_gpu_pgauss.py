@@ -1,6 +1,6 @@
 """svihmm_set_emission_pgauss on the MI355X: D real-valued columns, single entries may be missing.
 
-The lookup (k_emission_pgauss) is held to the contract's loop bit for bit; the statistics (k_stats_pgauss, a GEMM on
+The lookup (k_emission_pgauss) is held to the contract's loop bit for bit; the statistics (k_stats_columns, a GEMM on
 v_mfma_f64_16x16x4_f64 whose A operand is r * r, r or one, r = x - origin[d]) to the project's tolerances for summed
 statistics (tests/test_gpu_poisson.py): A_raw and n rtol 1e-6 with atol 1e-9 x (rows of the batch), sx the same with
 atol additionally x the largest |r| of the data set, sxx x its square (the scales of their summands), lb rtol 1e-10.

@@ -1,6 +1,6 @@
 """svihmm_set_emission_poisson on the MI355X: D count columns, independent Poisson rates given the state.
 
-The lookup (k_emission_poisson) is held to the contract's loop bit for bit; the statistics (k_stats_poisson, a GEMM on
+The lookup (k_emission_poisson) is held to the contract's loop bit for bit; the statistics (k_stats_columns, a GEMM on
 v_mfma_f64_16x16x4_f64 whose A operand is the count or one) to the project's tolerances for count statistics
 (tests/test_categorical.py, tests/test_gpu_mcat.py): A_raw and n rtol 1e-6 with atol 1e-9 x (rows of the batch), sx the
 same with atol additionally x the largest present count of the data set (the scale of its summands), lb rtol 1e-10.
