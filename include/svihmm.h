@@ -810,6 +810,33 @@ int svihmm_heldout_rows(svihmm_ctx* h, double out2[2], double* out_lp /*[nrows] 
 int svihmm_heldout_entries(svihmm_ctx* h, int64_t n, const int64_t* row /*[n]*/, const int32_t* col /*[n]*/,
                            const double* val /*[n]*/, double out2[2], double* out_lp /*[n] or NULL*/);
 
+/* Posterior expectations of a per-state table against the POSTERIOR BATCH CURRENTLY HELD, under the contract of the
+ * two held-out calls above: the nrows = lastB * lastLm rows svihmm_read_rows(what = 3) hands out (window-major after a
+ * window batch, a row in two windows once per window; all T rows after svihmm_estep_sequences; the R gathered rows
+ * after svihmm_estep_sequence_subset), no E-step, always fp64, K <= 256; the packed statistics, the precision report,
+ * var_x and the batch itself stay as they are (a held-out call afterwards finds the batch).  Towards a running
+ * resident SVI loop they behave as svihmm_suffstats does.  They do not depend on the emission family: `table`
+ * (host, [K][F] row-major, 1 <= F <= SVIHMM_MCAT_MAX_F) is whatever the caller wants averaged -- state means for the
+ * smoothed signal and for imputation, rates, predictive symbol probabilities --, no family need be set, a batch that
+ * ran on host lliks (SVIHMM_USE_HOST_LLIKS) is taken and the resident observations are not read.  A batch computed in
+ * the fp32 mode is taken as well: its var_x is handed out as fp64 rows.
+ *
+ * svihmm_posterior_expect: out[g][f] = sum_k var_x[g][k] table[k][f] for every batch row g (host, [nrows][F]), an fp64
+ *   MFMA GEMM.  The order in which the K products of an output are added is fixed by the kernel and is the same for
+ *   every row and grid: two calls give the same bits, and so does the same var_x row met in two batches.  Within
+ *   K 2^-52 sum_k |var_x[g][k] table[k][f]| of the exact sum.
+ * svihmm_posterior_expect_entries: out[e] = sum_k var_x[row[e]][k] table[k][col[e]] (host, [n]) for a sparse list,
+ *   k ascending from s = 0.0, p = var_x * table rounded, s = s + p rounded (never fused): a host loop restates it bit
+ *   for bit.  Duplicates are allowed; n = 0 launches nothing.
+ *
+ * Both fail with a message before any device work, the handle staying usable: NULL handle, table or out; F outside
+ * [1, SVIHMM_MCAT_MAX_F]; n < 0; NULL row / col with n > 0; a row[e] outside [0, nrows) or a col[e] outside [0, F)
+ * (the message gives e and the value); a non-finite table entry (the message gives k and f); no posterior batch held
+ * (as the held-out calls say it); K > 256 or a K of the globals that is not the batch's. */
+int svihmm_posterior_expect(svihmm_ctx* h, int32_t F, const double* table /*[K][F]*/, double* out /*[nrows][F]*/);
+int svihmm_posterior_expect_entries(svihmm_ctx* h, int32_t F, const double* table /*[K][F]*/, int64_t n,
+                                    const int64_t* row /*[n]*/, const int32_t* col /*[n]*/, double* out /*[n]*/);
+
 /* State decoding of the last estep/forward_backward call for the evaluation metrics
  * (hmmbase.py:346-355 hamming_dist; util.py:236-277 munkres_match's count matrix):
  * z[r] = argmax_k var_x[r, k] for the n = B*Lm rows (window-major; the first maximum wins like

@@ -119,6 +119,9 @@ SIGNATURES = {
     "svihmm_heldout_rows": (C.c_int, [C.c_void_p, _c_double_p, _c_double_p]),
     "svihmm_heldout_entries": (C.c_int, [C.c_void_p, C.c_int64, _c_int64_p, C.POINTER(C.c_int32), _c_double_p,
                                          _c_double_p, _c_double_p]),
+    "svihmm_posterior_expect": (C.c_int, [C.c_void_p, C.c_int32, _c_double_p, _c_double_p]),
+    "svihmm_posterior_expect_entries": (C.c_int, [C.c_void_p, C.c_int32, _c_double_p, C.c_int64, _c_int64_p,
+                                                  C.POINTER(C.c_int32), _c_double_p]),
     "svihmm_alloc_obs": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32]),
     "svihmm_set_obs_rows": (C.c_int, [C.c_void_p, C.c_int64, C.c_int64, _c_double_p, C.c_void_p]),
     "svihmm_shift_obs": (C.c_int, [C.c_void_p, _c_double_p]),
@@ -220,6 +223,18 @@ def i64ptr(a):
 
 def u8ptr(a):
     return None if a is None else a.ctypes.data_as(_c_uint8_p)
+
+
+def as_state_table(table, K, who):
+    """``table`` of the posterior-expectation calls as a contiguous float64 ``[K, F]`` array (``[K]`` counts as
+    F = 1)."""
+    t = np.asarray(table, dtype=np.float64)
+    if t.ndim == 1:
+        t = t[:, None]
+    if t.ndim != 2 or t.shape[0] != K or t.shape[1] < 1:
+        raise ValueError("%s: table must be a [K = %d, F] array (or [K] for F = 1), got %s"
+                         % (who, K, np.shape(table)))
+    return np.ascontiguousarray(t)
 
 
 def as_f64(a, shape=None):

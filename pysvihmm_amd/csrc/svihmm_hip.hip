@@ -24,6 +24,7 @@
 #include "device_helpers.h"
 #include "kernels_misc.h"
 #include "kernels_heldout.h"
+#include "kernels_expect.h"
 #include "kernels_svi.h"
 
 thread_local std::string g_err;
@@ -3123,6 +3124,134 @@ int svihmm_heldout_entries(svihmm_ctx* h, int64_t n, const int64_t* row, const i
   return heldout_finish(h, nblk, part, dlp, n, out2, out_lp);
 }
 #undef HELDOUT_KT
+
+// ---- posterior expectations of per-state tables against the posterior batch held (kernels_expect.h) ----------
+// heldout_batch's contract: no E-step, always fp64, K <= 256; everything that can be wrong is found before any device
+// work.  The emission family is not asked for and the resident rows are not read: a batch on host lliks is taken.
+// (var_x is handed out as doubles whatever mode computed the batch -- intermediate_ptr(h, 3): ensure_q writes fp64
+//  rows in the fp32 mode too -- so no batch has to be refused for its precision.)
+static int expect_table_check(const char* fn, int K, int F, const double* table) {
+  for (int k = 0; k < K; ++k)
+    for (int f = 0; f < F; ++f)
+      if (!std::isfinite(table[(size_t)k * F + f]))
+        return fail(std::string(fn) + ": table[" + std::to_string(k) + "][" + std::to_string(f) + "] is not finite");
+  return 0;
+}
+// rows of one pass of the dense call: the device copy of the result is at most this large, a call on more rows
+// runs the kernel pass by pass (a row's bits do not depend on where it sits in a launch)
+#define EXPECT_OUT_BYTES ((size_t)256 << 20)
+
+int svihmm_posterior_expect(svihmm_ctx* h, int32_t F, const double* table, double* out) {
+  const char* fn = "svihmm_posterior_expect";
+  const auto bad = [fn](const std::string& what) { return fail(std::string(fn) + ": " + what); };
+  if (!h) return bad("NULL handle");
+  if (!table) return bad("table is NULL");
+  if (!out) return bad("out is NULL");
+  if (F < 1 || F > SVIHMM_MCAT_MAX_F)
+    return bad("F = " + std::to_string(F) + " is outside [1, " + std::to_string(SVIHMM_MCAT_MAX_F) + "]");
+  int64_t nrows = 0;
+  CK(heldout_batch(h, fn, &nrows));
+  const int K = h->K;
+  CK(expect_table_check(fn, K, F, table));
+  CK(set_device(h));
+  CK(wait_side_streams(h));
+  const double* q = nullptr;
+  CK(intermediate_ptr(h, 3, 0, nrows, &q));
+  // the widest feature group (16 NT features) whose staged slice leaves room for two workgroups on a CU
+  const int Kpad = (K + EXPECT_KC - 1) / EXPECT_KC * EXPECT_KC;
+  const auto lds_of = [Kpad](int nt) { return (size_t)Kpad * (16 * nt + EXPECT_LD_PAD) * sizeof(double); };
+  int NT = F > 32 ? 4 : F > 16 ? 2 : 1;
+  while (NT > 1 && lds_of(NT) > (size_t)72 << 10) NT >>= 1;
+  const size_t lds = lds_of(NT);
+  const int VEC = K % 4 == 0 ? 4 : K % 2 == 0 ? 2 : 1;
+  const int64_t pass_rows = std::max<int64_t>(EXPECT_ROWS, (int64_t)(EXPECT_OUT_BYTES / ((size_t)F * sizeof(double))) /
+                                                             EXPECT_ROWS * EXPECT_ROWS);
+  const size_t tb = ((size_t)K * F * sizeof(double) + 255) & ~(size_t)255;
+  // heldout: [ table K F (to 256 bytes) | result of one pass ]
+  CK(ensure(h->heldout, tb + (size_t)std::min(nrows, pass_rows) * F * sizeof(double)));
+  double* dtab = (double*)h->heldout.p;
+  double* dout = (double*)((char*)h->heldout.p + tb);
+  CK(upload_staged(h, dtab, table, (size_t)K * F * sizeof(double)));
+  // workgroups a CU holds at once: the registers allow 3 (NT = 4: 150 VGPRs) or 4 waves per SIMD, the LDS the rest
+  const int wgs_per_cu = (int)std::min<size_t>(NT == 4 ? 3 : 4, ((size_t)160 << 10) / lds);
+  for (int64_t r0 = 0; r0 < nrows; r0 += pass_rows) {
+    const int64_t nr = std::min(pass_rows, nrows - r0);
+    const int64_t wg_tiles = (nr + 4 * EXPECT_ROWS - 1) / (4 * EXPECT_ROWS);
+    const dim3 grid((unsigned)std::min<int64_t>(wg_tiles, (int64_t)std::max(h->ncu, 1) * wgs_per_cu),
+                    (unsigned)((F + 16 * NT - 1) / (16 * NT)));
+    {
+      ProfScope ps(h, KS_MISC);
+#define PE(NTV, VV)                                                                                                 \
+  do {                                                                                                              \
+    if (lds > ((size_t)64 << 10))                                                                                   \
+      HIPCK(hipFuncSetAttribute((const void*)k_posterior_expect<NTV, VV>, hipFuncAttributeMaxDynamicSharedMemorySize, \
+                                (int)lds));                                                                         \
+    hipLaunchKernelGGL((k_posterior_expect<NTV, VV>), grid, dim3(256), lds, h->stream, q + (size_t)r0 * K,          \
+                       (const double*)dtab, nr, K, (int)F, dout);                                                   \
+  } while (0)
+#define PEV(NTV) do { if (VEC == 4) PE(NTV, 4); else if (VEC == 2) PE(NTV, 2); else PE(NTV, 1); } while (0)
+      if (NT == 4) PEV(4); else if (NT == 2) PEV(2); else PEV(1);
+#undef PEV
+#undef PE
+      HIPCK(hipGetLastError());
+    }
+    CK(d2h(h, out + (size_t)r0 * F, dout, (size_t)nr * F * sizeof(double)));
+    if (r0 + pass_rows < nrows) HIPCK(hipStreamSynchronize(h->stream));   // (the next pass rewrites the device copy)
+  }
+  HIPCK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+int svihmm_posterior_expect_entries(svihmm_ctx* h, int32_t F, const double* table, int64_t n, const int64_t* row,
+                                    const int32_t* col, double* out) {
+  const char* fn = "svihmm_posterior_expect_entries";
+  const auto bad = [fn](const std::string& what) { return fail(std::string(fn) + ": " + what); };
+  if (!h) return bad("NULL handle");
+  if (!table) return bad("table is NULL");
+  if (!out) return bad("out is NULL");
+  if (F < 1 || F > SVIHMM_MCAT_MAX_F)
+    return bad("F = " + std::to_string(F) + " is outside [1, " + std::to_string(SVIHMM_MCAT_MAX_F) + "]");
+  if (n < 0) return bad("n = " + std::to_string(n) + " must not be negative");
+  if (n > 0 && (!row || !col)) return bad("row and col must be given when n > 0");
+  int64_t nrows = 0;
+  CK(heldout_batch(h, fn, &nrows));
+  for (int64_t e = 0; e < n; ++e) {
+    if (row[e] < 0 || row[e] >= nrows)
+      return bad("row[" + std::to_string(e) + "] = " + std::to_string(row[e]) + " is outside [0, nrows = " +
+                 std::to_string(nrows) + ")");
+    if (col[e] < 0 || col[e] >= F)
+      return bad("col[" + std::to_string(e) + "] = " + std::to_string(col[e]) + " is outside [0, F = " +
+                 std::to_string(F) + ")");
+  }
+  const int K = h->K;
+  CK(expect_table_check(fn, K, F, table));
+  if (n == 0) return 0;
+  const int64_t nblk = (n + 255) / 256;
+  if (nblk > 0x3fffffff) return bad("n = " + std::to_string(n) + " entries are too many for one launch");
+  CK(set_device(h));
+  CK(wait_side_streams(h));
+  const double* q = nullptr;
+  CK(intermediate_ptr(h, 3, 0, nrows, &q));
+  const size_t tb = ((size_t)K * F * sizeof(double) + 255) & ~(size_t)255;
+  // heldout: [ table K F (to 256 bytes) | out n | row n int64 | col n int32 ]
+  CK(ensure(h->heldout, tb + 2 * (size_t)n * sizeof(double) + (size_t)n * sizeof(int32_t)));
+  double* dtab = (double*)h->heldout.p;
+  double* dout = (double*)((char*)h->heldout.p + tb);
+  int64_t* drow = (int64_t*)(dout + n);
+  int32_t* dcol = (int32_t*)(drow + n);
+  CK(upload_staged(h, dtab, table, (size_t)K * F * sizeof(double)));
+  CK(upload_staged(h, drow, row, (size_t)n * sizeof(int64_t)));
+  CK(upload_staged(h, dcol, col, (size_t)n * sizeof(int32_t)));
+  {
+    ProfScope ps(h, KS_MISC);
+    hipLaunchKernelGGL(k_posterior_expect_entries, dim3((unsigned)nblk), dim3(256), 0, h->stream, q,
+                       (const int64_t*)drow, (const int32_t*)dcol, (const double*)dtab, n, K, (int)F, dout);
+    HIPCK(hipGetLastError());
+  }
+  CK(d2h(h, out, dout, (size_t)n * sizeof(double)));
+  HIPCK(hipStreamSynchronize(h->stream));
+  return 0;
+}
 
 int svihmm_state_argmax(svihmm_ctx* h, const int32_t* true_sts, int32_t* out_z,
                         int64_t* out_conf) {

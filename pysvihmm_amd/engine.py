@@ -754,6 +754,48 @@ class HipEngine(object):
             return res
         return res + (lp[:n],) + ((src,) if resident else ())
 
+    def _batch_row_exists(self, g):
+        """Whether the library hands out row ``g`` of ``var_x`` (``svihmm_read_rows``; a row at or past the batch's
+        ``lastB * lastLm`` rows is refused by a host-side check there, nothing runs)."""
+        return self._lib.svihmm_read_rows(self._h, 3, int(g), 1, L.dptr(np.empty(max(self.K, 1)))) == 0
+
+    def posterior_expect(self, table):
+        """Posterior expectation of a per-state table over the posterior batch the last E-step-type call left
+        (``svihmm_posterior_expect``; ``forward_backward``, ``estep``, ``estep_sequences``, ``estep_sequence_subset``):
+        ``out[g, f] = sum_k var_x[g, k] table[k, f]`` for every batch row ``g``, ``[nrows, F]``, on the device without
+        another E-step and without reading ``var_x`` back.  ``table`` is ``[K, F]`` float64 (``[K]`` counts as
+        ``F = 1``), any finite values: no emission family is involved."""
+        t = L.as_state_table(table, self.K, "posterior_expect")
+        n = int(getattr(self, "_rows", 0))
+        # the library writes lastB * lastLm rows: no call before it is known that they fit the buffer
+        if self._batch_row_exists(n):
+            raise RuntimeError("posterior_expect: the posterior batch held has more than the %d rows this engine "
+                               "counted at its last E-step-type call" % n)
+        out = np.empty((max(n, 1), t.shape[1]))
+        L.check(self._lib.svihmm_posterior_expect(self._h, t.shape[1], L.dptr(t), L.dptr(out)),
+                "svihmm_posterior_expect")
+        if n > 0 and not self._batch_row_exists(n - 1):
+            raise RuntimeError("posterior_expect: the posterior batch held has fewer than the %d rows this engine "
+                               "counted at its last E-step-type call" % n)
+        return out[:n]
+
+    def posterior_expect_entries(self, table, rows, cols):
+        """``out[e] = sum_k var_x[rows[e], k] table[k, cols[e]]`` for a sparse list of (batch row, table column) pairs
+        (``svihmm_posterior_expect_entries``), ``[n]``: ``k`` ascending, every product and sum rounded on its own, so
+        a NumPy loop restates it bit for bit.  ``rows`` are batch rows (the rows ``read_rows("var_x")`` numbers);
+        duplicates are allowed, an empty list launches nothing."""
+        t = L.as_state_table(table, self.K, "posterior_expect_entries")
+        r = np.ascontiguousarray(np.asarray(rows, dtype=np.int64).ravel())
+        c = np.ascontiguousarray(np.asarray(cols, dtype=np.int32).ravel())
+        if len(r) != len(c):
+            raise ValueError("posterior_expect_entries: rows and cols must have one length")
+        n = len(r)
+        out = np.empty(max(n, 1))
+        L.check(self._lib.svihmm_posterior_expect_entries(
+            self._h, t.shape[1], L.dptr(t), n, L.i64ptr(r) if n else None,
+            c.ctypes.data_as(C.POINTER(C.c_int32)) if n else None, L.dptr(out)), "svihmm_posterior_expect_entries")
+        return out[:n]
+
     def state_argmax(self, true_sts=None, want_z=True):
         """``np.argmax(var_x, axis=1)`` over the rows of the last E-step (window-major) and, with
         labels, the count matrix ``DM[pred, true]`` of ``util.munkres_match`` (reference

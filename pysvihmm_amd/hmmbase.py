@@ -1015,6 +1015,161 @@ class VariationalHMMBase(object, metaclass=abc.ABCMeta):
             return res[0]
         return res[0], (res[2] if len(r) else np.empty(0))
 
+    # -- posterior expectations of per-state tables ----------------------------------------
+    def _expect_engine(self):
+        """The engine, where ``posterior_expect`` can run on the device: it has the two calls and the posterior
+        batch it holds is this model's whole-chain / all-sequences E-step (the batch ``var_x`` is read from after
+        ``infer()`` of the batch classes and after ``full_local_update()``); else None.  No engine is created."""
+        eng = self.__dict__.get("_engine")
+        if eng is None or not callable(getattr(eng, "posterior_expect", None)) \
+                or not callable(getattr(eng, "posterior_expect_entries", None)):
+            return None
+        if getattr(eng, "_obs_owner", None) != id(self):
+            return None
+        held, T = getattr(eng, "_held", None), self.obs.shape[0]
+        if held is None or int(getattr(eng, "_rows", 0)) != T:
+            return None
+        whole = held[0] == "sequences" or (held[0] == "windows" and len(held[1]) == 1 and int(held[1][0]) == 0
+                                           and int(held[2]) == T)
+        return eng if whole else None
+
+    def _expect_route(self, device_call, prepare):
+        """``(device result or None, var_x for the host route or None for self.var_x)``.  ``prepare``: the caller needs
+        posteriors of all rows (``_expect_prepare``).  A call the engine refuses because it holds no posterior batch
+        any more -- a decoder, ``loglik`` or a new upload ran since the E-step, which the engine's own note of the
+        batch does not record -- clears that note and, with ``prepare``, prepares again: a class whose ``var_x`` does
+        not cover the rows then averages a fresh whole-chain E-step, never a stale or shorter ``self.var_x``."""
+        var_x = self._expect_prepare() if prepare else None
+        eng = self._expect_engine()
+        if eng is None:
+            return None, var_x
+        try:
+            return device_call(eng), None
+        except RuntimeError as e:
+            if "no posterior batch held" not in str(e):
+                raise
+        eng._held = None
+        if prepare:
+            var_x = self._expect_prepare()
+            eng = self._expect_engine()
+            if eng is not None:
+                return device_call(eng), None
+        return None, var_x
+
+    def _posterior_expect(self, t, prepare=False):
+        out, var_x = self._expect_route(lambda eng: eng.posterior_expect(t), prepare)
+        if out is None:
+            out = np.asarray(self.var_x if var_x is None else var_x, dtype=np.float64) @ t
+        so = self.__dict__.get("seq_off")
+        if so is not None and out.shape[0] == int(so[-1]):
+            return [out[int(so[s]):int(so[s + 1])] for s in range(len(so) - 1)]
+        return out
+
+    def _posterior_expect_entries(self, t, rows, cols, prepare=False):
+        r = np.asarray(rows, dtype=np.int64).ravel()
+        c = np.asarray(cols, dtype=np.int64).ravel()
+        if len(r) != len(c):
+            raise ValueError("posterior_expect_entries: rows and cols must have one length")
+        out, var_x = self._expect_route(lambda eng: eng.posterior_expect_entries(t, r, c), prepare)
+        if out is not None:
+            return out
+        q = np.asarray(self.var_x if var_x is None else var_x, dtype=np.float64)
+        if len(r) and (r.min() < 0 or r.max() >= q.shape[0] or c.min() < 0 or c.max() >= t.shape[1]):
+            raise ValueError("posterior_expect_entries: an entry lies outside [0, %d) x [0, %d)"
+                             % (q.shape[0], t.shape[1]))
+        # the device's order: k ascending from 0.0, every product and every sum rounded on its own
+        out = np.zeros(len(r))
+        for k in range(self.K):
+            out = out + q[r, k] * t[k, c]
+        return out
+
+    def posterior_expect(self, table):
+        """Posterior expectation of a per-state table: ``out[t, f] = sum_k var_x[t, k] table[k, f]``, ``[rows, F]``.
+        ``table`` is a ``[K, F]`` float64 array of any finite values (a ``[K]`` array counts as ``F = 1``).  On an
+        engine that has ``posterior_expect`` and holds this model's whole-chain posterior batch -- after ``infer()``
+        of the batch classes on one chain, after ``full_local_update()`` -- the product is formed on the device
+        against the rows in HBM (``svihmm_posterior_expect``) and only ``[rows, F]`` crosses the bus; otherwise it is
+        ``self.var_x @ table`` in NumPy.  When ``obs`` was a list the result is a list of per-sequence arrays.
+
+        The device averages the batch the engine HOLDS.  After ``infer()`` and ``full_local_update()`` that is the
+        batch ``var_x`` was read from, and both routes see the same bits.  A later whole-chain E-step that sets no
+        attribute (``heldout_logprob()``, ``hamming_dist(None, ..)``) under changed parameters replaces the batch
+        held and leaves ``self.var_x``: the device route then answers for the newer posteriors, the NumPy route for
+        ``self.var_x``.  ``local_update()`` brings the two together again."""
+        return self._posterior_expect(L.as_state_table(table, self.K, "posterior_expect"))
+
+    def posterior_expect_entries(self, table, rows, cols):
+        """``out[e] = sum_k var_x[rows[e], k] table[k, cols[e]]`` for a list of single (row, table column) pairs,
+        ``[n]``; rows are numbered over the concatenation when ``obs`` was a list, as ``heldout_entries_logprob``
+        numbers them.  Device or NumPy as ``posterior_expect`` chooses; both add ``k`` ascending with every product
+        and sum rounded on its own, so they agree bit for bit."""
+        return self._posterior_expect_entries(L.as_state_table(table, self.K, "posterior_expect_entries"), rows, cols)
+
+    def _expect_family_table(self, who):
+        """``(family name, table [K, F])`` of the per-state means ``reconstruct()`` averages, by the emitters' types."""
+        fam = self._heldout_family()
+        ve = self.var_emit
+        if fam is None and len(ve) and all(is_niw_gaussian(e) for e in ve):
+            fam = "niw"                     # (rows wider than the device's NIW kernels take: the table is the same)
+        if fam == "niw":
+            tab = [np.ravel(e.mu_mf) for e in ve]
+        elif fam in ("diag", "pgauss"):
+            tab = [np.ravel(e.mf_mu) for e in ve]
+        elif fam == "poisson":
+            tab = [np.ravel(e.alpha_mf) / np.ravel(e.beta_mf) for e in ve]
+        elif fam == "cat":
+            tab = [np.ravel(e.alpha_mf) / np.sum(e.alpha_mf) for e in ve]
+        elif fam == "mcat":
+            tab = [np.concatenate([np.ravel(a) / np.sum(a) for a in e.alpha_mf]) for e in ve]
+        else:
+            raise NotImplementedError("%s: emitters of type %s have no table of per-state means known here; build "
+                                      "the [K, F] table yourself and call posterior_expect(table)"
+                                      % (who, type(ve[0]).__name__ if len(ve) else None))
+        return fam, np.array(tab, dtype=np.float64)
+
+    def _expect_prepare(self):
+        """Posteriors of all the model's rows: ``var_x`` to average where the device does not hold them (None:
+        ``self.var_x``).  The batch classes have them after ``infer()``; ``hmmsgd_metaobs.VBHMM`` overrides this."""
+        return None
+
+    def reconstruct(self):
+        """Posterior mean of every observation column, the smoothed / denoised signal
+        ``xhat[t, d] = sum_k var_x[t, k] mean[k, d]`` through ``posterior_expect``: the table is ``mu_mf``
+        (``Gaussian``), ``mf_mu`` (``DiagonalGaussian`` / ``ProductGaussian``), ``alpha_mf / beta_mf`` (the expected
+        rates of ``ProductPoisson``) or, for ``Categorical`` / ``ProductCategorical``, the predictive symbol
+        probabilities ``alpha / alpha.sum()`` of the columns side by side (``[T, sum V_d]``, the columns' blocks in
+        ascending ``d``).  Needs posteriors for all the model's rows: after ``infer()`` of the batch classes that
+        holds; ``hmmsgd_metaobs.VBHMM``, whose last batch is a minibatch of windows, runs ``full_local_update()``
+        first when the batch held does not cover the T rows.  Other emitters raise ``NotImplementedError``."""
+        _, t = self._expect_family_table("reconstruct")
+        return self._posterior_expect(t, prepare=True)
+
+    def impute(self):
+        """A copy of the data in which every absent entry is replaced by its posterior mean
+        (``posterior_expect_entries`` on the family's table of means); present entries come back bit-identical.
+        Absent: NaN for ``Gaussian`` / ``DiagonalGaussian``, not ``_present()`` for ``ProductGaussian`` and
+        ``ProductPoisson``.  Masked rows are not special: their present entries stay, their absent ones are filled.
+        A list ``obs`` comes back as a list.  The symbol families raise ``NotImplementedError``: a mean symbol is
+        not a symbol, ``reconstruct()`` gives the predictive probabilities.  Needs what ``reconstruct()`` needs."""
+        fam, t = self._expect_family_table("impute")
+        if fam in ("cat", "mcat"):
+            raise NotImplementedError("impute: symbol columns have no mean to fill in; reconstruct() returns the "
+                                      "predictive symbol probabilities of every row")
+        x = np.asarray(self.obs)
+        x2 = x.reshape(x.shape[0], -1)
+        if fam in ("pgauss", "poisson"):
+            absent = ~self.var_emit[0]._present(x2)[1]
+        else:
+            absent = np.isnan(np.asarray(x2, dtype=np.float64))
+        rows, cols = np.nonzero(absent)
+        out = np.array(x2, dtype=x2.dtype if np.issubdtype(x2.dtype, np.floating) else np.float64)
+        out[rows, cols] = self._posterior_expect_entries(t, rows, cols, prepare=True)
+        out = out.reshape(x.shape)
+        so = self.__dict__.get("seq_off")
+        if so is not None:
+            return [out[int(so[s]):int(so[s + 1])] for s in range(len(so) - 1)]
+        return out
+
     # -- Viterbi / MAP path -------------------------------------------------------------
     def viterbi(self, metaobs=None):
         """Most probable state sequence of the whole chain (or of one meta-observation

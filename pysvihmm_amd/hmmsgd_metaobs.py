@@ -1094,6 +1094,16 @@ class VBHMM(VariationalHMMBase):
         flags = self._push_emission(nan_mask=True)
         self.engine.forward_backward([0], self.T, flags=flags, want=())
 
+    def _expect_prepare(self):
+        """``reconstruct()`` / ``impute()`` need posteriors of all T rows; this class's last batch is a minibatch of
+        windows.  Where the engine does not hold the whole chain's batch, ``full_local_update()`` runs first: on an
+        engine with ``posterior_expect`` its rows stay in HBM for the device call, elsewhere the returned ``var_x``
+        is averaged on the host.  The window attributes (``var_x`` of the last window) stay as they are."""
+        if self._expect_engine() is not None:
+            return None
+        var_x = self.full_local_update()
+        return None if self._expect_engine() is not None else var_x
+
     def full_local_update(self):
         """Whole-chain E-step with missing rows treated as NaN (lliks row = 0),
         reference :1147-1205.  obs is not mutated (the reference NaN-masks it in place
